@@ -47,6 +47,8 @@ torch.distributed.run, one rank per GPU).  Prints ONE JSON line on rank 0.
               --cpu-seconds, the passes after that are parity work, not timed.  N > 1 (and --parity budget): final list when the CPU
               run converges inside its budget, else an order-independent checksum of all registers + Kahan state after the last
               pass the CPU finished.
+  outputs   = --dump-outputs DIR: the (NodeID, f64) list of the last timed run as float64 .npy files (dump_outputs), a seeded
+              sample of result positions when the list is long; the inputs are seeded, so two builds can be compared file for file.
   process   = the measurement runs in THIS process; any failure of the product path - hb_append_edges / hb_finalize not
               reducing the record stream to the clean graph, a HIP error, a GPU fault that aborts the process - ends the
               bench with a non-zero exit code and no JSON line (no fallback to hb_load_dense, no restart: round 3 had both
@@ -77,6 +79,8 @@ import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 HBM_COPY_GBS = 6290.0
+DUMP_SAMPLE = 1 << 20  # result positions in a --dump-outputs sample: 48 B each over the files = 48 MiB at most
+DUMP_SEED = 0x5712AC7
 
 
 def parse():
@@ -125,7 +129,14 @@ def parse():
     ap.add_argument("--tune", default="", help="comma separated hb_options.tune values")
     ap.add_argument("--verify", action="store_true", help="run the CPU oracle to convergence and compare the final result")
     ap.add_argument("--pass-log", default="", help="write per-pass stats JSON here")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the (NodeID, f64) result list of the last timed run as float64 .npy files into DIR (a seeded sample of "
+                         "at most %d result positions, the whole list when it is shorter), to compare two builds output for output"
+                         % DUMP_SAMPLE)
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed runs)")
+    return a
 
 
 def pass_bytes(ps, n, m_eff, rows_with_in):
@@ -186,6 +197,25 @@ def measure(ctx, steps, warmup, barrier, td, torch):
     r["dt"] = dt
     r["stats"] = ctx.stats()
     return r
+
+
+def dump_outputs(path, ids, vals, passes):
+    """--dump-outputs: what hb_run + hb_result_copy handed the caller in the last timed run, as float64 .npy files that two builds
+    of the project can be compared by (the inputs are seeded, so equal builds write equal files).  The u128 NodeIDs go as four
+    32-bit limbs (exact in float64, least significant first).  A list longer than DUMP_SAMPLE is represented by a sample of
+    result positions drawn with a fixed seed from the result count alone (result_positions.npy says which)."""
+    os.makedirs(path, exist_ok=True)
+    k = len(vals)
+    pos = np.arange(k) if k <= DUMP_SAMPLE else np.sort(np.random.default_rng(DUMP_SEED).choice(k, DUMP_SAMPLE, replace=False))
+    lo, hi = ids["lo"][pos], ids["hi"][pos]
+    mask = np.uint64(0xFFFFFFFF)
+    out = {"result_count": np.array([k], dtype=np.float64),
+           "passes": np.array([passes], dtype=np.float64),
+           "result_positions": pos.astype(np.float64),
+           "result_ids_u32x4": np.stack([lo & mask, lo >> np.uint64(32), hi & mask, hi >> np.uint64(32)], axis=1).astype(np.float64),
+           "result_values": np.ascontiguousarray(vals[pos], dtype=np.float64)}
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def load_records(ctx, g, salt=2, slab=1 << 24):
@@ -565,6 +595,8 @@ def main():
     ids, vals = ctx.results()
     stats = ms["stats"]
     passes = ms["passes"]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, ids, vals, passes)
     last_pass_stats = ms["pass_stats"][-1] if ms["pass_stats"] else []
 
     # ---- parity + CPU baseline (rank 0 computes; a checksum rerun, if needed, is collective)

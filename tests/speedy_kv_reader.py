@@ -16,6 +16,7 @@ import json
 import os
 import struct
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -157,8 +158,10 @@ _shim = None
 def _xxh3(tmpdir):
     global _shim
     if _shim is None:
-        src = os.path.join(tmpdir, "xxh3_shim.c")
-        lib = os.path.join(tmpdir, "xxh3_shim.so")
+        # a directory of its own: tmpdir may be a shared /tmp that already holds another user's shim
+        own = tempfile.mkdtemp(prefix="xxh3_shim_", dir=tmpdir)
+        src = os.path.join(own, "xxh3_shim.c")
+        lib = os.path.join(own, "xxh3_shim.so")
         with open(src, "w") as f:
             f.write('#define XXH_INLINE_ALL\n#include "%s"\n'
                     "void hash42(const void *p, unsigned long n, unsigned long long *out) {\n"

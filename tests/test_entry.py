@@ -63,6 +63,51 @@ def test_bench_line_at_one_gpu_is_the_scaling_runs_first_point(monkeypatch):
     assert 'main_part = "single" if world == 1 else ("dest" if a.partition == "dest" else "edge")' in src  # `value` at N > 1 = edge partition
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float64 files only, NodeIDs exact as 32-bit limbs, the whole list when it is short, a seeded sample of at most
+    DUMP_SAMPLE positions (the same one for the same result count) when it is long; --steps below 1 is refused."""
+    import numpy as np
+
+    import bench
+    from stract_amd._lib import U128
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "2", "--dump-outputs", str(tmp_path)])
+    assert bench.parse().steps == 2
+
+    def lst(k):
+        rng = np.random.default_rng(k)
+        ids = np.zeros(k, U128)
+        ids["lo"] = rng.integers(0, 1 << 63, k, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+        ids["hi"] = rng.integers(0, 1 << 63, k, dtype=np.uint64)
+        return ids, rng.random(k)
+
+    ids, vals = lst(1000)
+    bench.dump_outputs(str(tmp_path / "short"), ids, vals, 7)
+    d = {f[:-4]: np.load(str(tmp_path / "short" / f)) for f in os.listdir(str(tmp_path / "short"))}
+    assert set(d) == {"result_count", "passes", "result_positions", "result_ids_u32x4", "result_values"}
+    assert all(x.dtype == np.float64 for x in d.values())
+    assert d["result_count"].tolist() == [1000] and d["passes"].tolist() == [7]
+    assert d["result_positions"].tolist() == list(range(1000)) and np.array_equal(d["result_values"], vals)
+    limbs = d["result_ids_u32x4"].astype(np.uint64)
+    assert np.array_equal(limbs[:, 0] | (limbs[:, 1] << np.uint64(32)), ids["lo"])
+    assert np.array_equal(limbs[:, 2] | (limbs[:, 3] << np.uint64(32)), ids["hi"])
+
+    k = bench.DUMP_SAMPLE + 12345
+    ids, vals = lst(k)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), ids, vals, 3)
+    total = sum(os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a")))
+    assert total <= 64 * 1000 * 1000
+    for f in os.listdir(str(tmp_path / "a")):
+        assert open(str(tmp_path / "a" / f), "rb").read() == open(str(tmp_path / "b" / f), "rb").read(), f
+    pos = np.load(str(tmp_path / "a" / "result_positions.npy")).astype(np.int64)
+    assert len(pos) == bench.DUMP_SAMPLE and np.all(np.diff(pos) > 0) and pos[-1] < k
+    assert np.array_equal(np.load(str(tmp_path / "a" / "result_values.npy")), vals[pos])
+
+
 @pytest.mark.gpu
 def test_smoke_entry_point():
     import __graft_entry__ as g
