@@ -50,6 +50,10 @@ typedef struct hbw_reader hbw_reader;
 #define HBW_VERIFY_CRC 0x1u /* check every .col file's CRC-32 against its footer (reads the whole file once) */
 #define HBW_PAGE_IDS   0x2u /* also locate the page-level `from_id` / `to_id` columns (webgraph/schema.rs:132-180): the records
                                the reference's tail mode queries (harmonic.rs:82-87), see HB_FLAG_REFERENCE_TAIL */
+#define HBW_PAGE_GRAPH 0x4u /* hb_load_webgraph only: the PAGE graph is the context's graph - every document's {from_id, to_id,
+                               rel_flags} streams in instead of the host ids (page_edges(), webgraph/mod.rs:165-174), for
+                               hb_sampled_harmonic (create the context with HB_FLAG_ALL_RELS: ForwardlinksQuery has no rel
+                               filter).  Refused together with HBW_PAGE_IDS, and on an HB_FLAG_REFERENCE_TAIL context */
 
 /* Opens `<webgraph>/edges` (the directory holding meta.json).  Maps every segment's .col file and locates the three
  * columns; fails if a column is missing, has another codec than Raw, or row counts disagree with meta.json. */
@@ -74,7 +78,8 @@ int hbw_read_page_edges(const hbw_reader *r, uint64_t first, uint64_t count, hb_
 /* Replaces `HarmonicCentrality::calculate(&Webgraph)`'s input side end to end (harmonic.rs:292, :58-72, :116-131):
  * streams the store's records into ctx in slabs (hb_append_edges) and finalizes with the node set derived from all
  * endpoints (= host_nodes()).  Then hb_run() as usual.  With HBW_PAGE_IDS (ctx created with HB_FLAG_REFERENCE_TAIL) the
- * page-level records follow through hb_append_tail_edges, so the run is `stract centrality harmonic` as written. */
+ * page-level records follow through hb_append_tail_edges, so the run is `stract centrality harmonic` as written.  With
+ * HBW_PAGE_GRAPH the page-level records ARE the graph (node set = their endpoints): then hb_sampled_harmonic. */
 int hb_load_webgraph(hb_ctx *ctx, const char *edges_dir, uint32_t flags);
 
 /* ---- test exports ------------------------------------------------------------------------------------------- */

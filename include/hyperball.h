@@ -101,6 +101,9 @@ typedef struct hb_edge {
 #define HB_FLAG_NO_INIT_PASS  0x4000u /* pass 0 like every other dense pass (64-byte gathers) instead of streaming the sources'
                                          single initial register with the edge list (2 bytes per edge, written at load time);
                                          same results, measurement switch */
+#define HB_FLAG_ALL_RELS      0x8000u /* every edge record is an edge: no SKIPPED_REL filter at ingest (then m_eff == m_unique).  The page
+                                          graph of ApproxHarmonic follows every ForwardlinksQuery edge (query/forwardlink.rs:44-53); use
+                                          with hb_sampled_harmonic.  Not with HB_FLAG_REFERENCE_TAIL                                     */
 #define HB_FLAG_RCCL_SELF     0x80u /* world_size == 1 but still create a 1-rank communicator and run
                                        the collectives (exercises the RCCL call path on one GPU)   */
 
@@ -297,6 +300,53 @@ int hb_result_ranks(hb_ctx *ctx, uint64_t *ranks, uint64_t cap);
  * unstable sort keyed by the centrality alone: the order of ties, and which of them make the cut, are unspecified
  * there.)  ids or vals may be NULL; *written = number of entries. */
 int hb_result_top(hb_ctx *ctx, uint64_t k, hb_u128 *ids, double *vals, uint64_t *written);
+
+/* ---- sampled page-level harmonic centrality: ApproxHarmonic::build (approx_harmonic.rs:40-89) ------------------------------------ */
+/* k sources, one BFS each to distance max_dist + 1 (dijkstra_multi returns when it POPS a cost above max_dist, so nodes at max_dist + 1
+ * are already in its map: shortest_path.rs:85-95), all run at once as bit sets over the device plan, 512 sources per batch.  Single
+ * rank only.  Definitions (deterministic; the reference sums f32 terms from rayon threads):
+ *   c_d(v)   = number of sources at distance exactly d from v, d = 1 .. max_dist + 1 (a source itself, d = 0, never counts: :63)
+ *   norm     = (float)N / ((float)k_req * ((float)N - 1.0f))       (:57; N = num_nodes, k_req = requested samples)
+ *   w_d      = (1.0f / (float)d) * norm                             (:69, f32)
+ *   value(v) = (double)(float)S(v),  S(v) = sum over d ascending with c_d(v) > 0 of (double)c_d(v) * (double)w_d, from +0.0 in f64
+ * v is a result iff some c_d(v) > 0.  The result replaces the context's results (hb_result_*, hb_store_harmonic_results) until the next
+ * hb_begin / hb_run; the HyperBall state is not part of it (hb_run afterwards computes what it computed before).
+ * Sampler (sources == NULL): candidates = the nodes with >= 1 out-edge in the loaded graph (self links included), ascending NodeID
+ * (`page_edges().map(from).unique()`); min(k, candidates) distinct indices by Floyd's algorithm driven by splitmix64(seed) (index
+ * j = next() % (i + 1)), sorted ascending.  Source i of the sorted list is bit i % 512 of batch i / 512. */
+#define HB_SAMPLE_MAX_LEVELS 16
+typedef struct hb_sample_options {
+    uint32_t struct_size;   /* = sizeof(hb_sample_options); 0 = this version                                            */
+    uint32_t max_dist;      /* 0 = 7 (approx_harmonic.rs:62); <= 15, else HB_ERR_LIMIT                                   */
+    uint64_t seed;          /* sampler seed                                                                               */
+    uint64_t samples;       /* k_req; 0 = ceil(log2((double)N) / (epsilon * epsilon)) (0 for N <= 1), or source_count
+                               when sources are given; <= 65535, else HB_ERR_LIMIT                                        */
+    uint64_t num_nodes;     /* N; 0 = the loaded graph's n                                                                */
+    double   epsilon;       /* 0 = 0.3 (approx_harmonic.rs:29)                                                            */
+    const hb_u128 *sources; /* NULL = seeded sampler; else source_count distinct node ids of the loaded graph              */
+    uint64_t source_count;
+} hb_sample_options;
+
+typedef struct hb_sample_stats {
+    uint32_t struct_size;   /* = sizeof(hb_sample_stats); 0 = this version                                               */
+    uint32_t levels;        /* D = max_dist + 1                                                                           */
+    uint64_t k_req;         /* requested samples (norm uses it)                                                           */
+    uint64_t sources;       /* sources used                                                                               */
+    uint64_t batches;       /* ceil(sources / 512)                                                                        */
+    uint64_t results;       /* nodes with a value                                                                         */
+    double   ms_total;      /* wall time of the call                                                                      */
+    uint64_t level_changed[HB_SAMPLE_MAX_LEVELS]; /* node rows whose set grew at level d + 1, summed over the batches      */
+    uint32_t level_modes[HB_SAMPLE_MAX_LEVELS];   /* bit m set = some batch ran level d + 1 in mode m (0 dense, 1 bitmap,
+                                                     2 sweep; the A_t rule of hb_run); 0 = never run (every batch ended)  */
+    double   level_ms[HB_SAMPLE_MAX_LEVELS];      /* GPU time of level d + 1, summed over the batches                     */
+} hb_sample_stats;
+
+int hb_sampled_harmonic(hb_ctx *ctx, const hb_sample_options *opt, hb_sample_stats *stats);
+/* The sampler alone: the sorted sources hb_sampled_harmonic would use for (seed, k); *written = min(k, candidates).  out needs
+ * min(k, candidates) entries (may be NULL to ask for the count). */
+int hb_sample_sources(hb_ctx *ctx, uint64_t seed, uint64_t k, hb_u128 *out, uint64_t *written);
+/* c_d(v) of the last hb_sampled_harmonic: out[v * D + d - 1], v in ascending NodeID order (n x D entries, D = stats.levels). */
+int hb_debug_sample_histogram(hb_ctx *ctx, uint16_t *out);
 
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) -------------------------------------- */
 /* Rank 0 calls this and distributes the 128 bytes (e.g. torch.distributed broadcast);

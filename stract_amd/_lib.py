@@ -43,6 +43,8 @@ HB_FLAG_HOST_PLAN = 0x800
 HB_FLAG_CHANGED_ONLY = 0x1000
 HB_FLAG_REFERENCE_TAIL = 0x2000
 HB_FLAG_NO_INIT_PASS = 0x4000
+HB_FLAG_ALL_RELS = 0x8000
+HB_SAMPLE_MAX_LEVELS = 16
 
 # numpy views of the plain-data structs
 U128 = np.dtype([("lo", "<u8"), ("hi", "<u8")])
@@ -118,6 +120,40 @@ class HbPassStats(ctypes.Structure):
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["pass"] = d.pop("pass_")
+        return d
+
+
+class HbSampleOptions(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("max_dist", ctypes.c_uint32),
+        ("seed", ctypes.c_uint64),
+        ("samples", ctypes.c_uint64),
+        ("num_nodes", ctypes.c_uint64),
+        ("epsilon", ctypes.c_double),
+        ("sources", ctypes.c_void_p),
+        ("source_count", ctypes.c_uint64),
+    ]
+
+
+class HbSampleStats(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("levels", ctypes.c_uint32),
+        ("k_req", ctypes.c_uint64),
+        ("sources", ctypes.c_uint64),
+        ("batches", ctypes.c_uint64),
+        ("results", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+        ("level_changed", ctypes.c_uint64 * HB_SAMPLE_MAX_LEVELS),
+        ("level_modes", ctypes.c_uint32 * HB_SAMPLE_MAX_LEVELS),
+        ("level_ms", ctypes.c_double * HB_SAMPLE_MAX_LEVELS),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        for k in ("level_changed", "level_modes", "level_ms"):
+            d[k] = list(d[k])[:self.levels]
         return d
 
 
@@ -202,6 +238,12 @@ _SIGNATURES += [
     ("hb_store_write", ctypes.c_int, [ctypes.c_char_p, _P, _P, ctypes.c_int, _U64, ctypes.c_char_p, ctypes.c_size_t]),
     ("hb_store_harmonic", ctypes.c_int, [ctypes.c_char_p, _P, _P, _P, _U64, ctypes.c_char_p, ctypes.c_size_t]),
     ("hb_store_harmonic_results", ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_char_p, _U64]),
+]
+# include/hyperball.h: sampled harmonic centrality (ApproxHarmonic)
+_SIGNATURES += [
+    ("hb_sampled_harmonic", ctypes.c_int, [_P, ctypes.POINTER(HbSampleOptions), ctypes.POINTER(HbSampleStats)]),
+    ("hb_sample_sources", ctypes.c_int, [_P, _U64, _U64, _P, ctypes.POINTER(_U64)]),
+    ("hb_debug_sample_histogram", ctypes.c_int, [_P, _P]),
 ]
 SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -477,6 +519,43 @@ class Context:
         buf = ctypes.create_string_buffer(64)
         self._check(self.lib.hb_device_name(self.h, buf, 64))
         return buf.value.decode()
+
+    # -- sampled harmonic centrality (ApproxHarmonic::build, approx_harmonic.rs:40-89)
+    def sampled_harmonic(self, seed=0, samples=0, num_nodes=0, max_dist=0, epsilon=0.0, sources=None):
+        """hb_sampled_harmonic: the results (results / ranks / top / store_harmonic) become the sampled values; returns hb_sample_stats.
+        sources: U128 array of node ids (None = the seeded sampler)."""
+        o = HbSampleOptions()
+        o.struct_size = ctypes.sizeof(HbSampleOptions)
+        o.max_dist, o.seed, o.samples, o.num_nodes, o.epsilon = int(max_dist), int(seed), int(samples), int(num_nodes), float(epsilon)
+        if sources is not None:
+            # (an empty list stays a list: the library refuses sources with source_count == 0 instead of sampling)
+            count = len(sources)
+            sources = np.ascontiguousarray(sources, dtype=U128) if count else np.zeros(1, dtype=U128)
+            o.sources = sources.ctypes.data
+            o.source_count = count
+        st = HbSampleStats()
+        st.struct_size = ctypes.sizeof(HbSampleStats)
+        self._sample_levels = 0
+        self._check(self.lib.hb_sampled_harmonic(self.h, ctypes.byref(o), ctypes.byref(st)))
+        self._sample_levels = st.levels
+        return st.as_dict()
+
+    def sample_sources(self, seed, k):
+        """hb_sample_sources: the sorted node ids the seeded sampler picks for (seed, k)."""
+        w = ctypes.c_uint64(0)
+        self._check(self.lib.hb_sample_sources(self.h, int(seed), int(k), None, ctypes.byref(w)))
+        out = np.zeros(w.value, dtype=U128)
+        self._check(self.lib.hb_sample_sources(self.h, int(seed), int(k), _ptr(out), ctypes.byref(w)))
+        return out[:w.value]
+
+    def sample_histogram(self):
+        """c_d per node of the last sampled run: (n, D) uint16, ascending NodeID, D = max_dist + 1 of that run."""
+        levels = getattr(self, "_sample_levels", 0)
+        if not levels:
+            raise HyperballError(HB_ERR_INVALID, "no sampled result (call sampled_harmonic first)")
+        out = np.zeros((self.n(), int(levels)), dtype=np.uint16)
+        self._check(self.lib.hb_debug_sample_histogram(self.h, _ptr(out)))
+        return out
 
     # -- results
     def results(self):

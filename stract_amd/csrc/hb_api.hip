@@ -20,6 +20,7 @@
 #include "hb_internal.h"
 #include "hb_experiments.h" // HB_XBITS: the switches of the experiments build (none in the product library)
 #include "hb_kernels.hip.h"
+#include "hb_sample.hip.h"
 #ifdef HB_EXPERIMENTS
 #include "hb_experiments.hip.h"
 #endif
@@ -198,6 +199,17 @@ struct hb_ctx {
         hipStream_t stream = nullptr;                 // the snapshots' downloads run here, beside the passes
         hipEvent_t ready = nullptr, copied = nullptr; // out[] built (main stream) / downloaded (side stream)
     } rs;
+    // hb_sampled_harmonic (hb_api_sample.inc): per-level histograms and scratch, hipMalloc'ed on first use, freed with the graph
+    struct SampleState {
+        uint16_t *d_hist = nullptr;           // levels x n_pad, level-major: c_d of device row r at [(d - 1) n_pad + r]
+        uint32_t levels = 0;                  // D of d_hist (0 = no sampled result)
+        unsigned long long *d_cnt = nullptr;  // (kMaxLevels + 1) x 4 counters of the current batch
+        uint32_t *d_srcs = nullptr;           // sids of a batch's sources (<= 512)
+        uint32_t *d_rows = nullptr;           // ... their device rows
+        double *d_w = nullptr;                // w_d as f64, kMaxLevels entries
+        std::vector<uint32_t> cand;           // the sampler's candidates (sids with an out-edge), ascending
+        bool cand_valid = false;              // cand describes the loaded graph (built by the first sampler call after a load)
+    } smp;
 };
 
 namespace {
@@ -307,6 +319,9 @@ void free_graph_buffers(hb_ctx *c)
     c->rs.d_kept = nullptr;
     c->rs.cap = 0;
     c->rs.on = c->rs.valid = false;
+    for (void *q : {(void *)c->smp.d_hist, (void *)c->smp.d_cnt, (void *)c->smp.d_srcs, (void *)c->smp.d_rows, (void *)c->smp.d_w})
+        if (q) (void)hipFree(q);
+    c->smp = hb_ctx::SampleState{};
 }
 
 // hb_options.chunk / tune[3..5] -> planner knobs
@@ -386,6 +401,9 @@ bool dest_mode(const hb_ctx *c)
 // edge partition: every rank holds some in-edges of every row; one all-reduce(max) of all counters per pass
 bool edge_partitioned(const hb_ctx *c) { return multi_rank(c) && !dest_mode(c); }
 bool ref_tail(const hb_ctx *c) { return (c->opt.flags & HB_FLAG_REFERENCE_TAIL) != 0; }
+// rel-flag bits that drop a record at ingest: SKIPPED_REL (harmonic.rs:131), none with HB_FLAG_ALL_RELS (ForwardlinksQuery has no
+// rel filter, query/forwardlink.rs:44-53: the page graph of approx_harmonic.rs follows every edge)
+uint64_t skip_mask(const hb_ctx *c) { return (c->opt.flags & HB_FLAG_ALL_RELS) ? 0ull : HB_SKIPPED_REL_MASK; }
 bool unfused(const hb_ctx *c)
 {
     return edge_partitioned(c) || (linked(c) && !dest_mode(c)) || (c->opt.flags & HB_FLAG_UNFUSED) || ref_tail(c);
@@ -559,6 +577,8 @@ int hb_create(const hb_options *opt, hb_ctx **out)
 #endif
         if ((o.flags & HB_FLAG_REFERENCE_TAIL) && (o.world_size > 1 || (o.flags & (HB_FLAG_RCCL_SELF | HB_FLAG_DEST_PARTITION))))
             return fail(c, HB_ERR_INVALID, "HB_FLAG_REFERENCE_TAIL is a single-rank mode (no partition / RCCL flags)");
+        if ((o.flags & HB_FLAG_ALL_RELS) && (o.flags & HB_FLAG_REFERENCE_TAIL))
+            return fail(c, HB_ERR_INVALID, "HB_FLAG_ALL_RELS and HB_FLAG_REFERENCE_TAIL exclude each other (the tail mode replays the rel filter)");
         hb_ctx *ctx = new (std::nothrow) hb_ctx();
         if (!ctx) return fail(c, HB_ERR_NOMEM, "out of host memory");
         ctx->opt = o;
@@ -720,15 +740,16 @@ int hb_load_edges(hb_ctx *c, const hb_u128 *node_ids, uint64_t n, const hb_edge 
         DeviceCsr csr;
         const bool keep_on_device = !on_host && device_plan(c);
         uint64_t peak = 0;
-        std::string e = on_host ? ingest_edges(node_ids, n, edges, m, &c->g)
-                                : gpu_ingest_edges((void *)c->stream, node_ids, n, edges, m, &c->g, keep_on_device ? &csr : nullptr, &peak);
+        const uint64_t skip = skip_mask(c);
+        std::string e = on_host ? ingest_edges(node_ids, n, edges, m, &c->g, skip)
+                                : gpu_ingest_edges((void *)c->stream, node_ids, n, edges, m, &c->g, keep_on_device ? &csr : nullptr, &peak, skip);
         // (the id space of the device table exhausted is a limit of the DEVICE ingest only: endpoints outside a caller-supplied
         // node list are legal and ignored by the reference, store.rs:338-357 - the host path takes over, like for memory)
         if (!on_host && !e.empty() && (e.find("out of memory") != std::string::npos || e.find("OutOfMemory") != std::string::npos ||
                                        e.find("too many nodes for the device ingest") != std::string::npos)) {
             (void)hipGetLastError(); // clear the sticky allocation error
             peak = 0;
-            e = ingest_edges(node_ids, n, edges, m, &c->g);
+            e = ingest_edges(node_ids, n, edges, m, &c->g, skip);
         }
         if (!e.empty())
             return fail(c, e.find("memory") != std::string::npos ? HB_ERR_NOMEM : (e.find("hip") != std::string::npos ? HB_ERR_HIP : HB_ERR_LIMIT), e);
@@ -765,6 +786,7 @@ int hb_append_edges(hb_ctx *c, const hb_edge *edges, uint64_t m)
             c->app.max_records = c->lim_records;
             c->app.max_bytes = c->lim_bytes;
             c->app.chunk_records = c->lim_chunk;
+            c->app.skip_mask = skip_mask(c);
             const std::string err = gpu_ingest_append((void *)c->stream, &c->app, edges, m);
             if (err.empty()) return HB_OK;
             if (err.find("out of memory") == std::string::npos && err.find("too many records") == std::string::npos &&
@@ -1406,3 +1428,5 @@ int hb_store_harmonic_results(hb_ctx *c, const char *output, char *err, uint64_t
 #include "hb_api_debug.inc"
 
 } // extern "C"
+
+#include "hb_api_sample.inc"

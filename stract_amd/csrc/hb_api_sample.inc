@@ -1,0 +1,361 @@
+// hb_api_sample.inc - part of the hb_api.hip translation unit (included at its end; uses its hb_ctx and helpers).
+// hb_sampled_harmonic: ApproxHarmonic::build (crates/core/src/webgraph/centrality/approx_harmonic.rs:40-89) on the loaded graph.
+// The reference runs k single-source dijkstra_multi walks (shortest_path.rs:57-103, max_dist 7) over ForwardlinksQuery lookups
+// (query/forwardlink.rs:44-53); here all k walks run at once, 512 per batch, as one bit per source in the 64-byte rows of the
+// HyperBall plan (kernels: hb_sample.hip.h).  Definitions: include/hyperball.h.
+
+namespace {
+
+// dijkstra_multi returns when it POPS a cost above max_dist; by then the nodes one hop further have already been inserted into its
+// map (shortest_path.rs:85-95), and approx_harmonic.rs:62-70 counts every entry but the source.  So distances 1 .. max_dist + 1 count.
+uint32_t sample_levels(uint32_t max_dist) { return max_dist + 1; }
+
+// splitmix64 (Steele, Lea, Flood 2014): the sampler's generator
+uint64_t splitmix64_next(uint64_t &state)
+{
+    uint64_t z = (state += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// k = ceil(log2(N) / eps^2) (approx_harmonic.rs:49), with Rust's saturating float -> integer cast (NaN / negative -> 0)
+uint64_t sample_count_formula(uint64_t num_nodes, double eps)
+{
+    const double x = std::ceil(std::log2((double)num_nodes) / (eps * eps));
+    if (!(x > 0.0)) return 0;
+    if (x >= 18446744073709551615.0) return ~0ull;
+    return (uint64_t)x;
+}
+
+// the seeded sampler: candidates = nodes with an out-edge (page_edges().map(from).unique(): self links count), ascending NodeID;
+// min(k, candidates) distinct indices by Floyd's algorithm, index j = splitmix64() % (i + 1); the chosen sids, ascending
+int sample_sids(hb_ctx *c, uint64_t seed, uint64_t k, std::vector<uint32_t> *sids)
+{
+    const Plan &p = c->plan;
+    sids->clear();
+    if (!p.n || !k) return HB_OK;
+    auto &sm = c->smp;
+    if (!sm.cand_valid) { // once per loaded graph: one flag byte per node from the device, then the ascending list
+        std::vector<uint8_t> has_out(p.n);
+        uint8_t *d_flags = nullptr;
+        HB_HIP(hipMalloc((void **)&d_flags, p.n));
+        const unsigned blocks = (unsigned)std::min<uint64_t>((p.n_pad + 255) / 256, (uint64_t)c->num_cu * 8);
+        hipLaunchKernelGGL(hbk::sample_candidates_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t *)c->d_outdeg, (const uint32_t *)c->d_sid_of,
+                           p.n_pad, d_flags);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(has_out.data(), d_flags, p.n, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        (void)hipFree(d_flags);
+        if (e != hipSuccess) return fail(c, HB_ERR_HIP, std::string("hb_sampled_harmonic: candidate flags: ") + hipGetErrorString(e));
+        sm.cand.clear();
+        for (uint64_t s = 0; s < p.n; s++)
+            if (has_out[s]) sm.cand.push_back((uint32_t)s);
+        sm.cand_valid = true;
+    }
+    const std::vector<uint32_t> &cand = sm.cand;
+    const uint64_t C = cand.size(), K = std::min<uint64_t>(k, C);
+    // Floyd: K distinct indices out of C with K draws (a set of the taken ones: K <= 65535 is small next to C)
+    std::vector<uint64_t> taken;
+    taken.reserve(K);
+    auto has = [&](uint64_t x) { return std::find(taken.begin(), taken.end(), x) != taken.end(); };
+    std::vector<uint8_t> seen; // (membership by bytes when K is large)
+    const bool dense = K > 4096;
+    if (dense) seen.assign(C, 0);
+    uint64_t state = seed;
+    for (uint64_t i = C - K; i < C; i++) {
+        const uint64_t j = splitmix64_next(state) % (i + 1);
+        const bool j_taken = dense ? seen[j] != 0 : has(j);
+        const uint64_t pick = j_taken ? i : j;
+        taken.push_back(pick);
+        if (dense) seen[pick] = 1;
+    }
+    std::sort(taken.begin(), taken.end());
+    for (uint64_t i : taken) sids->push_back(cand[i]);
+    return HB_OK;
+}
+
+int sample_alloc(hb_ctx *c, uint32_t levels)
+{
+    auto &s = c->smp;
+    const uint64_t n_pad = c->plan.n_pad;
+    if (s.d_hist && s.levels != levels) {
+        (void)hipFree(s.d_hist);
+        s.d_hist = nullptr;
+    }
+    s.levels = 0;
+    if (!s.d_hist) HB_HIP(hipMalloc((void **)&s.d_hist, std::max<uint64_t>((uint64_t)levels * n_pad, 64) * sizeof(uint16_t)));
+    if (!s.d_cnt) HB_HIP(hipMalloc((void **)&s.d_cnt, (hbk::kSampleMaxLevels + 1) * 4 * sizeof(unsigned long long)));
+    if (!s.d_srcs) HB_HIP(hipMalloc((void **)&s.d_srcs, hbk::kSampleBatch * sizeof(uint32_t)));
+    if (!s.d_rows) HB_HIP(hipMalloc((void **)&s.d_rows, hbk::kSampleBatch * sizeof(uint32_t)));
+    if (!s.d_w) HB_HIP(hipMalloc((void **)&s.d_w, hbk::kSampleMaxLevels * sizeof(double)));
+    return HB_OK;
+}
+
+// launch shape of one level: a wave per 32-row word, grid-stride; XCD-affine groups for the first hub-chunk level (as hb_run's dense pass)
+void sample_launch(hb_ctx *c, hbk::SampleParams sp, bool real, int mode)
+{
+    const uint64_t words = (sp.row_hi - sp.row_lo + 31) / 32;
+    if (!words) return;
+    uint64_t blocks = std::min<uint64_t>((words + 3) / 4, (uint64_t)c->num_cu * 8);
+    if (sp.xcd_map) blocks = std::max<uint64_t>((blocks + 7) / 8 * 8, 8);
+    const dim3 grid((unsigned)blocks), blk(256);
+#define HB_SAMPLE_LAUNCH(R, M) hipLaunchKernelGGL((hbk::sample_level_kernel<R, M>), grid, blk, 0, c->stream, sp)
+    if (real) {
+        if (mode == hbk::kSampleDense) HB_SAMPLE_LAUNCH(true, hbk::kSampleDense);
+        else if (mode == hbk::kSampleBitmap) HB_SAMPLE_LAUNCH(true, hbk::kSampleBitmap);
+        else HB_SAMPLE_LAUNCH(true, hbk::kSampleSweep);
+    } else {
+        if (mode == hbk::kSampleDense) HB_SAMPLE_LAUNCH(false, hbk::kSampleDense);
+        else if (mode == hbk::kSampleBitmap) HB_SAMPLE_LAUNCH(false, hbk::kSampleBitmap);
+        else HB_SAMPLE_LAUNCH(false, hbk::kSampleSweep);
+    }
+#undef HB_SAMPLE_LAUNCH
+}
+
+int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats *st_out)
+{
+    const double t0 = now_ms();
+    hb_sample_options o{};
+    if (opt_in) std::memcpy(&o, opt_in, opt_in->struct_size ? std::min<size_t>(opt_in->struct_size, sizeof(o)) : sizeof(o));
+    if (multi_rank(c)) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: single rank only (world_size > 1)");
+    if (!c->loaded) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: no graph loaded");
+    if (c->rs.stream) HB_HIP(hipStreamSynchronize(c->rs.stream)); // (no result snapshot of an earlier run may still be landing in h_out)
+    c->rs.valid = false;
+    const uint32_t max_dist = o.max_dist ? o.max_dist : 7; // approx_harmonic.rs:62
+    if (max_dist > hbk::kSampleMaxLevels - 1) return fail(c, HB_ERR_LIMIT, "hb_sampled_harmonic: max_dist > 15");
+    const uint32_t D = sample_levels(max_dist);
+    const Plan &p = c->plan;
+    const uint64_t N = o.num_nodes ? o.num_nodes : p.n;
+    const double eps = o.epsilon != 0.0 ? o.epsilon : 0.3; // approx_harmonic.rs:29
+    if (o.sources && !o.source_count) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: sources given with source_count == 0");
+    const uint64_t k_req = o.samples ? o.samples : (o.sources ? o.source_count : sample_count_formula(N, eps));
+    if (k_req > 65535 || (o.sources && o.source_count > 65535)) return fail(c, HB_ERR_LIMIT, "hb_sampled_harmonic: more than 65535 sources");
+    if (p.n_pad % 32 || (p.level_begin.size() && p.level_begin.back() > p.n_pad + p.nv))
+        return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: unexpected plan layout");
+    for (uint64_t b : p.level_begin)
+        if (b % 32) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: level boundary not a multiple of 32 rows");
+    int rc = HB_OK;
+    {
+        hipError_t stale = hipGetLastError();
+        if (stale != hipSuccess) return fail(c, HB_ERR_HIP, std::string("stale HIP error before hb_sampled_harmonic: ") + hipGetErrorString(stale));
+    }
+    // the sources, as ascending sids
+    std::vector<uint32_t> sids;
+    if (o.sources) {
+        sids.reserve(o.source_count);
+        for (uint64_t i = 0; i < o.source_count; i++) {
+            const hb_u128 id = o.sources[i];
+            auto it = std::lower_bound(c->g.ids.begin(), c->g.ids.end(), id, u128_less);
+            if (it == c->g.ids.end() || !u128_eq(*it, id)) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: source " + std::to_string(i) + " is not a node of the graph");
+            sids.push_back((uint32_t)(it - c->g.ids.begin()));
+        }
+        std::sort(sids.begin(), sids.end());
+        if (std::adjacent_find(sids.begin(), sids.end()) != sids.end()) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: duplicate sources");
+    } else if ((rc = sample_sids(c, o.seed, k_req, &sids))) {
+        return rc;
+    }
+    // weights, f32 exactly as approx_harmonic.rs:57,69 writes them (norm from the REQUESTED sample count)
+    const float norm = (float)N / ((float)k_req * ((float)N - 1.0f));
+    double w[hbk::kSampleMaxLevels] = {0};
+    for (uint32_t d = 1; d <= D; d++) w[d - 1] = (double)((1.0f / (float)d) * norm);
+    if ((rc = sample_alloc(c, D))) return rc;
+    auto &sm = c->smp;
+    const uint64_t n_pad = p.n_pad, rows_total = p.n_pad + p.nv;
+    HB_HIP(hipMemsetAsync(sm.d_hist, 0, std::max<uint64_t>((uint64_t)D * n_pad, 64) * sizeof(uint16_t), c->stream));
+    HB_HIP(hipMemcpyAsync(sm.d_w, w, sizeof(w), hipMemcpyHostToDevice, c->stream));
+    // bitmap / sweep thresholds of hb_run (hb_api_pass.inc step_local): the A_t rule on the out-degree sum of the rows changed at d - 1
+    const uint32_t thr = c->opt.tune[2] ? c->opt.tune[2] : 50;
+    const uint64_t sparse_div = c->opt.tune[6] ? c->opt.tune[6] : 10;
+    const bool xcd_ok = p.xcd_groups == 8 && p.level_begin.size() > 1 && p.xcd_begin[0] == p.level_begin[0] && p.xcd_begin[8] == p.level_begin[1] &&
+                        std::all_of(p.xcd_begin, p.xcd_begin + 9, [](uint64_t b) { return b % 32 == 0; });
+    hb_sample_stats st{};
+    st.levels = D;
+    st.k_req = k_req;
+    st.sources = sids.size();
+    const uint64_t S = sids.size();
+    unsigned long long *h = c->h_counters; // (pinned words of the context; hb_run rewrites them before it reads them)
+    for (uint64_t b0 = 0; b0 < S; b0 += hbk::kSampleBatch) {
+        const uint32_t count = (uint32_t)std::min<uint64_t>(hbk::kSampleBatch, S - b0);
+        st.batches++;
+        // level -1 = all rows empty (both buffers, the partials, the changed bits); level 0 = every source's own bit
+        HB_HIP(hipMemsetAsync(c->d_regs[0], 0, n_pad * 64, c->stream));
+        HB_HIP(hipMemsetAsync(c->d_regs[1], 0, n_pad * 64, c->stream));
+        if (p.nv) HB_HIP(hipMemsetAsync(c->d_part, 0, p.nv * 64, c->stream));
+        HB_HIP(hipMemsetAsync(c->d_bits[0], 0, c->bits_words * 4, c->stream));
+        HB_HIP(hipMemsetAsync(c->d_bits[1], 0, c->bits_words * 4, c->stream));
+        HB_HIP(hipMemsetAsync(sm.d_cnt, 0, (hbk::kSampleMaxLevels + 1) * 4 * sizeof(unsigned long long), c->stream));
+        HB_HIP(hipMemcpyAsync(sm.d_srcs, sids.data() + b0, count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(hbk::sample_rows_of_kernel, dim3((count + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)sm.d_srcs, count,
+                           (const uint32_t *)c->d_dev_of, sm.d_rows); // (only the sources' rows: no n-entry map to the host)
+        hipLaunchKernelGGL(hbk::sample_seed_kernel, dim3((count * 4 + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)sm.d_rows, count, c->d_regs[0],
+                           c->d_bits[0], (const uint32_t *)c->d_outdeg, sm.d_cnt);
+        HB_HIP(hipGetLastError());
+        HB_HIP(hipMemcpyAsync(h, sm.d_cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HB_HIP(hipStreamSynchronize(c->stream));
+        uint64_t last_changed = h[0], last_active = h[1];
+        int cur = 0;
+        for (uint32_t d = 1; d <= D && last_changed; d++) {
+            const bool frontier = !(c->opt.flags & HB_FLAG_NO_FRONTIER) && (last_active * 100ull < (uint64_t)thr * c->m_global || thr > 100);
+            const bool sweep = frontier && c->sparse_ok && (last_active * sparse_div < c->m_global || c->opt.tune[6] == 1);
+            const int mode = sweep ? hbk::kSampleSweep : (frontier ? hbk::kSampleBitmap : hbk::kSampleDense);
+            hbk::SampleParams sp{};
+            sp.row_ptr = c->d_row_ptr;
+            sp.src = c->d_src;
+            sp.rd = c->d_regs[cur];
+            sp.wr = c->d_regs[cur ^ 1];
+            sp.part = c->d_part;
+            sp.bits_rd = c->d_bits[cur];
+            sp.bits_wr = c->d_bits[cur ^ 1];
+            sp.touch = c->d_touch;
+            sp.out_ptr = c->d_out_ptr;
+            sp.out_rows = c->d_out_rows;
+            sp.outdeg = c->d_outdeg;
+            sp.hist = sm.d_hist + (uint64_t)(d - 1) * n_pad;
+            sp.cnt = sm.d_cnt + 4 * d;
+            sp.n_pad = n_pad;
+            sp.rows_total = rows_total;
+            HB_HIP(hipEventRecord(c->ev[0], c->stream));
+            if (sweep) {
+                // the rows changed at d - 1 -> touch bits of their readers: hb_run's seed / expand kernels, unchanged (hb_sweep.hip.h)
+                hbk::SweepParams sw{};
+                sw.p.bits_rd = c->d_bits[cur];
+                sw.p.n_pad = n_pad;
+                sw.p.rows_total = rows_total;
+                sw.out_ptr = c->d_out_ptr;
+                sw.out_rows = c->d_out_rows;
+                sw.touch = c->d_touch;
+                sw.seeds = c->d_seeds;
+                sw.heavy = c->d_heavy;
+                sw.counts = c->d_sparse_counts;
+                sw.counts_next = c->d_sparse_counts + 2;
+                sw.guard = nullptr;
+                HB_HIP(hipMemsetAsync(c->d_sparse_counts, 0, 4 * sizeof(unsigned int), c->stream));
+                const uint64_t real_words = n_pad / 32;
+                const unsigned sblocks = (unsigned)std::min<uint64_t>(std::max<uint64_t>(real_words / 256, 1), (uint64_t)c->num_cu * 4);
+                const unsigned wblocks = (unsigned)c->num_cu * 4;
+                if (last_changed <= 4096) {
+                    hipLaunchKernelGGL(hbk::sweep_seed_small_kernel, dim3(sblocks), dim3(256), 0, c->stream, sw);
+                } else {
+                    hipLaunchKernelGGL(hbk::sweep_collect_kernel, dim3(sblocks), dim3(256), 0, c->stream, sw);
+                    hipLaunchKernelGGL(hbk::sweep_expand_kernel, dim3(wblocks), dim3(256), 0, c->stream, sw);
+                    hipLaunchKernelGGL(hbk::sweep_expand_heavy_kernel, dim3(wblocks), dim3(256), 0, c->stream, sw);
+                }
+                HB_HIP(hipGetLastError());
+            }
+            for (size_t l = 0; l + 1 < p.level_begin.size(); l++) { // virtual levels: partials of level d from the rows of level d - 1
+                sp.row_lo = p.level_begin[l];
+                sp.row_hi = p.level_begin[l + 1];
+                sp.xcd_map = (l == 0 && xcd_ok && mode == hbk::kSampleDense) ? 1 : 0;
+                for (int x = 0; x < 8; x++) {
+                    sp.xcd_lo[x] = p.xcd_begin[x];
+                    sp.xcd_hi[x] = p.xcd_begin[x + 1];
+                }
+                sample_launch(c, sp, false, mode);
+            }
+            sp.xcd_map = 0;
+            sp.row_lo = 0;
+            sp.row_hi = n_pad;
+            sample_launch(c, sp, true, mode);
+            HB_HIP(hipGetLastError());
+            HB_HIP(hipEventRecord(c->ev[1], c->stream));
+            HB_HIP(hipMemcpyAsync(h, sp.cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+            HB_HIP(hipStreamSynchronize(c->stream));
+            float ms = 0.f;
+            HB_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+            st.level_changed[d - 1] += h[0];
+            st.level_modes[d - 1] |= 1u << mode;
+            st.level_ms[d - 1] += ms;
+            last_changed = h[0]; // no node row grew: nothing can change at d + 1 either (the batch has converged)
+            last_active = h[1];
+            cur ^= 1;
+        }
+    }
+    // the result image
+    if (c->out_len) {
+        unsigned long long *cnt = sm.d_cnt; // (slot 0 is free again)
+        HB_HIP(hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned long long), c->stream));
+        const unsigned blocks = (unsigned)std::min<uint64_t>((n_pad + 255) / 256, (uint64_t)c->num_cu * 8);
+        hipLaunchKernelGGL(hbk::sample_result_kernel, dim3(std::max(blocks, 1u)), dim3(256), 0, c->stream, (const uint16_t *)sm.d_hist, D, n_pad,
+                           (const double *)sm.d_w, (const uint32_t *)c->d_cid_of, c->d_out, cnt);
+        HB_HIP(hipGetLastError());
+        HB_HIP(hipMemcpyAsync(c->h_out, c->d_out, c->out_len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HB_HIP(hipMemcpyAsync(h, cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HB_HIP(hipStreamSynchronize(c->stream));
+        c->res_count = h[0];
+    } else {
+        c->res_count = 0;
+    }
+    sm.levels = D;
+    c->begun = false; // (the HyperBall state is gone: hb_step needs a new hb_begin)
+    c->finished = true;
+    st.results = c->res_count;
+    st.ms_total = now_ms() - t0;
+    if (st_out) {
+        const size_t sz = st_out->struct_size ? std::min<size_t>(st_out->struct_size, sizeof(st)) : sizeof(st);
+        st.struct_size = (uint32_t)sz;
+        std::memcpy(st_out, &st, sz);
+    }
+    return HB_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int hb_sampled_harmonic(hb_ctx *c, const hb_sample_options *opt, hb_sample_stats *stats)
+{
+    return guarded(c, [&]() -> int {
+        if (!c) return HB_ERR_INVALID;
+        int rc = set_device(c);
+        if (rc) return rc;
+        // between hb_begin and hb_finish the HyperBall state (and a result snapshot on its way to h_out) belongs to that run
+        if (c->begun && !c->finished) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: a HyperBall run is in progress (hb_begin without hb_finish)");
+        c->finished = false; // (a refusal leaves no result behind)
+        c->smp.levels = 0;
+        return sampled_harmonic(c, opt, stats);
+    });
+}
+
+int hb_sample_sources(hb_ctx *c, uint64_t seed, uint64_t k, hb_u128 *out, uint64_t *written)
+{
+    return guarded(c, [&]() -> int {
+        if (!c || !written) return c ? fail(c, HB_ERR_INVALID, "hb_sample_sources: written == NULL") : HB_ERR_INVALID;
+        if (!c->loaded) return fail(c, HB_ERR_INVALID, "hb_sample_sources: no graph loaded");
+        int rc = set_device(c);
+        if (rc) return rc;
+        std::vector<uint32_t> sids;
+        if ((rc = sample_sids(c, seed, k, &sids))) return rc;
+        *written = sids.size();
+        if (out)
+            for (size_t i = 0; i < sids.size(); i++) out[i] = c->g.ids[sids[i]];
+        return HB_OK;
+    });
+}
+
+int hb_debug_sample_histogram(hb_ctx *c, uint16_t *out)
+{
+    return guarded(c, [&]() -> int {
+        if (!c || !out) return HB_ERR_INVALID;
+        if (!c->finished || !c->smp.levels) return fail(c, HB_ERR_INVALID, "hb_debug_sample_histogram: no sampled result (call hb_sampled_harmonic)");
+        int rc = set_device(c);
+        if (rc) return rc;
+        const Plan &p = c->plan;
+        const uint32_t D = c->smp.levels;
+        std::vector<uint16_t> hist((size_t)D * p.n_pad);
+        std::vector<uint32_t> sid_of(p.n_pad);
+        if (p.n_pad) {
+            HB_HIP(hipMemcpyAsync(hist.data(), c->smp.d_hist, hist.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+            HB_HIP(hipMemcpyAsync(sid_of.data(), c->d_sid_of, p.n_pad * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HB_HIP(hipStreamSynchronize(c->stream));
+        }
+        for (uint64_t r = 0; r < p.n_pad; r++) {
+            const uint32_t sid = sid_of[r];
+            if (sid == kNone) continue;
+            for (uint32_t d = 0; d < D; d++) out[(uint64_t)sid * D + d] = hist[(uint64_t)d * p.n_pad + r];
+        }
+        return HB_OK;
+    });
+}
+
+} // extern "C"

@@ -157,7 +157,7 @@ struct KeyPos {
 } // namespace
 
 std::string ingest_edges(const hb_u128 *node_ids, uint64_t n_in, const hb_edge *edges, uint64_t m,
-                         DenseGraph *out)
+                         DenseGraph *out, uint64_t skip_mask)
 {
     out->ids.clear();
     out->row_ptr.clear();
@@ -216,7 +216,7 @@ std::string ingest_edges(const hb_u128 *node_ids, uint64_t n_in, const hb_edge *
         uint64_t j = i + 1;
         while (j < m && recs[j].key == key) j++;
         m_unique++;
-        if ((edges[recs[i].pos].rel_flags & HB_SKIPPED_REL_MASK) == 0) {
+        if ((edges[recs[i].pos].rel_flags & skip_mask) == 0) { // (skip_mask = 0: HB_FLAG_ALL_RELS)
             src.push_back((uint32_t)key);
             row_ptr[(key >> 32) + 1]++;
         }

@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void table_clear_kernel(uint32_t *pids, uint64
 }
 
 // one thread per record of the slab: both endpoints -> pids, (from pid | to pid << 32) and the "flagged" byte
-__global__ __launch_bounds__(256) void insert_kernel(const hb_edge *slab, uint64_t count, uint64_t base, Table t, uint64_t *pair, uint8_t *bad)
+__global__ __launch_bounds__(256) void insert_kernel(const hb_edge *slab, uint64_t count, uint64_t base, Table t, uint64_t *pair, uint8_t *bad, uint64_t skip_mask)
 {
     HB_GRID_STRIDE(i, count)
     {
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void insert_kernel(const hb_edge *slab, uint64
         const uint32_t f = table_get(t, make_key(e.from), kEmpty);
         const uint32_t to = table_get(t, make_key(e.to), kEmpty);
         pair[base + i] = (uint64_t)f | ((uint64_t)to << 32);
-        bad[base + i] = (e.rel_flags & HB_SKIPPED_REL_MASK) ? 1 : 0;
+        bad[base + i] = (e.rel_flags & skip_mask) ? 1 : 0;
     }
 }
 
@@ -532,7 +532,7 @@ std::string gpu_ingest_append(void *stream_v, IngestStream *st, const hb_edge *e
         IG_HIP(hipEventRecord(evs.copied[b], stream));
         IG_HIP(hipStreamWaitEvent(kstream, evs.copied[b], 0));
         hipLaunchKernelGGL(insert_kernel, dim3(grid_for(cnt)), dim3(256), 0, kstream, (const hb_edge *)st->d_slab[b], cnt, c.count, table_of(st), c.d_pair,
-                           c.d_bad);
+                           c.d_bad, st->skip_mask);
         IG_HIP(hipGetLastError());
         IG_HIP(hipMemcpyAsync(&st->h_counter[1 + b], st->d_counter, sizeof(unsigned long long), hipMemcpyDeviceToHost, kstream));
         IG_HIP(hipEventRecord(evs.consumed[b], kstream));
@@ -599,11 +599,12 @@ std::string gpu_ingest_spill(void *stream_v, IngestStream *st, std::vector<hb_ed
 }
 
 std::string gpu_ingest_edges(void *stream_v, const hb_u128 *node_ids, uint64_t n_in, const hb_edge *edges, uint64_t m,
-                             DenseGraph *out, DeviceCsr *keep, uint64_t *peak_bytes)
+                             DenseGraph *out, DeviceCsr *keep, uint64_t *peak_bytes, uint64_t skip_mask)
 {
     if (keep) *keep = DeviceCsr{};
     if (m && !edges) return "edges == NULL with m > 0";
     IngestStream st;
+    st.skip_mask = skip_mask;
     std::string e = gpu_ingest_append(stream_v, &st, edges, m);
     if (!e.empty()) {
         st.free_all();

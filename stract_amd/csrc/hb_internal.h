@@ -153,8 +153,9 @@ struct PlanTune {
 // --- hb_host.cpp ---------------------------------------------------------------------
 // Reference ingest semantics: node set (store.rs:338-357), first-occurrence dedup
 // (store.rs:313), then rel-flag filter (harmonic.rs:131).  Returns "" or an error text.
+// skip_mask: the rel-flag bits that drop a record (HB_SKIPPED_REL_MASK; 0 with HB_FLAG_ALL_RELS)
 std::string ingest_edges(const hb_u128 *node_ids, uint64_t n, const hb_edge *edges, uint64_t m,
-                         DenseGraph *out);
+                         DenseGraph *out, uint64_t skip_mask = HB_SKIPPED_REL_MASK);
 void keep_owned_rows(DenseGraph *g, uint64_t world, uint64_t rank);
 // HB_FLAG_REFERENCE_TAIL: page-level records -> keys (source device row << 32 | target device row) of the records
 // between two host nodes that pass the rel filter; all keys -> CSR by source
@@ -175,7 +176,8 @@ std::string build_tail_csr(std::vector<uint64_t> *keys, uint64_t n_pad, std::vec
 // keep != NULL: the CSR stays on the device (returned in *keep, owned by the caller) and out->row_ptr / out->src
 // are only filled for small graphs (m_eff <= kKeepHostGraph, for hb_debug_copy_graph)
 std::string gpu_ingest_edges(void *stream, const hb_u128 *node_ids, uint64_t n, const hb_edge *edges, uint64_t m,
-                             DenseGraph *out, struct DeviceCsr *keep = nullptr, uint64_t *peak_bytes = nullptr);
+                             DenseGraph *out, struct DeviceCsr *keep = nullptr, uint64_t *peak_bytes = nullptr,
+                             uint64_t skip_mask = HB_SKIPPED_REL_MASK);
 constexpr uint64_t kKeepHostGraph = 1ull << 26;
 // the two halves of gpu_ingest_edges, for streamed input (hb_append_edges): every endpoint of a batch goes through a device
 // hash table (NodeID -> 32-bit provisional id) as the batch arrives, a record is kept as (from pid, to pid) + 1 flag byte
@@ -208,6 +210,7 @@ struct IngestStream {
     uint64_t max_records = 0;   // refuse to hold this many records or more ("too many records")
     uint64_t max_bytes = 0;     // treat chunk / table memory beyond this as a failed allocation ("out of memory")
     uint64_t chunk_records = 0; // records per chunk (default 2^27)
+    uint64_t skip_mask = HB_SKIPPED_REL_MASK; // rel-flag bits that mark a record "bad" (0 with HB_FLAG_ALL_RELS: every record is an edge)
     void free_all();
 };
 std::string gpu_ingest_append(void *stream, IngestStream *st, const hb_edge *edges, uint64_t m);

@@ -746,7 +746,22 @@ int hb_load_webgraph(hb_ctx *ctx, const char *edges_dir, uint32_t flags)
     // HBW_VERIFY_CRC: the files are NOT checked in a pass of their own here (hbw_open does that for its direct users) - the
     // check runs on a second thread WHILE the records stream to the device (the column bytes are read once, the cores idle
     // while the device reduces); its verdict is taken before hb_finalize, a mismatch discards what was appended
-    int rc = hbw_open(edges_dir, flags & ~(uint32_t)HBW_VERIFY_CRC, &raw);
+    const bool page_graph = (flags & HBW_PAGE_GRAPH) != 0;
+    if (page_graph) {
+        if (flags & HBW_PAGE_IDS) {
+            g_open_error = "hb_load_webgraph: HBW_PAGE_GRAPH and HBW_PAGE_IDS exclude each other (the page graph IS the page-level records)";
+            return HB_ERR_INVALID;
+        }
+        // an HB_FLAG_REFERENCE_TAIL context accepts (or asks for a loaded graph before) tail records; any other refuses them
+        const int rc0 = hb_load_tail_edges(ctx, nullptr, 0);
+        const char *msg = hb_last_error(ctx);
+        if (rc0 == HB_OK || !msg || !std::strstr(msg, "create the context with HB_FLAG_REFERENCE_TAIL")) {
+            g_open_error = "hb_load_webgraph: HBW_PAGE_GRAPH on an HB_FLAG_REFERENCE_TAIL context (the tail mode is host-level)";
+            return HB_ERR_INVALID;
+        }
+    }
+    // (the page graph needs the page-level id columns located)
+    int rc = hbw_open(edges_dir, (flags & ~(uint32_t)(HBW_VERIFY_CRC | HBW_PAGE_GRAPH)) | (page_graph ? HBW_PAGE_IDS : 0u), &raw);
     if (rc != HB_OK) return rc; // message: hbw_last_error(NULL)
     const double s_open = since(t_begin);
     // closed on every path, exceptions included - on a thread of its own: unmapping a 100 GB store takes seconds (3.3 of 9.4 s
@@ -838,7 +853,7 @@ int hb_load_webgraph(hb_ctx *ctx, const char *edges_dir, uint32_t flags)
                 }
                 const uint64_t at = k * slab, n = std::min(slab, r->total - at);
                 const auto t_g = std::chrono::steady_clock::now();
-                const int rc = hbw_read_host_edges(r, at, n, pin.p[k & 1]);
+                const int rc = page_graph ? hbw_read_page_edges(r, at, n, pin.p[k & 1]) : hbw_read_host_edges(r, at, n, pin.p[k & 1]);
                 s_gather += since(t_g);
                 {
                     std::lock_guard<std::mutex> lk(mu);
@@ -899,7 +914,7 @@ int hb_load_webgraph(hb_ctx *ctx, const char *edges_dir, uint32_t flags)
             return HB_ERR_INVALID;
         }
         const auto t_f = std::chrono::steady_clock::now();
-        if (rc2 == HB_OK) rc2 = hb_finalize(ctx, nullptr, 0); // node set = all endpoints = host_nodes() (store.rs:338-357)
+        if (rc2 == HB_OK) rc2 = hb_finalize(ctx, nullptr, 0); // node set = all endpoints = host_nodes() (store.rs:338-357); page_nodes() with HBW_PAGE_GRAPH
         if (trace)
             std::fprintf(stderr, "[hb webgraph] %llu records in %zu segments: open %.3f s; %llu slabs: reader thread gathering %.3f s, this thread waiting "
                                  "for a slab %.3f s, in hb_append_edges %.3f s; CRC-32 of every file on a second thread %.3f s; hb_finalize %.3f s; total "

@@ -8,6 +8,7 @@ from . import _lib
 
 HBW_VERIFY_CRC = 0x1
 HBW_PAGE_IDS = 0x2
+HBW_PAGE_GRAPH = 0x4
 
 
 class EdgeStoreReader:
@@ -70,10 +71,11 @@ class EdgeStoreReader:
         return out
 
 
-def load_webgraph(ctx, edges_dir, verify_crc=False, page_ids=False):
+def load_webgraph(ctx, edges_dir, verify_crc=False, page_ids=False, page_graph=False):
     """hb_load_webgraph: stream the store into a Context (then ctx.run()).  page_ids: also the page-level records the
-    reference's tail mode follows (ctx created with HB_FLAG_REFERENCE_TAIL)."""
-    flags = (HBW_VERIFY_CRC if verify_crc else 0) | (HBW_PAGE_IDS if page_ids else 0)
+    reference's tail mode follows (ctx created with HB_FLAG_REFERENCE_TAIL).  page_graph: the page-level records are the
+    graph (then ctx.sampled_harmonic(); ctx created with HB_FLAG_ALL_RELS)."""
+    flags = (HBW_VERIFY_CRC if verify_crc else 0) | (HBW_PAGE_IDS if page_ids else 0) | (HBW_PAGE_GRAPH if page_graph else 0)
     rc = ctx.lib.hb_load_webgraph(ctx.h, edges_dir.encode(), flags)
     if rc != _lib.HB_OK:
         msg = (ctx.lib.hb_last_error(ctx.h) or b"").decode() or (ctx.lib.hbw_last_error(None) or b"").decode()
