@@ -4,6 +4,15 @@
 Contract: `python bench.py --gpus N --steps K --warmup W` (for N > 1 launched by
 torch.distributed.run, one rank per GPU).  Prints ONE JSON line on rank 0.
 
+  plain run = what the headline needs and nothing else: generate + load the graph, W warm-up runs, K timed runs, --dump-outputs,
+              the line (value, ms_per_step, first_run_ms, roofline and detail from the timed runs' own statistics).  At N = 1 with
+              record input the graph and its record stream are generated on the GPU (stract_amd/synth.py DeviceRmatGraph: the
+              graph hb_synth.cpp builds, the same records) and released before the warm-up; the host generator takes over
+              minutes at C4 (configs with a tail, --input dense and --verify still use it).
+  --full    = everything else as well: the CPU baseline and parity, the end-to-end chain, the C3 (or C4) leg, the N > 1
+              partition legs (all described below), with the host generator as before.  Their options (--c3-leg, --c4-leg,
+              --end-to-end, --partition both, --parity, --cpu-seconds) act only with --full.
+
   step      = one complete HyperBall run over the resident graph: initialize + every pass of
               the loop harmonic.rs:237-280 until a pass changes nothing (T passes, the last
               one being the reference's no-change pass) + normalize + result download.
@@ -20,15 +29,15 @@ torch.distributed.run, one rank per GPU).  Prints ONE JSON line on rank 0.
               holds no torch and the library runs on /opt/rocm's HIP runtime.
   N > 1     = the same graph partitioned over the ranks (strong scaling), one RCCL collective of
               the counters per pass.  `value` = the north-star decomposition: edge
-              partition + ncclAllReduce(max, u8); with --partition both (default) its changed-only form, the
+              partition + ncclAllReduce(max, u8); with --full and --partition both (default) its changed-only form, the
               destination partition (+ ncclAllGather) and its changed-only variant run as extra legs under
               detail.partitions, each with GTEPS, ms_collective, wire bytes and a same-result field.
               --collectives host-staged: the same N > 1 path as a FUNCTIONAL run where N GPUs do not exist (gloo, host-staged
               exchanges through hb_set_collectives, ranks share the devices there are); the line says so, its numbers are no measurement.
-  c3 leg    = with the default config at N = 1 the line also carries detail.c3: BASELINE configs[2] (10M hosts / 200M edges, the
+  c3 leg    = --full, default config, N = 1: the line also carries detail.c3: BASELINE configs[2] (10M hosts / 200M edges, the
               headline of rounds 1-4) - GTEPS, roofline fractions, parity, its own end-to-end chain (~1.5 min, a child process).
               (--c4-leg on: the same for configs[3] under detail.c4 when another config is the main one.)
-  end to end= N = 1, record input (default): detail.end_to_end (and detail.c4.end_to_end) = the reference command's whole chain
+  end to end= --full, N = 1, record input: detail.end_to_end (and detail.c4.end_to_end) = the reference command's whole chain
               on the same graph (entrypoint/centrality.rs:41-71): an on-disk edge store (written by the harness, untimed) ->
               hb_load_webgraph (CRC-32 checked, native column reader, GPU ingest) -> hb_run -> hb_store_harmonic_results (the result
               list, the ranks and the key order of both speedy_kv databases from the device, then the files), seconds per stage, records/s of the load, entries/s of the
@@ -42,7 +51,7 @@ torch.distributed.run, one rank per GPU).  Prints ONE JSON line on rank 0.
               `dominant_kernel` = the level-1 hub-chunk launch alone: 68 B x the REAL edges it
               gathers (no partial-row traffic booked), over its own event-timed duration.
               `whole_loop` = sum_t B_t / t_loop with B_t = 68*A_t + 4*(m-A_t) + 184*V_t + 8n + n/4.
-  parity    = every line carries `parity_bit_exact`.  N = 1: the oracle always runs to CONVERGENCE (C4: ~10 passes, ~1 min on the
+  parity    = every --full line carries `parity_bit_exact` (null in a plain line).  N = 1: the oracle always runs to CONVERGENCE (C4: ~10 passes, ~1 min on the
               box's host cores) and the final (NodeID, f64) list is compared - the CPU-baseline SAMPLE is the first passes that fit
               --cpu-seconds, the passes after that are parity work, not timed.  N > 1 (and --parity budget): final list when the CPU
               run converges inside its budget, else an order-independent checksum of all registers + Kahan state after the last
@@ -55,7 +64,7 @@ torch.distributed.run, one rank per GPU).  Prints ONE JSON line on rank 0.
               and the review rightly called them nets under a broken boundary).  Only the C4 leg is a child process (the
               2 B-edge generator needs tens of GB of host memory); its failure is reported in detail.c4.error AND makes
               the exit code non-zero.  N > 1: a watchdog thread around the extra partition legs (--legs-timeout).
-  cpu_baseline = the CPU oracle's dense OpenMP port of the reference arithmetic, timed on
+  cpu_baseline = --full: the CPU oracle's dense OpenMP port of the reference arithmetic, timed on
               this box's host cores on the same graph for a bounded number of passes; the GPU time
               of the SAME passes is reported next to it (like for like); `cpu_faithful` = the
               single-thread structure-faithful form on C1.
@@ -86,6 +95,9 @@ DUMP_SEED = 0x5712AC7
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU baseline + parity, the end-to-end chain, the other BASELINE "
+                         "config's leg, the N > 1 partition legs (a plain run does only setup, warm-up, timed steps, outputs, the line)")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default=os.environ.get("HB_BENCH_CONFIG", "C4"), help="C1|C2|C3|C4|C5|LT or scale:m (default C4 = BASELINE configs[3])")
@@ -136,7 +148,14 @@ def parse():
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1 (the number of timed runs)")
+    if not a.full and "on" in (a.c3_leg, a.c4_leg, a.end_to_end):
+        ap.error("--c3-leg on, --c4-leg on and --end-to-end on need --full")
     return a
+
+
+def lean_input(a, world):
+    """A plain N = 1 record-input run generates its graph on the GPU (what it needs of it: n, m, the record stream)."""
+    return world == 1 and not a.full and not a.verify and a.input != "dense"
 
 
 def pass_bytes(ps, n, m_eff, rows_with_in):
@@ -553,7 +572,8 @@ def main():
             g, scale, label = synth.make_config(a.config)
         os.environ.pop("HB_SYNTH_CACHE", None)
     else:
-        g, scale, label = synth.make_config(a.config)
+        made = synth.make_config_on_device(a.config, device) if lean_input(a, world) else None
+        g, scale, label = made if made is not None else synth.make_config(a.config)
     t_gen = time.perf_counter() - t0
     n, m_eff = int(g.n), int(g.m)
     tune = tuple(int(x) for x in a.tune.split(",")) if a.tune else ()
@@ -586,6 +606,8 @@ def main():
         else:
             ctx.load_dense(g.ids, g.row_ptr, g.src)
         info["s_load"] = round(time.perf_counter() - t0, 2)
+        if isinstance(g, synth.DeviceRmatGraph):
+            g.close()  # (its device memory: nothing after the load reads the generated graph)
         live_ctx[0] = ctx
         return ctx, measure(ctx, a.steps, a.warmup, barrier, td, torch), info
 
@@ -602,7 +624,7 @@ def main():
     # ---- parity + CPU baseline (rank 0 computes; a checksum rerun, if needed, is collective)
     cpu, parity = None, None
     cores_used = [None]
-    if a.cpu_seconds > 0 or a.verify:
+    if (a.full and a.cpu_seconds > 0) or a.verify:
         cpu, parity = cpu_and_parity(a, g, ctx, td, rank, world, passes, ids, vals, last_pass_stats, cores_out=cores_used)
 
     steps = max(a.steps, 1)
@@ -661,7 +683,7 @@ def main():
     ctx.close()
 
     # ---- N > 1: the other decompositions, same graph, same K / W (extra legs; `value` stays the edge partition)
-    if world > 1 and a.partition == "both":
+    if a.full and world > 1 and a.partition == "both":
         # The main line must survive the extra legs: a rank that fails inside one leaves the others waiting in a collective,
         # and a blocked ctypes call cannot be interrupted from Python.  A watchdog THREAD prints the line as it stands and ends
         # every rank once the legs exceed their allowance.
@@ -712,7 +734,7 @@ def main():
             dog.join()  # a leg failed here: wait for the watchdog (it prints on rank 0 and ends the process)
 
     # ---- the whole reference command on the same graph: store -> load -> run -> ranks -> store_harmonic
-    want_e2e = world == 1 and rank == 0 and (a.end_to_end == "on" or (a.end_to_end == "auto" and a.input == "records" and a.config in ("C3", "C4", "LT")
+    want_e2e = a.full and world == 1 and rank == 0 and (a.end_to_end == "on" or (a.end_to_end == "auto" and a.input == "records" and a.config in ("C3", "C4", "LT")
                                                           and not a.flags and not a.tune and not a.chunk))
     if want_e2e:
         out["detail"]["end_to_end"] = end_to_end(a, g, ref_sig, passes)
@@ -724,9 +746,9 @@ def main():
     # config with --c4-leg on)
     plain = not a.flags and not a.tune and not a.chunk
     legs_wanted = []
-    if world == 1 and a.config != "C3" and (a.c3_leg == "on" or (a.c3_leg == "auto" and a.config == "C4" and plain)):
+    if a.full and world == 1 and a.config != "C3" and (a.c3_leg == "on" or (a.c3_leg == "auto" and a.config == "C4" and plain)):
         legs_wanted.append("C3")
-    if world == 1 and a.config != "C4" and a.c4_leg == "on":
+    if a.full and world == 1 and a.config != "C4" and a.c4_leg == "on":
         legs_wanted.append("C4")
     if legs_wanted:
         g.close()
@@ -833,7 +855,7 @@ def sub_leg(a, config):
     runs); `--c4-leg on` appends C4 (1 + 2 runs) to another main config.  Runs as a CHILD process (this script with --config ...):
     the main process has just released a graph of tens of GB, and a child that is killed must not take the main line down with it."""
     runs = ["--steps", "20", "--warmup", "5"] if config == "C3" else ["--steps", "2", "--warmup", "1"]
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", config] + runs + ["--c4-leg", "off", "--c3-leg", "off", "--parity", a.parity,
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--config", config] + runs + ["--c4-leg", "off", "--c3-leg", "off", "--parity", a.parity,
            "--cpu-seconds", str(a.cpu_seconds), "--input", a.input, "--end-to-end", a.end_to_end] + (["--verify"] if a.verify else []) + (
                ["--e2e-dir", a.e2e_dir] if a.e2e_dir else [])
     env = dict(os.environ, HB_BENCH_CHILD="1")  # measured in the child itself, not under another supervisor

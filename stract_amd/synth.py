@@ -115,6 +115,82 @@ class RmatGraph:
             pass
 
 
+GPU_LIB_PATH = os.path.join(_HERE, "lib", "libhb_synth_gpu.so")
+_gpu_lib = None
+
+
+def _load_gpu():
+    global _gpu_lib
+    if _gpu_lib is None:
+        L = ctypes.CDLL(GPU_LIB_PATH)
+        L.hbg_last_error.restype = ctypes.c_char_p
+        L.hbg_rmat.restype = ctypes.c_void_p
+        L.hbg_rmat.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int]
+        L.hbg_free.argtypes = [ctypes.c_void_p]
+        for f in ("hbg_num_nodes", "hbg_num_edges", "hbg_raw_drawn"):
+            getattr(L, f).restype = ctypes.c_uint64
+            getattr(L, f).argtypes = [ctypes.c_void_p]
+        L.hbg_stream_len.restype = ctypes.c_uint64
+        L.hbg_stream_len.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        L.hbg_copy.restype = ctypes.c_int
+        L.hbg_copy.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.hbg_stream_fill.restype = ctypes.c_uint64
+        L.hbg_stream_fill.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+        _gpu_lib = L
+    return _gpu_lib
+
+
+class DeviceRmatGraph:
+    """The graph RmatGraph(scale, m_target, seed) builds, generated on the GPU and kept there (stract_amd/csrc/hb_synth_gpu.hip):
+    n, m and the record stream (stream_len / stream_fill, the same records) - what a record-input run needs.  The host
+    arrays are downloaded on request (host_arrays), for the tests that compare both generators.  Plain R-MAT only."""
+
+    def __init__(self, scale, m_target, seed=SEED, device=0):
+        L = _load_gpu()
+        self._g = L.hbg_rmat(scale, m_target, seed, device)
+        if not self._g:
+            raise RuntimeError("hbg_rmat failed: %s" % L.hbg_last_error().decode())
+        self.scale = scale
+        self.n = L.hbg_num_nodes(self._g)
+        self.m = L.hbg_num_edges(self._g)
+        self.raw_drawn = L.hbg_raw_drawn(self._g)
+
+    def stream_len(self, salt=0):
+        return int(_load_gpu().hbg_stream_len(self._g, salt))
+
+    def stream_fill(self, out, first, salt=0):
+        """Fills out[:k] (EDGE records, any writable contiguous host buffer; page-locked ones copy fastest) with records first..
+        of the stream; returns k."""
+        assert out.dtype == EDGE and out.flags["C_CONTIGUOUS"]
+        L = _load_gpu()
+        k = L.hbg_stream_fill(self._g, salt, first, len(out), out.ctypes.data)
+        if k == 0xFFFFFFFFFFFFFFFF:
+            raise RuntimeError("hbg_stream_fill failed: %s" % L.hbg_last_error().decode())
+        return int(k)
+
+    def host_arrays(self):
+        """(ids, row_ptr, src) as RmatGraph holds them."""
+        L = _load_gpu()
+        ids = np.empty(self.n, U128)
+        row_ptr = np.empty(self.n + 1, np.uint64)
+        edges = np.empty(self.m, np.uint64)
+        for what, arr in ((0, ids), (1, row_ptr), (2, edges)):
+            if L.hbg_copy(self._g, what, arr.ctypes.data):
+                raise RuntimeError("hbg_copy failed")
+        return ids, row_ptr, (edges & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+
+    def close(self):
+        if self._g:
+            _load_gpu().hbg_free(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # BASELINE.json configs: id-space scale and unique-edge target chosen so that the
 # TOUCHED host count lands at the config's host count (SURVEY.md §8 preamble).
 CONFIGS = {
@@ -174,3 +250,18 @@ def make_config(name):
     tail = tuple(parts[2:5]) if len(parts) >= 5 else None
     label = "R-MAT scale %d / %d edges%s" % (scale, m_target, " + tail %s" % (tail,) if tail else "")
     return RmatGraph(scale, m_target, tail=tail), scale, label
+
+
+def make_config_on_device(name, device=0):
+    """make_config's graph generated on the GPU (DeviceRmatGraph), or None for a config with a tail (host generator only)."""
+    if name in CONFIGS:
+        cfg = CONFIGS[name]
+        if cfg.get("tail"):
+            return None
+        label = "%s (R-MAT scale %d, a,b,c,d=.57,.19,.19,.05, seed 0x5712AC7)" % (cfg["label"], cfg["scale"])
+        return DeviceRmatGraph(cfg["scale"], cfg["m"], device=device), cfg["scale"], label
+    parts = [int(x) for x in name.split(":")]
+    if len(parts) >= 5:
+        return None
+    scale, m_target = parts[0], parts[1]
+    return DeviceRmatGraph(scale, m_target, device=device), scale, "R-MAT scale %d / %d edges" % (scale, m_target)

@@ -91,7 +91,7 @@ def test_bench_multi_rank_control_flow_on_the_interpreter(simt_lib, tmp_path):
     # [r6] launched the way the driver launches `--gpus 1`: plain `python bench.py --gpus 2` with NO launcher - the script must re-execute
     # itself under torch.distributed.run (one rank per GPU, rendezvous on 127.0.0.1, a free port) instead of exiting (VERDICT r5 #3a)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--config", "C1", "--collectives", "host-staged",
-                        "--cpu-seconds", "5"], capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=1500)
+                        "--cpu-seconds", "5", "--full"], capture_output=True, text=True, env=env, cwd=str(tmp_path), timeout=1500)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-1500:] + r.stderr[-3000:]
     assert "re-executing as" in r.stderr and "torch.distributed.run" in r.stderr, r.stderr[-1500:]
