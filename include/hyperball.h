@@ -348,6 +348,50 @@ int hb_sample_sources(hb_ctx *ctx, uint64_t seed, uint64_t k, hb_u128 *out, uint
 /* c_d(v) of the last hb_sampled_harmonic: out[v * D + d - 1], v in ascending NodeID order (n x D entries, D = stats.levels). */
 int hb_debug_sample_histogram(hb_ctx *ctx, uint16_t *out);
 
+/* ---- exact shortest-path distances: ShortestPaths (webgraph/shortest_path.rs:26-227) ---------------------------------------------- */
+/* dijkstra_multi (shortest_path.rs:57-103) with unit edge costs = one breadth-first search from a set of sources, over the loaded
+ * graph (host- or page-level; HB_FLAG_ALL_RELS contexts = the ShortestPaths trait, default contexts = the AMPC shortest-path job,
+ * which drops SKIPPED_REL edges).  Every source has distance 0, an edge adds 1, and a u8 holds the distance: a node is only inserted
+ * while cost + 1 < 255, so the largest distance reported is 254 and everything further is absent.  With HB_DIST_WITH_MAX the nodes at
+ * distance <= max_dist are expanded (the reference returns when it POPS a larger cost), so distances up to min(max_dist + 1, 254) are
+ * reported.  HB_DIST_REVERSED follows the edges backwards: the distance from every node TO the nearest source.  A source id that is not
+ * a node of the graph contributes nothing and is counted in unknown_sources; duplicates count once.
+ * Level-synchronous and direction-optimising (top-down / bottom-up steps); single rank only.  The call keeps its
+ * result in buffers of its own: hb_result_* of an earlier hb_run / hb_sampled_harmonic stay as they are, a later hb_run computes what it
+ * computed before, and the distances stay readable until the next hb_distances or the next load.  Refused (HB_ERR_INVALID) between
+ * hb_begin and hb_finish, without a loaded graph, with world_size > 1, with source_count == 0 and with both debug flags set. */
+#define HB_DIST_REVERSED        0x1u  /* follow edges backwards: distance from every node TO the source set (raw_reversed_distances*) */
+#define HB_DIST_WITH_MAX        0x2u  /* max_dist is meaningful (raw_*_with_max); without it the walk runs to exhaustion */
+#define HB_DIST_TOP_DOWN_ONLY   0x4u  /* debug: never switch to the bottom-up step (same result) */
+#define HB_DIST_BOTTOM_UP_ONLY  0x8u  /* debug: bottom-up from level 1 on (same result) */
+#define HB_DIST_UNREACHED       255u
+
+typedef struct hb_distance_options {
+    uint32_t struct_size, flags;                    /* struct_size = sizeof(hb_distance_options); 0 = this version; flags = HB_DIST_* */
+    uint32_t max_dist;                              /* 0..255, as the reference's u8 */
+    const hb_u128 *sources; uint64_t source_count;  /* dijkstra_multi takes a slice: >= 1 ids */
+} hb_distance_options;
+
+typedef struct hb_distance_stats {
+    uint32_t struct_size;       /* = sizeof(hb_distance_stats); 0 = this version */
+    uint32_t levels;            /* levels run */
+    uint32_t max_distance;      /* largest distance found */
+    uint64_t reached;           /* nodes with a distance, sources included */
+    uint64_t unknown_sources;   /* ids not in the loaded graph */
+    uint64_t edges_inspected;   /* src / reader entries actually read */
+    uint64_t frontier[256];     /* nodes first reached at each level */
+    uint8_t  step[256];         /* per level: 0 = top-down, 1 = bottom-up */
+    double   ms_total, ms_levels; /* wall time of the call / GPU time of the level loop */
+} hb_distance_stats;
+
+int hb_distances(hb_ctx *ctx, const hb_distance_options *opt, hb_distance_stats *stats);
+/* The result of the last hb_distances.  count = reached nodes; copy = those nodes only, ascending NodeID (the reference's
+ * BTreeMap<NodeID, u8>), at most cap entries, ids or dist may be NULL; all = one byte per node in ascending-NodeID order (the order of
+ * hb_result_copy's ids and hb_debug_copy_graph), HB_DIST_UNREACHED = no distance, cap >= n. */
+int hb_distance_count(hb_ctx *ctx, uint64_t *count);
+int hb_distance_copy(hb_ctx *ctx, hb_u128 *ids, uint8_t *dist, uint64_t cap);
+int hb_distance_all(hb_ctx *ctx, uint8_t *dist, uint64_t cap);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) -------------------------------------- */
 /* Rank 0 calls this and distributes the 128 bytes (e.g. torch.distributed broadcast);
  * every rank puts them in hb_options.rccl_id. */

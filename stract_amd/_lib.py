@@ -157,6 +157,44 @@ class HbSampleStats(ctypes.Structure):
         return d
 
 
+HB_DIST_REVERSED = 0x1
+HB_DIST_WITH_MAX = 0x2
+HB_DIST_TOP_DOWN_ONLY = 0x4
+HB_DIST_BOTTOM_UP_ONLY = 0x8
+HB_DIST_UNREACHED = 255
+
+
+class HbDistanceOptions(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("max_dist", ctypes.c_uint32),
+        ("sources", ctypes.c_void_p),
+        ("source_count", ctypes.c_uint64),
+    ]
+
+
+class HbDistanceStats(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("levels", ctypes.c_uint32),
+        ("max_distance", ctypes.c_uint32),
+        ("reached", ctypes.c_uint64),
+        ("unknown_sources", ctypes.c_uint64),
+        ("edges_inspected", ctypes.c_uint64),
+        ("frontier", ctypes.c_uint64 * 256),
+        ("step", ctypes.c_uint8 * 256),
+        ("ms_total", ctypes.c_double),
+        ("ms_levels", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        for k in ("frontier", "step"):
+            d[k] = list(d[k])[:self.levels + 1]  # [0] = the sources, [d] = level d
+        return d
+
+
 # every symbol include/hyperball.h declares: (name, restype, argtypes)
 _P = ctypes.c_void_p
 _U64 = ctypes.c_uint64
@@ -244,6 +282,13 @@ _SIGNATURES += [
     ("hb_sampled_harmonic", ctypes.c_int, [_P, ctypes.POINTER(HbSampleOptions), ctypes.POINTER(HbSampleStats)]),
     ("hb_sample_sources", ctypes.c_int, [_P, _U64, _U64, _P, ctypes.POINTER(_U64)]),
     ("hb_debug_sample_histogram", ctypes.c_int, [_P, _P]),
+]
+# include/hyperball.h: exact shortest-path distances (ShortestPaths)
+_SIGNATURES += [
+    ("hb_distances", ctypes.c_int, [_P, ctypes.POINTER(HbDistanceOptions), ctypes.POINTER(HbDistanceStats)]),
+    ("hb_distance_count", ctypes.c_int, [_P, ctypes.POINTER(_U64)]),
+    ("hb_distance_copy", ctypes.c_int, [_P, _P, _P, _U64]),
+    ("hb_distance_all", ctypes.c_int, [_P, _P, _U64]),
 ]
 SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -556,6 +601,57 @@ class Context:
         out = np.zeros((self.n(), int(levels)), dtype=np.uint16)
         self._check(self.lib.hb_debug_sample_histogram(self.h, _ptr(out)))
         return out
+
+    # -- exact shortest-path distances (ShortestPaths, shortest_path.rs:26-227)
+    _DIST_MODES = {None: 0, "auto": 0, "top_down": HB_DIST_TOP_DOWN_ONLY, "bottom_up": HB_DIST_BOTTOM_UP_ONLY}
+
+    def _distances(self, sources, reversed, max_dist, mode, flags):
+        o = HbDistanceOptions()
+        o.struct_size = ctypes.sizeof(HbDistanceOptions)
+        o.flags = int(flags) | (HB_DIST_REVERSED if reversed else 0) | self._DIST_MODES[mode]
+        if max_dist is not None:
+            o.flags |= HB_DIST_WITH_MAX
+            o.max_dist = int(max_dist)
+        count = len(sources)
+        sources = np.ascontiguousarray(sources, dtype=U128) if count else np.zeros(1, dtype=U128)
+        o.sources = sources.ctypes.data
+        o.source_count = count
+        st = HbDistanceStats()
+        st.struct_size = ctypes.sizeof(HbDistanceStats)
+        self._check(self.lib.hb_distances(self.h, ctypes.byref(o), ctypes.byref(st)))
+        return st.as_dict()
+
+    def distance_count(self):
+        k = ctypes.c_uint64(0)
+        self._check(self.lib.hb_distance_count(self.h, ctypes.byref(k)))
+        return k.value
+
+    def distance_copy(self):
+        """The reached nodes of the last distances() call: (ids ascending, dist uint8)."""
+        k = self.distance_count()
+        ids = np.zeros(k, dtype=U128)
+        dist = np.zeros(k, dtype=np.uint8)
+        self._check(self.lib.hb_distance_copy(self.h, _ptr(ids), _ptr(dist), k))
+        return ids, dist
+
+    def distance_all(self):
+        """One byte per node of the last distances() call, ascending NodeID; HB_DIST_UNREACHED = no distance."""
+        out = np.full(self.n(), HB_DIST_UNREACHED, dtype=np.uint8)
+        self._check(self.lib.hb_distance_all(self.h, _ptr(out), len(out)))
+        return out
+
+    def distances(self, sources, reversed=False, max_dist=None, mode=None, flags=0):
+        """hb_distances from `sources` (U128 array of node ids): (ids, dist, stats) - the reached nodes in ascending NodeID order with
+        their distances (dijkstra_multi's map).  reversed: distances TO the sources; max_dist: None = run to exhaustion, else the
+        *_with_max methods' bound (nodes up to max_dist + 1 are reported); mode: None / "top_down" / "bottom_up" (forced step, same result)."""
+        st = self._distances(sources, reversed, max_dist, mode, flags)
+        ids, dist = self.distance_copy()
+        return ids, dist, st
+
+    def distances_all(self, sources, reversed=False, max_dist=None, mode=None, flags=0):
+        """The same call; the result as one byte per node (ascending NodeID, 255 = unreached): (dist, stats)."""
+        st = self._distances(sources, reversed, max_dist, mode, flags)
+        return self.distance_all(), st
 
     # -- results
     def results(self):

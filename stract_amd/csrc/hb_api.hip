@@ -21,6 +21,7 @@
 #include "hb_experiments.h" // HB_XBITS: the switches of the experiments build (none in the product library)
 #include "hb_kernels.hip.h"
 #include "hb_sample.hip.h"
+#include "hb_bfs.hip.h"
 #ifdef HB_EXPERIMENTS
 #include "hb_experiments.hip.h"
 #endif
@@ -210,6 +211,28 @@ struct hb_ctx {
         std::vector<uint32_t> cand;           // the sampler's candidates (sids with an out-edge), ascending
         bool cand_valid = false;              // cand describes the loaded graph (built by the first sampler call after a load)
     } smp;
+    // hb_distances (hb_api_distance.inc): the BFS state and the last result, allocated at the first call after a load, freed with the graph
+    struct DistanceState {
+        bool ready = false;     // the buffers below exist
+        bool valid = false;     // they hold the result of a finished hb_distances
+        bool extracted = false; // d_by_sid / d_sel_* describe that result
+        uint8_t *d_dist = nullptr;                                       // n_pad: distance per device row, 255 = unreached
+        uint32_t *d_vis = nullptr, *d_front = nullptr, *d_next = nullptr; // one bit per row (hb_bfs.hip.h)
+        uint32_t *d_heavy = nullptr;
+        uint32_t heavy_cap = 0;
+        unsigned int *d_heavy_cnt = nullptr;
+        unsigned long long *d_cnt = nullptr; // 256 levels x 4 counters
+        uint32_t *d_indeg = nullptr;         // rows_total: node sources under every row (reversed switch rule), built at the first reversed call
+        bool indeg_valid = false;
+        const uint64_t *d_out_ptr = nullptr; // the row -> readers transpose: the context's (sweep support), or one of this state's own
+        const uint32_t *d_out_rows = nullptr;
+        uint8_t *d_by_sid = nullptr;         // n: distance per sid
+        uint32_t *d_sel_sid = nullptr;       // n: the reached sids, ascending
+        uint8_t *d_sel_dist = nullptr;       // n: their distances
+        uint64_t *d_sel_cnt = nullptr;
+        uint64_t words_total = 0;            // words of d_vis / d_next
+        uint64_t reached = 0;
+    } dst;
 };
 
 namespace {
@@ -322,6 +345,7 @@ void free_graph_buffers(hb_ctx *c)
     for (void *q : {(void *)c->smp.d_hist, (void *)c->smp.d_cnt, (void *)c->smp.d_srcs, (void *)c->smp.d_rows, (void *)c->smp.d_w})
         if (q) (void)hipFree(q);
     c->smp = hb_ctx::SampleState{};
+    c->dst = hb_ctx::DistanceState{}; // (its buffers were dev_alloc'ed: freed with the list above)
 }
 
 // hb_options.chunk / tune[3..5] -> planner knobs
@@ -1430,3 +1454,5 @@ int hb_store_harmonic_results(hb_ctx *c, const char *output, char *err, uint64_t
 } // extern "C"
 
 #include "hb_api_sample.inc"
+
+#include "hb_api_distance.inc"

@@ -1,0 +1,348 @@
+// hb_api_distance.inc - part of the hb_api.hip translation unit (included at its end; uses its hb_ctx and helpers).
+// hb_distances: ShortestPaths (crates/core/src/webgraph/shortest_path.rs:26-227) on the loaded graph - dijkstra_multi (:57-103) with
+// unit costs as one level-synchronous, direction-optimising BFS, forward or reversed (kernels: hb_bfs.hip.h).  Definitions:
+// include/hyperball.h.
+
+namespace {
+
+// Beamer's switch rule (Beamer, Asanovic, Patterson: "Direction-Optimizing Breadth-First Search", SC 2012) on this layout's edge
+// counts.  m_f = degree sum of the frontier (out-degrees forward, in-degrees reversed), m_u = the same sum over the nodes not reached
+// yet, n_f = frontier size.  top-down -> bottom-up when m_f * alpha > m_u; bottom-up -> top-down when n_f * beta < n and the frontier
+// shrinks.  HB_DIST_ALPHA / HB_DIST_BETA in the environment override them (tools/distance_bench.py sweeps them; DESIGN.md section 14).
+constexpr uint64_t kDistAlpha = 14, kDistBeta = 24;
+
+uint64_t dist_env(const char *name, uint64_t dflt)
+{
+    const char *v = std::getenv(name);
+    if (!v || !*v) return dflt;
+    const unsigned long long x = std::strtoull(v, nullptr, 10);
+    return x ? (uint64_t)x : dflt;
+}
+
+// the buffers of the BFS, once per loaded graph
+int distance_alloc(hb_ctx *c)
+{
+    auto &d = c->dst;
+    if (d.ready) return HB_OK;
+    const Plan &p = c->plan;
+    const uint64_t rows_total = p.n_pad + p.nv;
+    int rc;
+    d.words_total = (rows_total + 31) / 32 + 64;
+    if ((rc = dev_alloc(c, &d.d_dist, p.n_pad))) return rc;
+    if ((rc = dev_alloc(c, &d.d_vis, d.words_total))) return rc;
+    if ((rc = dev_alloc(c, &d.d_front, p.n_pad / 32 + 64))) return rc;
+    if ((rc = dev_alloc(c, &d.d_next, d.words_total))) return rc;
+    d.heavy_cap = (uint32_t)std::min<uint64_t>(c->plan_entries / hbk::kBfsHeavy + 64, 0x7FFFFFFFull); // rows with more than kBfsHeavy entries
+    if ((rc = dev_alloc(c, &d.d_heavy, d.heavy_cap))) return rc;
+    if ((rc = dev_alloc(c, &d.d_heavy_cnt, 64))) return rc;
+    if ((rc = dev_alloc(c, &d.d_cnt, 256 * 4))) return rc;
+    if ((rc = dev_alloc(c, &d.d_by_sid, p.n))) return rc;
+    if ((rc = dev_alloc(c, &d.d_sel_sid, p.n))) return rc;
+    if ((rc = dev_alloc(c, &d.d_sel_dist, p.n))) return rc;
+    if ((rc = dev_alloc(c, &d.d_sel_cnt, 8))) return rc;
+    if (c->sparse_ok) { // the sweep passes' transpose
+        d.d_out_ptr = c->d_out_ptr;
+        d.d_out_rows = c->d_out_rows;
+    } else { // a context without sweep support (HB_FLAG_NO_SPARSE, unfused passes): the same transpose, owned by this state
+        uint64_t *op = nullptr;
+        uint32_t *orow = nullptr;
+        if ((rc = dev_alloc(c, &op, rows_total + 1))) return rc;
+        if ((rc = dev_alloc(c, &orow, c->plan_entries))) return rc;
+        const std::string e = gpu_transpose_rows((void *)c->stream, c->d_row_ptr, c->d_src, rows_total, c->plan_entries, op, orow);
+        if (!e.empty()) return fail(c, e.find("out of memory") != std::string::npos ? HB_ERR_NOMEM : HB_ERR_HIP, "hb_distances: " + e);
+        d.d_out_ptr = op;
+        d.d_out_rows = orow;
+    }
+    HB_HIP(hipMemsetAsync(d.d_next, 0, d.words_total * sizeof(uint32_t), c->stream)); // all-zero between levels from here on
+    HB_HIP(hipMemsetAsync(d.d_heavy_cnt, 0, 64 * sizeof(unsigned int), c->stream));
+    d.ready = true;
+    return HB_OK;
+}
+
+// in-degrees through the chunk trees (the reversed switch rule): once per loaded graph
+int distance_indegrees(hb_ctx *c)
+{
+    auto &d = c->dst;
+    if (d.indeg_valid) return HB_OK;
+    const Plan &p = c->plan;
+    const uint64_t rows_total = p.n_pad + p.nv;
+    int rc;
+    if (!d.d_indeg && (rc = dev_alloc(c, &d.d_indeg, rows_total))) return rc;
+    HB_HIP(hipMemsetAsync(d.d_indeg, 0, std::max<uint64_t>(rows_total, 1) * sizeof(uint32_t), c->stream));
+    auto launch = [&](uint64_t lo, uint64_t hi) {
+        if (hi <= lo) return;
+        const unsigned blocks = (unsigned)std::min<uint64_t>((hi - lo + 255) / 256, (uint64_t)c->num_cu * 8);
+        hipLaunchKernelGGL(hbk::bfs_indegree_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr, (const uint32_t *)c->d_src, d.d_indeg,
+                           p.n_pad, rows_total, lo, hi);
+    };
+    for (size_t l = 0; l + 1 < p.level_begin.size(); l++) launch(p.level_begin[l], p.level_begin[l + 1]);
+    launch(0, p.n_pad);
+    HB_HIP(hipGetLastError());
+    d.indeg_valid = true;
+    return HB_OK;
+}
+
+int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *st_out)
+{
+    const double t0 = now_ms();
+    hb_distance_options o{};
+    if (opt_in) std::memcpy(&o, opt_in, opt_in->struct_size ? std::min<size_t>(opt_in->struct_size, sizeof(o)) : sizeof(o));
+    if (multi_rank(c)) return fail(c, HB_ERR_INVALID, "hb_distances: single rank only (world_size > 1)");
+    if (!c->loaded) return fail(c, HB_ERR_INVALID, "hb_distances: no graph loaded");
+    if (!o.sources || !o.source_count) return fail(c, HB_ERR_INVALID, "hb_distances: no sources (source_count == 0)");
+    if ((o.flags & HB_DIST_TOP_DOWN_ONLY) && (o.flags & HB_DIST_BOTTOM_UP_ONLY))
+        return fail(c, HB_ERR_INVALID, "hb_distances: HB_DIST_TOP_DOWN_ONLY and HB_DIST_BOTTOM_UP_ONLY exclude each other");
+    if ((o.flags & HB_DIST_WITH_MAX) && o.max_dist > 255) return fail(c, HB_ERR_INVALID, "hb_distances: max_dist > 255 (the reference's is a u8)");
+    const Plan &p = c->plan;
+    if (p.n_pad % 32) return fail(c, HB_ERR_INVALID, "hb_distances: unexpected plan layout");
+    for (uint64_t b : p.level_begin)
+        if (b % 32 || b < p.n_pad || b > p.n_pad + p.nv) return fail(c, HB_ERR_INVALID, "hb_distances: unexpected plan layout (virtual level boundary)");
+    {
+        hipError_t stale = hipGetLastError();
+        if (stale != hipSuccess) return fail(c, HB_ERR_HIP, std::string("stale HIP error before hb_distances: ") + hipGetErrorString(stale));
+    }
+    auto &d = c->dst;
+    d.valid = d.extracted = false;
+    d.reached = 0;
+    hb_distance_stats st{};
+    auto finish = [&]() {
+        st.ms_total = now_ms() - t0;
+        if (st_out) {
+            const size_t sz = st_out->struct_size ? std::min<size_t>(st_out->struct_size, sizeof(st)) : sizeof(st);
+            st.struct_size = (uint32_t)sz;
+            std::memcpy(st_out, &st, sz);
+        }
+        return HB_OK;
+    };
+    // the sources as distinct sids
+    std::vector<uint32_t> sids;
+    sids.reserve(o.source_count);
+    for (uint64_t i = 0; i < o.source_count; i++) {
+        const hb_u128 id = o.sources[i];
+        auto it = std::lower_bound(c->g.ids.begin(), c->g.ids.end(), id, u128_less);
+        if (it == c->g.ids.end() || !u128_eq(*it, id)) st.unknown_sources++;
+        else sids.push_back((uint32_t)(it - c->g.ids.begin()));
+    }
+    std::sort(sids.begin(), sids.end());
+    sids.erase(std::unique(sids.begin(), sids.end()), sids.end());
+    int rc;
+    if (p.n == 0) { // an empty graph: every source is unknown
+        d.valid = true;
+        return finish();
+    }
+    if ((rc = distance_alloc(c))) return rc;
+    const bool reversed = (o.flags & HB_DIST_REVERSED) != 0;
+    if (reversed && (rc = distance_indegrees(c))) return rc;
+    const uint64_t n_pad = p.n_pad, rows_total = p.n_pad + p.nv;
+    const uint32_t d_max = (o.flags & HB_DIST_WITH_MAX) ? std::min<uint32_t>(sample_levels(o.max_dist), 254u) : 254u; // cost + 1 < u8::MAX
+    const uint64_t alpha = dist_env("HB_DIST_ALPHA", kDistAlpha), beta = dist_env("HB_DIST_BETA", kDistBeta);
+
+    hbk::BfsParams bp{};
+    bp.push_ptr = reversed ? c->d_row_ptr : d.d_out_ptr;
+    bp.push_idx = reversed ? c->d_src : d.d_out_rows;
+    bp.pull_ptr = reversed ? d.d_out_ptr : c->d_row_ptr;
+    bp.pull_idx = reversed ? d.d_out_rows : c->d_src;
+    bp.deg = reversed ? d.d_indeg : c->d_outdeg;
+    bp.dist = d.d_dist;
+    bp.vis = d.d_vis;
+    bp.front = d.d_front;
+    bp.next = d.d_next;
+    bp.heavy = d.d_heavy;
+    bp.heavy_cnt = d.d_heavy_cnt;
+    bp.heavy_cap = 0;
+    bp.cnt = d.d_cnt;
+    bp.n_pad = n_pad;
+    bp.rows_total = rows_total;
+
+    HB_HIP(hipMemsetAsync(d.d_dist, 0xFF, n_pad, c->stream));
+    HB_HIP(hipMemsetAsync(d.d_vis, 0, d.words_total * sizeof(uint32_t), c->stream));
+    HB_HIP(hipMemsetAsync(d.d_front, 0, (n_pad / 32 + 64) * sizeof(uint32_t), c->stream));
+    HB_HIP(hipMemsetAsync(d.d_cnt, 0, 256 * 4 * sizeof(unsigned long long), c->stream));
+    unsigned long long *h = c->h_counters; // (pinned words of the context; hb_run rewrites them before it reads them)
+    uint64_t n_f = 0, m_f = 0;
+    if (!sids.empty()) {
+        uint32_t *d_srcs = nullptr;
+        HB_HIP(hipMalloc((void **)&d_srcs, sids.size() * sizeof(uint32_t)));
+        hipError_t e = hipMemcpyAsync(d_srcs, sids.data(), sids.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(hbk::bfs_seed_kernel, dim3((unsigned)((sids.size() + 255) / 256)), dim3(256), 0, c->stream, (const uint32_t *)d_srcs,
+                               (uint32_t)sids.size(), (const uint32_t *)c->d_dev_of, bp);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(h, d.d_cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        (void)hipFree(d_srcs);
+        if (e != hipSuccess) return fail(c, HB_ERR_HIP, std::string("hb_distances: seeding the sources: ") + hipGetErrorString(e));
+        n_f = h[0];
+        m_f = h[1];
+    }
+    st.frontier[0] = n_f;
+    st.reached = n_f;
+    uint64_t m_seen = m_f; // degree sum of the reached nodes
+    uint64_t prev_n_f = 0;
+    bool bottom_up = false;
+    const unsigned wblocks = (unsigned)std::max<uint64_t>(std::min<uint64_t>((n_pad / 32 + 255) / 256, (uint64_t)c->num_cu * 8), 1);
+    auto grid_words = [&](uint64_t lo, uint64_t hi, uint64_t words_per_block) {
+        const uint64_t words = (hi - lo + 31) / 32;
+        return dim3((unsigned)std::max<uint64_t>(std::min<uint64_t>((words + words_per_block - 1) / words_per_block, (uint64_t)c->num_cu * 8), 1));
+    };
+    const size_t nlev = p.level_begin.size() > 1 ? p.level_begin.size() - 1 : 0;
+    HB_HIP(hipEventRecord(c->ev[0], c->stream));
+    for (uint32_t lvl = 1; lvl <= d_max && n_f; lvl++) {
+        // the step: Beamer's rule, with hysteresis (a bottom-up phase ends only when the frontier is small AND shrinking)
+        const uint64_t m_u = c->m_global > m_seen ? c->m_global - m_seen : 0;
+        if (o.flags & HB_DIST_TOP_DOWN_ONLY) bottom_up = false;
+        else if (o.flags & HB_DIST_BOTTOM_UP_ONLY) bottom_up = true;
+        else if (!bottom_up) bottom_up = m_f * alpha > m_u && m_f > 0;
+        else if (n_f * beta < p.n && n_f < prev_n_f) bottom_up = false;
+        bp.level = lvl;
+        bp.cnt = d.d_cnt + 4 * (uint64_t)lvl;
+        if (!bottom_up) {
+            // node rows of the frontier, then the virtual levels relay: ascending forward (a chunk feeds higher levels and its hub),
+            // descending reversed (a hub feeds its chunks, a chunk the lower levels)
+            bp.row_lo = 0;
+            bp.row_hi = n_pad;
+            bp.heavy_cap = m_f > hbk::kBfsHeavy ? d.heavy_cap : 0; // (no frontier row can be heavy otherwise)
+            hipLaunchKernelGGL((hbk::bfs_push_kernel<false>), grid_words(0, n_pad, 256), dim3(256), 0, c->stream, bp);
+            if (bp.heavy_cap) hipLaunchKernelGGL(hbk::bfs_push_heavy_kernel, dim3((unsigned)c->num_cu * 4), dim3(256), 0, c->stream, bp);
+            bp.heavy_cap = 0;
+            for (size_t k = 0; k < nlev; k++) {
+                const size_t l = reversed ? nlev - 1 - k : k;
+                bp.row_lo = p.level_begin[l];
+                bp.row_hi = p.level_begin[l + 1];
+                if (bp.row_hi > bp.row_lo) hipLaunchKernelGGL((hbk::bfs_push_kernel<true>), grid_words(bp.row_lo, bp.row_hi, 256), dim3(256), 0, c->stream, bp);
+            }
+        } else {
+            // the virtual rows' bits first (ascending forward: a chunk looks at its sources; descending reversed: at its readers)
+            for (size_t k = 0; k < nlev; k++) {
+                const size_t l = reversed ? nlev - 1 - k : k;
+                bp.row_lo = p.level_begin[l];
+                bp.row_hi = p.level_begin[l + 1];
+                if (bp.row_hi > bp.row_lo) hipLaunchKernelGGL((hbk::bfs_pull_kernel<true>), grid_words(bp.row_lo, bp.row_hi, 4), dim3(256), 0, c->stream, bp);
+            }
+            bp.row_lo = 0;
+            bp.row_hi = n_pad;
+            hipLaunchKernelGGL((hbk::bfs_pull_kernel<false>), grid_words(0, n_pad, 4), dim3(256), 0, c->stream, bp);
+        }
+        hipLaunchKernelGGL(hbk::bfs_finalize_kernel, dim3(wblocks), dim3(256), 0, c->stream, bp);
+        HB_HIP(hipGetLastError());
+        HB_HIP(hipMemcpyAsync(h, bp.cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HB_HIP(hipStreamSynchronize(c->stream));
+        prev_n_f = n_f;
+        n_f = h[0];
+        m_f = h[1];
+        m_seen += m_f;
+        st.levels = lvl;
+        st.step[lvl] = bottom_up ? 1 : 0;
+        st.frontier[lvl] = n_f;
+        st.reached += n_f;
+        st.edges_inspected += h[2];
+        if (n_f) st.max_distance = lvl;
+    }
+    HB_HIP(hipEventRecord(c->ev[1], c->stream));
+    HB_HIP(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HB_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    st.ms_levels = ms;
+    d.reached = st.reached;
+    d.valid = true;
+    return finish();
+}
+
+// the result in sid order and its compacted form, on the device (once per result)
+int distance_extract(hb_ctx *c)
+{
+    auto &d = c->dst;
+    if (d.extracted) return HB_OK;
+    const Plan &p = c->plan;
+    if (p.n && d.ready) {
+        const unsigned blocks = (unsigned)std::max<uint64_t>(std::min<uint64_t>((p.n + 255) / 256, (uint64_t)c->num_cu * 8), 1);
+        hipLaunchKernelGGL(hbk::bfs_by_sid_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint8_t *)d.d_dist, (const uint32_t *)c->d_dev_of, p.n, p.n_pad,
+                           d.d_by_sid);
+        HB_HIP(hipGetLastError());
+        const std::string e = gpu_select_reached((void *)c->stream, d.d_by_sid, p.n, d.d_sel_sid, d.d_sel_dist, d.d_sel_cnt);
+        if (!e.empty()) return fail(c, HB_ERR_HIP, "hb_distance_copy: " + e);
+        uint64_t got = 0;
+        HB_HIP(hipMemcpyAsync(&got, d.d_sel_cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        HB_HIP(hipStreamSynchronize(c->stream));
+        if (got != d.reached) return fail(c, HB_ERR_INVALID, "hb_distance_copy: the compacted list and the level counters disagree");
+    }
+    d.extracted = true;
+    return HB_OK;
+}
+
+int distance_result_ready(hb_ctx *c, const char *who)
+{
+    if (!c->loaded || !c->dst.valid) return fail(c, HB_ERR_INVALID, std::string(who) + ": no distances (call hb_distances)");
+    return set_device(c);
+}
+
+} // namespace
+
+extern "C" {
+
+int hb_distances(hb_ctx *c, const hb_distance_options *opt, hb_distance_stats *stats)
+{
+    return guarded(c, [&]() -> int {
+        if (!c) return HB_ERR_INVALID;
+        int rc = set_device(c);
+        if (rc) return rc;
+        // between hb_begin and hb_finish the pinned counter words (and the stream's event pair) belong to that run
+        if (c->begun && !c->finished) return fail(c, HB_ERR_INVALID, "hb_distances: a HyperBall run is in progress (hb_begin without hb_finish)");
+        return distances(c, opt, stats);
+    });
+}
+
+int hb_distance_count(hb_ctx *c, uint64_t *count)
+{
+    return guarded(c, [&]() -> int {
+        if (!c || !count) return c ? fail(c, HB_ERR_INVALID, "hb_distance_count: count == NULL") : HB_ERR_INVALID;
+        int rc = distance_result_ready(c, "hb_distance_count");
+        if (rc) return rc;
+        *count = c->dst.reached;
+        return HB_OK;
+    });
+}
+
+int hb_distance_copy(hb_ctx *c, hb_u128 *ids, uint8_t *dist, uint64_t cap)
+{
+    return guarded(c, [&]() -> int {
+        if (!c) return HB_ERR_INVALID;
+        int rc = distance_result_ready(c, "hb_distance_copy");
+        if (rc) return rc;
+        auto &d = c->dst;
+        const uint64_t k = std::min<uint64_t>(cap, d.reached);
+        if (!k || (!ids && !dist)) return HB_OK;
+        if ((rc = distance_extract(c))) return rc;
+        // only the reached nodes come down: k sids (and k bytes); the ids are looked up in the host's sorted id array
+        if (ids) {
+            std::vector<uint32_t> sid(k);
+            HB_HIP(hipMemcpyAsync(sid.data(), d.d_sel_sid, k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HB_HIP(hipStreamSynchronize(c->stream));
+            for (uint64_t i = 0; i < k; i++) ids[i] = c->g.ids[sid[i]];
+        }
+        if (dist) {
+            HB_HIP(hipMemcpyAsync(dist, d.d_sel_dist, k, hipMemcpyDeviceToHost, c->stream));
+            HB_HIP(hipStreamSynchronize(c->stream));
+        }
+        return HB_OK;
+    });
+}
+
+int hb_distance_all(hb_ctx *c, uint8_t *dist, uint64_t cap)
+{
+    return guarded(c, [&]() -> int {
+        if (!c || !dist) return c ? fail(c, HB_ERR_INVALID, "hb_distance_all: dist == NULL") : HB_ERR_INVALID;
+        int rc = distance_result_ready(c, "hb_distance_all");
+        if (rc) return rc;
+        const uint64_t n = c->plan.n;
+        if (cap < n) return fail(c, HB_ERR_INVALID, "hb_distance_all: cap < n");
+        if (!n) return HB_OK;
+        if ((rc = distance_extract(c))) return rc;
+        HB_HIP(hipMemcpyAsync(dist, c->dst.d_by_sid, n, hipMemcpyDeviceToHost, c->stream));
+        HB_HIP(hipStreamSynchronize(c->stream));
+        return HB_OK;
+    });
+}
+
+} // extern "C"

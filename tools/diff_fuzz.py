@@ -5,7 +5,7 @@ Runs against whatever library HB_LIB_PATH names: the gfx950 library on a GPU box
 interpreted test build of the device sources (tests/simt, with HB_ALLOW_SIMT_INTERPRETER=1; add the AddressSanitizer preload
 for the `make asan` build).  A failure prints the seed and case that reproduce it and makes the exit code non-zero.
 
-usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed] [--seconds S] [--seed N] [--max-nodes N]"""
+usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|distances] [--seconds S] [--seed N] [--max-nodes N]"""
 import argparse
 import json
 import os
@@ -249,9 +249,39 @@ def ranks_case(rng, max_nodes, case):
     return what
 
 
+def distances_case(rng, max_nodes, case):
+    """hb_distances: random graph x random source set x direction x max_dist x forced step, against the host restatement
+    (tests/distance_ref.py: the literal dijkstra_multi with the u8 rule)."""
+    from stract_amd.harmonic import EdgeListGraph
+    from tests import distance_ref as dref
+    kind, tuples = graphs.random_graph(rng)
+    if not tuples:
+        return None
+    chunk = int(rng.choice([0, 0, 4, 8, 64]))
+    flags = _lib.HB_FLAG_ALL_RELS | int(rng.choice([0, 0, _lib.HB_FLAG_NO_REORDER, _lib.HB_FLAG_NO_XCD_MAP, _lib.HB_FLAG_NO_SPARSE]))
+    with _lib.Context(flags=flags, chunk=chunk) as ctx:
+        ctx.load_edges(EdgeListGraph.from_tuples(tuples).host_edges())
+        ids, row_ptr, src = ctx.graph()
+        n = len(ids)
+        what = dict(case=case, kind="distances:" + kind, n=n, m=int(len(src)), chunk=chunk, flags=flags, passes=0)
+        for _ in range(4):
+            srcs = sorted(set(int(x) for x in rng.integers(0, n, int(rng.integers(1, 5)))))
+            rev = bool(rng.integers(0, 2))
+            md = [None, 0, 1, 7, 15, 200][int(rng.integers(0, 6))]
+            mode = [None, "top_down", "bottom_up"][int(rng.integers(0, 3))]
+            want = dref.dijkstra(n, row_ptr, src, srcs, reversed=rev, max_dist=md)
+            gids, gdist, st = ctx.distances(ids[np.asarray(srcs, dtype=np.int64)], reversed=rev, max_dist=md, mode=mode)
+            keep = want != dref.UNREACHED
+            run = dict(what, sources=srcs, reversed=rev, max_dist=md, mode=mode)
+            assert np.array_equal(gids, ids[keep]) and np.array_equal(gdist, want[keep]), ("distance list", run)
+            assert np.array_equal(ctx.distance_all(), want) and st["reached"] == int(keep.sum()) == sum(st["frontier"]), ("distance array / counters", run)
+            what["passes"] += st["levels"]
+    return what
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed"], default="passes")
+    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "distances"], default="passes")
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-nodes", type=int, default=6000)
@@ -262,7 +292,9 @@ def main():
     case = 0
     while time.time() - t0 < a.seconds:
         try:
-            if a.mode == "ranks" or (a.mode == "mixed" and case % 6 == 4):
+            if a.mode == "distances":
+                w = distances_case(rng, a.max_nodes, case)
+            elif a.mode == "ranks" or (a.mode == "mixed" and case % 6 == 4):
                 w = ranks_case(rng, a.max_nodes, case)
             elif a.mode == "tail" or (a.mode == "mixed" and case % 6 == 5):
                 w = tail_case(rng, case)
