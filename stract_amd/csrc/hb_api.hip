@@ -36,30 +36,69 @@ struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
 };
+
+// The one owner of a hipMalloc'ed buffer that is not on a context's `allocs` list (dev_alloc below): scratch of a single call, the input
+// CSR of a load, the sampled operator's state.  Move-only; freed when the holder goes out of scope or is assigned over.  (hipMalloc /
+// hipFree are the ones this file sees: the caching allocator, or the debug allocators of hb_guard_alloc.h.)
+template <class T>
+struct DevPtr {
+    DevPtr() = default;
+    explicit DevPtr(T *q) : p(q) {}
+    DevPtr(DevPtr &&o) noexcept : p(o.release()) {}
+    DevPtr &operator=(DevPtr &&o) noexcept
+    {
+        reset(o.release());
+        return *this;
+    }
+    DevPtr(const DevPtr &) = delete;
+    DevPtr &operator=(const DevPtr &) = delete;
+    ~DevPtr() { reset(); }
+    T *get() const { return p; }
+    explicit operator bool() const { return p != nullptr; }
+    T *release()
+    {
+        T *q = p;
+        p = nullptr;
+        return q;
+    }
+    void reset(T *q = nullptr)
+    {
+        if (p) (void)hipFree(p);
+        p = q;
+    }
+    hipError_t alloc(size_t count) // `count` elements; whatever the holder had is freed first
+    {
+        reset();
+        return hipMalloc((void **)&p, count * sizeof(T));
+    }
+
+private:
+    T *p = nullptr;
+};
+
+// DeviceCsr (hb_internal.h: a plain struct, the host-only sources include it too) with an owner: the device ingest or hb_load_dense fills
+// `d`, plan_and_upload takes the whole thing by move and frees it when the plan exists
+struct OwnedCsr {
+    DeviceCsr d;
+    OwnedCsr() = default;
+    OwnedCsr(OwnedCsr &&o) noexcept : d(o.d) { o.d = DeviceCsr{}; }
+    OwnedCsr(const OwnedCsr &) = delete;
+    OwnedCsr &operator=(const OwnedCsr &) = delete;
+    ~OwnedCsr() { reset(); }
+    void reset()
+    {
+        for (void *q : {(void *)d.d_row_ptr, (void *)d.d_src, (void *)d.d_id_lo})
+            if (q) (void)hipFree(q);
+        d = DeviceCsr{};
+    }
+};
 } // namespace
 
-struct hb_ctx {
-    hb_options opt{};
-    int device = 0;
-    int num_cu = 256;
-    hipStream_t stream = nullptr;
-    ncclComm_t comm = nullptr;
-    hb_collectives coll{}; // hb_set_collectives: the per-pass exchanges go through these instead of RCCL (HB_FLAG_NO_RCCL contexts)
-    std::string err;
-    std::string arch;
-
-    // host-side graph / plan
-    std::vector<hb_edge> pending;  // hb_append_edges, host-ingest mode only
-    // hb_append_edges, default: records are unpacked on the device as they arrive (2 x 16-byte endpoint keys + 1
-    // flag byte each); nothing is buffered on the host
-    IngestStream app;
-    uint64_t lim_records = 0, lim_bytes = 0, lim_chunk = 0; // hb_debug_set_ingest_limits (0 = no limit / default)
-    DenseGraph g;                  // ids kept; row_ptr/src kept only for hb_debug_copy_graph
-    Plan plan;
-    bool loaded = false, begun = false, finished = false;
-
-    // device
-    std::vector<DevBuf> allocs;
+// ---- graph lifetime ---------------------------------------------------------------------------------------------------------------
+// What describes the loaded graph on the device: written by plan_and_upload (and, on first use after a load, by the operators), gone
+// with the graph.  free_graph_buffers() frees what owns memory here and then assigns a default-constructed state: a member added to
+// this struct cannot survive a reload.  The d_* pointers are carved from hb_ctx::allocs (dev_alloc) unless they say otherwise.
+struct GraphDeviceState {
     uint64_t *d_row_ptr = nullptr;
     uint32_t *d_src = nullptr;
     uint16_t *d_src_jp = nullptr; // parallel to d_src: the sources' initial register (pass 0 streams it, hb_kernels.hip.h)
@@ -76,8 +115,6 @@ struct hb_ctx {
     uint32_t *d_dev_of = nullptr;
     uint32_t *d_sid_of = nullptr; // device row -> sid, kNone for padding rows
     uint32_t *d_outdeg = nullptr; // device row -> (global) out-degree
-    uint64_t m_global = 0;        // edges of the whole graph (all ranks)
-    uint64_t last_active = 0;     // out-degree sum of the nodes changed in the previous pass
     unsigned long long *d_counters = nullptr; // (max_passes + 1) * kCounterWords, striped (hb_kernels.hip.h)
     double *d_raw = nullptr, *d_bias = nullptr;
     uint8_t *d_lc = nullptr;
@@ -88,50 +125,19 @@ struct hb_ctx {
     uint32_t *d_seeds = nullptr, *d_heavy = nullptr;
     unsigned int *d_sparse_counts = nullptr;
     bool sparse_ok = false;
-    uint64_t plan_entries = 0; // entries of all work rows' source lists
-    unsigned long long *h_counters = nullptr; // pinned, kCounterWords words; [0..3] hold the stripe sums after a pass
-    void *h_block = nullptr;                  // ONE page-locked block, allocated by hb_create, that h_counters / h_slot / h_tl_count / h_rank_cnt are
-                                              // carved from: no hipHostMalloc ever happens inside a run (the first hb_run of a process is the ONLY one
-                                              // a drop-in user makes, entrypoint/centrality.rs:49)
-    uint64_t bits_words = 0;
-    uint64_t ksum_len = 0; // entries allocated for ksum (world * slice in RCCL mode)
-    uint64_t slice_rows = 0;
     // changed-only exchange (HB_FLAG_CHANGED_ONLY): packed changed counters, popcounts / prefix of the bitmap words
     uint4 *d_pack = nullptr;
     uint32_t *d_wpop = nullptr;
     uint64_t *d_wprefix = nullptr;
     // edge partition + HB_FLAG_CHANGED_ONLY: rows the local merge changed, the ranks' bitmaps gathered, their union
     uint32_t *d_lbits = nullptr, *d_lbits_all = nullptr, *d_ubits = nullptr;
-    uint64_t co_rows = 0;     // rows in the union of this pass
     bool ubits_valid = false; // d_ubits holds this pass' union (set by the exchange, consumed by the epilogue)
-    std::vector<uint64_t> ex_off; // world + 1: first packed position of every rank's slice
     unsigned long long *d_rank_cnt = nullptr; // world words: every rank's changed rows of this pass (summed over the ranks)
-    unsigned long long *h_rank_cnt = nullptr; // pinned
-    // destination partition + changed-only: the pass' only host round trip sits in the MIDDLE of the pass (counters + run lengths,
-    // before the broadcasts); what follows it is left in flight, so the pass' timing events are read later (resolve_pass_times)
-    struct EvSet {
-        hipEvent_t e[6];
-    };
-    std::vector<EvSet> ev_pool;         // deferred timing (destination partition + changed-only on a communicator): one set per pass of a run
-    EvSet ev_ring[4]{};                 // hb_run's tail pipeline (two passes in flight): pass t uses set t & 3; created by hb_create
-    std::vector<uint64_t> pending_times; // passes whose ms_* fields still have to be read from their events
-    // hb_run's tail pipeline: pass q + 1 is queued (guarded on the device by pass q's changed count) before pass q's counters are
-    // read, so the convergence tail runs without a host round trip between passes
-    const unsigned long long *spec_guard = nullptr; // set while step_local queues a guarded pass
-    bool pipelined = false;                         // step_local: take this pass' events from ev_pool
-    uint64_t pipelined_passes = 0;                  // passes of this run queued ahead of their predecessor's read-back
     // the far tail as one workgroup (hb_tail.hip.h): work lists, their counts / status words, and whether the lists describe the
     // bitmaps as they are now (any pass run by other kernels invalidates them: the next entry collects them again)
     uint32_t *d_tl_changed[2] = {nullptr, nullptr}, *d_tl_vchanged[2] = {nullptr, nullptr}, *d_tl_dirty[2] = {nullptr, nullptr};
     uint32_t *d_tl_work = nullptr, *d_tl_count = nullptr;
-    uint32_t *h_tl_count = nullptr; // pinned, kTcWords
     bool tl_valid = false;
-    bool tl_declined = false;       // the kernel found the next pass too large for its lists: do not ask again before an ordinary pass has run
-    uint64_t tail_kernel_passes = 0;
-    hipEvent_t tl_ev[2] = {nullptr, nullptr};
-    unsigned long long *h_slot = nullptr;           // pinned, 2 x kCounterWords: the counters of the two passes in flight
-    hipEvent_t slot_done[2] = {nullptr, nullptr};   // pass q's counters have arrived in h_slot[q & 1]
-    uint64_t wire_bytes = 0;      // counter bytes this rank received over the run (changed-only accounting)
     // reference-tail mode (HB_FLAG_REFERENCE_TAIL): the reference's changed-node machinery as written
     uint64_t *d_tail_ptr = nullptr; // page-level records by source device row (hb_load_tail_edges), n_pad + 1
     uint32_t *d_tail_to = nullptr;
@@ -139,41 +145,13 @@ struct hb_ctx {
     std::vector<uint64_t> tail_keys; // records of the closed segments, mapped (hb_host.cpp tail_close_segment)
     std::vector<TailDoc> tail_open;  // documents of the segment being appended (hb_tail_segment_end closes it)
     bool tail_dirty = false;         // tail_keys differ from what d_tail_* hold: rebuilt by hb_begin
-    TailIndex *tail_index = nullptr; // id -> sid index for the batches of tail records (built at the first batch)
+    TailIndex *tail_index = nullptr; // id -> sid index for the batches of tail records (built at the first batch); tail_index_free
     uint32_t *d_bloom = nullptr;    // new_changed_nodes of the last pass (U64BloomFilter), bloom_bits bits
-    uint64_t bloom_bits = 0;
     unsigned long long *d_bloom_ones = nullptr; // [0] count_ones, [1] (low word) length of d_list
     uint32_t *d_list = nullptr;     // exact_changed_nodes as device rows, <= ref_threshold entries
-    uint64_t ref_threshold = 0;     // exact_counting_threshold (harmonic.rs:228)
-    bool exact_counting = false;    // harmonic.rs:231,277-279
-    bool exact_valid = false;       // the previous pass filled exact_changed_nodes (ran with Some(..) or was a tail pass)
-    bool stale = false;             // a tail pass has run: host-level edges may have been skipped, the bloom filter's
-                                    // false positives are no longer results-inert
-
-    // loop state
-    bool lean_init = false; // hb_begin left the initial counters / Kahan words / sizes to pass 0 (PassParams::rd_init); cleared by pass 0, or by
-                            // ensure_initial_state() when something wants to look at the state before pass 0
-    uint64_t t = 0;
-    int cur = 0; // d_regs[cur] = "old"
-    bool has_changes = false;
-    bool pending_local = false; // between hb_step_local and hb_step_finish
-    uint64_t last_changed = 0;
-    uint32_t max_passes = 4096;
-    std::vector<hb_pass_stats> pstats;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // [5] = after the level-1 hub launch
-    // edge partition with a communicator: the node rows are merged, all-reduced and finished in kOverlap row ranges - range
-    // k's ncclAllReduce runs on comm_stream while range k + 1 is still being merged, its epilogue while k + 1 is reduced
-    static constexpr int kOverlap = 4;
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t ov_merged[kOverlap] = {nullptr, nullptr, nullptr, nullptr}, ov_reduced[kOverlap] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t ov_lo[kOverlap + 1] = {0, 0, 0, 0, 0};
-    int ov_ranges = 0; // ranges of the pending pass (0 = one launch over all rows, no overlap)
-    uint32_t cur_mode = 0;
-
-    hb_stats stats{};
     // results: one f64 per node in ascending-NodeID order, -1.0 = absent (centrality <= 0)
     double *d_out = nullptr;
-    double *h_out = nullptr; // pinned, n entries
+    double *h_out = nullptr; // pinned (hipHostFree), n entries
     uint64_t h_out_len = 0;
     // [r6] the image's layout: out_len live entries.  Identity (out_len = n, index = sid, d_cid_of = d_sid_of) or, when the results travel in
     // stages (rs.on: single rank), COMPACT: one entry per node with in-edges, ascending NodeID (hb_aux.hip.h "the compact result image");
@@ -181,37 +159,36 @@ struct hb_ctx {
     uint64_t out_len = 0;
     uint32_t *d_cid_of = nullptr; // n_pad: device row -> index into out[] (kNone = not in the image)
     std::vector<uint64_t> h_in_bits;
-    uint64_t res_count = 0;
-    // results that travel while the passes still run (results_stage below; hb_aux.hip.h results_sync_kernel)
+    // results that travel while the passes still run (results_stage; hb_aux.hip.h results_sync_kernel).  The side stream and its two events
+    // are the context's (hb_ctx::rs_stream)
     struct ResultSync {
         bool on = false;          // this graph ships its results in stages (single rank, large enough or forced by tune[1] bit 15)
         bool valid = false;       // d_out / d_sent (and h_out, once `copied` has fired) hold one consistent snapshot of the sums
-        uint64_t changed_since = 0; // counters changed since that snapshot (= sums that moved, give or take a `+= 0.0` flush)
-        uint32_t stages = 0;      // snapshots shipped during the current run
+        uint64_t changed_since = 0; // (run) counters changed since that snapshot (= sums that moved, give or take a `+= 0.0` flush)
+        uint32_t stages = 0;      // (run) snapshots shipped during the current run
         double *d_sent = nullptr; // device order: the sum out[] was last built from
         uint32_t *d_sid = nullptr; // the final list: (sid, value) of what moved after the last snapshot
         double *d_val = nullptr;
         unsigned long long *d_count = nullptr;
         unsigned long long *d_kept = nullptr; // kCounterWords scratch words of the snapshots' kernel (side stream)
-        uint32_t *h_sid = nullptr; // pinned
+        uint32_t *h_sid = nullptr; // pinned (hipHostFree)
         double *h_val = nullptr;
         unsigned long long *h_count = nullptr;
         uint64_t cap = 0;
-        hipStream_t stream = nullptr;                 // the snapshots' downloads run here, beside the passes
-        hipEvent_t ready = nullptr, copied = nullptr; // out[] built (main stream) / downloaded (side stream)
     } rs;
-    // hb_sampled_harmonic (hb_api_sample.inc): per-level histograms and scratch, hipMalloc'ed on first use, freed with the graph
+    // hb_sampled_harmonic (hb_api_sample.inc): per-level histograms and scratch, allocated on first use.  The holders own them: they are
+    // not on the `allocs` list and hb_stats.device_bytes does not count them
     struct SampleState {
-        uint16_t *d_hist = nullptr;           // levels x n_pad, level-major: c_d of device row r at [(d - 1) n_pad + r]
+        DevPtr<uint16_t> d_hist;              // levels x n_pad, level-major: c_d of device row r at [(d - 1) n_pad + r]
         uint32_t levels = 0;                  // D of d_hist (0 = no sampled result)
-        unsigned long long *d_cnt = nullptr;  // (kMaxLevels + 1) x 4 counters of the current batch
-        uint32_t *d_srcs = nullptr;           // sids of a batch's sources (<= 512)
-        uint32_t *d_rows = nullptr;           // ... their device rows
-        double *d_w = nullptr;                // w_d as f64, kMaxLevels entries
+        DevPtr<unsigned long long> d_cnt;     // (kMaxLevels + 1) x 4 counters of the current batch
+        DevPtr<uint32_t> d_srcs;              // sids of a batch's sources (<= 512)
+        DevPtr<uint32_t> d_rows;              // ... their device rows
+        DevPtr<double> d_w;                   // w_d as f64, kMaxLevels entries
         std::vector<uint32_t> cand;           // the sampler's candidates (sids with an out-edge), ascending
         bool cand_valid = false;              // cand describes the loaded graph (built by the first sampler call after a load)
     } smp;
-    // hb_distances (hb_api_distance.inc): the BFS state and the last result, allocated at the first call after a load, freed with the graph
+    // hb_distances (hb_api_distance.inc): the BFS state and the last result, dev_alloc'ed at the first call after a load
     struct DistanceState {
         bool ready = false;     // the buffers below exist
         bool valid = false;     // they hold the result of a finished hb_distances
@@ -233,6 +210,93 @@ struct hb_ctx {
         uint64_t words_total = 0;            // words of d_vis / d_next
         uint64_t reached = 0;
     } dst;
+};
+
+struct hb_ctx : GraphDeviceState {
+    // ---- context lifetime: hb_create .. hb_destroy ------------------------------------------------------------------------------------
+    hb_options opt{};
+    int device = 0;
+    int num_cu = 256;
+    hipStream_t stream = nullptr;
+    ncclComm_t comm = nullptr;
+    hb_collectives coll{}; // hb_set_collectives: the per-pass exchanges go through these instead of RCCL (HB_FLAG_NO_RCCL contexts)
+    std::string err;
+    std::string arch;
+    uint64_t lim_records = 0, lim_bytes = 0, lim_chunk = 0; // hb_debug_set_ingest_limits (0 = no limit / default)
+    uint32_t max_passes = 4096;
+    void *h_block = nullptr;                  // ONE page-locked block, allocated by hb_create, that h_counters / h_slot / h_tl_count / h_rank_cnt are
+                                              // carved from: no hipHostMalloc ever happens inside a run (the first hb_run of a process is the ONLY one
+                                              // a drop-in user makes, entrypoint/centrality.rs:49)
+    unsigned long long *h_counters = nullptr; // kCounterWords words; [0..3] hold the stripe sums after a pass
+    unsigned long long *h_slot = nullptr;     // 2 x kCounterWords: the counters of the two passes in flight
+    uint32_t *h_tl_count = nullptr;           // kTcWords
+    unsigned long long *h_rank_cnt = nullptr; // world words
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // [5] = after the level-1 hub launch
+    // destination partition + changed-only: the pass' only host round trip sits in the MIDDLE of the pass (counters + run lengths,
+    // before the broadcasts); what follows it is left in flight, so the pass' timing events are read later (resolve_pass_times)
+    struct EvSet {
+        hipEvent_t e[6];
+    };
+    std::vector<EvSet> ev_pool;         // deferred timing (destination partition + changed-only on a communicator): one set per pass of a run
+    EvSet ev_ring[4]{};                 // hb_run's tail pipeline (two passes in flight): pass t uses set t & 3; created by hb_create
+    hipEvent_t tl_ev[2] = {nullptr, nullptr};
+    hipEvent_t slot_done[2] = {nullptr, nullptr};   // pass q's counters have arrived in h_slot[q & 1]
+    // edge partition with a communicator: the node rows are merged, all-reduced and finished in kOverlap row ranges - range
+    // k's ncclAllReduce runs on comm_stream while range k + 1 is still being merged, its epilogue while k + 1 is reduced
+    static constexpr int kOverlap = 4;
+    hipStream_t comm_stream = nullptr;
+    hipEvent_t ov_merged[kOverlap] = {nullptr, nullptr, nullptr, nullptr}, ov_reduced[kOverlap] = {nullptr, nullptr, nullptr, nullptr};
+    hipStream_t rs_stream = nullptr;                    // the result snapshots' downloads run here, beside the passes (GraphDeviceState::rs)
+    hipEvent_t rs_ready = nullptr, rs_copied = nullptr; // out[] built (main stream) / downloaded (side stream)
+
+    // ---- load lifetime: the input and the plan on the host, and the sizes plan_and_upload derives from them.  Every load rewrites them
+    // before `loaded` is set again; free_graph_buffers() does not touch them -------------------------------------------------------------
+    std::vector<hb_edge> pending;  // hb_append_edges, host-ingest mode only
+    // hb_append_edges, default: records are unpacked on the device as they arrive (2 x 16-byte endpoint keys + 1
+    // flag byte each); nothing is buffered on the host
+    IngestStream app;
+    DenseGraph g;                  // ids kept; row_ptr/src kept only for hb_debug_copy_graph
+    Plan plan;
+    bool loaded = false, begun = false, finished = false;
+    std::vector<DevBuf> allocs;   // what dev_alloc / adopt gave the graph state above; hb_stats.device_bytes is their sum
+    uint64_t m_global = 0;        // edges of the whole graph (all ranks)
+    uint64_t plan_entries = 0; // entries of all work rows' source lists
+    uint64_t bits_words = 0;
+    uint64_t ksum_len = 0; // entries allocated for ksum (world * slice in RCCL mode)
+    uint64_t slice_rows = 0;
+    uint64_t bloom_bits = 0;        // (hb_begin) bits of d_bloom
+    uint64_t ref_threshold = 0;     // (hb_begin) exact_counting_threshold (harmonic.rs:228)
+    hb_stats stats{};
+
+    // ---- run lifetime: hb_begin .. hb_finish (or one call of hb_sampled_harmonic / hb_distances) ------------------------------------
+    bool lean_init = false; // hb_begin left the initial counters / Kahan words / sizes to pass 0 (PassParams::rd_init); cleared by pass 0, or by
+                            // ensure_initial_state() when something wants to look at the state before pass 0
+    uint64_t t = 0;
+    int cur = 0; // d_regs[cur] = "old"
+    bool has_changes = false;
+    bool pending_local = false; // between hb_step_local and hb_step_finish
+    uint64_t last_changed = 0;
+    uint64_t last_active = 0;     // out-degree sum of the nodes changed in the previous pass
+    std::vector<hb_pass_stats> pstats;
+    uint64_t co_rows = 0;     // rows in the union of this pass
+    std::vector<uint64_t> ex_off; // world + 1: first packed position of every rank's slice
+    std::vector<uint64_t> pending_times; // passes whose ms_* fields still have to be read from their events
+    // hb_run's tail pipeline: pass q + 1 is queued (guarded on the device by pass q's changed count) before pass q's counters are
+    // read, so the convergence tail runs without a host round trip between passes
+    const unsigned long long *spec_guard = nullptr; // set while step_local queues a guarded pass
+    bool pipelined = false;                         // step_local: take this pass' events from ev_pool
+    uint64_t pipelined_passes = 0;                  // passes of this run queued ahead of their predecessor's read-back
+    bool tl_declined = false;       // the tail kernel found the next pass too large for its lists: do not ask again before an ordinary pass has run
+    uint64_t tail_kernel_passes = 0;
+    uint64_t wire_bytes = 0;      // counter bytes this rank received over the run (changed-only accounting)
+    bool exact_counting = false;    // harmonic.rs:231,277-279
+    bool exact_valid = false;       // the previous pass filled exact_changed_nodes (ran with Some(..) or was a tail pass)
+    bool stale = false;             // a tail pass has run: host-level edges may have been skipped, the bloom filter's
+                                    // false positives are no longer results-inert
+    uint64_t ov_lo[kOverlap + 1] = {0, 0, 0, 0, 0};
+    int ov_ranges = 0; // ranges of the pending pass (0 = one launch over all rows, no overlap)
+    uint32_t cur_mode = 0;
+    uint64_t res_count = 0;
 };
 
 namespace {
@@ -272,80 +336,66 @@ int dev_alloc(hb_ctx *c, T **out, size_t count)
     return HB_OK;
 }
 
+// The same, but the failure is reported as `what` + the error string (messages that name the step rather than the call)
+#define HB_HIP_AS(what, call)                                                                     \
+    do {                                                                                          \
+        hipError_t e_ = (call);                                                                   \
+        if (e_ != hipSuccess) return fail(c, HB_ERR_HIP, std::string(what) + hipGetErrorString(e_)); \
+    } while (0)
+
 void free_graph_buffers(hb_ctx *c)
 {
+    if (c->rs_stream) (void)hipStreamSynchronize(c->rs_stream); // (a snapshot may still be landing in h_out)
     for (auto &b : c->allocs) (void)hipFree(b.p);
     c->allocs.clear();
-    c->stats.device_bytes = 0;
-    c->d_row_ptr = nullptr;
-    c->d_src = nullptr;
-    c->d_src_jp = nullptr;
-    c->d_self_jp = nullptr;
-    c->d_virt_rows = nullptr;
-    c->level0_all_real = false;
-    c->d_regs[0] = c->d_regs[1] = nullptr;
-    c->d_part = nullptr;
-    c->d_bits[0] = c->d_bits[1] = nullptr;
-    c->d_kdirty = nullptr;
-    c->d_ksum = c->d_kerr = nullptr;
-    c->d_size = nullptr;
-    c->d_idlow = nullptr;
-    c->d_dev_of = nullptr;
-    c->d_sid_of = nullptr;
-    c->d_outdeg = nullptr;
-    c->d_counters = nullptr;
-    c->d_raw = c->d_bias = nullptr;
-    c->d_lc = nullptr;
-    c->d_out = nullptr;
-    c->d_cid_of = nullptr;
-    c->out_len = 0;
-    std::vector<uint64_t>().swap(c->h_in_bits);
-    c->d_pack = nullptr;
-    c->d_wpop = nullptr;
-    c->d_wprefix = nullptr;
-    c->d_lbits = c->d_lbits_all = c->d_ubits = nullptr;
-    c->d_rank_cnt = nullptr;
-    c->ubits_valid = false;
-    c->d_out_ptr = nullptr;
-    c->d_out_rows = nullptr;
-    c->d_touch = nullptr;
-    c->d_seeds = c->d_heavy = nullptr;
-    c->d_sparse_counts = nullptr;
-    c->sparse_ok = false;
-    c->d_tl_changed[0] = c->d_tl_changed[1] = c->d_tl_vchanged[0] = c->d_tl_vchanged[1] = c->d_tl_dirty[0] = c->d_tl_dirty[1] = nullptr;
-    c->d_tl_work = c->d_tl_count = nullptr;
-    c->tl_valid = false;
-    c->d_tail_ptr = nullptr;
-    c->d_tail_to = nullptr;
-    c->tail_count = 0;
-    std::vector<uint64_t>().swap(c->tail_keys);
-    std::vector<TailDoc>().swap(c->tail_open);
-    c->tail_dirty = false;
-    tail_index_free(c->tail_index);
-    c->tail_index = nullptr;
-    c->d_bloom = nullptr;
-    c->d_bloom_ones = nullptr;
-    c->d_list = nullptr;
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    c->h_out = nullptr;
-    c->h_out_len = 0;
-    if (c->rs.stream) (void)hipStreamSynchronize(c->rs.stream);
-    for (void *q : {(void *)c->rs.h_sid, (void *)c->rs.h_val, (void *)c->rs.h_count})
+    for (void *q : {(void *)c->h_out, (void *)c->rs.h_sid, (void *)c->rs.h_val, (void *)c->rs.h_count})
         if (q) (void)hipHostFree(q);
-    c->rs.h_sid = nullptr;
-    c->rs.h_val = nullptr;
-    c->rs.h_count = nullptr;
-    c->rs.d_sent = nullptr;
-    c->rs.d_sid = nullptr;
-    c->rs.d_val = nullptr;
-    c->rs.d_count = nullptr;
-    c->rs.d_kept = nullptr;
-    c->rs.cap = 0;
-    c->rs.on = c->rs.valid = false;
-    for (void *q : {(void *)c->smp.d_hist, (void *)c->smp.d_cnt, (void *)c->smp.d_srcs, (void *)c->smp.d_rows, (void *)c->smp.d_w})
-        if (q) (void)hipFree(q);
-    c->smp = hb_ctx::SampleState{};
-    c->dst = hb_ctx::DistanceState{}; // (its buffers were dev_alloc'ed: freed with the list above)
+    tail_index_free(c->tail_index);
+    static_cast<GraphDeviceState &>(*c) = GraphDeviceState{}; // (the sampled operator's holders free their buffers here)
+    c->stats.device_bytes = 0;
+}
+
+// ---- the operators' common prologue ----------------------------------------------------------------------------------------------
+// Versioned structs of the C ABI (include/hyperball.h): the caller says how much of the struct it knows in struct_size (0 = all of it);
+// that many bytes are copied, the rest of an input keeps its defaults, and an output's struct_size says how many were written.
+template <class T>
+void copy_in(const T *from, T *to)
+{
+    if (from) std::memcpy(to, from, from->struct_size ? std::min<size_t>(from->struct_size, sizeof(T)) : sizeof(T));
+}
+template <class T>
+void copy_out(T *to, T &from)
+{
+    if (!to) return;
+    const size_t sz = to->struct_size ? std::min<size_t>(to->struct_size, sizeof(T)) : sizeof(T);
+    from.struct_size = (uint32_t)sz;
+    std::memcpy(to, &from, sz);
+}
+
+// an unchecked failure of an earlier call on this thread would be reported by the first HB_HIP(hipGetLastError()) of `who`
+int refuse_stale_error(hb_ctx *c, const char *who)
+{
+    const hipError_t stale = hipGetLastError();
+    if (stale != hipSuccess) return fail(c, HB_ERR_HIP, std::string("stale HIP error before ") + who + ": " + hipGetErrorString(stale));
+    return HB_OK;
+}
+
+// NodeID -> sid of the loaded graph (c->g.ids is ascending); false = not a node
+bool find_sid(const hb_ctx *c, const hb_u128 &id, uint32_t *sid)
+{
+    const auto it = std::lower_bound(c->g.ids.begin(), c->g.ids.end(), id, u128_less);
+    if (it == c->g.ids.end() || !u128_eq(*it, id)) return false;
+    *sid = (uint32_t)(it - c->g.ids.begin());
+    return true;
+}
+
+// the bit-per-row kernels of the operators walk the plan in 32-row words: the node rows and every virtual level begin on one
+int plan_rows_word_aligned(hb_ctx *c, const char *who)
+{
+    const Plan &p = c->plan;
+    if (p.n_pad % 32 || std::any_of(p.level_begin.begin(), p.level_begin.end(), [](uint64_t b) { return b % 32 != 0; }))
+        return fail(c, HB_ERR_INVALID, std::string(who) + ": unexpected plan layout (a level does not begin on a 32-row word)");
+    return HB_OK;
 }
 
 // hb_options.chunk / tune[3..5] -> planner knobs
@@ -575,12 +625,8 @@ int hb_create(const hb_options *opt, hb_ctx **out)
         if (!out) return fail(c, HB_ERR_INVALID, "out == NULL");
         *out = nullptr;
         hb_options o{};
-        if (opt) {
-            size_t sz = opt->struct_size ? std::min<size_t>(opt->struct_size, sizeof(hb_options)) : sizeof(hb_options);
-            std::memcpy(&o, opt, sz);
-        } else {
-            o.device = -1;
-        }
+        if (!opt) o.device = -1;
+        copy_in(opt, &o);
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
             return fail(c, HB_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU fallback");
@@ -643,9 +689,9 @@ int hb_create(const hb_options *opt, hb_ctx **out)
         for (auto &es : ctx->ev_ring)
             for (auto &e : es.e)
                 if (hipEventCreate(&e) != hipSuccess) { ctx->err = "hipEventCreate failed"; return bail(HB_ERR_HIP); }
-        if (hipStreamCreateWithFlags(&ctx->rs.stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&ctx->rs.ready, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&ctx->rs.copied, hipEventDisableTiming) != hipSuccess) { ctx->err = "hipStreamCreate / hipEventCreate failed"; return bail(HB_ERR_HIP); }
+        if (hipStreamCreateWithFlags(&ctx->rs_stream, hipStreamNonBlocking) != hipSuccess ||
+            hipEventCreateWithFlags(&ctx->rs_ready, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&ctx->rs_copied, hipEventDisableTiming) != hipSuccess) { ctx->err = "hipStreamCreate / hipEventCreate failed"; return bail(HB_ERR_HIP); }
         if ((o.world_size > 1 && !(o.flags & HB_FLAG_NO_RCCL)) || (o.flags & HB_FLAG_RCCL_SELF)) {
             if (hipStreamCreateWithFlags(&ctx->comm_stream, hipStreamNonBlocking) != hipSuccess) { ctx->err = "hipStreamCreate failed"; return bail(HB_ERR_HIP); }
             for (int i = 0; i < hb_ctx::kOverlap; i++)
@@ -700,9 +746,9 @@ void hb_destroy(hb_ctx *ctx)
         (void)hipStreamSynchronize(ctx->comm_stream);
         (void)hipStreamDestroy(ctx->comm_stream);
     }
-    if (ctx->rs.ready) (void)hipEventDestroy(ctx->rs.ready);
-    if (ctx->rs.copied) (void)hipEventDestroy(ctx->rs.copied);
-    if (ctx->rs.stream) (void)hipStreamDestroy(ctx->rs.stream);
+    if (ctx->rs_ready) (void)hipEventDestroy(ctx->rs_ready);
+    if (ctx->rs_copied) (void)hipEventDestroy(ctx->rs_copied);
+    if (ctx->rs_stream) (void)hipStreamDestroy(ctx->rs_stream);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -761,12 +807,12 @@ int hb_load_edges(hb_ctx *c, const hb_u128 *node_ids, uint64_t n, const hb_edge 
             const double need = 18.0 * (double)m + 48.0 * (double)((node_ids && n) ? n : 0) + 160.0 * endpoints + 1024e6;
             if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > (double)free_b + (double)HB_POOL_CACHED_FREE()) on_host = true;
         }
-        DeviceCsr csr;
+        OwnedCsr csr;
         const bool keep_on_device = !on_host && device_plan(c);
         uint64_t peak = 0;
         const uint64_t skip = skip_mask(c);
         std::string e = on_host ? ingest_edges(node_ids, n, edges, m, &c->g, skip)
-                                : gpu_ingest_edges((void *)c->stream, node_ids, n, edges, m, &c->g, keep_on_device ? &csr : nullptr, &peak, skip);
+                                : gpu_ingest_edges((void *)c->stream, node_ids, n, edges, m, &c->g, keep_on_device ? &csr.d : nullptr, &peak, skip);
         // (the id space of the device table exhausted is a limit of the DEVICE ingest only: endpoints outside a caller-supplied
         // node list are legal and ignored by the reference, store.rs:338-357 - the host path takes over, like for memory)
         if (!on_host && !e.empty() && (e.find("out of memory") != std::string::npos || e.find("OutOfMemory") != std::string::npos ||
@@ -777,20 +823,12 @@ int hb_load_edges(hb_ctx *c, const hb_u128 *node_ids, uint64_t n, const hb_edge 
         }
         if (!e.empty())
             return fail(c, e.find("memory") != std::string::npos ? HB_ERR_NOMEM : (e.find("hip") != std::string::npos ? HB_ERR_HIP : HB_ERR_LIMIT), e);
-        if ((rc = keep_owned(c, &csr))) {
-            if (csr.d_row_ptr) (void)hipFree(csr.d_row_ptr);
-            if (csr.d_src) (void)hipFree(csr.d_src);
-            if (csr.d_id_lo) (void)hipFree(csr.d_id_lo);
-            return rc;
-        }
+        if ((rc = keep_owned(c, &csr.d))) return rc;
         const uint64_t nn = c->g.ids.size();
-        const uint64_t m_eff = csr.d_row_ptr ? csr.m : (nn && c->g.row_ptr.size() == nn + 1 ? c->g.row_ptr[nn] : 0);
+        const uint64_t m_eff = csr.d.d_row_ptr ? csr.d.m : (nn && c->g.row_ptr.size() == nn + 1 ? c->g.row_ptr[nn] : 0);
         c->stats.ms_ingest = now_ms() - t0;
         double ing = c->stats.ms_ingest;
-        rc = plan_and_upload(c, csr.d_row_ptr ? &csr : nullptr, m_eff);
-        if (csr.d_row_ptr) (void)hipFree(csr.d_row_ptr); // only if plan_and_upload bailed out before taking them
-        if (csr.d_src) (void)hipFree(csr.d_src);
-            if (csr.d_id_lo) (void)hipFree(csr.d_id_lo);
+        rc = plan_and_upload(c, std::move(csr), m_eff);
         c->stats.ms_ingest = ing;
         c->stats.ingest_peak_bytes = peak;
         return rc;
@@ -843,26 +881,18 @@ int hb_finalize(hb_ctx *c, const hb_u128 *node_ids, uint64_t n)
         c->stats = hb_stats{};
         const double t0 = now_ms();
         const bool trace = std::getenv("HB_TRACE_INGEST") != nullptr;
-        DeviceCsr csr;
+        OwnedCsr csr;
         const bool keep_on_device = device_plan(c);
         uint64_t peak = 0;
-        const std::string e = gpu_ingest_reduce((void *)c->stream, node_ids, n, &c->app, &c->g, keep_on_device ? &csr : nullptr, &peak);
+        const std::string e = gpu_ingest_reduce((void *)c->stream, node_ids, n, &c->app, &c->g, keep_on_device ? &csr.d : nullptr, &peak);
         if (trace) std::fprintf(stderr, "[hb finalize] gpu_ingest_reduce returned after %.1f ms\n", now_ms() - t0);
         if (!e.empty())
             return fail(c, e.find("memory") != std::string::npos ? HB_ERR_NOMEM : (e.find("hip") != std::string::npos ? HB_ERR_HIP : HB_ERR_LIMIT), e);
-        if ((rc = keep_owned(c, &csr))) {
-            if (csr.d_row_ptr) (void)hipFree(csr.d_row_ptr);
-            if (csr.d_src) (void)hipFree(csr.d_src);
-            if (csr.d_id_lo) (void)hipFree(csr.d_id_lo);
-            return rc;
-        }
+        if ((rc = keep_owned(c, &csr.d))) return rc;
         const uint64_t nn = c->g.ids.size();
-        const uint64_t m_eff = csr.d_row_ptr ? csr.m : (nn && c->g.row_ptr.size() == nn + 1 ? c->g.row_ptr[nn] : 0);
+        const uint64_t m_eff = csr.d.d_row_ptr ? csr.d.m : (nn && c->g.row_ptr.size() == nn + 1 ? c->g.row_ptr[nn] : 0);
         const double ing = now_ms() - t0;
-        rc = plan_and_upload(c, csr.d_row_ptr ? &csr : nullptr, m_eff);
-        if (csr.d_row_ptr) (void)hipFree(csr.d_row_ptr);
-        if (csr.d_src) (void)hipFree(csr.d_src);
-            if (csr.d_id_lo) (void)hipFree(csr.d_id_lo);
+        rc = plan_and_upload(c, std::move(csr), m_eff);
         c->stats.ms_ingest = ing;
         c->stats.ingest_peak_bytes = peak;
         if (trace) std::fprintf(stderr, "[hb finalize] done after %.1f ms (plan %.1f ms, state %.1f ms)\n", now_ms() - t0, c->stats.ms_plan, c->stats.ms_h2d);
@@ -941,16 +971,14 @@ int hb_debug_h2d_rate(hb_ctx *c, const void *host, uint64_t bytes, int reps, dou
         if (!c || !host || !bytes || reps < 1 || !gb_per_s) return HB_ERR_INVALID;
         int rc = set_device(c);
         if (rc) return rc;
-        void *d = nullptr;
-        HB_HIP(hipMalloc(&d, bytes));
-        hipError_t e = hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, c->stream); // warm-up (first touch of the mapping)
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        DevPtr<uint8_t> d;
+        HB_HIP(d.alloc(bytes));
+        HB_HIP_AS("hb_debug_h2d_rate: ", hipMemcpyAsync(d.get(), host, bytes, hipMemcpyHostToDevice, c->stream)); // warm-up (first touch of the mapping)
+        HB_HIP_AS("hb_debug_h2d_rate: ", hipStreamSynchronize(c->stream));
         const double t0 = now_ms();
-        for (int r = 0; r < reps && e == hipSuccess; r++) e = hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        for (int r = 0; r < reps; r++) HB_HIP_AS("hb_debug_h2d_rate: ", hipMemcpyAsync(d.get(), host, bytes, hipMemcpyHostToDevice, c->stream));
+        HB_HIP_AS("hb_debug_h2d_rate: ", hipStreamSynchronize(c->stream));
         const double ms = now_ms() - t0;
-        (void)hipFree(d);
-        if (e != hipSuccess) return fail(c, HB_ERR_HIP, std::string("hb_debug_h2d_rate: ") + hipGetErrorString(e));
         *gb_per_s = (double)bytes * reps / (ms * 1e-3) / 1e9;
         return HB_OK;
     });
@@ -1038,33 +1066,21 @@ int hb_load_dense(hb_ctx *c, const hb_u128 *sorted_ids, uint64_t n, const uint64
         }
         c->g.m_input = m_eff;
         c->g.m_unique = m_eff;
-        DeviceCsr csr;
+        OwnedCsr csr;
         if (on_device && n) { // straight from the caller's arrays to the device: no host copy of a multi-GB CSR
-            HB_HIP(hipMalloc((void **)&csr.d_row_ptr, (n + 1) * sizeof(uint64_t)));
-            hipError_t he = hipMalloc((void **)&csr.d_src, std::max<uint64_t>(m_eff, 1) * sizeof(uint32_t));
-            if (he == hipSuccess) he = hipMemcpyAsync(csr.d_row_ptr, row_ptr, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
-            if (he == hipSuccess && m_eff) he = hipMemcpyAsync(csr.d_src, src, m_eff * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+            HB_HIP(hipMalloc((void **)&csr.d.d_row_ptr, (n + 1) * sizeof(uint64_t)));
+            hipError_t he = hipMalloc((void **)&csr.d.d_src, std::max<uint64_t>(m_eff, 1) * sizeof(uint32_t));
+            if (he == hipSuccess) he = hipMemcpyAsync(csr.d.d_row_ptr, row_ptr, (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream);
+            if (he == hipSuccess && m_eff) he = hipMemcpyAsync(csr.d.d_src, src, m_eff * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
             if (he == hipSuccess) he = hipStreamSynchronize(c->stream);
-            if (he != hipSuccess) {
-                (void)hipFree(csr.d_row_ptr);
-                if (csr.d_src) (void)hipFree(csr.d_src);
-            if (csr.d_id_lo) (void)hipFree(csr.d_id_lo);
+            if (he != hipSuccess) // (one message and the out-of-memory code for whichever step failed)
                 return fail(c, he == hipErrorOutOfMemory ? HB_ERR_NOMEM : HB_ERR_HIP, std::string("uploading the graph: ") + hipGetErrorString(he));
-            }
-            csr.m = m_eff;
+            csr.d.m = m_eff;
         }
-        if ((rc = keep_owned(c, &csr))) {
-            if (csr.d_row_ptr) (void)hipFree(csr.d_row_ptr);
-            if (csr.d_src) (void)hipFree(csr.d_src);
-            if (csr.d_id_lo) (void)hipFree(csr.d_id_lo);
-            return rc;
-        }
-        const uint64_t m_local = csr.d_row_ptr ? csr.m : ((dest_mode(c) && n) ? c->g.row_ptr[n] : m_eff);
+        if ((rc = keep_owned(c, &csr.d))) return rc;
+        const uint64_t m_local = csr.d.d_row_ptr ? csr.d.m : ((dest_mode(c) && n) ? c->g.row_ptr[n] : m_eff);
         double ing = now_ms() - t0;
-        rc = plan_and_upload(c, csr.d_row_ptr ? &csr : nullptr, m_local);
-        if (csr.d_row_ptr) (void)hipFree(csr.d_row_ptr);
-        if (csr.d_src) (void)hipFree(csr.d_src);
-            if (csr.d_id_lo) (void)hipFree(csr.d_id_lo);
+        rc = plan_and_upload(c, std::move(csr), m_local);
         c->stats.ms_ingest = ing;
         return rc;
     });
@@ -1080,10 +1096,7 @@ int hb_begin(hb_ctx *c)
         if (rc) return rc;
         const Plan &p = c->plan;
         if (p.n_pad * 4 >= 0xFFFFFFFFull) return fail(c, HB_ERR_LIMIT, "more than 2^30 nodes: init_kernel is one quad per node in one dispatch");
-        {
-            hipError_t stale = hipGetLastError(); // an unchecked failure of an earlier call on this thread
-            if (stale != hipSuccess) return fail(c, HB_ERR_HIP, std::string("stale HIP error before hb_begin: ") + hipGetErrorString(stale));
-        }
+        if ((rc = refuse_stale_error(c, "hb_begin"))) return rc;
         // d_part needs no clearing: pass 0 is always dense, and a dense pass overwrites every partial without
         // reading it (hb_kernels.hip.h)
         HB_HIP(hipMemsetAsync(c->d_bits[0], 0, c->bits_words * 4, c->stream));
@@ -1122,7 +1135,7 @@ int hb_begin(hb_ctx *c)
             c->exact_counting = c->exact_valid = c->stale = false;
         }
         HB_HIP(hipStreamSynchronize(c->stream));
-        if (c->rs.stream) HB_HIP(hipStreamSynchronize(c->rs.stream)); // (a download of an abandoned run)
+        if (c->rs_stream) HB_HIP(hipStreamSynchronize(c->rs_stream)); // (a download of an abandoned run)
         c->rs.valid = false;
         c->rs.changed_since = 0;
         c->rs.stages = 0;
@@ -1227,10 +1240,10 @@ int hb_finish(hb_ctx *c)
                     HB_HIP(hipMemcpyAsync(rs.h_val, rs.d_val, moved * sizeof(double), hipMemcpyDeviceToHost, c->stream));
                     HB_HIP(hipStreamSynchronize(c->stream));
                 }
-                HB_HIP(hipEventSynchronize(rs.copied)); // the snapshot's download is over before the list is applied on top of it
+                HB_HIP(hipEventSynchronize(c->rs_copied)); // the snapshot's download is over before the list is applied on top of it
                 host_scatter_f64(c->h_out, rs.h_sid, rs.h_val, moved); // every sid occurs once: the shares are independent (hb_host.cpp, OpenMP team)
             } else { // more moved than the list holds: out[] on the device is complete anyway, ship it whole
-                HB_HIP(hipStreamWaitEvent(c->stream, rs.copied, 0)); // (behind the snapshot's download: both write h_out)
+                HB_HIP(hipStreamWaitEvent(c->stream, c->rs_copied, 0)); // (behind the snapshot's download: both write h_out)
                 HB_HIP(hipMemcpyAsync(c->h_out, c->d_out, c->out_len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
                 HB_HIP(hipStreamSynchronize(c->stream));
             }

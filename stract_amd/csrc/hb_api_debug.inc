@@ -11,15 +11,13 @@ int hb_debug_copy_registers(hb_ctx *c, uint8_t *out)
         if ((rc = ensure_initial_state(c))) return rc;
         const uint64_t n = c->plan.n;
         if (!n) return HB_OK;
-        uint4 *tmp = nullptr;
-        HB_HIP(hipMalloc((void **)&tmp, n * 64));
+        DevPtr<uint4> tmp;
+        HB_HIP(tmp.alloc(n * 4));
         unsigned blocks = (unsigned)((n * 4 + 255) / 256);
         hipLaunchKernelGGL(hbk::gather_rows_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint4 *)c->d_regs[c->cur],
-                           (const uint32_t *)c->d_dev_of, n, tmp);
-        hipError_t e = hipMemcpyAsync(out, tmp, n * 64, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(tmp);
-        if (e != hipSuccess) return fail(c, HB_ERR_HIP, hipGetErrorString(e));
+                           (const uint32_t *)c->d_dev_of, n, tmp.get());
+        HB_HIP_AS("", hipMemcpyAsync(out, tmp.get(), n * 64, hipMemcpyDeviceToHost, c->stream));
+        HB_HIP_AS("", hipStreamSynchronize(c->stream));
         return HB_OK;
     });
 }
@@ -73,31 +71,27 @@ int hb_debug_hll_size(hb_ctx *c, const uint8_t *regs, uint64_t count, uint64_t *
         if (rc) return rc;
         if (!count) return HB_OK;
         // tables may not be on the device yet (no graph loaded): stage private copies
-        double *d_raw = nullptr, *d_bias = nullptr;
-        uint8_t *d_lc = nullptr, *d_regs = nullptr;
-        uint64_t *d_out = nullptr;
+        DevPtr<double> d_raw, d_bias;
+        DevPtr<uint8_t> d_lc, d_regs;
+        DevPtr<uint64_t> d_out;
         uint8_t lc[68];
         if (!build_lc_table(lc)) return fail(c, HB_ERR_INVALID, "linear-counting table not robust on this libm");
         const uint64_t rows_pad = (count + 15) & ~15ull;
-        hipError_t e = hipMalloc((void **)&d_raw, sizeof(HLL64_RAW_ESTIMATE));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_bias, sizeof(HLL64_BIAS));
-        if (e == hipSuccess) e = hipMalloc((void **)&d_lc, 256);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_regs, rows_pad * 64);
-        if (e == hipSuccess) e = hipMalloc((void **)&d_out, rows_pad * 8);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_raw, HLL64_RAW_ESTIMATE, sizeof(HLL64_RAW_ESTIMATE), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_bias, HLL64_BIAS, sizeof(HLL64_BIAS), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_lc, lc, 68, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_regs, regs, count * 64, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            unsigned blocks = (unsigned)((rows_pad * 4 + 255) / 256);
-            hipLaunchKernelGGL(hbk::hll_size_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint4 *)d_regs, count, d_out,
-                               (const double *)d_raw, (const double *)d_bias, (const uint8_t *)d_lc);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, count * 8, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_raw); (void)hipFree(d_bias); (void)hipFree(d_lc); (void)hipFree(d_regs); (void)hipFree(d_out);
-        if (e != hipSuccess) return fail(c, HB_ERR_HIP, hipGetErrorString(e));
+        HB_HIP_AS("", d_raw.alloc(HLL64_TABLE_LEN));
+        HB_HIP_AS("", d_bias.alloc(HLL64_TABLE_LEN));
+        HB_HIP_AS("", d_lc.alloc(256));
+        HB_HIP_AS("", d_regs.alloc(rows_pad * 64));
+        HB_HIP_AS("", d_out.alloc(rows_pad));
+        HB_HIP_AS("", hipMemcpyAsync(d_raw.get(), HLL64_RAW_ESTIMATE, sizeof(HLL64_RAW_ESTIMATE), hipMemcpyHostToDevice, c->stream));
+        HB_HIP_AS("", hipMemcpyAsync(d_bias.get(), HLL64_BIAS, sizeof(HLL64_BIAS), hipMemcpyHostToDevice, c->stream));
+        HB_HIP_AS("", hipMemcpyAsync(d_lc.get(), lc, 68, hipMemcpyHostToDevice, c->stream));
+        HB_HIP_AS("", hipMemcpyAsync(d_regs.get(), regs, count * 64, hipMemcpyHostToDevice, c->stream));
+        unsigned blocks = (unsigned)((rows_pad * 4 + 255) / 256);
+        hipLaunchKernelGGL(hbk::hll_size_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint4 *)d_regs.get(), count, d_out.get(),
+                           (const double *)d_raw.get(), (const double *)d_bias.get(), (const uint8_t *)d_lc.get());
+        HB_HIP_AS("", hipGetLastError());
+        HB_HIP_AS("", hipMemcpyAsync(out, d_out.get(), count * 8, hipMemcpyDeviceToHost, c->stream));
+        HB_HIP_AS("", hipStreamSynchronize(c->stream));
         return HB_OK;
     });
 }

@@ -86,7 +86,7 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
 {
     const double t0 = now_ms();
     hb_distance_options o{};
-    if (opt_in) std::memcpy(&o, opt_in, opt_in->struct_size ? std::min<size_t>(opt_in->struct_size, sizeof(o)) : sizeof(o));
+    copy_in(opt_in, &o);
     if (multi_rank(c)) return fail(c, HB_ERR_INVALID, "hb_distances: single rank only (world_size > 1)");
     if (!c->loaded) return fail(c, HB_ERR_INVALID, "hb_distances: no graph loaded");
     if (!o.sources || !o.source_count) return fail(c, HB_ERR_INVALID, "hb_distances: no sources (source_count == 0)");
@@ -94,38 +94,30 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
         return fail(c, HB_ERR_INVALID, "hb_distances: HB_DIST_TOP_DOWN_ONLY and HB_DIST_BOTTOM_UP_ONLY exclude each other");
     if ((o.flags & HB_DIST_WITH_MAX) && o.max_dist > 255) return fail(c, HB_ERR_INVALID, "hb_distances: max_dist > 255 (the reference's is a u8)");
     const Plan &p = c->plan;
-    if (p.n_pad % 32) return fail(c, HB_ERR_INVALID, "hb_distances: unexpected plan layout");
+    int rc;
+    if ((rc = plan_rows_word_aligned(c, "hb_distances"))) return rc;
     for (uint64_t b : p.level_begin)
-        if (b % 32 || b < p.n_pad || b > p.n_pad + p.nv) return fail(c, HB_ERR_INVALID, "hb_distances: unexpected plan layout (virtual level boundary)");
-    {
-        hipError_t stale = hipGetLastError();
-        if (stale != hipSuccess) return fail(c, HB_ERR_HIP, std::string("stale HIP error before hb_distances: ") + hipGetErrorString(stale));
-    }
+        if (b < p.n_pad || b > p.n_pad + p.nv) return fail(c, HB_ERR_INVALID, "hb_distances: unexpected plan layout (virtual level boundary)");
+    if ((rc = refuse_stale_error(c, "hb_distances"))) return rc;
     auto &d = c->dst;
     d.valid = d.extracted = false;
     d.reached = 0;
     hb_distance_stats st{};
     auto finish = [&]() {
         st.ms_total = now_ms() - t0;
-        if (st_out) {
-            const size_t sz = st_out->struct_size ? std::min<size_t>(st_out->struct_size, sizeof(st)) : sizeof(st);
-            st.struct_size = (uint32_t)sz;
-            std::memcpy(st_out, &st, sz);
-        }
+        copy_out(st_out, st);
         return HB_OK;
     };
     // the sources as distinct sids
     std::vector<uint32_t> sids;
     sids.reserve(o.source_count);
     for (uint64_t i = 0; i < o.source_count; i++) {
-        const hb_u128 id = o.sources[i];
-        auto it = std::lower_bound(c->g.ids.begin(), c->g.ids.end(), id, u128_less);
-        if (it == c->g.ids.end() || !u128_eq(*it, id)) st.unknown_sources++;
-        else sids.push_back((uint32_t)(it - c->g.ids.begin()));
+        uint32_t sid;
+        if (find_sid(c, o.sources[i], &sid)) sids.push_back(sid);
+        else st.unknown_sources++;
     }
     std::sort(sids.begin(), sids.end());
     sids.erase(std::unique(sids.begin(), sids.end()), sids.end());
-    int rc;
     if (p.n == 0) { // an empty graph: every source is unknown
         d.valid = true;
         return finish();
@@ -161,18 +153,15 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
     unsigned long long *h = c->h_counters; // (pinned words of the context; hb_run rewrites them before it reads them)
     uint64_t n_f = 0, m_f = 0;
     if (!sids.empty()) {
-        uint32_t *d_srcs = nullptr;
-        HB_HIP(hipMalloc((void **)&d_srcs, sids.size() * sizeof(uint32_t)));
-        hipError_t e = hipMemcpyAsync(d_srcs, sids.data(), sids.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(hbk::bfs_seed_kernel, dim3((unsigned)((sids.size() + 255) / 256)), dim3(256), 0, c->stream, (const uint32_t *)d_srcs,
-                               (uint32_t)sids.size(), (const uint32_t *)c->d_dev_of, bp);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(h, d.d_cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_srcs);
-        if (e != hipSuccess) return fail(c, HB_ERR_HIP, std::string("hb_distances: seeding the sources: ") + hipGetErrorString(e));
+        const char *const what = "hb_distances: seeding the sources: ";
+        DevPtr<uint32_t> d_srcs;
+        HB_HIP(d_srcs.alloc(sids.size()));
+        HB_HIP_AS(what, hipMemcpyAsync(d_srcs.get(), sids.data(), sids.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(hbk::bfs_seed_kernel, dim3((unsigned)((sids.size() + 255) / 256)), dim3(256), 0, c->stream, (const uint32_t *)d_srcs.get(),
+                           (uint32_t)sids.size(), (const uint32_t *)c->d_dev_of, bp);
+        HB_HIP_AS(what, hipGetLastError());
+        HB_HIP_AS(what, hipMemcpyAsync(h, d.d_cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HB_HIP_AS(what, hipStreamSynchronize(c->stream));
         n_f = h[0];
         m_f = h[1];
     }

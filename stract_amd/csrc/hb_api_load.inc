@@ -29,10 +29,12 @@ __global__ __launch_bounds__(256) void idlow_kernel(const uint64_t *lo_by_sid, c
     idlow[d] = s == kNone ? 0ull : lo_by_sid[s];
 }
 
-void adopt(hb_ctx *c, void *p, size_t bytes) // a buffer allocated elsewhere becomes the context's
+template <class T>
+T *adopt(hb_ctx *c, DevPtr<T> &b, size_t bytes) // a buffer allocated elsewhere becomes the context's
 {
-    c->allocs.push_back({p, bytes});
+    c->allocs.push_back({b.get(), bytes});
     c->stats.device_bytes += bytes;
+    return b.release();
 }
 
 // Page-locked result buffers are touched by the host for the first time at LOAD, not by the run: the CPU mapping of a hipHostMalloc
@@ -108,7 +110,8 @@ struct HostResultBuffers {
 // launch has row_lo == row_hi (no tile, no seed, no word) and adds zero to its counter stripes.
 int warm_kernels(hb_ctx *c);
 
-int plan_and_upload(hb_ctx *c, DeviceCsr *csr_in, uint64_t m_eff)
+// `in`: the reduced graph on the device, if the ingest left it there (else empty: uploaded here from c->g); freed when the plan exists
+int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
 {
     const uint64_t n = c->g.ids.size();
     c->loaded = false;
@@ -126,20 +129,7 @@ int plan_and_upload(hb_ctx *c, DeviceCsr *csr_in, uint64_t m_eff)
     c->rs.cap = c->rs.on ? ((HB_XBITS(c->opt.tune[1]) & 0x10000u) ? 16 : n / 8 + 4096) : 0; // (bit 16: a list that overflows - the test of that path)
     HostResultBuffers hostbuf; // (declared here: joined, and what the context has not taken freed, on every return path below)
     hostbuf.start(c->device, n, c->rs.cap);
-    // the input CSR on the device (uploaded here if it is not there yet); freed when the plan exists
-    struct InputCsr {
-        DeviceCsr d;
-        ~InputCsr()
-        {
-            if (d.d_row_ptr) (void)hipFree(d.d_row_ptr);
-            if (d.d_src) (void)hipFree(d.d_src);
-            if (d.d_id_lo) (void)hipFree(d.d_id_lo);
-        }
-    } in;
-    if (csr_in) {
-        in.d = *csr_in;
-        *csr_in = DeviceCsr{};
-    }
+    if (!in.d.d_row_ptr) in.reset(); // (no row pointers: no CSR)
     if (!on_device && n && c->g.row_ptr.size() != n + 1) {
         // host planner, but the reduced graph only exists on the device: bring it back
         try {
@@ -164,26 +154,18 @@ int plan_and_upload(hb_ctx *c, DeviceCsr *csr_in, uint64_t m_eff)
     // global out-degree (the device order must be identical on every rank): histogram on the device
     bool reorder = !(c->opt.flags & HB_FLAG_NO_REORDER);
     if (multi_rank(c) && !linked(c)) reorder = false; // logical ranks without a communicator
-    struct Tmp {
-        uint32_t *d_deg = nullptr;
-        uint64_t *d_lo = nullptr;
-        ~Tmp()
-        {
-            if (d_deg) (void)hipFree(d_deg);
-            if (d_lo) (void)hipFree(d_lo);
-        }
-    } tmp;
-    tmp.d_lo = in.d.d_id_lo; // (from the device ingest, else NULL: uploaded below)
+    DevPtr<uint64_t> d_lo(in.d.d_id_lo); // (from the device ingest, else NULL: uploaded below)
     in.d.d_id_lo = nullptr;
+    DevPtr<uint32_t> d_deg;
     if (n) {
-        HB_HIP(hipMalloc((void **)&tmp.d_deg, n * sizeof(uint32_t)));
-        HB_HIP(hipMemsetAsync(tmp.d_deg, 0, n * sizeof(uint32_t), c->stream));
+        HB_HIP(d_deg.alloc(n));
+        HB_HIP(hipMemsetAsync(d_deg.get(), 0, n * sizeof(uint32_t), c->stream));
         if (m_eff) {
             const unsigned blocks = (unsigned)std::min<uint64_t>((m_eff + 255) / 256, (uint64_t)c->num_cu * 16);
-            hipLaunchKernelGGL(hbk::histogram_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t *)in.d.d_src, m_eff, tmp.d_deg);
+            hipLaunchKernelGGL(hbk::histogram_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t *)in.d.d_src, m_eff, d_deg.get());
             HB_HIP(hipGetLastError());
         }
-        if (linked(c)) HB_COLL(coll_all_reduce(c, tmp.d_deg, n, ncclUint32, ncclSum, c->stream));
+        if (linked(c)) HB_COLL(coll_all_reduce(c, d_deg.get(), n, ncclUint32, ncclSum, c->stream));
     }
     PlanTune pt = plan_tune(c->opt.chunk, c->opt.tune);
     pt.xcd_map = !(c->opt.flags & HB_FLAG_NO_XCD_MAP);
@@ -200,28 +182,26 @@ int plan_and_upload(hb_ctx *c, DeviceCsr *csr_in, uint64_t m_eff)
     }
     std::vector<uint32_t> outdeg; // host planner only
     DevicePlan dp;
+    DevPtr<uint64_t> dp_row_ptr; // the planner's buffers (whatever it had allocated, if it failed), until the context adopts them below
+    DevPtr<uint32_t> dp_src, dp_order, dp_dev_of, dp_outdeg;
     if (on_device) {
-        std::string perr = gpu_build_plan((void *)c->stream, n, in.d.d_row_ptr, in.d.d_src, tmp.d_deg, reorder, pt, &c->plan, &dp);
+        std::string perr = gpu_build_plan((void *)c->stream, n, in.d.d_row_ptr, in.d.d_src, d_deg.get(), reorder, pt, &c->plan, &dp);
+        dp_row_ptr.reset(dp.d_row_ptr); dp_src.reset(dp.d_src); dp_order.reset(dp.d_order); dp_dev_of.reset(dp.d_dev_of); dp_outdeg.reset(dp.d_outdeg_dev);
         if (!perr.empty()) {
-            for (void *q : {(void *)dp.d_row_ptr, (void *)dp.d_src, (void *)dp.d_order, (void *)dp.d_dev_of, (void *)dp.d_outdeg_dev})
-                if (q) (void)hipFree(q);
             (void)hipGetLastError();
             return fail(c, perr.find("memory") != std::string::npos ? HB_ERR_NOMEM : (perr.find("exhausted") != std::string::npos ? HB_ERR_LIMIT : HB_ERR_HIP), perr);
         }
     } else {
         outdeg.assign(n, 0);
         if (n) {
-            HB_HIP(hipMemcpyAsync(outdeg.data(), tmp.d_deg, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HB_HIP(hipMemcpyAsync(outdeg.data(), d_deg.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             HB_HIP(hipStreamSynchronize(c->stream));
         }
         static const uint64_t zero = 0;
         std::string perr = build_plan(n, n ? c->g.row_ptr.data() : &zero, c->g.src.data(), outdeg, reorder, pt, &c->plan);
         if (!perr.empty()) return fail(c, perr.find("memory") != std::string::npos ? HB_ERR_NOMEM : HB_ERR_LIMIT, perr);
     }
-    // the input CSR is no longer needed on the device
-    if (in.d.d_row_ptr) (void)hipFree(in.d.d_row_ptr);
-    if (in.d.d_src) (void)hipFree(in.d.d_src);
-    in.d = DeviceCsr{};
+    in.reset(); // the input CSR is no longer needed on the device
     c->stats.ms_plan = now_ms() - t0;
     const Plan &p = c->plan;
     const uint64_t rows_total = p.n_pad + p.nv;
@@ -248,16 +228,11 @@ int plan_and_upload(hb_ctx *c, DeviceCsr *csr_in, uint64_t m_eff)
     c->bits_words = (rows_total + 31) / 32 + 2;
     int rc;
     if (on_device) {
-        c->d_row_ptr = dp.d_row_ptr;
-        c->d_src = dp.d_src;
-        c->d_sid_of = dp.d_order;
-        c->d_dev_of = dp.d_dev_of;
-        c->d_outdeg = dp.d_outdeg_dev;
-        adopt(c, dp.d_row_ptr, (rows_total + 2) * sizeof(uint64_t));
-        adopt(c, dp.d_src, (src_len + 4) * sizeof(uint32_t));
-        adopt(c, dp.d_order, std::max<uint64_t>(p.n_pad, 64) * sizeof(uint32_t));
-        adopt(c, dp.d_dev_of, std::max<uint64_t>(n, 64) * sizeof(uint32_t));
-        adopt(c, dp.d_outdeg_dev, std::max<uint64_t>(p.n_pad, 64) * sizeof(uint32_t));
+        c->d_row_ptr = adopt(c, dp_row_ptr, (rows_total + 2) * sizeof(uint64_t));
+        c->d_src = adopt(c, dp_src, (src_len + 4) * sizeof(uint32_t));
+        c->d_sid_of = adopt(c, dp_order, std::max<uint64_t>(p.n_pad, 64) * sizeof(uint32_t));
+        c->d_dev_of = adopt(c, dp_dev_of, std::max<uint64_t>(n, 64) * sizeof(uint32_t));
+        c->d_outdeg = adopt(c, dp_outdeg, std::max<uint64_t>(p.n_pad, 64) * sizeof(uint32_t));
         c->m_global = dp.m_global;
     } else {
         if ((rc = dev_alloc(c, &c->d_row_ptr, rows_total + 1))) return rc;
@@ -335,37 +310,30 @@ int plan_and_upload(hb_ctx *c, DeviceCsr *csr_in, uint64_t m_eff)
     c->out_len = n;
     c->d_cid_of = c->d_sid_of;
     if (c->rs.on && n) {
-        struct Scratch {
-            uint32_t *d_flags = nullptr;
-            uint64_t *d_cpos = nullptr;
-            unsigned long long *d_words = nullptr;
-            ~Scratch()
-            {
-                for (void *q : {(void *)d_flags, (void *)d_cpos, (void *)d_words})
-                    if (q) (void)hipFree(q);
-            }
-        } sc;
+        DevPtr<uint32_t> d_flags;
+        DevPtr<uint64_t> d_cpos;
+        DevPtr<unsigned long long> d_words;
         const uint64_t nw = (n + 63) / 64;
-        HB_HIP(hipMalloc((void **)&sc.d_flags, (n + 1) * sizeof(uint32_t)));
-        HB_HIP(hipMalloc((void **)&sc.d_cpos, (n + 2) * sizeof(uint64_t)));
-        HB_HIP(hipMalloc((void **)&sc.d_words, nw * sizeof(unsigned long long)));
+        HB_HIP(d_flags.alloc(n + 1));
+        HB_HIP(d_cpos.alloc(n + 2));
+        HB_HIP(d_words.alloc(nw));
         if ((rc = dev_alloc(c, &c->d_cid_of, p.n_pad))) return rc;
-        HB_HIP(hipMemsetAsync(sc.d_flags, 0, (n + 1) * sizeof(uint32_t), c->stream));
+        HB_HIP(hipMemsetAsync(d_flags.get(), 0, (n + 1) * sizeof(uint32_t), c->stream));
         const unsigned blocks = (unsigned)std::min<uint64_t>((p.n_pad + 255) / 256, (uint64_t)c->num_cu * 16);
-        hipLaunchKernelGGL(hbk::in_flags_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr, (const uint32_t *)c->d_sid_of, p.n_pad, sc.d_flags);
+        hipLaunchKernelGGL(hbk::in_flags_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr, (const uint32_t *)c->d_sid_of, p.n_pad, d_flags.get());
         HB_HIP(hipGetLastError());
-        const std::string e = device_prefix((void *)c->stream, sc.d_flags, n, sc.d_cpos);
+        const std::string e = device_prefix((void *)c->stream, d_flags.get(), n, d_cpos.get());
         if (!e.empty()) return fail(c, HB_ERR_HIP, e);
         hipLaunchKernelGGL(hbk::cid_of_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr, (const uint32_t *)c->d_sid_of,
-                           (const uint64_t *)sc.d_cpos, p.n_pad, c->d_cid_of);
+                           (const uint64_t *)d_cpos.get(), p.n_pad, c->d_cid_of);
         HB_HIP(hipGetLastError());
         hipLaunchKernelGGL(hbk::pack_flags_kernel, dim3((unsigned)std::min<uint64_t>((nw + 3) / 4, (uint64_t)c->num_cu * 16)), dim3(256), 0, c->stream,
-                           (const uint32_t *)sc.d_flags, n, sc.d_words);
+                           (const uint32_t *)d_flags.get(), n, d_words.get());
         HB_HIP(hipGetLastError());
         uint64_t n_c = 0;
         c->h_in_bits.assign(nw, 0);
-        HB_HIP(hipMemcpyAsync(&n_c, sc.d_cpos + n, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        HB_HIP(hipMemcpyAsync(c->h_in_bits.data(), sc.d_words, nw * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        HB_HIP(hipMemcpyAsync(&n_c, d_cpos.get() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        HB_HIP(hipMemcpyAsync(c->h_in_bits.data(), d_words.get(), nw * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
         HB_HIP(hipStreamSynchronize(c->stream));
         if (n_c != p.rows_with_in_edges)
             return fail(c, HB_ERR_INVALID, "result image: " + std::to_string(n_c) + " nodes with in-edges counted on the device, the plan says " + std::to_string(p.rows_with_in_edges));
@@ -374,14 +342,14 @@ int plan_and_upload(hb_ctx *c, DeviceCsr *csr_in, uint64_t m_eff)
     }
     // low 64 bits of every NodeID in device order (HyperLogLog::add_u128 hashes only those, hyperloglog.rs:4398-4400)
     if (n) {
-        if (!tmp.d_lo) {
+        if (!d_lo) {
             uvec<uint64_t> lo(n);
             host_gather_id_lo(c->g.ids.data(), n, lo.data()); // (hb_host.cpp, OpenMP team)
-            HB_HIP(hipMalloc((void **)&tmp.d_lo, n * sizeof(uint64_t)));
-            HB_HIP(hipMemcpyAsync(tmp.d_lo, lo.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+            HB_HIP(d_lo.alloc(n));
+            HB_HIP(hipMemcpyAsync(d_lo.get(), lo.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
             HB_HIP(hipStreamSynchronize(c->stream)); // lo goes out of scope
         }
-        hipLaunchKernelGGL(idlow_kernel, dim3((unsigned)((p.n_pad + 255) / 256)), dim3(256), 0, c->stream, (const uint64_t *)tmp.d_lo,
+        hipLaunchKernelGGL(idlow_kernel, dim3((unsigned)((p.n_pad + 255) / 256)), dim3(256), 0, c->stream, (const uint64_t *)d_lo.get(),
                            (const uint32_t *)c->d_sid_of, p.n_pad, c->d_idlow);
         HB_HIP(hipGetLastError());
         HB_HIP(hipStreamSynchronize(c->stream));
@@ -457,14 +425,14 @@ int plan_and_upload(hb_ctx *c, DeviceCsr *csr_in, uint64_t m_eff)
         // one pass over each buffer (14 ms at C4), in the order a run uses them
         HB_HIP(hipEventRecord(c->ev[0], c->stream));
         if (c->rs.on) {
-            HB_HIP(hipEventRecord(c->rs.ready, c->stream));
-            HB_HIP(hipStreamWaitEvent(c->rs.stream, c->rs.ready, 0));
-            HB_HIP(hipMemcpyAsync(c->h_out, c->d_out, c->out_len * sizeof(double), hipMemcpyDeviceToHost, c->rs.stream));
-            HB_HIP(hipEventRecord(c->rs.copied, c->rs.stream));
+            HB_HIP(hipEventRecord(c->rs_ready, c->stream));
+            HB_HIP(hipStreamWaitEvent(c->rs_stream, c->rs_ready, 0));
+            HB_HIP(hipMemcpyAsync(c->h_out, c->d_out, c->out_len * sizeof(double), hipMemcpyDeviceToHost, c->rs_stream));
+            HB_HIP(hipEventRecord(c->rs_copied, c->rs_stream));
             HB_HIP(hipMemcpyAsync(c->rs.h_sid, c->rs.d_sid, c->rs.cap * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             HB_HIP(hipMemcpyAsync(c->rs.h_val, c->rs.d_val, c->rs.cap * sizeof(double), hipMemcpyDeviceToHost, c->stream));
             HB_HIP(hipMemcpyAsync(c->rs.h_count, c->rs.d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-            HB_HIP(hipStreamWaitEvent(c->stream, c->rs.copied, 0));
+            HB_HIP(hipStreamWaitEvent(c->stream, c->rs_copied, 0));
         } else {
             HB_HIP(hipMemcpyAsync(c->h_out, c->d_out, c->out_len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         }
@@ -476,7 +444,7 @@ int plan_and_upload(hb_ctx *c, DeviceCsr *csr_in, uint64_t m_eff)
         HB_HIP(hipEventRecord(c->ev[1], c->stream));
         HB_HIP(hipEventSynchronize(c->slot_done[1]));
         if (c->rs.on) {
-            (void)hipEventQuery(c->rs.copied);
+            (void)hipEventQuery(c->rs_copied);
             (void)hipGetLastError();
         }
         HB_HIP(hipStreamSynchronize(c->stream));
@@ -484,7 +452,7 @@ int plan_and_upload(hb_ctx *c, DeviceCsr *csr_in, uint64_t m_eff)
         HB_HIP(hipEventElapsedTime(&ms_warm, c->ev[0], c->ev[1]));
     }
     HB_HIP(hipStreamSynchronize(c->stream));
-    if (c->rs.stream) HB_HIP(hipStreamSynchronize(c->rs.stream));
+    if (c->rs_stream) HB_HIP(hipStreamSynchronize(c->rs_stream));
     lap("read-back paths warmed");
     c->stats.ms_h2d = now_ms() - t0;
     c->stats.pool_peak_bytes = (uint64_t)HB_POOL_PEAK(); // since the load began (hb_append_edges of an empty stream / this call)

@@ -443,7 +443,7 @@ int upload_tail_index(hb_ctx *c)
         for (size_t i = 0; i < c->allocs.size(); i++)
             if (c->allocs[i].p == old) {
                 c->stats.device_bytes -= c->allocs[i].bytes;
-                (void)hipFree(old);
+                (void)hipFree(old); // (one entry leaves the `allocs` list before the graph does: the list is its owner, this its only early exit)
                 c->allocs.erase(c->allocs.begin() + (long)i);
                 break;
             }
@@ -477,10 +477,10 @@ int results_stage(hb_ctx *c)
     hipLaunchKernelGGL(hbk::results_sync_kernel, dim3(blocks), dim3(256), 0, c->stream, (const double *)c->d_ksum, rs.d_sent, (const uint32_t *)c->d_cid_of,
                        p.n_pad, norm, rs.valid ? 0 : 1, c->d_out, (uint32_t *)nullptr, (double *)nullptr, 0ull, rs.d_count, rs.d_kept);
     HB_HIP(hipGetLastError());
-    HB_HIP(hipEventRecord(rs.ready, c->stream));
-    HB_HIP(hipStreamWaitEvent(rs.stream, rs.ready, 0));
-    HB_HIP(hipMemcpyAsync(c->h_out, c->d_out, c->out_len * sizeof(double), hipMemcpyDeviceToHost, rs.stream)); // (compact image: hb_ctx::out_len entries)
-    HB_HIP(hipEventRecord(rs.copied, rs.stream));
+    HB_HIP(hipEventRecord(c->rs_ready, c->stream));
+    HB_HIP(hipStreamWaitEvent(c->rs_stream, c->rs_ready, 0));
+    HB_HIP(hipMemcpyAsync(c->h_out, c->d_out, c->out_len * sizeof(double), hipMemcpyDeviceToHost, c->rs_stream)); // (compact image: hb_ctx::out_len entries)
+    HB_HIP(hipEventRecord(c->rs_copied, c->rs_stream));
     if (std::getenv("HB_TRACE_RESULTS")) std::fprintf(stderr, "[hb results] snapshot %u queued after pass %llu at %.3f ms (host clock)\n", rs.stages + 1, (unsigned long long)c->t - 1, now_ms());
     rs.valid = true;
     rs.changed_since = 0;
@@ -501,9 +501,25 @@ int results_stage_policy(hb_ctx *c, uint64_t changed)
     bool go;
     const uint32_t dense_thr = c->opt.tune[2] ? c->opt.tune[2] : 50; // (step_local's threshold: the next pass is dense at or above it)
     if (!rs.valid) go = forced || c->last_active * 100ull < (uint64_t)dense_thr * c->m_global;
-    else go = (forced || rs.changed_since * 8 > c->plan.n) && !(HB_XBITS(c->opt.tune[1]) & 0x20000u) && hipEventQuery(rs.copied) == hipSuccess; // (bit 17: one snapshot only - test switch)
+    else go = (forced || rs.changed_since * 8 > c->plan.n) && !(HB_XBITS(c->opt.tune[1]) & 0x20000u) && hipEventQuery(c->rs_copied) == hipSuccess; // (bit 17: one snapshot only - test switch)
     (void)hipGetLastError(); // (hipErrorNotReady of the query is not an error)
     return go ? results_stage(c) : HB_OK;
+}
+
+// Sweep mode, first step: the changed node rows -> touch bits of their readers.  `small` (few changed rows): one launch instead of
+// collect + expand + heavy.  Shared by step_local and hb_sampled_harmonic; the caller checks hipGetLastError.
+void launch_sweep_seeding(hb_ctx *c, const hbk::SweepParams &sp, bool small)
+{
+    const uint64_t real_words = sp.p.n_pad / 32;
+    const unsigned sblocks = (unsigned)std::min<uint64_t>(std::max<uint64_t>(real_words / 256, 1), (uint64_t)c->num_cu * 4);
+    const unsigned wblocks = (unsigned)c->num_cu * 4;
+    if (small) {
+        hipLaunchKernelGGL(hbk::sweep_seed_small_kernel, dim3(sblocks), dim3(256), 0, c->stream, sp);
+    } else {
+        hipLaunchKernelGGL(hbk::sweep_collect_kernel, dim3(sblocks), dim3(256), 0, c->stream, sp);
+        hipLaunchKernelGGL(hbk::sweep_expand_kernel, dim3(wblocks), dim3(256), 0, c->stream, sp);
+        hipLaunchKernelGGL(hbk::sweep_expand_heavy_kernel, dim3(wblocks), dim3(256), 0, c->stream, sp);
+    }
 }
 
 int step_local(hb_ctx *c)
@@ -575,7 +591,6 @@ int step_local(hb_ctx *c)
         sp.touch = c->d_touch;
         sp.seeds = c->d_seeds;
         sp.heavy = c->d_heavy;
-        const uint64_t real_words = p.n_pad / 32;
         // the seed / heavy counters live in two slots used by alternate passes: this pass' first kernel zeroes the other one
         // (no memset launch per pass; hb_begin clears both)
         sp.counts = c->d_sparse_counts + 2 * (c->t & 1);
@@ -583,16 +598,8 @@ int step_local(hb_ctx *c)
         sp.guard = c->spec_guard;
         // no bitmap is cleared here: the sweep kernels rewrite every word of this pass' changed bits (node rows in
         // bits_wr, virtual rows in the upper part of bits_rd) and keep the touch bitmap all-zero between passes
-        const unsigned sblocks = (unsigned)std::min<uint64_t>(std::max<uint64_t>(real_words / 256, 1), (uint64_t)c->num_cu * 4);
-        const unsigned wblocks = (unsigned)c->num_cu * 4;
-        if (c->last_changed <= 4096 && !(HB_XBITS(c->opt.tune[1]) & 0x800u)) {
-            // convergence tail: one launch instead of collect + expand + heavy (tune[1] bit 11 = the general path, measurement switch)
-            hipLaunchKernelGGL(hbk::sweep_seed_small_kernel, dim3(sblocks), dim3(256), 0, c->stream, sp);
-        } else {
-            hipLaunchKernelGGL(hbk::sweep_collect_kernel, dim3(sblocks), dim3(256), 0, c->stream, sp);
-            hipLaunchKernelGGL(hbk::sweep_expand_kernel, dim3(wblocks), dim3(256), 0, c->stream, sp);
-            hipLaunchKernelGGL(hbk::sweep_expand_heavy_kernel, dim3(wblocks), dim3(256), 0, c->stream, sp);
-        }
+        // convergence tail: the one-launch form (tune[1] bit 11 = the general path, measurement switch)
+        launch_sweep_seeding(c, sp, c->last_changed <= 4096 && !(HB_XBITS(c->opt.tune[1]) & 0x800u));
         HB_HIP(hipEventRecord(E[5], c->stream)); // sweep passes: ms_level1 = seed collection + expansion
         auto sweep_blocks = [&](uint64_t rows) { // a wave-iteration covers 16 groups of 128 rows
             const uint64_t waves = (rows + 2047) / 2048;

@@ -38,16 +38,14 @@ int sample_sids(hb_ctx *c, uint64_t seed, uint64_t k, std::vector<uint32_t> *sid
     auto &sm = c->smp;
     if (!sm.cand_valid) { // once per loaded graph: one flag byte per node from the device, then the ascending list
         std::vector<uint8_t> has_out(p.n);
-        uint8_t *d_flags = nullptr;
-        HB_HIP(hipMalloc((void **)&d_flags, p.n));
+        DevPtr<uint8_t> d_flags;
+        HB_HIP(d_flags.alloc(p.n));
         const unsigned blocks = (unsigned)std::min<uint64_t>((p.n_pad + 255) / 256, (uint64_t)c->num_cu * 8);
         hipLaunchKernelGGL(hbk::sample_candidates_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t *)c->d_outdeg, (const uint32_t *)c->d_sid_of,
-                           p.n_pad, d_flags);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(has_out.data(), d_flags, p.n, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_flags);
-        if (e != hipSuccess) return fail(c, HB_ERR_HIP, std::string("hb_sampled_harmonic: candidate flags: ") + hipGetErrorString(e));
+                           p.n_pad, d_flags.get());
+        HB_HIP_AS("hb_sampled_harmonic: candidate flags: ", hipGetLastError());
+        HB_HIP_AS("hb_sampled_harmonic: candidate flags: ", hipMemcpyAsync(has_out.data(), d_flags.get(), p.n, hipMemcpyDeviceToHost, c->stream));
+        HB_HIP_AS("hb_sampled_harmonic: candidate flags: ", hipStreamSynchronize(c->stream));
         sm.cand.clear();
         for (uint64_t s = 0; s < p.n; s++)
             if (has_out[s]) sm.cand.push_back((uint32_t)s);
@@ -79,16 +77,13 @@ int sample_alloc(hb_ctx *c, uint32_t levels)
 {
     auto &s = c->smp;
     const uint64_t n_pad = c->plan.n_pad;
-    if (s.d_hist && s.levels != levels) {
-        (void)hipFree(s.d_hist);
-        s.d_hist = nullptr;
-    }
+    if (s.levels != levels) s.d_hist.reset(); // (another level count: another size)
     s.levels = 0;
-    if (!s.d_hist) HB_HIP(hipMalloc((void **)&s.d_hist, std::max<uint64_t>((uint64_t)levels * n_pad, 64) * sizeof(uint16_t)));
-    if (!s.d_cnt) HB_HIP(hipMalloc((void **)&s.d_cnt, (hbk::kSampleMaxLevels + 1) * 4 * sizeof(unsigned long long)));
-    if (!s.d_srcs) HB_HIP(hipMalloc((void **)&s.d_srcs, hbk::kSampleBatch * sizeof(uint32_t)));
-    if (!s.d_rows) HB_HIP(hipMalloc((void **)&s.d_rows, hbk::kSampleBatch * sizeof(uint32_t)));
-    if (!s.d_w) HB_HIP(hipMalloc((void **)&s.d_w, hbk::kSampleMaxLevels * sizeof(double)));
+    if (!s.d_hist) HB_HIP(s.d_hist.alloc(std::max<uint64_t>((uint64_t)levels * n_pad, 64)));
+    if (!s.d_cnt) HB_HIP(s.d_cnt.alloc((hbk::kSampleMaxLevels + 1) * 4));
+    if (!s.d_srcs) HB_HIP(s.d_srcs.alloc(hbk::kSampleBatch));
+    if (!s.d_rows) HB_HIP(s.d_rows.alloc(hbk::kSampleBatch));
+    if (!s.d_w) HB_HIP(s.d_w.alloc(hbk::kSampleMaxLevels));
     return HB_OK;
 }
 
@@ -117,10 +112,10 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
 {
     const double t0 = now_ms();
     hb_sample_options o{};
-    if (opt_in) std::memcpy(&o, opt_in, opt_in->struct_size ? std::min<size_t>(opt_in->struct_size, sizeof(o)) : sizeof(o));
+    copy_in(opt_in, &o);
     if (multi_rank(c)) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: single rank only (world_size > 1)");
     if (!c->loaded) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: no graph loaded");
-    if (c->rs.stream) HB_HIP(hipStreamSynchronize(c->rs.stream)); // (no result snapshot of an earlier run may still be landing in h_out)
+    if (c->rs_stream) HB_HIP(hipStreamSynchronize(c->rs_stream)); // (no result snapshot of an earlier run may still be landing in h_out)
     c->rs.valid = false;
     const uint32_t max_dist = o.max_dist ? o.max_dist : 7; // approx_harmonic.rs:62
     if (max_dist > hbk::kSampleMaxLevels - 1) return fail(c, HB_ERR_LIMIT, "hb_sampled_harmonic: max_dist > 15");
@@ -131,24 +126,18 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
     if (o.sources && !o.source_count) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: sources given with source_count == 0");
     const uint64_t k_req = o.samples ? o.samples : (o.sources ? o.source_count : sample_count_formula(N, eps));
     if (k_req > 65535 || (o.sources && o.source_count > 65535)) return fail(c, HB_ERR_LIMIT, "hb_sampled_harmonic: more than 65535 sources");
-    if (p.n_pad % 32 || (p.level_begin.size() && p.level_begin.back() > p.n_pad + p.nv))
-        return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: unexpected plan layout");
-    for (uint64_t b : p.level_begin)
-        if (b % 32) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: level boundary not a multiple of 32 rows");
-    int rc = HB_OK;
-    {
-        hipError_t stale = hipGetLastError();
-        if (stale != hipSuccess) return fail(c, HB_ERR_HIP, std::string("stale HIP error before hb_sampled_harmonic: ") + hipGetErrorString(stale));
-    }
+    if (p.level_begin.size() && p.level_begin.back() > p.n_pad + p.nv) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: unexpected plan layout");
+    int rc;
+    if ((rc = plan_rows_word_aligned(c, "hb_sampled_harmonic"))) return rc;
+    if ((rc = refuse_stale_error(c, "hb_sampled_harmonic"))) return rc;
     // the sources, as ascending sids
     std::vector<uint32_t> sids;
     if (o.sources) {
         sids.reserve(o.source_count);
         for (uint64_t i = 0; i < o.source_count; i++) {
-            const hb_u128 id = o.sources[i];
-            auto it = std::lower_bound(c->g.ids.begin(), c->g.ids.end(), id, u128_less);
-            if (it == c->g.ids.end() || !u128_eq(*it, id)) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: source " + std::to_string(i) + " is not a node of the graph");
-            sids.push_back((uint32_t)(it - c->g.ids.begin()));
+            uint32_t sid;
+            if (!find_sid(c, o.sources[i], &sid)) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: source " + std::to_string(i) + " is not a node of the graph");
+            sids.push_back(sid);
         }
         std::sort(sids.begin(), sids.end());
         if (std::adjacent_find(sids.begin(), sids.end()) != sids.end()) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: duplicate sources");
@@ -162,8 +151,8 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
     if ((rc = sample_alloc(c, D))) return rc;
     auto &sm = c->smp;
     const uint64_t n_pad = p.n_pad, rows_total = p.n_pad + p.nv;
-    HB_HIP(hipMemsetAsync(sm.d_hist, 0, std::max<uint64_t>((uint64_t)D * n_pad, 64) * sizeof(uint16_t), c->stream));
-    HB_HIP(hipMemcpyAsync(sm.d_w, w, sizeof(w), hipMemcpyHostToDevice, c->stream));
+    HB_HIP(hipMemsetAsync(sm.d_hist.get(), 0, std::max<uint64_t>((uint64_t)D * n_pad, 64) * sizeof(uint16_t), c->stream));
+    HB_HIP(hipMemcpyAsync(sm.d_w.get(), w, sizeof(w), hipMemcpyHostToDevice, c->stream));
     // bitmap / sweep thresholds of hb_run (hb_api_pass.inc step_local): the A_t rule on the out-degree sum of the rows changed at d - 1
     const uint32_t thr = c->opt.tune[2] ? c->opt.tune[2] : 50;
     const uint64_t sparse_div = c->opt.tune[6] ? c->opt.tune[6] : 10;
@@ -184,14 +173,14 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
         if (p.nv) HB_HIP(hipMemsetAsync(c->d_part, 0, p.nv * 64, c->stream));
         HB_HIP(hipMemsetAsync(c->d_bits[0], 0, c->bits_words * 4, c->stream));
         HB_HIP(hipMemsetAsync(c->d_bits[1], 0, c->bits_words * 4, c->stream));
-        HB_HIP(hipMemsetAsync(sm.d_cnt, 0, (hbk::kSampleMaxLevels + 1) * 4 * sizeof(unsigned long long), c->stream));
-        HB_HIP(hipMemcpyAsync(sm.d_srcs, sids.data() + b0, count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(hbk::sample_rows_of_kernel, dim3((count + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)sm.d_srcs, count,
-                           (const uint32_t *)c->d_dev_of, sm.d_rows); // (only the sources' rows: no n-entry map to the host)
-        hipLaunchKernelGGL(hbk::sample_seed_kernel, dim3((count * 4 + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)sm.d_rows, count, c->d_regs[0],
-                           c->d_bits[0], (const uint32_t *)c->d_outdeg, sm.d_cnt);
+        HB_HIP(hipMemsetAsync(sm.d_cnt.get(), 0, (hbk::kSampleMaxLevels + 1) * 4 * sizeof(unsigned long long), c->stream));
+        HB_HIP(hipMemcpyAsync(sm.d_srcs.get(), sids.data() + b0, count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(hbk::sample_rows_of_kernel, dim3((count + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)sm.d_srcs.get(), count,
+                           (const uint32_t *)c->d_dev_of, sm.d_rows.get()); // (only the sources' rows: no n-entry map to the host)
+        hipLaunchKernelGGL(hbk::sample_seed_kernel, dim3((count * 4 + 255) / 256), dim3(256), 0, c->stream, (const uint32_t *)sm.d_rows.get(), count, c->d_regs[0],
+                           c->d_bits[0], (const uint32_t *)c->d_outdeg, sm.d_cnt.get());
         HB_HIP(hipGetLastError());
-        HB_HIP(hipMemcpyAsync(h, sm.d_cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HB_HIP(hipMemcpyAsync(h, sm.d_cnt.get(), 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         HB_HIP(hipStreamSynchronize(c->stream));
         uint64_t last_changed = h[0], last_active = h[1];
         int cur = 0;
@@ -211,13 +200,13 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
             sp.out_ptr = c->d_out_ptr;
             sp.out_rows = c->d_out_rows;
             sp.outdeg = c->d_outdeg;
-            sp.hist = sm.d_hist + (uint64_t)(d - 1) * n_pad;
-            sp.cnt = sm.d_cnt + 4 * d;
+            sp.hist = sm.d_hist.get() + (uint64_t)(d - 1) * n_pad;
+            sp.cnt = sm.d_cnt.get() + 4 * d;
             sp.n_pad = n_pad;
             sp.rows_total = rows_total;
             HB_HIP(hipEventRecord(c->ev[0], c->stream));
             if (sweep) {
-                // the rows changed at d - 1 -> touch bits of their readers: hb_run's seed / expand kernels, unchanged (hb_sweep.hip.h)
+                // the rows changed at d - 1 -> touch bits of their readers: hb_run's seed / expand kernels, unchanged (launch_sweep_seeding)
                 hbk::SweepParams sw{};
                 sw.p.bits_rd = c->d_bits[cur];
                 sw.p.n_pad = n_pad;
@@ -231,16 +220,7 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
                 sw.counts_next = c->d_sparse_counts + 2;
                 sw.guard = nullptr;
                 HB_HIP(hipMemsetAsync(c->d_sparse_counts, 0, 4 * sizeof(unsigned int), c->stream));
-                const uint64_t real_words = n_pad / 32;
-                const unsigned sblocks = (unsigned)std::min<uint64_t>(std::max<uint64_t>(real_words / 256, 1), (uint64_t)c->num_cu * 4);
-                const unsigned wblocks = (unsigned)c->num_cu * 4;
-                if (last_changed <= 4096) {
-                    hipLaunchKernelGGL(hbk::sweep_seed_small_kernel, dim3(sblocks), dim3(256), 0, c->stream, sw);
-                } else {
-                    hipLaunchKernelGGL(hbk::sweep_collect_kernel, dim3(sblocks), dim3(256), 0, c->stream, sw);
-                    hipLaunchKernelGGL(hbk::sweep_expand_kernel, dim3(wblocks), dim3(256), 0, c->stream, sw);
-                    hipLaunchKernelGGL(hbk::sweep_expand_heavy_kernel, dim3(wblocks), dim3(256), 0, c->stream, sw);
-                }
+                launch_sweep_seeding(c, sw, last_changed <= 4096);
                 HB_HIP(hipGetLastError());
             }
             for (size_t l = 0; l + 1 < p.level_begin.size(); l++) { // virtual levels: partials of level d from the rows of level d - 1
@@ -273,11 +253,11 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
     }
     // the result image
     if (c->out_len) {
-        unsigned long long *cnt = sm.d_cnt; // (slot 0 is free again)
+        unsigned long long *cnt = sm.d_cnt.get(); // (slot 0 is free again)
         HB_HIP(hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned long long), c->stream));
         const unsigned blocks = (unsigned)std::min<uint64_t>((n_pad + 255) / 256, (uint64_t)c->num_cu * 8);
-        hipLaunchKernelGGL(hbk::sample_result_kernel, dim3(std::max(blocks, 1u)), dim3(256), 0, c->stream, (const uint16_t *)sm.d_hist, D, n_pad,
-                           (const double *)sm.d_w, (const uint32_t *)c->d_cid_of, c->d_out, cnt);
+        hipLaunchKernelGGL(hbk::sample_result_kernel, dim3(std::max(blocks, 1u)), dim3(256), 0, c->stream, (const uint16_t *)sm.d_hist.get(), D, n_pad,
+                           (const double *)sm.d_w.get(), (const uint32_t *)c->d_cid_of, c->d_out, cnt);
         HB_HIP(hipGetLastError());
         HB_HIP(hipMemcpyAsync(c->h_out, c->d_out, c->out_len * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HB_HIP(hipMemcpyAsync(h, cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -291,11 +271,7 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
     c->finished = true;
     st.results = c->res_count;
     st.ms_total = now_ms() - t0;
-    if (st_out) {
-        const size_t sz = st_out->struct_size ? std::min<size_t>(st_out->struct_size, sizeof(st)) : sizeof(st);
-        st.struct_size = (uint32_t)sz;
-        std::memcpy(st_out, &st, sz);
-    }
+    copy_out(st_out, st);
     return HB_OK;
 }
 
@@ -345,7 +321,7 @@ int hb_debug_sample_histogram(hb_ctx *c, uint16_t *out)
         std::vector<uint16_t> hist((size_t)D * p.n_pad);
         std::vector<uint32_t> sid_of(p.n_pad);
         if (p.n_pad) {
-            HB_HIP(hipMemcpyAsync(hist.data(), c->smp.d_hist, hist.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+            HB_HIP(hipMemcpyAsync(hist.data(), c->smp.d_hist.get(), hist.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
             HB_HIP(hipMemcpyAsync(sid_of.data(), c->d_sid_of, p.n_pad * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             HB_HIP(hipStreamSynchronize(c->stream));
         }

@@ -63,6 +63,15 @@ def test_device_sources_match_the_oracle_under_the_interpreter(simt_lib):
     assert " passed" in tail and "failed" not in tail and "error" not in tail.lower(), tail
 
 
+def test_reload_after_all_three_operators_under_the_interpreter(simt_lib):
+    """tests/test_reload.py: what a load has to forget about the graph before it.  Device memory is poisoned host memory here, so a
+    pointer or a size kept from the previous graph shows up without a GPU."""
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_reload.py"), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"],
+                       capture_output=True, text=True, env=_child_env(simt_lib), cwd=ROOT, timeout=1700)
+    tail = "\n".join((r.stdout + r.stderr).splitlines()[-40:])
+    assert r.returncode == 0 and "2 passed" in tail and "failed" not in tail, tail
+
+
 def test_no_dependence_on_workgroup_or_lane_order(simt_lib):
     """The machine promises no order among the workgroups of a launch, nor among the lanes of a workgroup between two cross-lane
     operations.  The interpreter's default is ascending; HB_SIMT_ORDER=shuffle:<seed> takes a new random order of the workgroups for
