@@ -46,6 +46,25 @@ HB_FLAG_NO_INIT_PASS = 0x4000
 HB_FLAG_ALL_RELS = 0x8000
 HB_SAMPLE_MAX_LEVELS = 16
 
+# switches of the experiments build in hb_options.tune[1] (stract_amd/csrc/hb_experiments.h describes each)
+HB_X_TILE_EPILOGUE = 0x100
+HB_X_SEED_3LAUNCH = 0x800
+HB_X_NO_EDGE_OVERLAP = 0x1000
+HB_X_BITMAP_SLOTWISE = 0x2000
+HB_X_NO_STAGED_RESULTS = 0x4000
+HB_X_SNAPSHOT_EVERY_PASS = 0x8000
+HB_X_SHORT_FINAL_LIST = 0x10000
+HB_X_ONE_SNAPSHOT = 0x20000
+HB_X_NO_TAIL_PIPELINE = 0x100000
+HB_X_TAIL_KERNEL = 0x200000
+HB_X_TAIL_KERNEL_ANY = 0x400000
+HB_X_FULL_INIT = 0x800000
+HB_X_WIRE_64B = 0x1000000
+HB_X_SCATTER_TRANSPOSE = 0x2000000
+HB_X_SWEEP_ROUNDS = 0x4000000
+HB_X_GENERIC_LEVEL1 = 0x8000000
+HB_X_PROBE_NO_SIZE = 0x10000000
+
 # numpy views of the plain-data structs
 U128 = np.dtype([("lo", "<u8"), ("hi", "<u8")])
 EDGE = np.dtype([("from", U128), ("to", U128), ("rel_flags", "<u8")])

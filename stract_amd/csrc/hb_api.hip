@@ -162,7 +162,7 @@ struct GraphDeviceState {
     // results that travel while the passes still run (results_stage; hb_aux.hip.h results_sync_kernel).  The side stream and its two events
     // are the context's (hb_ctx::rs_stream)
     struct ResultSync {
-        bool on = false;          // this graph ships its results in stages (single rank, large enough or forced by tune[1] bit 15)
+        bool on = false;          // this graph ships its results in stages (single rank, large enough or forced by HB_X_SNAPSHOT_EVERY_PASS)
         bool valid = false;       // d_out / d_sent (and h_out, once `copied` has fired) hold one consistent snapshot of the sums
         uint64_t changed_since = 0; // (run) counters changed since that snapshot (= sums that moved, give or take a `+= 0.0` flush)
         uint32_t stages = 0;      // (run) snapshots shipped during the current run
@@ -212,6 +212,19 @@ struct GraphDeviceState {
     } dst;
 };
 
+// The timing events of a pass (one set: hb_ctx::ev, or an EvSet), in the order a pass records them; kEvLevel1 lies between kEvStart and
+// kEvLevels.
+enum PassEvent {
+    kEvStart,      // the pass begins
+    kEvLevels,     // the virtual levels (hub chunks) are done
+    kEvEnd = kEvLevels, // what is no HyperBall pass (load warm-up, sampled walks, distances, the tail kernel) times itself from kEvStart to here
+    kEvMerge,      // the node rows' local merge is done
+    kEvCollective, // the exchange with the other ranks is done
+    kEvEpilogue,   // the unfused epilogue is done
+    kEvLevel1,     // the first hub-chunk level is done (sweep passes: seed collection + expansion)
+    kEvSlots
+};
+
 struct hb_ctx : GraphDeviceState {
     // ---- context lifetime: hb_create .. hb_destroy ------------------------------------------------------------------------------------
     hb_options opt{};
@@ -231,15 +244,15 @@ struct hb_ctx : GraphDeviceState {
     unsigned long long *h_slot = nullptr;     // 2 x kCounterWords: the counters of the two passes in flight
     uint32_t *h_tl_count = nullptr;           // kTcWords
     unsigned long long *h_rank_cnt = nullptr; // world words
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // [5] = after the level-1 hub launch
+    hipEvent_t ev[kEvSlots] = {}; // indexed by PassEvent
     // destination partition + changed-only: the pass' only host round trip sits in the MIDDLE of the pass (counters + run lengths,
     // before the broadcasts); what follows it is left in flight, so the pass' timing events are read later (resolve_pass_times)
     struct EvSet {
-        hipEvent_t e[6];
+        hipEvent_t e[kEvSlots];
     };
     std::vector<EvSet> ev_pool;         // deferred timing (destination partition + changed-only on a communicator): one set per pass of a run
     EvSet ev_ring[4]{};                 // hb_run's tail pipeline (two passes in flight): pass t uses set t & 3; created by hb_create
-    hipEvent_t tl_ev[2] = {nullptr, nullptr};
+    hipEvent_t tl_ev[2] = {nullptr, nullptr}; // the tail kernel's launch: kEvStart, kEvEnd
     hipEvent_t slot_done[2] = {nullptr, nullptr};   // pass q's counters have arrived in h_slot[q & 1]
     // edge partition with a communicator: the node rows are merged, all-reduced and finished in kOverlap row ranges - range
     // k's ncclAllReduce runs on comm_stream while range k + 1 is still being merged, its epilogue while k + 1 is reduced
@@ -413,6 +426,13 @@ PlanTune plan_tune(uint32_t chunk, const uint32_t *tune)
 }
 
 bool multi_rank(const hb_ctx *c) { return c->opt.world_size > 1; }
+// a switch of the experiments build (hb_experiments.h HB_X_*; several or-ed: any of them); always off in the product library
+bool xbit(const hb_ctx *c, uint32_t bits) { return (HB_XBITS(c->opt.tune[1]) & bits) != 0; }
+// blocks for `groups` groups of work items, at most `per_cu` per CU and at least `floor`
+unsigned grid_blocks(const hb_ctx *c, uint64_t groups, uint64_t per_cu, uint64_t floor = 0)
+{
+    return (unsigned)std::max<uint64_t>(std::min<uint64_t>(groups, (uint64_t)c->num_cu * per_cu), floor);
+}
 // the context can exchange with the other ranks by itself: an RCCL communicator, or the caller's collectives
 bool linked(const hb_ctx *c) { return c->comm != nullptr || c->coll.all_reduce != nullptr; }
 
@@ -511,10 +531,9 @@ int build_sparse_support(hb_ctx *c)
 #endif
     HB_HIP(hipMemsetAsync(c->d_touch, 0, (c->bits_words + 64) * sizeof(uint32_t), c->stream));
     {   // [r6] by sorting (hb_plan.hip gpu_transpose_rows: streaming traffic only); the scatter form below only when the device cannot
-        // lend the sort 16 bytes per entry, or on request (experiments build, tune[1] bit 25: A/B runs and the parity variant that
+        // lend the sort 16 bytes per entry, or on request (HB_X_SCATTER_TRANSPOSE: A/B runs and the parity variant that
         // keeps the fallback exact)
-        const bool scatter = (HB_XBITS(c->opt.tune[1]) & 0x2000000u) != 0;
-        if (!scatter) {
+        if (!xbit(c, HB_X_SCATTER_TRANSPOSE)) {
             const std::string e = gpu_transpose_rows((void *)c->stream, c->d_row_ptr, c->d_src, rows_total, entries, c->d_out_ptr, c->d_out_rows);
             if (e.empty()) {
                 c->sparse_ok = true;
@@ -526,7 +545,7 @@ int build_sparse_support(hb_ctx *c)
     }
     if ((rc = dev_alloc(c, &d_count, rows_total))) return rc; // stays allocated (small next to out_rows)
     HB_HIP(hipMemsetAsync(d_count, 0, rows_total * sizeof(uint32_t), c->stream));
-    const unsigned blocks = (unsigned)std::min<uint64_t>((rows_total * 4 + 255) / 256, (uint64_t)c->num_cu * 16);
+    const unsigned blocks = grid_blocks(c, (rows_total * 4 + 255) / 256, 16);
     hipLaunchKernelGGL(hbk::transpose_count_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr,
                        (const uint32_t *)c->d_src, rows_total, d_count);
     HB_HIP(hipGetLastError());
@@ -641,7 +660,7 @@ int hb_create(const hb_options *opt, hb_ctx **out)
             return fail(c, HB_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
         if (o.world_size > 1 && (o.rank < 0 || o.rank >= o.world_size)) return fail(c, HB_ERR_INVALID, "rank out of range");
 #ifndef HB_EXPERIMENTS
-        if ((o.tune[1] & ~0xFFu) || o.tune[7])
+        if ((o.tune[1] & ~HB_TUNE1_UNROLL) || o.tune[7])
             return fail(c, HB_ERR_INVALID, "hb_options.tune[1] bits above the low byte and tune[7] are switches of the experiments build (libhyperball_exp.so, "
                                            "-DHB_EXPERIMENTS: stract_amd/csrc/hb_experiments.h); the product library has none of them");
 #endif
@@ -665,7 +684,7 @@ int hb_create(const hb_options *opt, hb_ctx **out)
         };
         if (hipSetDevice(dev) != hipSuccess) { ctx->err = "hipSetDevice failed"; return bail(HB_ERR_HIP); }
         if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { ctx->err = "hipStreamCreate failed"; return bail(HB_ERR_HIP); }
-        for (int i = 0; i < 6; i++)
+        for (int i = 0; i < kEvSlots; i++)
             if (hipEventCreate(&ctx->ev[i]) != hipSuccess) { ctx->err = "hipEventCreate failed"; return bail(HB_ERR_HIP); }
         {   // every small page-locked word the pass driver will ever read back, in one block, NOW: a hipHostMalloc inside the first run
             // cost that run 13 ms at C3 and ~200 ms at C4 under a loaded page cache (profiles/r05j_e2e_C4_first_run_and_store_phases.txt)
@@ -736,7 +755,7 @@ void hb_destroy(hb_ctx *ctx)
     for (auto &es : ctx->ev_pool)
         for (hipEvent_t e : es.e)
             if (e) (void)hipEventDestroy(e);
-    for (int i = 0; i < 6; i++)
+    for (int i = 0; i < kEvSlots; i++)
         if (ctx->ev[i]) (void)hipEventDestroy(ctx->ev[i]);
     for (int i = 0; i < hb_ctx::kOverlap; i++) {
         if (ctx->ov_merged[i]) (void)hipEventDestroy(ctx->ov_merged[i]);
@@ -1226,7 +1245,7 @@ int hb_finish(hb_ctx *c)
             // puts on the list, and the host applies the list AFTER the download has landed (hipEventSynchronize below): whichever of the
             // two values of such an entry the copy carried, the list's is the one that stays.  If the list overflows, out[] is shipped
             // whole behind the download instead.
-            const unsigned blocks = (unsigned)std::min<uint64_t>((p.n_pad + 2047) / 2048, (uint64_t)c->num_cu * 8);
+            const unsigned blocks = grid_blocks(c, (p.n_pad + 2047) / 2048, 8);
             hipLaunchKernelGGL(hbk::results_sync_kernel, dim3(blocks), dim3(256), 0, c->stream, (const double *)c->d_ksum, rs.d_sent,
                                (const uint32_t *)c->d_cid_of, p.n_pad, norm, 0, c->d_out, rs.d_sid, rs.d_val, (unsigned long long)rs.cap, rs.d_count, cnt);
             HB_HIP(hipGetLastError());
@@ -1253,11 +1272,11 @@ int hb_finish(hb_ctx *c)
             if (c->rs.on) {
                 // no snapshot was taken (the loop ended before the policy asked for one): the compact image whole, from the same kernel
                 // (all rows, no list; sent[] is rewritten - nobody reads it before the next run's first snapshot does the same)
-                const unsigned blocks = (unsigned)std::min<uint64_t>((p.n_pad + 2047) / 2048, (uint64_t)c->num_cu * 8);
+                const unsigned blocks = grid_blocks(c, (p.n_pad + 2047) / 2048, 8);
                 hipLaunchKernelGGL(hbk::results_sync_kernel, dim3(blocks), dim3(256), 0, c->stream, (const double *)c->d_ksum, c->rs.d_sent,
                                    (const uint32_t *)c->d_cid_of, p.n_pad, norm, 1, c->d_out, (uint32_t *)nullptr, (double *)nullptr, 0ull, c->rs.d_count, cnt);
             } else {
-                unsigned blocks = (unsigned)std::min<uint64_t>((p.n + 255) / 256, (uint64_t)c->num_cu * 8);
+                unsigned blocks = grid_blocks(c, (p.n + 255) / 256, 8);
                 hipLaunchKernelGGL(hbk::finish_kernel, dim3(blocks), dim3(256), 0, c->stream, (const double *)c->d_ksum,
                                    (const uint32_t *)c->d_dev_of, p.n, norm, c->d_out, cnt);
             }

@@ -109,7 +109,7 @@ int hb_debug_state_hash(hb_ctx *c, uint64_t out[2])
         if (!n) return HB_OK;
         unsigned long long *cnt = c->d_counters + (size_t)c->max_passes * hbk::kCounterWords; // the spare slot
         HB_HIP(hipMemsetAsync(cnt, 0, hbk::kCounterWords * sizeof(unsigned long long), c->stream));
-        const unsigned blocks = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)c->num_cu * 8);
+        const unsigned blocks = grid_blocks(c, (n + 255) / 256, 8);
         hipLaunchKernelGGL(hbk::state_hash_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint4 *)c->d_regs[c->cur],
                            (const double *)c->d_ksum, (const double *)c->d_kerr, (const uint32_t *)c->d_dev_of, n, cnt);
         HB_HIP(hipGetLastError());

@@ -71,7 +71,7 @@ int distance_indegrees(hb_ctx *c)
     HB_HIP(hipMemsetAsync(d.d_indeg, 0, std::max<uint64_t>(rows_total, 1) * sizeof(uint32_t), c->stream));
     auto launch = [&](uint64_t lo, uint64_t hi) {
         if (hi <= lo) return;
-        const unsigned blocks = (unsigned)std::min<uint64_t>((hi - lo + 255) / 256, (uint64_t)c->num_cu * 8);
+        const unsigned blocks = grid_blocks(c, (hi - lo + 255) / 256, 8);
         hipLaunchKernelGGL(hbk::bfs_indegree_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr, (const uint32_t *)c->d_src, d.d_indeg,
                            p.n_pad, rows_total, lo, hi);
     };
@@ -170,13 +170,13 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
     uint64_t m_seen = m_f; // degree sum of the reached nodes
     uint64_t prev_n_f = 0;
     bool bottom_up = false;
-    const unsigned wblocks = (unsigned)std::max<uint64_t>(std::min<uint64_t>((n_pad / 32 + 255) / 256, (uint64_t)c->num_cu * 8), 1);
+    const unsigned wblocks = grid_blocks(c, (n_pad / 32 + 255) / 256, 8, 1);
     auto grid_words = [&](uint64_t lo, uint64_t hi, uint64_t words_per_block) {
         const uint64_t words = (hi - lo + 31) / 32;
-        return dim3((unsigned)std::max<uint64_t>(std::min<uint64_t>((words + words_per_block - 1) / words_per_block, (uint64_t)c->num_cu * 8), 1));
+        return dim3(grid_blocks(c, (words + words_per_block - 1) / words_per_block, 8, 1));
     };
     const size_t nlev = p.level_begin.size() > 1 ? p.level_begin.size() - 1 : 0;
-    HB_HIP(hipEventRecord(c->ev[0], c->stream));
+    HB_HIP(hipEventRecord(c->ev[kEvStart], c->stream));
     for (uint32_t lvl = 1; lvl <= d_max && n_f; lvl++) {
         // the step: Beamer's rule, with hysteresis (a bottom-up phase ends only when the frontier is small AND shrinking)
         const uint64_t m_u = c->m_global > m_seen ? c->m_global - m_seen : 0;
@@ -228,10 +228,10 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
         st.edges_inspected += h[2];
         if (n_f) st.max_distance = lvl;
     }
-    HB_HIP(hipEventRecord(c->ev[1], c->stream));
+    HB_HIP(hipEventRecord(c->ev[kEvEnd], c->stream));
     HB_HIP(hipStreamSynchronize(c->stream));
     float ms = 0.f;
-    HB_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    HB_HIP(hipEventElapsedTime(&ms, c->ev[kEvStart], c->ev[kEvEnd]));
     st.ms_levels = ms;
     d.reached = st.reached;
     d.valid = true;
@@ -245,7 +245,7 @@ int distance_extract(hb_ctx *c)
     if (d.extracted) return HB_OK;
     const Plan &p = c->plan;
     if (p.n && d.ready) {
-        const unsigned blocks = (unsigned)std::max<uint64_t>(std::min<uint64_t>((p.n + 255) / 256, (uint64_t)c->num_cu * 8), 1);
+        const unsigned blocks = grid_blocks(c, (p.n + 255) / 256, 8, 1);
         hipLaunchKernelGGL(hbk::bfs_by_sid_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint8_t *)d.d_dist, (const uint32_t *)c->d_dev_of, p.n, p.n_pad,
                            d.d_by_sid);
         HB_HIP(hipGetLastError());

@@ -124,9 +124,9 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
     double t0 = now_ms();
     const bool on_device = device_plan(c);
     // results shipped in stages while the passes run (results_stage): one rank, a download worth hiding (>= 8 MB) or forced
-    // (tune[1] bit 15; bit 14 = never)
-    c->rs.on = n && !multi_rank(c) && !linked(c) && !ref_tail(c) && !(HB_XBITS(c->opt.tune[1]) & 0x4000u) && (n >= (1u << 20) || (HB_XBITS(c->opt.tune[1]) & 0x8000u));
-    c->rs.cap = c->rs.on ? ((HB_XBITS(c->opt.tune[1]) & 0x10000u) ? 16 : n / 8 + 4096) : 0; // (bit 16: a list that overflows - the test of that path)
+    // (HB_X_SNAPSHOT_EVERY_PASS; HB_X_NO_STAGED_RESULTS = never)
+    c->rs.on = n && !multi_rank(c) && !linked(c) && !ref_tail(c) && !xbit(c, HB_X_NO_STAGED_RESULTS) && (n >= (1u << 20) || xbit(c, HB_X_SNAPSHOT_EVERY_PASS));
+    c->rs.cap = c->rs.on ? (xbit(c, HB_X_SHORT_FINAL_LIST) ? 16 : n / 8 + 4096) : 0;
     HostResultBuffers hostbuf; // (declared here: joined, and what the context has not taken freed, on every return path below)
     hostbuf.start(c->device, n, c->rs.cap);
     if (!in.d.d_row_ptr) in.reset(); // (no row pointers: no CSR)
@@ -161,7 +161,7 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
         HB_HIP(d_deg.alloc(n));
         HB_HIP(hipMemsetAsync(d_deg.get(), 0, n * sizeof(uint32_t), c->stream));
         if (m_eff) {
-            const unsigned blocks = (unsigned)std::min<uint64_t>((m_eff + 255) / 256, (uint64_t)c->num_cu * 16);
+            const unsigned blocks = grid_blocks(c, (m_eff + 255) / 256, 16);
             hipLaunchKernelGGL(hbk::histogram_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t *)in.d.d_src, m_eff, d_deg.get());
             HB_HIP(hipGetLastError());
         }
@@ -319,7 +319,7 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
         HB_HIP(d_words.alloc(nw));
         if ((rc = dev_alloc(c, &c->d_cid_of, p.n_pad))) return rc;
         HB_HIP(hipMemsetAsync(d_flags.get(), 0, (n + 1) * sizeof(uint32_t), c->stream));
-        const unsigned blocks = (unsigned)std::min<uint64_t>((p.n_pad + 255) / 256, (uint64_t)c->num_cu * 16);
+        const unsigned blocks = grid_blocks(c, (p.n_pad + 255) / 256, 16);
         hipLaunchKernelGGL(hbk::in_flags_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr, (const uint32_t *)c->d_sid_of, p.n_pad, d_flags.get());
         HB_HIP(hipGetLastError());
         const std::string e = device_prefix((void *)c->stream, d_flags.get(), n, d_cpos.get());
@@ -327,7 +327,7 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
         hipLaunchKernelGGL(hbk::cid_of_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr, (const uint32_t *)c->d_sid_of,
                            (const uint64_t *)d_cpos.get(), p.n_pad, c->d_cid_of);
         HB_HIP(hipGetLastError());
-        hipLaunchKernelGGL(hbk::pack_flags_kernel, dim3((unsigned)std::min<uint64_t>((nw + 3) / 4, (uint64_t)c->num_cu * 16)), dim3(256), 0, c->stream,
+        hipLaunchKernelGGL(hbk::pack_flags_kernel, dim3(grid_blocks(c, (nw + 3) / 4, 16)), dim3(256), 0, c->stream,
                            (const uint32_t *)d_flags.get(), n, d_words.get());
         HB_HIP(hipGetLastError());
         uint64_t n_c = 0;
@@ -357,9 +357,9 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
     lap("id_low");
     if (src_len && !(c->opt.flags & HB_FLAG_NO_INIT_PASS)) {
         if ((rc = dev_alloc(c, &c->d_src_jp, src_len + 4))) return rc;
-        const unsigned blocks = (unsigned)std::min<uint64_t>((src_len + 255) / 256, (uint64_t)c->num_cu * 16);
+        const unsigned blocks = grid_blocks(c, (src_len + 255) / 256, 16);
         if ((rc = dev_alloc(c, &c->d_self_jp, p.n_pad + 4))) return rc;
-        hipLaunchKernelGGL(hbk::self_jp_kernel, dim3((unsigned)std::min<uint64_t>((p.n_pad + 255) / 256, (uint64_t)c->num_cu * 16)), dim3(256), 0, c->stream,
+        hipLaunchKernelGGL(hbk::self_jp_kernel, dim3(grid_blocks(c, (p.n_pad + 255) / 256, 16)), dim3(256), 0, c->stream,
                            (const uint64_t *)c->d_idlow, (const uint32_t *)c->d_sid_of, p.n_pad, c->d_self_jp);
         HB_HIP(hipGetLastError());
         hipLaunchKernelGGL(hbk::src_jp_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t *)c->d_src, src_len, (const uint16_t *)c->d_self_jp, p.n_pad,
@@ -369,7 +369,7 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
         unsigned long long *d_l0 = c->d_counters + 8, h_l0 = ~0ull; // (d_counters is zeroed by hb_begin before every run)
         HB_HIP(hipMemsetAsync(d_l0, 0, sizeof(unsigned long long), c->stream));
         const uint64_t l0_lo = p.level_begin.size() > 1 ? p.level_begin[0] : 0, l0_hi = p.level_begin.size() > 1 ? p.level_begin[1] : 0;
-        hipLaunchKernelGGL(hbk::virt_rows_kernel, dim3((unsigned)std::min<uint64_t>((rows_total + 255) / 256, (uint64_t)c->num_cu * 16)), dim3(256), 0, c->stream,
+        hipLaunchKernelGGL(hbk::virt_rows_kernel, dim3(grid_blocks(c, (rows_total + 255) / 256, 16)), dim3(256), 0, c->stream,
                            (const uint64_t *)c->d_row_ptr, (const uint32_t *)c->d_src, rows_total, p.n_pad, c->d_virt_rows, l0_lo, l0_hi, d_l0);
         HB_HIP(hipGetLastError());
         HB_HIP(hipMemcpyAsync(&h_l0, d_l0, sizeof(h_l0), hipMemcpyDeviceToHost, c->stream));
@@ -383,7 +383,7 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
         unsigned long long h_bad[4] = {0, 0, 0, 0};
         HB_HIP(hipMemsetAsync(d_bad, 0, sizeof(h_bad), c->stream));
         if (rows_total) {
-            const unsigned blocks = (unsigned)std::min<uint64_t>((rows_total * 4 + 255) / 256, (uint64_t)c->num_cu * 16);
+            const unsigned blocks = grid_blocks(c, (rows_total * 4 + 255) / 256, 16);
             hipLaunchKernelGGL(hbk::validate_plan_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr, (const uint32_t *)c->d_src,
                                rows_total, p.n_pad, src_len, d_bad);
             HB_HIP(hipGetLastError());
@@ -423,7 +423,7 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
         // ... and the device's first writes into those pages, and the first use of everything the run's read-backs go through (the side
         // stream's copy queue, cross-stream event waits, event queries, elapsed times, the pinned counter words), happen now as well:
         // one pass over each buffer (14 ms at C4), in the order a run uses them
-        HB_HIP(hipEventRecord(c->ev[0], c->stream));
+        HB_HIP(hipEventRecord(c->ev[kEvStart], c->stream));
         if (c->rs.on) {
             HB_HIP(hipEventRecord(c->rs_ready, c->stream));
             HB_HIP(hipStreamWaitEvent(c->rs_stream, c->rs_ready, 0));
@@ -441,7 +441,7 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
             HB_HIP(hipMemcpyAsync(c->h_slot + (size_t)k * hbk::kCounterWords, c->d_counters, hbk::kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
             HB_HIP(hipEventRecord(c->slot_done[k], c->stream));
         }
-        HB_HIP(hipEventRecord(c->ev[1], c->stream));
+        HB_HIP(hipEventRecord(c->ev[kEvEnd], c->stream));
         HB_HIP(hipEventSynchronize(c->slot_done[1]));
         if (c->rs.on) {
             (void)hipEventQuery(c->rs_copied);
@@ -449,7 +449,7 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
         }
         HB_HIP(hipStreamSynchronize(c->stream));
         float ms_warm = 0.f;
-        HB_HIP(hipEventElapsedTime(&ms_warm, c->ev[0], c->ev[1]));
+        HB_HIP(hipEventElapsedTime(&ms_warm, c->ev[kEvStart], c->ev[kEvEnd]));
     }
     HB_HIP(hipStreamSynchronize(c->stream));
     if (c->rs_stream) HB_HIP(hipStreamSynchronize(c->rs_stream));

@@ -1,113 +1,113 @@
 // hb_api_pass.inc - part of the hb_api.hip translation unit (included there; uses its hb_ctx and helpers).
-// The pass driver: kernel dispatch, one pass in its three modes, the multi-GPU exchanges, the reference-tail mode.
+// The pass driver: the kernel selectors, one pass in its three modes and how it is booked, the multi-GPU exchanges, the reference-tail
+// mode, hb_run's tail pipeline, the load-time warm-up.
 // ---- kernel dispatch ----------------------------------------------------------------------
-// dense pass kernel: template instance from the run-time choices
-template <bool REAL, bool FUSED>
-void launch_dense(hb_ctx *c, const hbk::PassParams &pp, bool stats, int unroll, dim3 grid, bool init, bool epi4)
+// The run-time choices -> the template instance.  These selectors are the only place that names one: launch_pass, the sweep pass and
+// warm_kernels all ask here, so what is warmed at load is what a run launches.
+using PassKernel = void (*)(const hbk::PassParams);
+using SweepKernel = void (*)(const hbk::SweepParams);
+
+template <bool REAL, bool FUSED, bool STATS, bool INIT, bool EPI4>
+PassKernel dense_by_unroll(int unroll)
 {
-    hipStream_t s = c->stream;
-    if (init && !stats) { // pass 0: the sources' initial registers stream in with the edge list (hb_kernels.hip.h)
-        if constexpr (REAL && FUSED) {
-            if (epi4) {
-                if (unroll == 2) hipLaunchKernelGGL((hbk::pass_kernel<REAL, FUSED, false, 2, true, true>), grid, dim3(256), 0, s, pp);
-                else hipLaunchKernelGGL((hbk::pass_kernel<REAL, FUSED, false, 4, true, true>), grid, dim3(256), 0, s, pp);
-                return;
-            }
-        }
-        if (unroll == 2) hipLaunchKernelGGL((hbk::pass_kernel<REAL, FUSED, false, 2, true>), grid, dim3(256), 0, s, pp);
-        else hipLaunchKernelGGL((hbk::pass_kernel<REAL, FUSED, false, 4, true>), grid, dim3(256), 0, s, pp);
-        return;
+    if constexpr (!INIT) { // (the INIT form exists for 2 and 4 only)
+        if (unroll == 1) return hbk::pass_kernel<REAL, FUSED, STATS, 1, INIT, EPI4>;
     }
+    if (unroll == 2) return hbk::pass_kernel<REAL, FUSED, STATS, 2, INIT, EPI4>;
+    return hbk::pass_kernel<REAL, FUSED, STATS, 4, INIT, EPI4>;
+}
+template <bool REAL, bool FUSED>
+PassKernel dense_kernel_of(bool stats, int unroll, bool init, bool epi4)
+{
+    if (stats) return dense_by_unroll<REAL, FUSED, true, false, false>(unroll); // (a counting pass has neither the INIT nor the EPI4 form)
     if constexpr (REAL && FUSED) {
-        if (epi4 && !stats) { // once-per-row estimator / Kahan epilogue (default for the fused node rows)
-            if (unroll == 1) hipLaunchKernelGGL((hbk::pass_kernel<REAL, FUSED, false, 1, false, true>), grid, dim3(256), 0, s, pp);
-            else if (unroll == 2) hipLaunchKernelGGL((hbk::pass_kernel<REAL, FUSED, false, 2, false, true>), grid, dim3(256), 0, s, pp);
-            else hipLaunchKernelGGL((hbk::pass_kernel<REAL, FUSED, false, 4, false, true>), grid, dim3(256), 0, s, pp);
-            return;
-        }
+        // EPI4: the once-per-row estimator / Kahan epilogue (default for the fused node rows)
+        if (epi4) return init ? dense_by_unroll<true, true, false, true, true>(unroll) : dense_by_unroll<true, true, false, false, true>(unroll);
     }
-#define HB_LAUNCH(ST, UN) hipLaunchKernelGGL((hbk::pass_kernel<REAL, FUSED, ST, UN>), grid, dim3(256), 0, s, pp)
-    if (stats) {
-        if (unroll == 1) HB_LAUNCH(true, 1);
-        else if (unroll == 2) HB_LAUNCH(true, 2);
-        else HB_LAUNCH(true, 4);
-    } else {
-        if (unroll == 1) HB_LAUNCH(false, 1);
-        else if (unroll == 2) HB_LAUNCH(false, 2);
-        else HB_LAUNCH(false, 4);
-    }
-#undef HB_LAUNCH
+    return init ? dense_by_unroll<REAL, FUSED, false, true, false>(unroll) : dense_by_unroll<REAL, FUSED, false, false, false>(unroll);
+}
+// dense pass.  real: node rows (else hub chunks, which are never fused); init: pass 0, the sources' initial registers stream in with
+// the edge list (hb_kernels.hip.h)
+PassKernel dense_kernel(bool real, bool fused, bool stats, int unroll, bool init, bool epi4)
+{
+    init = init && unroll != 1;
+    if (real && fused) return dense_kernel_of<true, true>(stats, unroll, init, epi4);
+    if (real) return dense_kernel_of<true, false>(stats, unroll, init, false);
+    return dense_kernel_of<false, false>(stats, unroll, init, false);
+}
+
+template <bool REAL, bool FUSED>
+PassKernel bitmap_kernel_of(bool stats, bool compact)
+{
+    constexpr int W = REAL ? 4 : 16;
+    if (stats) return compact ? hbk::frontier_kernel<REAL, FUSED, true, W, true> : hbk::frontier_kernel<REAL, FUSED, true, W, false>;
+    return compact ? hbk::frontier_kernel<REAL, FUSED, false, W, true> : hbk::frontier_kernel<REAL, FUSED, false, W, false>;
+}
+// the bitmap pass: all indices / all bit words / needed gathers of a row as three batched round trips; !compact: gather slot by slot
+PassKernel bitmap_kernel(bool real, bool fused, bool stats, bool compact)
+{
+    if (real && fused) return bitmap_kernel_of<true, true>(stats, compact);
+    if (real) return bitmap_kernel_of<true, false>(stats, compact);
+    return bitmap_kernel_of<false, false>(stats, compact);
+}
+
+// the rows of a sweep pass; by_rounds (experiments build): a touched row's sources 8 per round
+SweepKernel sweep_rows_kernel_for(bool real, bool by_rounds)
+{
+#ifdef HB_EXPERIMENTS
+    if (by_rounds) return real ? hbk::sweep_rows_kernel<true, true> : hbk::sweep_rows_kernel<false, true>;
+#endif
+    (void)by_rounds;
+    return real ? hbk::sweep_rows_kernel<true> : hbk::sweep_rows_kernel<false>;
+}
+
+// gathers in flight: the low byte of tune[1], else 16 per quad for the hub chunks (pure gather loops) and 8 for the node rows, whose
+// fused estimator/Kahan epilogue needs the registers (unroll 4 drops them to 3 waves/SIMD)
+int pass_unroll(const hb_ctx *c, bool real)
+{
+    const int unroll = (int)(c->opt.tune[1] & HB_TUNE1_UNROLL);
+    return (unroll == 1 || unroll == 2 || unroll == 4) ? unroll : (real ? 2 : 4);
+}
+// pass 0 of this context, when it is a dense pass, is the INIT launch
+bool pass0_streams_initial_registers(const hb_ctx *c)
+{
+    return c->d_src_jp != nullptr && c->d_self_jp != nullptr && !(c->opt.flags & HB_FLAG_NO_INIT_PASS) && pass_unroll(c, true) != 1;
 }
 
 void launch_pass(hb_ctx *c, const hbk::PassParams &pp, bool real, bool frontier, bool fused, int level = -1)
 {
     const bool stats = (c->opt.flags & HB_FLAG_PASS_STATS) != 0;
-    int unroll = (int)(c->opt.tune[1] & 0xFFu);
-    const bool epi4 = !(HB_XBITS(c->opt.tune[1]) & 0x100u); // tune[1] bit 8: the per-tile epilogue (measurement switch)
-    // default: 16 gathers in flight per quad for the hub chunks (pure gather loops); 8 for the node rows,
-    // whose fused estimator/Kahan epilogue needs the registers (unroll 4 drops them to 3 waves/SIMD)
-    if (unroll != 1 && unroll != 2 && unroll != 4) unroll = real ? 2 : 4;
     const uint64_t ntiles = (pp.row_hi - pp.row_lo + 63) / 64;
     if (ntiles == 0) return;
+    const bool init = c->t == 0 && !frontier && pass0_streams_initial_registers(c);
     // workgroups per CU: low byte of tune[0] = node rows, second byte = hub chunks (0 = default).  Measured
     // (profiles/r02s_sweep_bpc_*): the hub-chunk gather loop is fastest with only 2 workgroups (8 waves) per CU - each
     // quad already keeps 16 gathers in flight, more waves only add contention (dense pass -12 % at C3, -16 % at C4);
     // the bitmap pass has dependent bit tests in front of the gathers and wants 5 (83 VGPRs: 5 waves per SIMD fit).  Node rows: many small
     // workgroups, the hardware scheduler levels the uneven tiles (1.13 -> 1.05 ms at C3).
     uint32_t bpc = real ? (c->opt.tune[0] & 0xFFu) : ((c->opt.tune[0] >> 8) & 0xFFu);
-    if (!bpc) bpc = real ? (frontier ? 32u : 64u) : (frontier ? 5u : 2u);
-    uint64_t blocks = std::min<uint64_t>(ntiles, (uint64_t)c->num_cu * bpc);
-    if (pp.xcd_map) blocks = std::max<uint64_t>((blocks + 7) / 8 * 8, 8); // 8 queues, equal shares of the grid
-    const bool init = c->t == 0 && !frontier && pp.src_jp != nullptr && !(c->opt.flags & HB_FLAG_NO_INIT_PASS) && unroll != 1;
-    if (init && !real && !((c->opt.tune[0] >> 8) & 0xFFu)) {
-        // pass 0 streams its sources: no L2 window to protect, the scratch-counter updates want every wave the CU can hold
-        blocks = std::min<uint64_t>(ntiles, (uint64_t)c->num_cu * 8);
-        if (pp.xcd_map) blocks = std::max<uint64_t>((blocks + 7) / 8 * 8, 8);
-    }
-    if (init && !real && level == 0 && c->level0_all_real && !stats && !(HB_XBITS(c->opt.tune[1]) & 0x8000000u)) {
-        // pass 0, first level of hub chunks: the streaming kernel of its own (bit 27 of the experiments build: the generic kernel, A/B)
-        hipLaunchKernelGGL(hbk::init_level1_kernel, dim3((unsigned)std::min<uint64_t>(ntiles, (uint64_t)c->num_cu * 8)), dim3(256), 0, c->stream, pp);
-        return;
-    }
-    dim3 grid((unsigned)blocks);
-    if (frontier) {
-        // the bitmap pass: all indices / all bit words / needed gathers of a row as three batched round trips
-        hipStream_t st = c->stream;
-        const bool compact = !(HB_XBITS(c->opt.tune[1]) & 0x2000u); // bit 13: gather slot by slot (the round-2 form), for A/B runs
-#define HB_FRONT2(R, F, S, C) hipLaunchKernelGGL((hbk::frontier_kernel<R, F, S, (R ? 4 : 16), C>), grid, dim3(256), 0, st, pp)
-#define HB_FRONT(R, F) \
-    do { \
-        if (stats && compact) HB_FRONT2(R, F, true, true); \
-        else if (stats) HB_FRONT2(R, F, true, false); \
-        else if (compact) HB_FRONT2(R, F, false, true); \
-        else HB_FRONT2(R, F, false, false); \
-    } while (0)
-        if (real && fused) HB_FRONT(true, true);
-        else if (real) HB_FRONT(true, false);
-        else HB_FRONT(false, false);
-#undef HB_FRONT
-#undef HB_FRONT2
-        return;
-    }
-    if (real) {
-        if (fused) launch_dense<true, true>(c, pp, stats, unroll, grid, init, epi4);
-        else launch_dense<true, false>(c, pp, stats, unroll, grid, init, false);
+    // pass 0 streams its sources: no L2 window to protect, the scratch-counter updates want every wave the CU can hold
+    if (!bpc) bpc = real ? (frontier ? 32u : 64u) : (frontier ? 5u : (init ? 8u : 2u));
+    PassKernel kernel;
+    unsigned blocks;
+    if (init && !real && level == 0 && c->level0_all_real && !stats && !xbit(c, HB_X_GENERIC_LEVEL1)) {
+        kernel = hbk::init_level1_kernel; // pass 0, first level of hub chunks: the streaming kernel of its own
+        blocks = grid_blocks(c, ntiles, 8);
     } else {
-        launch_dense<false, false>(c, pp, stats, unroll, grid, init, false);
+        blocks = grid_blocks(c, ntiles, bpc);
+        if (pp.xcd_map) blocks = std::max((blocks + 7) / 8 * 8, 8u); // 8 queues, equal shares of the grid
+        kernel = frontier ? bitmap_kernel(real, fused, stats, !xbit(c, HB_X_BITMAP_SLOTWISE))
+                          : dense_kernel(real, fused, stats, pass_unroll(c, real), init, !xbit(c, HB_X_TILE_EPILOGUE));
     }
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, c->stream, pp);
 }
 
 // ---- the initial state (harmonic.rs:53-73) ---------------------------------------------------------------------------------
 // written by init_kernel - or, when pass 0 will be the fused INIT launch of ONE rank, left to that launch (PassParams::rd_init)
-bool pass0_streams_initial_registers(const hb_ctx *c) // the condition launch_pass() uses for INIT at t == 0
-{
-    int unroll = (int)(c->opt.tune[1] & 0xFFu);
-    return c->d_src_jp != nullptr && c->d_self_jp != nullptr && !(c->opt.flags & HB_FLAG_NO_INIT_PASS) && unroll != 1;
-}
 bool lean_pass0(const hb_ctx *c)
 {
     return pass0_streams_initial_registers(c) && !unfused(c) && !multi_rank(c) && !linked(c) && !dest_mode(c) && !(c->opt.flags & HB_FLAG_PASS_STATS) &&
-           !(HB_XBITS(c->opt.tune[1]) & 0x800000u); // bit 23: hb_begin always writes the whole initial state (measurement / test switch)
+           !xbit(c, HB_X_FULL_INIT);
 }
 int launch_full_init(hb_ctx *c)
 {
@@ -163,14 +163,14 @@ hbk::PassParams make_params(hb_ctx *c)
     pp.rd_init = nullptr;
     pp.self_jp = c->d_self_jp;
     pp.virt_rows = c->d_virt_rows;
-    pp.xflags = (HB_XBITS(c->opt.tune[1]) & 0x10000000u) ? 1u : 0u;
+    pp.xflags = xbit(c, HB_X_PROBE_NO_SIZE) ? 1u : 0u;
     return pp;
 }
 
 bool changed_only(const hb_ctx *c) { return dest_mode(c) && (c->opt.flags & HB_FLAG_CHANGED_ONLY); }
 // bytes of one packed counter in the destination partition's changed-only exchange: 6 bits per register (hb_aux.hip.h pack6_quarter:
-// exact, the register set of this path has 60 members); experiments build, tune[1] bit 24: the 64-byte form (A/B)
-uint64_t packed_row_bytes(const hb_ctx *c) { return (HB_XBITS(c->opt.tune[1]) & 0x1000000u) ? 64 : 48; }
+// exact, the register set of this path has 60 members), or the 64-byte form (A/B)
+uint64_t packed_row_bytes(const hb_ctx *c) { return xbit(c, HB_X_WIRE_64B) ? 64 : 48; }
 // destination partition + changed-only on a communicator: the host round trip of a pass sits in its middle, the end is left in
 // flight and the timing events are read later; such passes need event sets of their own (the six shared ones would be re-recorded
 // by the next pass before they are read)
@@ -192,6 +192,14 @@ int pass_events(hb_ctx *c, hipEvent_t **out)
     *out = c->ev_pool[c->t].e;
     return HB_OK;
 }
+// ms_gpu / ms_main / ms_level1 of a pass from its events (`end`: the last one it recorded); ms_collective is the caller's
+int read_pass_times(hb_ctx *c, hipEvent_t *E, PassEvent end, hb_pass_stats *ps)
+{
+    HB_HIP(hipEventElapsedTime(&ps->ms_gpu, E[kEvStart], E[end]));
+    HB_HIP(hipEventElapsedTime(&ps->ms_main, E[kEvLevels], E[kEvMerge]));
+    if (ps->mode == 2 || (ps->mode < 2 && c->plan.level_begin.size() > 1)) HB_HIP(hipEventElapsedTime(&ps->ms_level1, E[kEvStart], E[kEvLevel1]));
+    return HB_OK;
+}
 // ms_* of the passes whose end was left in flight (hb_finish, hb_get_pass_stats)
 int resolve_pass_times(hb_ctx *c)
 {
@@ -199,26 +207,18 @@ int resolve_pass_times(hb_ctx *c)
         if (t >= c->pstats.size() || t >= c->ev_pool.size()) continue;
         hipEvent_t *E = c->ev_pool[t].e;
         hb_pass_stats &ps = c->pstats[t];
-        HB_HIP(hipEventSynchronize(E[3]));
-        float ms_all = 0.f, ms_main = 0.f, ms_coll = 0.f, ms_l1 = 0.f;
-        HB_HIP(hipEventElapsedTime(&ms_all, E[0], E[3]));
-        HB_HIP(hipEventElapsedTime(&ms_main, E[1], E[2]));
-        HB_HIP(hipEventElapsedTime(&ms_coll, E[2], E[3]));
-        ps.ms_gpu = ms_all;
-        ps.ms_main = ms_main;
-        ps.ms_collective = ms_coll;
-        if ((ps.mode < 2 && c->plan.level_begin.size() > 1) || ps.mode == 2) {
-            HB_HIP(hipEventElapsedTime(&ms_l1, E[0], E[5]));
-            ps.ms_level1 = ms_l1;
-        }
+        HB_HIP(hipEventSynchronize(E[kEvCollective]));
+        const int rc = read_pass_times(c, E, kEvCollective, &ps);
+        if (rc) return rc;
+        HB_HIP(hipEventElapsedTime(&ps.ms_collective, E[kEvMerge], E[kEvCollective]));
     }
     c->pending_times.clear();
     return HB_OK;
 }
-// plain edge partition on a communicator: pipeline merge / all-reduce / epilogue over row ranges (tune[1] bit 12 = off)
+// plain edge partition on a communicator: pipeline merge / all-reduce / epilogue over row ranges
 bool edge_overlap(const hb_ctx *c)
 {
-    return linked(c) && !dest_mode(c) && !ref_tail(c) && !(c->opt.flags & HB_FLAG_CHANGED_ONLY) && !(HB_XBITS(c->opt.tune[1]) & 0x1000u) && c->comm_stream;
+    return linked(c) && !dest_mode(c) && !ref_tail(c) && !(c->opt.flags & HB_FLAG_CHANGED_ONLY) && !xbit(c, HB_X_NO_EDGE_OVERLAP) && c->comm_stream;
 }
 // edge partition (all-reduce) with HB_FLAG_CHANGED_ONLY: only the rows some rank's local merge changed are exchanged
 bool edge_changed_only(const hb_ctx *c)
@@ -226,21 +226,39 @@ bool edge_changed_only(const hb_ctx *c)
     return (c->opt.flags & HB_FLAG_CHANGED_ONLY) && !dest_mode(c) && !ref_tail(c) && (multi_rank(c) || linked(c));
 }
 
+// the changed-only exchanges' packed rows and the prefix sums over a row bitmap's words, allocated by the first pass that exchanges
+int ensure_pack_buffers(hb_ctx *c)
+{
+    if (c->d_pack) return HB_OK;
+    const uint64_t n_pad = c->plan.n_pad, words = n_pad / 32;
+    int rc;
+    if ((rc = dev_alloc(c, &c->d_pack, n_pad * 4))) return rc;
+    if ((rc = dev_alloc(c, &c->d_wpop, words + 1))) return rc;
+    return dev_alloc(c, &c->d_wprefix, words + 2);
+}
+// d_wprefix = exclusive prefix sums of the set bits in the words of `bits` (one bit per node row): the packed position of every row
+int changed_word_prefix(hb_ctx *c, const uint32_t *bits)
+{
+    const uint64_t words = c->plan.n_pad / 32;
+    if (words) {
+        hipLaunchKernelGGL(hbk::popcount_words_kernel, dim3(grid_blocks(c, (words + 255) / 256, 8)), dim3(256), 0, c->stream, bits, words, c->d_wpop);
+        HB_HIP(hipGetLastError());
+    }
+    const std::string e = device_prefix((void *)c->stream, c->d_wpop, words, c->d_wprefix);
+    if (!e.empty()) return fail(c, HB_ERR_HIP, e);
+    return HB_OK;
+}
+
 int edge_co_alloc(hb_ctx *c)
 {
     if (c->d_lbits) return HB_OK;
-    const Plan &p = c->plan;
-    const uint64_t words = p.n_pad / 32;
+    const uint64_t words = c->plan.n_pad / 32;
     const uint64_t world = (uint64_t)std::max(c->opt.world_size, 1);
     int rc;
     if ((rc = dev_alloc(c, &c->d_lbits, words + 2))) return rc;
     if ((rc = dev_alloc(c, &c->d_lbits_all, world * words + 2))) return rc;
     if ((rc = dev_alloc(c, &c->d_ubits, words + 2))) return rc;
-    if (!c->d_pack) {
-        if ((rc = dev_alloc(c, &c->d_pack, p.n_pad * 4))) return rc;
-        if ((rc = dev_alloc(c, &c->d_wpop, words + 1))) return rc;
-        if ((rc = dev_alloc(c, &c->d_wprefix, words + 2))) return rc;
-    }
+    if ((rc = ensure_pack_buffers(c))) return rc;
     HB_HIP(hipMemsetAsync(c->d_lbits, 0, (words + 2) * 4, c->stream));
     return HB_OK;
 }
@@ -251,13 +269,8 @@ int edge_co_pack(hb_ctx *c)
     const Plan &p = c->plan;
     const uint64_t words = p.n_pad / 32;
     hbk::PassParams pp = make_params(c);
-    if (words) {
-        const unsigned blocks = (unsigned)std::min<uint64_t>((words + 255) / 256, (uint64_t)c->num_cu * 8);
-        hipLaunchKernelGGL(hbk::popcount_words_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t *)c->d_ubits, words, c->d_wpop);
-        HB_HIP(hipGetLastError());
-    }
-    const std::string e = device_prefix((void *)c->stream, c->d_wpop, words, c->d_wprefix);
-    if (!e.empty()) return fail(c, HB_ERR_HIP, e);
+    const int rc = changed_word_prefix(c, c->d_ubits);
+    if (rc) return rc;
     c->co_rows = 0;
     HB_HIP(hipMemcpyAsync(&c->co_rows, c->d_wprefix + words, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HB_HIP(hipStreamSynchronize(c->stream));
@@ -287,22 +300,12 @@ int edge_co_unpack(hb_ctx *c)
 int exchange_pack(hb_ctx *c, const uint64_t *host_off = nullptr)
 {
     const Plan &p = c->plan;
-    const uint64_t words = p.n_pad / 32, S = c->slice_rows;
+    const uint64_t S = c->slice_rows;
     const uint64_t world = (uint64_t)std::max(c->opt.world_size, 1), r = (uint64_t)c->opt.rank;
     int rc;
-    if (!c->d_pack) {
-        if ((rc = dev_alloc(c, &c->d_pack, p.n_pad * 4))) return rc;
-        if ((rc = dev_alloc(c, &c->d_wpop, words + 1))) return rc;
-        if ((rc = dev_alloc(c, &c->d_wprefix, words + 2))) return rc;
-    }
+    if ((rc = ensure_pack_buffers(c))) return rc;
     hbk::PassParams pp = make_params(c);
-    if (words) {
-        const unsigned blocks = (unsigned)std::min<uint64_t>((words + 255) / 256, (uint64_t)c->num_cu * 8);
-        hipLaunchKernelGGL(hbk::popcount_words_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t *)pp.bits_wr, words, c->d_wpop);
-        HB_HIP(hipGetLastError());
-    }
-    const std::string e = device_prefix((void *)c->stream, c->d_wpop, words, c->d_wprefix);
-    if (!e.empty()) return fail(c, HB_ERR_HIP, e);
+    if ((rc = changed_word_prefix(c, pp.bits_wr))) return rc;
     c->ex_off.assign(world + 1, 0);
     if (host_off) { // the pass driver: the run offsets follow from the ranks' changed counts, which came with the pass counters
         for (uint64_t k = 0; k <= world; k++) c->ex_off[k] = host_off[k];
@@ -388,15 +391,13 @@ int tail_pass(hb_ctx *c, const hbk::PassParams &pp)
     unsigned int *d_len = (unsigned int *)(c->d_bloom_ones + 1);
     HB_HIP(hipMemcpyAsync(pp.wr, pp.rd, p.n_pad * 64, hipMemcpyDeviceToDevice, c->stream));
     HB_HIP(hipMemsetAsync(d_len, 0, sizeof(unsigned int), c->stream));
-    const unsigned blocks = (unsigned)std::min<uint64_t>(std::max<uint64_t>(p.n_pad / 256, 1), (uint64_t)c->num_cu * 8);
-    hipLaunchKernelGGL(hbk::changed_list_kernel, dim3(blocks), dim3(256), 0, c->stream, pp.bits_rd, p.n_pad, c->d_list, d_len,
+    hipLaunchKernelGGL(hbk::changed_list_kernel, dim3(grid_blocks(c, p.n_pad / 256, 8, 1)), dim3(256), 0, c->stream, pp.bits_rd, p.n_pad, c->d_list, d_len,
                        (uint32_t)(c->ref_threshold + 1));
-    HB_HIP(hipEventRecord(c->ev[5], c->stream));
-    HB_HIP(hipEventRecord(c->ev[1], c->stream));
-    const unsigned tblocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((c->last_changed + 3) / 4, (uint64_t)c->num_cu * 8));
-    hipLaunchKernelGGL(hbk::tail_merge_kernel, dim3(tblocks), dim3(256), 0, c->stream, (const uint32_t *)c->d_list, (const unsigned int *)d_len,
+    HB_HIP(hipEventRecord(c->ev[kEvLevel1], c->stream));
+    HB_HIP(hipEventRecord(c->ev[kEvLevels], c->stream));
+    hipLaunchKernelGGL(hbk::tail_merge_kernel, dim3(grid_blocks(c, (c->last_changed + 3) / 4, 8, 1)), dim3(256), 0, c->stream, (const uint32_t *)c->d_list, (const unsigned int *)d_len,
                        (const uint64_t *)c->d_tail_ptr, (const uint32_t *)c->d_tail_to, (const uint32_t *)pp.rd, (uint32_t *)pp.wr);
-    HB_HIP(hipEventRecord(c->ev[2], c->stream));
+    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
     HB_HIP(hipGetLastError());
     c->pending_local = true;
     return HB_OK;
@@ -413,12 +414,10 @@ int reference_changed_state(hb_ctx *c, const uint32_t *bits_changed, uint64_t ch
         HB_HIP(hipMemsetAsync(c->d_bloom_ones, 0, sizeof(unsigned long long), c->stream));
         unsigned long long ones = 0;
         if (changed && c->bloom_bits) {
-            const unsigned blocks = (unsigned)std::min<uint64_t>(std::max<uint64_t>(p.n_pad / 256, 1), (uint64_t)c->num_cu * 8);
-            hipLaunchKernelGGL(hbk::bloom_insert_kernel, dim3(blocks), dim3(256), 0, c->stream, bits_changed, (const uint64_t *)c->d_idlow, p.n_pad,
+            hipLaunchKernelGGL(hbk::bloom_insert_kernel, dim3(grid_blocks(c, p.n_pad / 256, 8, 1)), dim3(256), 0, c->stream, bits_changed, (const uint64_t *)c->d_idlow, p.n_pad,
                                c->bloom_bits, c->d_bloom);
             if (!c->exact_counting) {
-                const unsigned cblocks = (unsigned)std::min<uint64_t>(std::max<uint64_t>(words / 256, 1), (uint64_t)c->num_cu * 8);
-                hipLaunchKernelGGL(hbk::bloom_count_kernel, dim3(cblocks), dim3(256), 0, c->stream, (const uint32_t *)c->d_bloom, words, c->d_bloom_ones);
+                hipLaunchKernelGGL(hbk::bloom_count_kernel, dim3(grid_blocks(c, words / 256, 8, 1)), dim3(256), 0, c->stream, (const uint32_t *)c->d_bloom, words, c->d_bloom_ones);
                 HB_HIP(hipMemcpyAsync(&ones, c->d_bloom_ones, sizeof(ones), hipMemcpyDeviceToHost, c->stream));
                 HB_HIP(hipStreamSynchronize(c->stream));
             }
@@ -461,6 +460,27 @@ int upload_tail_index(hb_ctx *c)
     return HB_OK;
 }
 
+// ---- the mode of a pass ------------------------------------------------------------------------------------------------------------------
+// A_t = edges whose source changed in the previous pass (= out-degree sum of those nodes, counted by the previous pass).  dense: every
+// source is gathered (no test) - while most nodes still change the frontier test would only cost; bitmap (frontier): every index is read
+// and bit-tested, only active sources are gathered (pays while A_t < ~half of the edges); sweep (sparse): only the work rows that read a
+// changed node are visited at all - the convergence tail.  Every mode gives the same bits (SURVEY App. C-1).
+enum PassMode : uint32_t { kModeDense = 0, kModeBitmap = 1, kModeSweep = 2 }; // (hb_pass_stats::mode; hb_sample.hip.h kSample* are the same numbers)
+// A_t < tune[2] % of the edges (default 50)
+bool below_dense_threshold(const hb_ctx *c, uint64_t active_edges)
+{
+    const uint32_t thr = c->opt.tune[2] ? c->opt.tune[2] : 50;
+    return active_edges * 100ull < (uint64_t)thr * c->m_global;
+}
+PassMode pass_mode(const hb_ctx *c, uint64_t active_edges)
+{
+    if ((c->opt.flags & HB_FLAG_NO_FRONTIER) || !(below_dense_threshold(c, active_edges) || c->opt.tune[2] > 100)) return kModeDense;
+    // sweep when A_t * tune[6] < edges: measured crossover with the bitmap pass at A_t = 10-12 % of the edges
+    // (profiles/r02c_sweep_*: 7.4 % -> 1.25 ms vs 2.15 ms, 16 % -> 4.1 ms vs 2.1 ms on the C3-sized graphs)
+    const uint64_t sparse_div = c->opt.tune[6] ? c->opt.tune[6] : 10;
+    return c->sparse_ok && (active_edges * sparse_div < c->m_global || c->opt.tune[6] == 1) ? kModeSweep : kModeBitmap;
+}
+
 // ---- results that travel while the passes run ------------------------------------------------------------------------------
 // A snapshot: out[] (ascending-NodeID order, normalised) is refreshed from the current sums on the MAIN stream (between two
 // passes: ~2.3 ms at C4 when every row is new, 1.1 ms for a third of them) and downloaded on the side stream while the next pass
@@ -473,8 +493,7 @@ int results_stage(hb_ctx *c)
     const Plan &p = c->plan;
     auto &rs = c->rs;
     const double norm = (double)(p.n ? p.n - 1 : 0);
-    const unsigned blocks = (unsigned)std::min<uint64_t>((p.n_pad + 2047) / 2048, (uint64_t)c->num_cu * 8);
-    hipLaunchKernelGGL(hbk::results_sync_kernel, dim3(blocks), dim3(256), 0, c->stream, (const double *)c->d_ksum, rs.d_sent, (const uint32_t *)c->d_cid_of,
+    hipLaunchKernelGGL(hbk::results_sync_kernel, dim3(grid_blocks(c, (p.n_pad + 2047) / 2048, 8)), dim3(256), 0, c->stream, (const double *)c->d_ksum, rs.d_sent, (const uint32_t *)c->d_cid_of,
                        p.n_pad, norm, rs.valid ? 0 : 1, c->d_out, (uint32_t *)nullptr, (double *)nullptr, 0ull, rs.d_count, rs.d_kept);
     HB_HIP(hipGetLastError());
     HB_HIP(hipEventRecord(c->rs_ready, c->stream));
@@ -488,7 +507,7 @@ int results_stage(hb_ctx *c)
     return HB_OK;
 }
 // after pass t (the loop goes on): is now the time for a snapshot?  The first one when the NEXT pass is no longer a dense one (A_{t+1}
-// below the dense threshold of step_local): the pass that just ended is then the last one that moved most sums.  [r6] Rounds 4-5 took
+// below_dense_threshold): the pass that just ended is then the last one that moved most sums.  [r6] Rounds 4-5 took
 // it at A_{t+1} <= 90 % of the edges; at C4 that is after pass 4 (A_5 = 79 %), pass 5 then moves 35.5 M of the 99 M sums again and a
 // second full image follows - the first snapshot's 2.4 ms on the main stream bought nothing (HB_TRACE_RESULTS timeline,
 // profiles/r06d_*).  Again whenever more than n / 8 sums moved since and the previous download is over (hb_finish's list holds n / 8).
@@ -497,21 +516,36 @@ int results_stage_policy(hb_ctx *c, uint64_t changed)
     auto &rs = c->rs;
     if (!rs.on || !c->has_changes) return HB_OK;
     rs.changed_since += changed;
-    const bool forced = (HB_XBITS(c->opt.tune[1]) & 0x8000u) != 0;
+    const bool forced = xbit(c, HB_X_SNAPSHOT_EVERY_PASS);
     bool go;
-    const uint32_t dense_thr = c->opt.tune[2] ? c->opt.tune[2] : 50; // (step_local's threshold: the next pass is dense at or above it)
-    if (!rs.valid) go = forced || c->last_active * 100ull < (uint64_t)dense_thr * c->m_global;
-    else go = (forced || rs.changed_since * 8 > c->plan.n) && !(HB_XBITS(c->opt.tune[1]) & 0x20000u) && hipEventQuery(c->rs_copied) == hipSuccess; // (bit 17: one snapshot only - test switch)
+    if (!rs.valid) go = forced || below_dense_threshold(c, c->last_active);
+    else go = (forced || rs.changed_since * 8 > c->plan.n) && !xbit(c, HB_X_ONE_SNAPSHOT) && hipEventQuery(c->rs_copied) == hipSuccess;
     (void)hipGetLastError(); // (hipErrorNotReady of the query is not an error)
     return go ? results_stage(c) : HB_OK;
 }
 
+// the parameters of the sweep kernels around `pp`.  The seed / heavy counters live in two slots used by alternate passes: a pass' first
+// kernel zeroes the other one (no memset launch per pass; hb_begin clears both)
+hbk::SweepParams make_sweep_params(const hb_ctx *c, const hbk::PassParams &pp, unsigned slot, const unsigned long long *guard)
+{
+    hbk::SweepParams sp{};
+    sp.p = pp;
+    sp.out_ptr = c->d_out_ptr;
+    sp.out_rows = c->d_out_rows;
+    sp.touch = c->d_touch;
+    sp.seeds = c->d_seeds;
+    sp.heavy = c->d_heavy;
+    sp.counts = c->d_sparse_counts + 2 * slot;
+    sp.counts_next = c->d_sparse_counts + 2 * (slot ^ 1);
+    sp.guard = guard;
+    return sp;
+}
+
 // Sweep mode, first step: the changed node rows -> touch bits of their readers.  `small` (few changed rows): one launch instead of
-// collect + expand + heavy.  Shared by step_local and hb_sampled_harmonic; the caller checks hipGetLastError.
+// collect + expand + heavy.  Shared by sweep_pass and hb_sampled_harmonic; the caller checks hipGetLastError.
 void launch_sweep_seeding(hb_ctx *c, const hbk::SweepParams &sp, bool small)
 {
-    const uint64_t real_words = sp.p.n_pad / 32;
-    const unsigned sblocks = (unsigned)std::min<uint64_t>(std::max<uint64_t>(real_words / 256, 1), (uint64_t)c->num_cu * 4);
+    const unsigned sblocks = grid_blocks(c, sp.p.n_pad / 32 / 256, 4, 1);
     const unsigned wblocks = (unsigned)c->num_cu * 4;
     if (small) {
         hipLaunchKernelGGL(hbk::sweep_seed_small_kernel, dim3(sblocks), dim3(256), 0, c->stream, sp);
@@ -522,6 +556,104 @@ void launch_sweep_seeding(hb_ctx *c, const hbk::SweepParams &sp, bool small)
     }
 }
 
+// ---- one pass, first half: its launches (step_local) -------------------------------------------------------------------------------------
+// sweep mode: changed nodes -> touch bits of their readers; then the levels, then the node rows.  No bitmap is cleared: the sweep
+// kernels rewrite every word of this pass' changed bits (node rows in bits_wr, virtual rows in the upper part of bits_rd) and keep the
+// touch bitmap all-zero between passes
+int sweep_pass(hb_ctx *c, const hbk::PassParams &pp, hipEvent_t *E)
+{
+    const Plan &p = c->plan;
+    hbk::SweepParams sp = make_sweep_params(c, pp, (unsigned)(c->t & 1), c->spec_guard);
+    launch_sweep_seeding(c, sp, c->last_changed <= 4096 && !xbit(c, HB_X_SEED_3LAUNCH)); // convergence tail: the one-launch form
+    HB_HIP(hipEventRecord(E[kEvLevel1], c->stream)); // sweep passes: ms_level1 = seed collection + expansion
+    const bool by_rounds = xbit(c, HB_X_SWEEP_ROUNDS);
+    auto launch_rows = [&](bool real, uint64_t lo, uint64_t hi) {
+        if (hi <= lo) return;
+        sp.p.row_lo = lo;
+        sp.p.row_hi = hi;
+        const uint64_t waves = (hi - lo + 2047) / 2048; // a wave-iteration covers 16 groups of 128 rows
+        hipLaunchKernelGGL(sweep_rows_kernel_for(real, by_rounds), dim3(grid_blocks(c, (waves + 3) / 4, 4, 1)), dim3(256), 0, c->stream, sp);
+    };
+    for (size_t l = 0; l + 1 < p.level_begin.size(); l++) launch_rows(false, p.level_begin[l], p.level_begin[l + 1]);
+    HB_HIP(hipEventRecord(E[kEvLevels], c->stream));
+    launch_rows(true, 0, p.n_pad);
+    HB_HIP(hipEventRecord(E[kEvMerge], c->stream));
+    return HB_OK;
+}
+
+// dense / bitmap mode: the hub-chunk levels bottom-up, then the node rows (in ranges when the exchange overlaps the merge: edge_overlap)
+int level_pass(hb_ctx *c, hbk::PassParams pp, hipEvent_t *E, bool frontier, bool fused, bool lean)
+{
+    const Plan &p = c->plan;
+    for (size_t l = 0; l + 1 < p.level_begin.size(); l++) {
+        pp.row_lo = p.level_begin[l];
+        pp.row_hi = p.level_begin[l + 1];
+        pp.xcd_map = (l == 0 && p.xcd_groups == 8) ? 1 : 0;
+        for (int x = 0; x < 8; x++) {
+            pp.xcd_lo[x] = p.xcd_begin[x];
+            pp.xcd_hi[x] = p.xcd_begin[x + 1];
+        }
+
+#ifdef HB_EXPERIMENTS
+        const uint32_t lds_tile = std::min<uint32_t>(c->opt.tune[7], 2048u); // experiment, see hub_lds_tile_kernel (hb_experiments.hip.h)
+        if (l == 0 && !frontier && lds_tile && !(c->opt.flags & HB_FLAG_PASS_STATS) && !multi_rank(c)) {
+            const uint64_t ntiles = (pp.row_hi - pp.row_lo + 63) / 64;
+            const size_t lds = (size_t)lds_tile * 64;
+            const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(8, (160 * 1024) / (lds + 1024)));
+            unsigned blocks = grid_blocks(c, ntiles, per_cu);
+            if (pp.xcd_map) blocks = std::max((blocks + 7) / 8 * 8, 8u);
+            if (lds > 48 * 1024)
+                HB_HIP(hipFuncSetAttribute((const void *)hbk::hub_lds_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            if (ntiles) hipLaunchKernelGGL(hbk::hub_lds_tile_kernel, dim3(blocks), dim3(256), lds, c->stream, pp, lds_tile);
+        } else
+#endif
+        {
+            launch_pass(c, pp, false, frontier, false, (int)l);
+        }
+        if (l == 0) HB_HIP(hipEventRecord(E[kEvLevel1], c->stream));
+    }
+    pp.xcd_map = 0;
+    HB_HIP(hipEventRecord(E[kEvLevels], c->stream));
+    pp.row_lo = dest_mode(c) ? pp.slice_lo : 0; // destination partition: only the owned rows
+    pp.row_hi = dest_mode(c) ? pp.slice_hi : p.n_pad;
+    if (edge_changed_only(c)) {
+        int rc = edge_co_alloc(c);
+        if (rc) return rc;
+        pp.lbits = c->d_lbits; // which rows the local merge changed
+        c->ubits_valid = false;
+    }
+    c->ov_ranges = 0;
+    if (edge_overlap(c) && p.n_pad >= 64ull * hb_ctx::kOverlap) {
+        // the node rows in kOverlap ranges: range k is all-reduced (step_finish, comm_stream) while k + 1 is merged here
+        const uint64_t tiles = p.n_pad / 64;
+        for (int k = 0; k <= hb_ctx::kOverlap; k++) c->ov_lo[k] = tiles * (uint64_t)k / hb_ctx::kOverlap * 64;
+        c->ov_ranges = hb_ctx::kOverlap;
+        for (int k = 0; k < hb_ctx::kOverlap; k++) {
+            pp.row_lo = c->ov_lo[k];
+            pp.row_hi = c->ov_lo[k + 1];
+            launch_pass(c, pp, true, frontier, fused);
+            HB_HIP(hipEventRecord(c->ov_merged[k], c->stream));
+        }
+    } else {
+        if (lean) pp.rd_init = c->d_regs[c->cur];
+        launch_pass(c, pp, true, frontier, fused);
+    }
+    HB_HIP(hipEventRecord(E[kEvMerge], c->stream));
+    return HB_OK;
+}
+
+// reference-tail mode, the pass after a tail pass (update_all_counters): sources pass `changed_nodes.contains_u128` (harmonic.rs:133) -
+// the bloom filter of the previous pass' changed nodes INCLUDING its false positives (they may hold updates a tail pass did not
+// deliver) become this pass' frontier bits
+int bloom_frontier_prelude(hb_ctx *c)
+{
+    const Plan &p = c->plan;
+    hipLaunchKernelGGL(hbk::bloom_frontier_kernel, dim3((unsigned)(p.n_pad / 256 + 1)), dim3(256), 0, c->stream, (const uint32_t *)c->d_bloom,
+                       (const uint64_t *)c->d_idlow, (const uint32_t *)c->d_sid_of, p.n_pad, c->bloom_bits, c->d_bits[c->cur]);
+    HB_HIP(hipGetLastError());
+    return HB_OK;
+}
+
 int step_local(hb_ctx *c)
 {
     if (!c->begun || c->finished) return fail(c, HB_ERR_INVALID, "hb_step*: call hb_begin first");
@@ -529,172 +661,69 @@ int step_local(hb_ctx *c)
     c->tl_declined = false;
     if (c->pending_local) return fail(c, HB_ERR_INVALID, "hb_step_local called twice");
     if (c->t >= c->max_passes) return fail(c, HB_ERR_LIMIT, "max_passes exceeded");
-    const Plan &p = c->plan;
-    // mode: dense while most nodes still change (the frontier test would only cost), frontier
-    // (bitmap) after, sparse (worklists over the transposed graph) for the convergence tail
-    // A_t = edges whose source changed in the previous pass (= out-degree sum of those nodes, counted by
-    // the previous pass).  dense: every source is gathered (no test); frontier: every index is read and
-    // bit-tested, only active sources are gathered (pays while A_t < ~half of the edges); sparse: only the
-    // work rows that read a changed node are visited at all.
-    const uint32_t thr = c->opt.tune[2] ? c->opt.tune[2] : 50; // frontier when A_t < thr % of the edges
-    bool frontier = !(c->opt.flags & HB_FLAG_NO_FRONTIER) && c->t > 0 &&
-                    (c->last_active * 100ull < (uint64_t)thr * c->m_global || thr > 100);
-    // sweep mode when A_t * div < edges: measured crossover with the bitmap pass at A_t = 10-12 % of the edges
-    // (profiles/r02c_sweep_*: 7.4 % -> 1.25 ms vs 2.15 ms, 16 % -> 4.1 ms vs 2.1 ms on the C3-sized graphs)
-    const uint64_t sparse_div = c->opt.tune[6] ? c->opt.tune[6] : 10;
-    bool sparse = frontier && c->sparse_ok && (c->last_active * sparse_div < c->m_global || c->opt.tune[6] == 1);
-    if (c->pipelined) {
-        // a pass of hb_run's tail pipeline is ALWAYS a sweep pass: only the sweep kernels carry the device guard, and the thresholds
-        // above would see the A_t of two passes ago (a late change of one node with a large out-degree share could ask for a bitmap
-        // or dense pass: found by tools/diff_fuzz.py on the MI355X, round 5).  Every mode gives the same bits (SURVEY App. C-1).
-        frontier = true;
-        sparse = true;
-    }
-    c->cur_mode = sparse ? 2 : (frontier ? 1 : 0);
+    // a pass of hb_run's tail pipeline is ALWAYS a sweep pass: only the sweep kernels carry the device guard, and pass_mode would see
+    // the A_t of two passes ago (a late change of one node with a large out-degree share could ask for a bitmap or dense pass: found
+    // by tools/diff_fuzz.py on the MI355X, round 5)
+    c->cur_mode = c->pipelined ? kModeSweep : (c->t > 0 ? pass_mode(c, c->last_active) : kModeDense);
     const bool fused = !unfused(c);
     // lean pass 0: only the fused dense INIT launch of one rank derives the initial state itself; anything else finds it in memory
-    const bool lean = c->lean_init && c->t == 0 && !frontier && fused && lean_pass0(c);
+    const bool lean = c->lean_init && c->t == 0 && c->cur_mode == kModeDense && fused && lean_pass0(c);
     if (c->lean_init && !lean) {
         const int rc_init = ensure_initial_state(c);
         if (rc_init) return rc_init;
     }
     c->lean_init = false;
     if (c->t == 0 && std::getenv("HB_TRACE_INIT")) std::fprintf(stderr, "[hb init] pass 0 runs %s\n", lean ? "lean (derives the initial state itself)" : "on the state init_kernel wrote");
-    hbk::PassParams pp = make_params(c);
+    const hbk::PassParams pp = make_params(c);
     hipEvent_t *E = nullptr; // this pass' timing events (hb_ctx::ev, or a set of its own: deferred_times)
-    {
-        const int rc_ev = pass_events(c, &E);
-        if (rc_ev) return rc_ev;
-    }
-    HB_HIP(hipEventRecord(E[0], c->stream));
+    int rc = pass_events(c, &E);
+    if (rc) return rc;
+    HB_HIP(hipEventRecord(E[kEvStart], c->stream));
     if (ref_tail(c)) {
         // harmonic.rs:244-246: `!exact_changed_nodes.is_empty() && exact_changed_nodes.len() <= threshold`
         if (c->exact_valid && c->last_changed != 0 && c->last_changed <= c->ref_threshold) return tail_pass(c, pp);
         if (c->stale && c->t > 0) {
-            // update_all_counters after a tail pass: sources pass `changed_nodes.contains_u128` (harmonic.rs:133) - the
-            // bloom filter of the previous pass' changed nodes INCLUDING its false positives (they may hold updates a
-            // tail pass did not deliver); never a dense pass (it would deliver all of them)
-            frontier = true;
-            sparse = false; // (the sweep support is never built in this mode anyway: it runs unfused)
-            c->cur_mode = 1;
-            hipLaunchKernelGGL(hbk::bloom_frontier_kernel, dim3((unsigned)(p.n_pad / 256 + 1)), dim3(256), 0, c->stream, (const uint32_t *)c->d_bloom,
-                               (const uint64_t *)c->d_idlow, (const uint32_t *)c->d_sid_of, p.n_pad, c->bloom_bits, c->d_bits[c->cur]);
-            HB_HIP(hipGetLastError());
+            c->cur_mode = kModeBitmap; // never a dense pass (it would deliver all updates); the sweep support is never built in this mode (it runs unfused)
+            if ((rc = bloom_frontier_prelude(c))) return rc;
         }
     }
-    if (sparse) {
-        // sweep mode: changed nodes -> touch bits of their readers; then the levels, then the node rows
-        hbk::SweepParams sp{};
-        sp.p = pp;
-        sp.out_ptr = c->d_out_ptr;
-        sp.out_rows = c->d_out_rows;
-        sp.touch = c->d_touch;
-        sp.seeds = c->d_seeds;
-        sp.heavy = c->d_heavy;
-        // the seed / heavy counters live in two slots used by alternate passes: this pass' first kernel zeroes the other one
-        // (no memset launch per pass; hb_begin clears both)
-        sp.counts = c->d_sparse_counts + 2 * (c->t & 1);
-        sp.counts_next = c->d_sparse_counts + 2 * ((c->t & 1) ^ 1);
-        sp.guard = c->spec_guard;
-        // no bitmap is cleared here: the sweep kernels rewrite every word of this pass' changed bits (node rows in
-        // bits_wr, virtual rows in the upper part of bits_rd) and keep the touch bitmap all-zero between passes
-        // convergence tail: the one-launch form (tune[1] bit 11 = the general path, measurement switch)
-        launch_sweep_seeding(c, sp, c->last_changed <= 4096 && !(HB_XBITS(c->opt.tune[1]) & 0x800u));
-        HB_HIP(hipEventRecord(E[5], c->stream)); // sweep passes: ms_level1 = seed collection + expansion
-        auto sweep_blocks = [&](uint64_t rows) { // a wave-iteration covers 16 groups of 128 rows
-            const uint64_t waves = (rows + 2047) / 2048;
-            return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((waves + 3) / 4, (uint64_t)c->num_cu * 4));
-        };
-        for (size_t l = 0; l + 1 < p.level_begin.size(); l++) {
-            sp.p.row_lo = p.level_begin[l];
-            sp.p.row_hi = p.level_begin[l + 1];
-            if (sp.p.row_hi > sp.p.row_lo) {
-#ifdef HB_EXPERIMENTS
-                if (HB_XBITS(c->opt.tune[1]) & 0x4000000u) // bit 26: 8 sources per round (the form before round 6), A/B
-                    hipLaunchKernelGGL((hbk::sweep_rows_kernel<false, true>), dim3(sweep_blocks(sp.p.row_hi - sp.p.row_lo)), dim3(256), 0, c->stream, sp);
-                else
-#endif
-                    hipLaunchKernelGGL(hbk::sweep_rows_kernel<false>, dim3(sweep_blocks(sp.p.row_hi - sp.p.row_lo)), dim3(256), 0, c->stream, sp);
-            }
-        }
-        HB_HIP(hipEventRecord(E[1], c->stream));
-        sp.p.row_lo = 0;
-        sp.p.row_hi = p.n_pad;
-        if (p.n_pad) {
-#ifdef HB_EXPERIMENTS
-            if (HB_XBITS(c->opt.tune[1]) & 0x4000000u) hipLaunchKernelGGL((hbk::sweep_rows_kernel<true, true>), dim3(sweep_blocks(p.n_pad)), dim3(256), 0, c->stream, sp);
-            else
-#endif
-                hipLaunchKernelGGL(hbk::sweep_rows_kernel<true>, dim3(sweep_blocks(p.n_pad)), dim3(256), 0, c->stream, sp);
-        }
-        HB_HIP(hipEventRecord(E[2], c->stream));
-    } else {
-        for (size_t l = 0; l + 1 < p.level_begin.size(); l++) {
-            pp.row_lo = p.level_begin[l];
-            pp.row_hi = p.level_begin[l + 1];
-            pp.xcd_map = (l == 0 && p.xcd_groups == 8) ? 1 : 0;
-            for (int x = 0; x < 8; x++) {
-                pp.xcd_lo[x] = p.xcd_begin[x];
-                pp.xcd_hi[x] = p.xcd_begin[x + 1];
-            }
-
-#ifdef HB_EXPERIMENTS
-            const uint32_t lds_tile = std::min<uint32_t>(c->opt.tune[7], 2048u); // experiment, see hub_lds_tile_kernel (hb_experiments.hip.h)
-            if (l == 0 && !frontier && lds_tile && !(c->opt.flags & HB_FLAG_PASS_STATS) && !multi_rank(c)) {
-                const uint64_t ntiles = (pp.row_hi - pp.row_lo + 63) / 64;
-                const size_t lds = (size_t)lds_tile * 64;
-                const uint64_t per_cu = std::max<uint64_t>(1, std::min<uint64_t>(8, (160 * 1024) / (lds + 1024)));
-                uint64_t blocks = std::min<uint64_t>(ntiles, (uint64_t)c->num_cu * per_cu);
-                if (pp.xcd_map) blocks = std::max<uint64_t>((blocks + 7) / 8 * 8, 8);
-                if (lds > 48 * 1024)
-                    HB_HIP(hipFuncSetAttribute((const void *)hbk::hub_lds_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                if (ntiles) hipLaunchKernelGGL(hbk::hub_lds_tile_kernel, dim3((unsigned)blocks), dim3(256), lds, c->stream, pp, lds_tile);
-            } else
-#endif
-            {
-                launch_pass(c, pp, false, frontier, false, (int)l);
-            }
-            if (l == 0) HB_HIP(hipEventRecord(E[5], c->stream));
-        }
-        pp.xcd_map = 0;
-        HB_HIP(hipEventRecord(E[1], c->stream));
-        pp.row_lo = dest_mode(c) ? pp.slice_lo : 0; // destination partition: only the owned rows
-        pp.row_hi = dest_mode(c) ? pp.slice_hi : p.n_pad;
-        if (edge_changed_only(c)) {
-            int rc = edge_co_alloc(c);
-            if (rc) return rc;
-            pp.lbits = c->d_lbits; // which rows the local merge changed
-            c->ubits_valid = false;
-        }
-        c->ov_ranges = 0;
-        if (edge_overlap(c) && p.n_pad >= 64ull * hb_ctx::kOverlap) {
-            // the node rows in kOverlap ranges: range k is all-reduced (step_finish, comm_stream) while k + 1 is merged here
-            const uint64_t tiles = p.n_pad / 64;
-            for (int k = 0; k <= hb_ctx::kOverlap; k++) c->ov_lo[k] = tiles * (uint64_t)k / hb_ctx::kOverlap * 64;
-            c->ov_ranges = hb_ctx::kOverlap;
-            for (int k = 0; k < hb_ctx::kOverlap; k++) {
-                pp.row_lo = c->ov_lo[k];
-                pp.row_hi = c->ov_lo[k + 1];
-                launch_pass(c, pp, true, frontier, fused);
-                HB_HIP(hipEventRecord(c->ov_merged[k], c->stream));
-            }
-        } else {
-            if (lean) pp.rd_init = c->d_regs[c->cur];
-            launch_pass(c, pp, true, frontier, fused);
-            pp.rd_init = nullptr;
-        }
-        HB_HIP(hipEventRecord(E[2], c->stream));
-    }
+    rc = c->cur_mode == kModeSweep ? sweep_pass(c, pp, E) : level_pass(c, pp, E, c->cur_mode == kModeBitmap, fused, lean);
+    if (rc) return rc;
     HB_HIP(hipGetLastError());
     c->pending_local = true;
     return HB_OK;
+}
+
+// ---- one pass, second half: exchange, epilogue, read-back and booking ------------------------------------------------------------------
+// the four counters of a pass - changed nodes, gathered edges (HB_FLAG_PASS_STATS), touched rows, A_{t+1} - summed over their stripes
+// (hb_kernels.hip.h); sum may be h itself
+void sum_stripes(const unsigned long long *h, unsigned long long *sum)
+{
+    for (int k = 0; k < 4; k++) {
+        unsigned long long v = 0;
+        for (int s = 0; s < hbk::kStripes; s++) v += h[4 * s + k];
+        sum[k] = v;
+    }
+}
+// A finished pass enters the statistics and the loop moves on: counters.step(); changed_nodes = new_changed_nodes; t += 1
+// (harmonic.rs:273-275).  sum: its summed counters; ps: what the caller knows (mode, A_t, times)
+void book_pass(hb_ctx *c, const unsigned long long *sum, hb_pass_stats ps)
+{
+    ps.pass = c->t;
+    ps.changed = sum[0];
+    ps.touched = sum[2];
+    c->pstats.push_back(ps);
+    c->last_changed = sum[0];
+    c->last_active = sum[3];
+    c->has_changes = sum[0] != 0;
+    c->cur ^= 1;
+    c->t += 1;
 }
 
 int step_finish(hb_ctx *c, int *has_changes)
 {
     if (!c->pending_local) return fail(c, HB_ERR_INVALID, "hb_step_finish without hb_step_local");
     const Plan &p = c->plan;
-    float ms_coll = 0.f;
     hipEvent_t *E = nullptr;
     {
         const int rc_ev = pass_events(c, &E);
@@ -746,12 +775,11 @@ int step_finish(hb_ctx *c, int *has_changes)
                 pp.row_hi = c->ov_lo[k + 1];
                 HB_HIP(hipStreamWaitEvent(c->stream, c->ov_reduced[k], 0));
             }
-            if (k == ranges - 1) HB_HIP(hipEventRecord(E[3], c->stream)); // (collective time: up to the last range reduced)
+            if (k == ranges - 1) HB_HIP(hipEventRecord(E[kEvCollective], c->stream)); // (collective time: up to the last range reduced)
             const uint64_t ntiles = (pp.row_hi - pp.row_lo) / 64;
             if (ntiles) {
-                uint32_t bpc = (c->opt.tune[0] & 0xFFu) ? (c->opt.tune[0] & 0xFFu) : 8;
-                uint64_t blocks = std::min<uint64_t>(ntiles, (uint64_t)c->num_cu * bpc);
-                hipLaunchKernelGGL(hbk::epilogue_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, pp);
+                const uint32_t bpc = (c->opt.tune[0] & 0xFFu) ? (c->opt.tune[0] & 0xFFu) : 8;
+                hipLaunchKernelGGL(hbk::epilogue_kernel, dim3(grid_blocks(c, ntiles, bpc)), dim3(256), 0, c->stream, pp);
             }
         }
         c->ov_ranges = 0;
@@ -803,158 +831,37 @@ int step_finish(hb_ctx *c, int *has_changes)
             HB_COLL(coll_group_end(c));
             c->wire_bytes += (p.n_pad - std::min<uint64_t>(S, p.n_pad)) * 64 + (p.n_pad - std::min<uint64_t>(S, p.n_pad)) / 8;
         }
-        HB_HIP(hipEventRecord(E[3], c->stream));
+        HB_HIP(hipEventRecord(E[kEvCollective], c->stream));
     }
-    hipEvent_t ev_end = E[2];
-    if (dest_mode(c) && linked(c)) ev_end = E[3];
+    PassEvent ev_end = (dest_mode(c) && linked(c)) ? kEvCollective : kEvMerge;
     if (unfused(c)) {
-        // events: [0] start, [1] after virtual levels, [2] after local merge, [3] after collective,
-        // [4] after the epilogue
-        HB_HIP(hipEventRecord(E[4], c->stream));
-        ev_end = E[4];
+        HB_HIP(hipEventRecord(E[kEvEpilogue], c->stream));
+        ev_end = kEvEpilogue;
     }
     if (!counters_read) {
         HB_HIP(hipMemcpyAsync(c->h_counters, c->d_counters + (size_t)hbk::kCounterWords * c->t,
                               hbk::kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         HB_HIP(hipStreamSynchronize(c->stream));
     }
-    for (int s = 1; s < hbk::kStripes; s++)
-        for (int k = 0; k < 4; k++) c->h_counters[k] += c->h_counters[4 * s + k];
-    const bool later = counters_read; // the end of this pass is still in flight: its events are read by resolve_pass_times
-    if (!later && (unfused(c) || (dest_mode(c) && linked(c)))) HB_HIP(hipEventElapsedTime(&ms_coll, E[2], E[3]));
+    sum_stripes(c->h_counters, c->h_counters);
     hb_pass_stats ps{};
-    ps.pass = c->t;
-    ps.changed = c->h_counters[0];
     ps.active_edges = (c->opt.flags & HB_FLAG_PASS_STATS) ? c->h_counters[1] : c->last_active; // A_t
-    ps.touched = c->h_counters[2];
     ps.mode = c->cur_mode;
-    float ms_all = 0.f, ms_main = 0.f;
-    if (!later) {
-        HB_HIP(hipEventElapsedTime(&ms_all, E[0], ev_end));
-        HB_HIP(hipEventElapsedTime(&ms_main, E[1], E[2]));
+    if (counters_read) { // the end of this pass is still in flight: its events are read by resolve_pass_times
+        c->pending_times.push_back(c->pstats.size());
+    } else {
+        const int rc = read_pass_times(c, E, ev_end, &ps);
+        if (rc) return rc;
+        if (linked(c) && (unfused(c) || dest_mode(c))) HB_HIP(hipEventElapsedTime(&ps.ms_collective, E[kEvMerge], E[kEvCollective]));
     }
-    ps.ms_gpu = ms_all;
-    ps.ms_main = ms_main;
-    ps.ms_collective = linked(c) ? ms_coll : 0.f;
-    if (!later && ((c->cur_mode < 2 && p.level_begin.size() > 1) || c->cur_mode == 2)) {
-        float ms_l1 = 0.f;
-        HB_HIP(hipEventElapsedTime(&ms_l1, E[0], E[5]));
-        ps.ms_level1 = ms_l1;
-    }
-    if (later) c->pending_times.push_back(c->pstats.size());
-    c->pstats.push_back(ps);
     if (ref_tail(c)) {
-        int rc = reference_changed_state(c, (const uint32_t *)c->d_bits[c->cur ^ 1], ps.changed);
+        const int rc = reference_changed_state(c, (const uint32_t *)c->d_bits[c->cur ^ 1], c->h_counters[0]);
         if (rc) return rc;
     }
-    // counters.step(); changed_nodes = new_changed_nodes; t += 1 (harmonic.rs:273-275)
-    c->last_changed = ps.changed;
-    c->last_active = c->h_counters[3];
-    c->has_changes = ps.changed != 0;
-    c->cur ^= 1;
-    c->t += 1;
+    book_pass(c, c->h_counters, ps);
     c->pending_local = false;
     if (has_changes) *has_changes = c->has_changes ? 1 : 0;
-    return results_stage_policy(c, ps.changed);
-}
-
-// ---- hb_run's tail pipeline [r5] ---------------------------------------------------------------------------------------------
-// In the convergence tail a pass is a handful of 5-10 us launches, and the host round trip that ends it (counters to the host,
-// hipStreamSynchronize, the next pass' launches) left the GPU idle about as long again.  Once a sweep pass has changed <= 4096
-// nodes, hb_run keeps ONE pass queued ahead: pass q + 1 goes into the stream - guarded on the device by pass q's changed count, see
-// SweepParams::guard - before pass q's counters are read.  The loop still ends on the first pass that changes nothing
-// (harmonic.rs:237-240): the pass queued behind it finds its guard closed and does nothing at all.  Mode, launch shapes and the
-// `last_changed <= 4096` kernel choice of the queued pass come from pass q - 1; every choice gives the same bits (SURVEY App. C-1).
-bool tail_kernel_ready(const hb_ctx *c); // (below; experiments build only: the single-workgroup kernel takes over from the pipeline when the changed set is small enough)
-bool tail_pipeline_ready(const hb_ctx *c)
-{
-    return c->begun && !c->finished && c->has_changes && c->t > 0 && c->cur_mode == 2 && c->last_changed <= 4096 && c->sparse_ok && !multi_rank(c) &&
-           !linked(c) && !unfused(c) && !ref_tail(c) && !(c->opt.flags & HB_FLAG_PASS_STATS) && !(HB_XBITS(c->opt.tune[1]) & 0x100000u) && // bit 20: off
-           c->t + 2 < c->max_passes;
-}
-
-// queue pass c->t (all its launches), then its counters' way to the host; nothing is waited for
-int tail_queue(hb_ctx *c, bool guarded_by_previous)
-{
-    c->pipelined = true;
-    c->spec_guard = guarded_by_previous ? c->d_counters + (size_t)hbk::kCounterWords * (c->t - 1) : nullptr;
-    const int rc = step_local(c);
-    c->spec_guard = nullptr;
-    c->pipelined = false;
-    if (rc) return rc;
-    c->pending_local = false;
-    const int slot = (int)(c->t & 1);
-    HB_HIP(hipMemcpyAsync(c->h_slot + (size_t)slot * hbk::kCounterWords, c->d_counters + (size_t)hbk::kCounterWords * c->t,
-                          hbk::kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HB_HIP(hipEventRecord(c->slot_done[slot], c->stream));
-    return HB_OK;
-}
-
-// wait for pass c->t (queued by tail_queue), book it like step_finish does, advance the loop state
-int tail_complete(hb_ctx *c)
-{
-    const int slot = (int)(c->t & 1);
-    HB_HIP(hipEventSynchronize(c->slot_done[slot]));
-    unsigned long long sum[4] = {0, 0, 0, 0};
-    const unsigned long long *h = c->h_slot + (size_t)slot * hbk::kCounterWords;
-    for (int s = 0; s < hbk::kStripes; s++)
-        for (int k = 0; k < 4; k++) sum[k] += h[4 * s + k];
-    hipEvent_t *E = c->ev_ring[c->t & 3].e;
-    hb_pass_stats ps{};
-    ps.pass = c->t;
-    ps.changed = sum[0];
-    ps.active_edges = c->last_active;
-    ps.touched = sum[2];
-    ps.mode = c->cur_mode;
-    float ms_all = 0.f, ms_main = 0.f, ms_l1 = 0.f;
-    HB_HIP(hipEventElapsedTime(&ms_all, E[0], E[2]));
-    HB_HIP(hipEventElapsedTime(&ms_main, E[1], E[2]));
-    HB_HIP(hipEventElapsedTime(&ms_l1, E[0], E[5]));
-    ps.ms_gpu = ms_all;
-    ps.ms_main = ms_main;
-    ps.ms_level1 = ms_l1;
-    c->pstats.push_back(ps);
-    c->last_changed = ps.changed;
-    c->last_active = sum[3];
-    c->has_changes = ps.changed != 0;
-    c->cur ^= 1;
-    c->t += 1;
-    return HB_OK;
-}
-
-int tail_pipeline(hb_ctx *c, int *has_changes)
-{
-    int rc = tail_queue(c, false); // pass q = c->t: the previous pass is known to have changed something
-    if (rc) return rc;
-    for (;;) {
-        // pass q + 1 behind it, as if pass q had changed something (if it has not, the device guard keeps it from running)
-        const bool ahead = c->t + 2 < c->max_passes;
-        if (ahead) {
-            c->t += 1;
-            c->cur ^= 1;
-            rc = tail_queue(c, true);
-            c->t -= 1;
-            c->cur ^= 1;
-            if (rc) return rc;
-        }
-        if ((rc = tail_complete(c))) return rc; // pass q is booked; c->t = q + 1 now
-        if (ahead && c->has_changes) c->pipelined_passes++; // (the pass behind it really runs)
-        if ((rc = results_stage_policy(c, c->last_changed))) return rc;
-        if (!c->has_changes) break;             // the loop's last pass; the pass queued behind it did nothing
-        if (!ahead) {                           // (max_passes is near: back to the one-pass-at-a-time loop, which reports the limit)
-            if (has_changes) *has_changes = 1;
-            return HB_OK;
-        }
-        if (c->last_changed > 4096 || c->cur_mode != 2 || tail_kernel_ready(c)) {
-            // the changed set grew again - or shrank enough for the single-workgroup kernel to take the rest of the tail: the pass
-            // already queued is a real one - take it, then leave the pipeline
-            if ((rc = tail_complete(c))) return rc;
-            if ((rc = results_stage_policy(c, c->last_changed))) return rc;
-            break;
-        }
-    }
-    if (has_changes) *has_changes = c->has_changes ? 1 : 0;
-    return HB_OK;
+    return results_stage_policy(c, c->last_changed);
 }
 
 // ---- the far tail as one workgroup (hb_tail.hip.h) [r5] -------------------------------------------------------------------------
@@ -974,9 +881,9 @@ bool tail_kernel_ready(const hb_ctx *c)
     return c->begun && !c->finished && c->has_changes && c->t > 0 && c->last_changed <= hbk::kTailSeeds && c->last_active <= hbk::kTailReaders &&
            c->sparse_ok && !c->tl_declined &&
            c->d_tl_count && !multi_rank(c) && !linked(c) && !unfused(c) && !ref_tail(c) && !(c->opt.flags & (HB_FLAG_PASS_STATS | HB_FLAG_NO_FRONTIER)) &&
-           (HB_XBITS(c->opt.tune[1]) & 0x600000u) && // OFF by default (measured: no faster than the launches it replaces, DESIGN.md §3); bit 21 / 22: on
+           xbit(c, HB_X_TAIL_KERNEL | HB_X_TAIL_KERNEL_ANY) && // OFF by default (measured: no faster than the launches it replaces, DESIGN.md §3)
            c->plan.level_begin.size() >= 1 && c->plan.level_begin.size() - 1 <= (size_t)hbk::kTailLevels && c->t < c->max_passes &&
-           (c->cur_mode == 2 || c->cur_mode == 4 || (HB_XBITS(c->opt.tune[1]) & 0x400000u)); // after a sweep / tail-kernel pass (bit 22: after any pass - tests)
+           (c->cur_mode == 2 || c->cur_mode == 4 || xbit(c, HB_X_TAIL_KERNEL_ANY)); // after a sweep / tail-kernel pass
 }
 
 // up to `budget` passes in one launch; *ran = passes completed (0: the kernel declined - the next pass does not fit its lists)
@@ -1022,14 +929,13 @@ int tail_kernel_run(hb_ctx *c, uint32_t budget, uint32_t *ran)
     if (!c->tl_valid) { // the five lists from the bitmaps as they are (one grid-wide scan per entry)
         HB_HIP(hipMemsetAsync(c->d_tl_count, 0, hbk::kTcWords * sizeof(uint32_t), c->stream));
         const uint64_t words = (P.rows_total + 31) / 32;
-        const unsigned blocks = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((words + 255) / 256, (uint64_t)c->num_cu * 4));
-        hipLaunchKernelGGL(hbk::tail_collect_kernel, dim3(blocks), dim3(256), 0, c->stream, P);
+        hipLaunchKernelGGL(hbk::tail_collect_kernel, dim3(grid_blocks(c, (words + 255) / 256, 4, 1)), dim3(256), 0, c->stream, P);
         HB_HIP(hipGetLastError());
     }
-    HB_HIP(hipEventRecord(c->tl_ev[0], c->stream));
+    HB_HIP(hipEventRecord(c->tl_ev[kEvStart], c->stream));
     hipLaunchKernelGGL(hbk::tail_loop_kernel, dim3(1), dim3(1024), 0, c->stream, P);
     HB_HIP(hipGetLastError());
-    HB_HIP(hipEventRecord(c->tl_ev[1], c->stream));
+    HB_HIP(hipEventRecord(c->tl_ev[kEvEnd], c->stream));
     HB_HIP(hipMemcpyAsync(c->h_tl_count, c->d_tl_count, hbk::kTcWords * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HB_HIP(hipStreamSynchronize(c->stream));
     const uint32_t done = c->h_tl_count[hbk::kTcPasses], reason = c->h_tl_count[hbk::kTcReason];
@@ -1042,25 +948,16 @@ int tail_kernel_run(hb_ctx *c, uint32_t budget, uint32_t *ran)
     HB_HIP(hipMemcpyAsync(cnt.data(), c->d_counters + (size_t)hbk::kCounterWords * c->t, cnt.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HB_HIP(hipStreamSynchronize(c->stream));
     float ms = 0.f;
-    HB_HIP(hipEventElapsedTime(&ms, c->tl_ev[0], c->tl_ev[1]));
+    HB_HIP(hipEventElapsedTime(&ms, c->tl_ev[kEvStart], c->tl_ev[kEvEnd]));
     for (uint32_t k = 0; k < done; k++) {
-        const unsigned long long *h = &cnt[(size_t)k * hbk::kCounterWords];
         hb_pass_stats ps{};
-        ps.pass = c->t;
-        ps.changed = h[0];
         ps.active_edges = c->last_active;
-        ps.touched = h[2];
         ps.mode = 4; // one workgroup, work lists (hb_tail.hip.h)
         ps.ms_gpu = ms / (float)done;
         ps.ms_main = ps.ms_gpu;
-        c->pstats.push_back(ps);
-        c->last_changed = ps.changed;
-        c->last_active = h[3];
-        c->has_changes = ps.changed != 0;
-        c->cur ^= 1;
-        c->t += 1;
+        book_pass(c, &cnt[(size_t)k * hbk::kCounterWords], ps); // (one workgroup: stripe 0 holds the whole counters)
         c->cur_mode = 4;
-        const int rc = results_stage_policy(c, ps.changed);
+        const int rc = results_stage_policy(c, c->last_changed);
         if (rc) return rc;
     }
     c->tail_kernel_passes += done;
@@ -1069,6 +966,88 @@ int tail_kernel_run(hb_ctx *c, uint32_t budget, uint32_t *ran)
     return HB_OK;
 }
 #endif // HB_EXPERIMENTS
+
+// ---- hb_run's tail pipeline [r5] ---------------------------------------------------------------------------------------------
+// In the convergence tail a pass is a handful of 5-10 us launches, and the host round trip that ends it (counters to the host,
+// hipStreamSynchronize, the next pass' launches) left the GPU idle about as long again.  Once a sweep pass has changed <= 4096
+// nodes, hb_run keeps ONE pass queued ahead: pass q + 1 goes into the stream - guarded on the device by pass q's changed count, see
+// SweepParams::guard - before pass q's counters are read.  The loop still ends on the first pass that changes nothing
+// (harmonic.rs:237-240): the pass queued behind it finds its guard closed and does nothing at all.  Mode, launch shapes and the
+// `last_changed <= 4096` kernel choice of the queued pass come from pass q - 1; every choice gives the same bits (SURVEY App. C-1).
+bool tail_pipeline_ready(const hb_ctx *c)
+{
+    return c->begun && !c->finished && c->has_changes && c->t > 0 && c->cur_mode == 2 && c->last_changed <= 4096 && c->sparse_ok && !multi_rank(c) &&
+           !linked(c) && !unfused(c) && !ref_tail(c) && !(c->opt.flags & HB_FLAG_PASS_STATS) && !xbit(c, HB_X_NO_TAIL_PIPELINE) &&
+           c->t + 2 < c->max_passes;
+}
+
+// queue pass c->t (all its launches), then its counters' way to the host; nothing is waited for
+int tail_queue(hb_ctx *c, bool guarded_by_previous)
+{
+    c->pipelined = true;
+    c->spec_guard = guarded_by_previous ? c->d_counters + (size_t)hbk::kCounterWords * (c->t - 1) : nullptr;
+    const int rc = step_local(c);
+    c->spec_guard = nullptr;
+    c->pipelined = false;
+    if (rc) return rc;
+    c->pending_local = false;
+    const int slot = (int)(c->t & 1);
+    HB_HIP(hipMemcpyAsync(c->h_slot + (size_t)slot * hbk::kCounterWords, c->d_counters + (size_t)hbk::kCounterWords * c->t,
+                          hbk::kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HB_HIP(hipEventRecord(c->slot_done[slot], c->stream));
+    return HB_OK;
+}
+
+// wait for pass c->t (queued by tail_queue), book it like step_finish does, advance the loop state
+int tail_complete(hb_ctx *c)
+{
+    const int slot = (int)(c->t & 1);
+    HB_HIP(hipEventSynchronize(c->slot_done[slot]));
+    unsigned long long sum[4];
+    sum_stripes(c->h_slot + (size_t)slot * hbk::kCounterWords, sum);
+    hb_pass_stats ps{};
+    ps.active_edges = c->last_active;
+    ps.mode = c->cur_mode;
+    const int rc = read_pass_times(c, c->ev_ring[c->t & 3].e, kEvMerge, &ps);
+    if (rc) return rc;
+    book_pass(c, sum, ps);
+    return HB_OK;
+}
+
+int tail_pipeline(hb_ctx *c, int *has_changes)
+{
+    int rc = tail_queue(c, false); // pass q = c->t: the previous pass is known to have changed something
+    if (rc) return rc;
+    for (;;) {
+        // pass q + 1 behind it, as if pass q had changed something (if it has not, the device guard keeps it from running)
+        const bool ahead = c->t + 2 < c->max_passes;
+        if (ahead) {
+            c->t += 1;
+            c->cur ^= 1;
+            rc = tail_queue(c, true);
+            c->t -= 1;
+            c->cur ^= 1;
+            if (rc) return rc;
+        }
+        if ((rc = tail_complete(c))) return rc; // pass q is booked; c->t = q + 1 now
+        if (ahead && c->has_changes) c->pipelined_passes++; // (the pass behind it really runs)
+        if ((rc = results_stage_policy(c, c->last_changed))) return rc;
+        if (!c->has_changes) break;             // the loop's last pass; the pass queued behind it did nothing
+        if (!ahead) {                           // (max_passes is near: back to the one-pass-at-a-time loop, which reports the limit)
+            if (has_changes) *has_changes = 1;
+            return HB_OK;
+        }
+        if (c->last_changed > 4096 || c->cur_mode != 2 || tail_kernel_ready(c)) {
+            // the changed set grew again - or shrank enough for the single-workgroup kernel to take the rest of the tail: the pass
+            // already queued is a real one - take it, then leave the pipeline
+            if ((rc = tail_complete(c))) return rc;
+            if ((rc = results_stage_policy(c, c->last_changed))) return rc;
+            break;
+        }
+    }
+    if (has_changes) *has_changes = c->has_changes ? 1 : 0;
+    return HB_OK;
+}
 
 // ---- first dispatches at load time (declared in hb_api_load.inc) ---------------------------------------------------------------------
 int warm_kernels(hb_ctx *c)
@@ -1081,42 +1060,30 @@ int warm_kernels(hb_ctx *c)
     pp.counters = c->d_counters + (size_t)c->max_passes * hbk::kCounterWords; // the spare slot (every kernel adds zero to it)
     hipStream_t s = c->stream;
     const dim3 one(1), blk(256);
-    const bool init_ok = pp.src_jp != nullptr;
-    if (!unfused(c)) {
-        hipLaunchKernelGGL((hbk::pass_kernel<false, false, false, 4>), one, blk, 0, s, pp);
-        hipLaunchKernelGGL((hbk::pass_kernel<true, true, false, 2, false, true>), one, blk, 0, s, pp);
-        if (init_ok) {
-            hipLaunchKernelGGL((hbk::pass_kernel<false, false, false, 4, true>), one, blk, 0, s, pp);
-            hipLaunchKernelGGL(hbk::init_level1_kernel, one, blk, 0, s, pp);
-            hipLaunchKernelGGL((hbk::pass_kernel<true, true, false, 2, true, true>), one, blk, 0, s, pp);
-        }
-        hipLaunchKernelGGL((hbk::frontier_kernel<false, false, false, 16, true>), one, blk, 0, s, pp);
-        hipLaunchKernelGGL((hbk::frontier_kernel<true, true, false, 4, true>), one, blk, 0, s, pp);
-    } else {
-        hipLaunchKernelGGL((hbk::pass_kernel<false, false, false, 4>), one, blk, 0, s, pp);
-        hipLaunchKernelGGL((hbk::pass_kernel<true, false, false, 2>), one, blk, 0, s, pp);
-        hipLaunchKernelGGL((hbk::frontier_kernel<false, false, false, 16, true>), one, blk, 0, s, pp);
-        hipLaunchKernelGGL((hbk::frontier_kernel<true, false, false, 4, true>), one, blk, 0, s, pp);
-        hipLaunchKernelGGL(hbk::epilogue_kernel, one, blk, 0, s, pp);
+    // the instances launch_pass will pick for this context's dense and bitmap passes (no HB_FLAG_PASS_STATS here), hub chunks and node rows
+    const bool fused = !unfused(c), epi4 = !xbit(c, HB_X_TILE_EPILOGUE), compact = !xbit(c, HB_X_BITMAP_SLOTWISE);
+    const int hub_unroll = pass_unroll(c, false), node_unroll = pass_unroll(c, true);
+    auto warm = [&](PassKernel k) { hipLaunchKernelGGL(k, one, blk, 0, s, pp); };
+    warm(dense_kernel(false, false, false, hub_unroll, false, false));
+    warm(dense_kernel(true, fused, false, node_unroll, false, epi4));
+    if (fused && pass0_streams_initial_registers(c)) { // pass 0 as the INIT launch
+        warm(dense_kernel(false, false, false, hub_unroll, true, false));
+        warm(hbk::init_level1_kernel);
+        warm(dense_kernel(true, true, false, node_unroll, true, epi4));
     }
+    warm(bitmap_kernel(false, false, false, compact));
+    warm(bitmap_kernel(true, fused, false, compact));
+    if (!fused) warm(hbk::epilogue_kernel);
     if (c->sparse_ok) {
-        hbk::SweepParams sp{};
-        sp.p = pp;
-        sp.out_ptr = c->d_out_ptr;
-        sp.out_rows = c->d_out_rows;
-        sp.touch = c->d_touch;
-        sp.seeds = c->d_seeds;
-        sp.heavy = c->d_heavy;
-        sp.counts = c->d_sparse_counts;     // zeroed here, and again by every hb_begin
-        sp.counts_next = c->d_sparse_counts + 2;
-        sp.guard = nullptr;
+        const hbk::SweepParams sp = make_sweep_params(c, pp, 0, nullptr); // (the counters: zeroed here, and again by every hb_begin)
         HB_HIP(hipMemsetAsync(c->d_sparse_counts, 0, 64 * sizeof(unsigned int), s));
         hipLaunchKernelGGL(hbk::sweep_collect_kernel, one, blk, 0, s, sp);
         hipLaunchKernelGGL(hbk::sweep_expand_kernel, one, blk, 0, s, sp);
         hipLaunchKernelGGL(hbk::sweep_expand_heavy_kernel, one, blk, 0, s, sp);
         hipLaunchKernelGGL(hbk::sweep_seed_small_kernel, one, blk, 0, s, sp);
-        hipLaunchKernelGGL(hbk::sweep_rows_kernel<false>, one, blk, 0, s, sp);
-        hipLaunchKernelGGL(hbk::sweep_rows_kernel<true>, one, blk, 0, s, sp);
+        const bool by_rounds = xbit(c, HB_X_SWEEP_ROUNDS);
+        hipLaunchKernelGGL(sweep_rows_kernel_for(false, by_rounds), one, blk, 0, s, sp);
+        hipLaunchKernelGGL(sweep_rows_kernel_for(true, by_rounds), one, blk, 0, s, sp);
     }
     if (c->rs.on) {
         hipLaunchKernelGGL(hbk::results_sync_kernel, one, blk, 0, s, (const double *)c->d_ksum, c->rs.d_sent, (const uint32_t *)c->d_cid_of, (uint64_t)0, 1.0, 0,

@@ -40,7 +40,7 @@ int sample_sids(hb_ctx *c, uint64_t seed, uint64_t k, std::vector<uint32_t> *sid
         std::vector<uint8_t> has_out(p.n);
         DevPtr<uint8_t> d_flags;
         HB_HIP(d_flags.alloc(p.n));
-        const unsigned blocks = (unsigned)std::min<uint64_t>((p.n_pad + 255) / 256, (uint64_t)c->num_cu * 8);
+        const unsigned blocks = grid_blocks(c, (p.n_pad + 255) / 256, 8);
         hipLaunchKernelGGL(hbk::sample_candidates_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint32_t *)c->d_outdeg, (const uint32_t *)c->d_sid_of,
                            p.n_pad, d_flags.get());
         HB_HIP_AS("hb_sampled_harmonic: candidate flags: ", hipGetLastError());
@@ -153,9 +153,6 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
     const uint64_t n_pad = p.n_pad, rows_total = p.n_pad + p.nv;
     HB_HIP(hipMemsetAsync(sm.d_hist.get(), 0, std::max<uint64_t>((uint64_t)D * n_pad, 64) * sizeof(uint16_t), c->stream));
     HB_HIP(hipMemcpyAsync(sm.d_w.get(), w, sizeof(w), hipMemcpyHostToDevice, c->stream));
-    // bitmap / sweep thresholds of hb_run (hb_api_pass.inc step_local): the A_t rule on the out-degree sum of the rows changed at d - 1
-    const uint32_t thr = c->opt.tune[2] ? c->opt.tune[2] : 50;
-    const uint64_t sparse_div = c->opt.tune[6] ? c->opt.tune[6] : 10;
     const bool xcd_ok = p.xcd_groups == 8 && p.level_begin.size() > 1 && p.xcd_begin[0] == p.level_begin[0] && p.xcd_begin[8] == p.level_begin[1] &&
                         std::all_of(p.xcd_begin, p.xcd_begin + 9, [](uint64_t b) { return b % 32 == 0; });
     hb_sample_stats st{};
@@ -185,9 +182,10 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
         uint64_t last_changed = h[0], last_active = h[1];
         int cur = 0;
         for (uint32_t d = 1; d <= D && last_changed; d++) {
-            const bool frontier = !(c->opt.flags & HB_FLAG_NO_FRONTIER) && (last_active * 100ull < (uint64_t)thr * c->m_global || thr > 100);
-            const bool sweep = frontier && c->sparse_ok && (last_active * sparse_div < c->m_global || c->opt.tune[6] == 1);
-            const int mode = sweep ? hbk::kSampleSweep : (frontier ? hbk::kSampleBitmap : hbk::kSampleDense);
+            // dense / bitmap / sweep as in hb_run (pass_mode): the A_t rule on the out-degree sum of the rows changed at d - 1
+            static_assert(hbk::kSampleDense == kModeDense && hbk::kSampleBitmap == kModeBitmap && hbk::kSampleSweep == kModeSweep, "one numbering of the modes");
+            const int mode = (int)pass_mode(c, last_active);
+            const bool sweep = mode == hbk::kSampleSweep;
             hbk::SampleParams sp{};
             sp.row_ptr = c->d_row_ptr;
             sp.src = c->d_src;
@@ -204,23 +202,15 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
             sp.cnt = sm.d_cnt.get() + 4 * d;
             sp.n_pad = n_pad;
             sp.rows_total = rows_total;
-            HB_HIP(hipEventRecord(c->ev[0], c->stream));
+            HB_HIP(hipEventRecord(c->ev[kEvStart], c->stream));
             if (sweep) {
                 // the rows changed at d - 1 -> touch bits of their readers: hb_run's seed / expand kernels, unchanged (launch_sweep_seeding)
-                hbk::SweepParams sw{};
-                sw.p.bits_rd = c->d_bits[cur];
-                sw.p.n_pad = n_pad;
-                sw.p.rows_total = rows_total;
-                sw.out_ptr = c->d_out_ptr;
-                sw.out_rows = c->d_out_rows;
-                sw.touch = c->d_touch;
-                sw.seeds = c->d_seeds;
-                sw.heavy = c->d_heavy;
-                sw.counts = c->d_sparse_counts;
-                sw.counts_next = c->d_sparse_counts + 2;
-                sw.guard = nullptr;
+                hbk::PassParams seed_pp{}; // (all the seeding kernels read of it)
+                seed_pp.bits_rd = c->d_bits[cur];
+                seed_pp.n_pad = n_pad;
+                seed_pp.rows_total = rows_total;
                 HB_HIP(hipMemsetAsync(c->d_sparse_counts, 0, 4 * sizeof(unsigned int), c->stream));
-                launch_sweep_seeding(c, sw, last_changed <= 4096);
+                launch_sweep_seeding(c, make_sweep_params(c, seed_pp, 0, nullptr), last_changed <= 4096);
                 HB_HIP(hipGetLastError());
             }
             for (size_t l = 0; l + 1 < p.level_begin.size(); l++) { // virtual levels: partials of level d from the rows of level d - 1
@@ -238,11 +228,11 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
             sp.row_hi = n_pad;
             sample_launch(c, sp, true, mode);
             HB_HIP(hipGetLastError());
-            HB_HIP(hipEventRecord(c->ev[1], c->stream));
+            HB_HIP(hipEventRecord(c->ev[kEvEnd], c->stream));
             HB_HIP(hipMemcpyAsync(h, sp.cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
             HB_HIP(hipStreamSynchronize(c->stream));
             float ms = 0.f;
-            HB_HIP(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+            HB_HIP(hipEventElapsedTime(&ms, c->ev[kEvStart], c->ev[kEvEnd]));
             st.level_changed[d - 1] += h[0];
             st.level_modes[d - 1] |= 1u << mode;
             st.level_ms[d - 1] += ms;
@@ -255,7 +245,7 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
     if (c->out_len) {
         unsigned long long *cnt = sm.d_cnt.get(); // (slot 0 is free again)
         HB_HIP(hipMemsetAsync(cnt, 0, 4 * sizeof(unsigned long long), c->stream));
-        const unsigned blocks = (unsigned)std::min<uint64_t>((n_pad + 255) / 256, (uint64_t)c->num_cu * 8);
+        const unsigned blocks = grid_blocks(c, (n_pad + 255) / 256, 8);
         hipLaunchKernelGGL(hbk::sample_result_kernel, dim3(std::max(blocks, 1u)), dim3(256), 0, c->stream, (const uint16_t *)sm.d_hist.get(), D, n_pad,
                            (const double *)sm.d_w.get(), (const uint32_t *)c->d_cid_of, c->d_out, cnt);
         HB_HIP(hipGetLastError());

@@ -30,7 +30,7 @@ def main():
             flags |= _lib.HB_FLAG_DEST_PARTITION
         if mode.endswith("changed"):
             flags |= _lib.HB_FLAG_CHANGED_ONLY
-        tune = (0, 0x1000) if mode == "edge_no_pipeline" else ()   # tune[1] bit 12: one all-reduce over all rows instead of 4 ranges
+        tune = (0, _lib.HB_X_NO_EDGE_OVERLAP) if mode == "edge_no_pipeline" else ()   # one all-reduce over all rows instead of 4 ranges
         split = dist.partition_dense_by_dest if mode.startswith("dest") else dist.partition_dense
         rp, src = split(g.row_ptr, g.src, rank, world)
         with _lib.Context(device=0, flags=flags, rank=rank, world_size=world, tune=tune) as ctx:

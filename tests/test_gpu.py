@@ -206,34 +206,34 @@ VARIANTS = {
     "banded_chunks": dict(chunk=16, tune=(0, 0, 0, 6, 4)),
     "banded_frontier_small_direct": dict(chunk=32, tune=(0, 0, 101, 5, 8, 8)),
     # measurement switches of round 3: the older kernels stay bit-identical
-    "old_per_tile_epilogue": dict(tune=(0, 0x100)),                                  # dense node rows: estimator/Kahan per quad, not once per row
+    "old_per_tile_epilogue": dict(tune=(0, _lib.HB_X_TILE_EPILOGUE)),                                  # dense node rows: estimator/Kahan per quad, not once per row
     "frontier_always_chunk128": dict(chunk=128, tune=(0, 0, 101, 0, 0, 0, 1000000)), # rows with > 64 sources: two batches per hub chunk
     "frontier_always_pass_stats": dict(flags=_lib.HB_FLAG_PASS_STATS, tune=(0, 0, 101, 0, 0, 0, 1000000)),
-    "sweep_general_seed_path": dict(chunk=8, tune=(0, 0x800, 101, 0, 0, 0, 1)),        # collect + expand + heavy also in the tail
-    "frontier_always_slot_by_slot": dict(chunk=8, tune=(0, 0x2000, 101, 0, 0, 0, 1000000)),  # bitmap passes without packing the surviving sources
-    "frontier_always_slot_by_slot_chunk128": dict(chunk=128, flags=_lib.HB_FLAG_PASS_STATS, tune=(0, 0x2000, 101, 0, 0, 0, 1000000)),
+    "sweep_general_seed_path": dict(chunk=8, tune=(0, _lib.HB_X_SEED_3LAUNCH, 101, 0, 0, 0, 1)),        # collect + expand + heavy also in the tail
+    "frontier_always_slot_by_slot": dict(chunk=8, tune=(0, _lib.HB_X_BITMAP_SLOTWISE, 101, 0, 0, 0, 1000000)),  # bitmap passes without packing the surviving sources
+    "frontier_always_slot_by_slot_chunk128": dict(chunk=128, flags=_lib.HB_FLAG_PASS_STATS, tune=(0, _lib.HB_X_BITMAP_SLOTWISE, 101, 0, 0, 0, 1000000)),
 }
 
 
 # round 5: the results travel in stages while the passes run (hb_api_pass.inc results_stage); bit 15 = a snapshot after EVERY pass
 # whatever the graph's size, bit 17 = only the first snapshot, bit 16 = a final list of 16 entries (with bit 17: it overflows and the
 # whole image is shipped instead)
-VARIANTS["staged_results_every_pass"] = dict(tune=(0, 0x8000))
-VARIANTS["staged_results_one_snapshot"] = dict(tune=(0, 0x28000))
-VARIANTS["staged_results_sweep_tiny_list"] = dict(chunk=8, tune=(0, 0x38000, 101, 0, 0, 0, 1))
-VARIANTS["staged_results_off"] = dict(tune=(0, 0x4000))
+VARIANTS["staged_results_every_pass"] = dict(tune=(0, _lib.HB_X_SNAPSHOT_EVERY_PASS))
+VARIANTS["staged_results_one_snapshot"] = dict(tune=(0, _lib.HB_X_SNAPSHOT_EVERY_PASS | _lib.HB_X_ONE_SNAPSHOT))
+VARIANTS["staged_results_sweep_tiny_list"] = dict(chunk=8, tune=(0, _lib.HB_X_SNAPSHOT_EVERY_PASS | _lib.HB_X_SHORT_FINAL_LIST | _lib.HB_X_ONE_SNAPSHOT, 101, 0, 0, 0, 1))
+VARIANTS["staged_results_off"] = dict(tune=(0, _lib.HB_X_NO_STAGED_RESULTS))
 EXPECT_MODES = {"frontier_always": {0, 1}, "frontier_always_slot_by_slot": {0, 1}, "frontier_always_multilevel": {0, 1}, "sparse_always_multilevel": {0, 2},
                 "long_tail_default": {0, 2}}
 VARIANTS["long_tail_default"] = dict()
 VARIANTS["long_tail_chunk8"] = dict(chunk=8)
-VARIANTS["long_tail_staged_results"] = dict(tune=(0, 0x8000))
+VARIANTS["long_tail_staged_results"] = dict(tune=(0, _lib.HB_X_SNAPSHOT_EVERY_PASS))
 # round 5: the far tail as one workgroup (hb_tail.hip.h; off by default; hb_step lets it run ONE pass per launch, so every pass is
 # compared): bit 21 = on, after a sweep pass that changed <= 4096 nodes with short reader lists; bit 22 = on, after any pass (right
 # behind the dense passes: stale virtual bits, large dirty sets, lists that overflow and make it decline)
-VARIANTS["long_tail_tail_kernel_after_any_pass"] = dict(tune=(0, 0x400000))
-VARIANTS["long_tail_tail_kernel_after_any_pass_chunk4"] = dict(chunk=4, tune=(0, 0x400000))
-VARIANTS["long_tail_tail_kernel_on"] = dict(tune=(0, 0x200000))
-VARIANTS["tail_kernel_after_any_pass_sparse_always"] = dict(chunk=8, tune=(0, 0x400000, 101, 0, 0, 0, 1))
+VARIANTS["long_tail_tail_kernel_after_any_pass"] = dict(tune=(0, _lib.HB_X_TAIL_KERNEL_ANY))
+VARIANTS["long_tail_tail_kernel_after_any_pass_chunk4"] = dict(chunk=4, tune=(0, _lib.HB_X_TAIL_KERNEL_ANY))
+VARIANTS["long_tail_tail_kernel_on"] = dict(tune=(0, _lib.HB_X_TAIL_KERNEL))
+VARIANTS["tail_kernel_after_any_pass_sparse_always"] = dict(chunk=8, tune=(0, _lib.HB_X_TAIL_KERNEL_ANY, 101, 0, 0, 0, 1))
 
 
 # round 6: hb_begin leaves the initial state (counters, Kahan words, sizes) to a LEAN pass 0 (hb_kernels.hip.h PassParams::rd_init) when
@@ -243,17 +243,17 @@ VARIANTS["tail_kernel_after_any_pass_sparse_always"] = dict(chunk=8, tune=(0, 0x
 for _base in ("default", "chunk4_multilevel", "sparse_always_multilevel", "frontier_always", "old_per_tile_epilogue", "no_reorder_unroll4",
               "long_tail_default", "staged_results_every_pass", "no_xcd_map"):
     VARIANTS[_base + "_lean"] = VARIANTS[_base]
-VARIANTS["full_init_switch"] = dict(tune=(0, 0x800000))  # hb_begin always writes the whole initial state (the pre-round-6 form)
+VARIANTS["full_init_switch"] = dict(tune=(0, _lib.HB_X_FULL_INIT))  # hb_begin always writes the whole initial state (the pre-round-6 form)
 # round 6: the transposed work-row graph (the sweep passes' reader lists) is built by ONE stable radix sort (hb_plan.hip gpu_transpose_rows);
 # bit 25 = the atomic-scatter form it replaced, which remains the out-of-memory fallback: same passes, same bits either way
-VARIANTS["sweep_transpose_by_scatter"] = dict(chunk=8, tune=(0, 0x2000000, 101, 0, 0, 0, 1))
-VARIANTS["long_tail_transpose_by_scatter"] = dict(tune=(0, 0x2000000))
+VARIANTS["sweep_transpose_by_scatter"] = dict(chunk=8, tune=(0, _lib.HB_X_SCATTER_TRANSPOSE, 101, 0, 0, 0, 1))
+VARIANTS["long_tail_transpose_by_scatter"] = dict(tune=(0, _lib.HB_X_SCATTER_TRANSPOSE))
 # round 6: a touched row of a sweep pass takes all its indices, then all their changed-bit words, then the needed gathers (hb_sweep.hip.h);
 # bit 26 = the round-by-round loop it replaced (A/B form)
-VARIANTS["pass0_level1_generic_kernel"] = dict(tune=(0, 0x8000000))  # bit 27: pass 0's first hub level through pass_kernel<.., INIT> (the form before init_level1_kernel)
+VARIANTS["pass0_level1_generic_kernel"] = dict(tune=(0, _lib.HB_X_GENERIC_LEVEL1))  # pass 0's first hub level through pass_kernel<.., INIT> (the form before init_level1_kernel)
 VARIANTS["pass0_level1_chunk128"] = dict(chunk=128)                   # init_level1_kernel with rows of more than 64 sources: two batches
-VARIANTS["sweep_rows_round_by_round"] = dict(chunk=8, tune=(0, 0x4000000, 101, 0, 0, 0, 1))
-VARIANTS["long_tail_rows_round_by_round"] = dict(tune=(0, 0x4000000))
+VARIANTS["sweep_rows_round_by_round"] = dict(chunk=8, tune=(0, _lib.HB_X_SWEEP_ROUNDS, 101, 0, 0, 0, 1))
+VARIANTS["long_tail_rows_round_by_round"] = dict(tune=(0, _lib.HB_X_SWEEP_ROUNDS))
 VARIANTS["sparse_always_chunk128"] = dict(chunk=128, tune=(0, 0, 101, 0, 0, 0, 1))  # sweep rows with more than 64 sources: two batches per hub chunk
 VARIANTS["sparse_always_direct32"] = dict(chunk=32, tune=(0, 0, 101, 5, 8, 8, 1))    # node rows with more than 16 direct sources: several batches
 
@@ -326,8 +326,8 @@ def test_run_pipelines_the_convergence_tail_and_books_it_like_single_steps(gpu_c
     vals, keep, k = o.finish()
     keys = ("pass", "changed", "active_edges", "touched", "mode")
     seen = {}
-    for name, kw in (("pipelined", dict()), ("stepwise", dict(tune=(0, 0x100000))), ("pipelined_chunk8", dict(chunk=8)),
-                     ("pipelined_staged_every_pass", dict(tune=(0, 0x8000)))):
+    for name, kw in (("pipelined", dict()), ("stepwise", dict(tune=(0, _lib.HB_X_NO_TAIL_PIPELINE))), ("pipelined_chunk8", dict(chunk=8)),
+                     ("pipelined_staged_every_pass", dict(tune=(0, _lib.HB_X_SNAPSHOT_EVERY_PASS)))):
         with gpu_ctx_factory(**kw) as ctx:
             ctx.load_dense(g.ids, g.row_ptr, g.src)
             for again in range(2):  # (a second run on the same context: the pipeline's buffers and events are reused)
@@ -365,8 +365,8 @@ def test_tail_kernel_runs_whole_passes_from_work_lists(gpu_ctx_factory):
     seen = {}
     # (the kernel is OFF by default - measured no faster than the launches it replaces; tune[1] bit 21 = on, bit 22 = on,
     # after any pass)
-    for name, kw in (("on", dict(tune=(0, 0x200000))), ("off", dict()), ("after_any_pass", dict(tune=(0, 0x400000))), ("on_chunk8", dict(chunk=8, tune=(0, 0x200000))),
-                     ("after_any_pass_chunk4_staged", dict(chunk=4, tune=(0, 0x408000)))):
+    for name, kw in (("on", dict(tune=(0, _lib.HB_X_TAIL_KERNEL))), ("off", dict()), ("after_any_pass", dict(tune=(0, _lib.HB_X_TAIL_KERNEL_ANY))), ("on_chunk8", dict(chunk=8, tune=(0, _lib.HB_X_TAIL_KERNEL))),
+                     ("after_any_pass_chunk4_staged", dict(chunk=4, tune=(0, _lib.HB_X_SNAPSHOT_EVERY_PASS | _lib.HB_X_TAIL_KERNEL_ANY)))):
         with gpu_ctx_factory(**kw) as ctx:
             ctx.load_dense(g.ids, g.row_ptr, g.src)
             for again in range(2):
@@ -394,7 +394,7 @@ def test_max_passes_is_reported_by_every_driver_of_the_tail(gpu_ctx_factory):
     o = hbo.Dense(g.id_low64(), g.row_ptr, g.src)
     T = o.run()
     vals, keep, k = o.finish()
-    for tune in ((), (0, 0x100000), (0, 0x200000), (0, 0x400000)):
+    for tune in ((), (0, _lib.HB_X_NO_TAIL_PIPELINE), (0, _lib.HB_X_TAIL_KERNEL), (0, _lib.HB_X_TAIL_KERNEL_ANY)):
         for limit in (T - 1, T - 2, T - 7):
             with gpu_ctx_factory(max_passes=limit, tune=tune) as ctx:
                 ctx.load_dense(g.ids, g.row_ptr, g.src)
@@ -422,8 +422,8 @@ def test_tail_pipeline_when_a_late_change_would_ask_for_a_dense_pass(gpu_ctx_fac
     T = o.run()
     vals, keep, k = o.finish()
     seen = {}
-    for name, kw in (("pipelined", dict()), ("stepwise", dict(tune=(0, 0x100000))), ("pipelined_chunk8", dict(chunk=8)),
-                     ("tail_kernel", dict(tune=(0, 0x200000))), ("tail_kernel_chunk8", dict(chunk=8, tune=(0, 0x200000)))):
+    for name, kw in (("pipelined", dict()), ("stepwise", dict(tune=(0, _lib.HB_X_NO_TAIL_PIPELINE))), ("pipelined_chunk8", dict(chunk=8)),
+                     ("tail_kernel", dict(tune=(0, _lib.HB_X_TAIL_KERNEL))), ("tail_kernel_chunk8", dict(chunk=8, tune=(0, _lib.HB_X_TAIL_KERNEL)))):
         with gpu_ctx_factory(**kw) as ctx:
             ctx.load_dense(ids, row_ptr, src)
             st = ctx.run()
@@ -622,7 +622,7 @@ def test_result_ranks_match_store_harmonic_order(gpu_ctx_factory, image):
     # image = compact [r6]: results shipped in stages (forced here; the default from 2^20 nodes on) keep one image entry per node WITH
     # in-edges only; list, ranks and top-k must come out of it exactly as out of the one-entry-per-node image
     g = synth.RmatGraph(13, 60_000)
-    kw = dict(tune=(0, 0x8000)) if image == "compact" else {}
+    kw = dict(tune=(0, _lib.HB_X_SNAPSHOT_EVERY_PASS)) if image == "compact" else {}
     _factory = gpu_ctx_factory
     gpu_ctx_factory = lambda: _factory(**kw)  # noqa: E731
     o = hbo.Dense(g.id_low64(), g.row_ptr, g.src)
@@ -734,7 +734,7 @@ def test_sweep_seeds_with_very_long_reader_lists(gpu_ctx_factory):
         tuples += [(leaf0 + k, leaf0 + K + (k % 7), 0) for k in range(0, K, 3)]   # a few leaves are read further on
         e = EdgeListGraph.from_tuples(tuples)
         fids, fvals, fst = hbo.faithful_run(e.host_edges())
-        for kw in (dict(tune=(0, 0, 101, 0, 0, 0, 1)), dict(tune=(0, 0x800, 101, 0, 0, 0, 1)), dict()):
+        for kw in (dict(tune=(0, 0, 101, 0, 0, 0, 1)), dict(tune=(0, _lib.HB_X_SEED_3LAUNCH, 101, 0, 0, 0, 1)), dict()):
             hc = HarmonicCentrality.calculate(e, **kw)
             ids, vals = hc.arrays()
             assert hc.stats["passes"] == fst["passes"] and hc.stats["n"] == fst["n"], (K, kw)
@@ -1016,7 +1016,7 @@ def test_packed_exchange_is_six_bits_per_register(gpu_ctx_factory):
     world = 2
     n_pad_slices = None
     wires = {}
-    for name, tune in (("six_bit", ()), ("bytes", (0, 0x1000000))):
+    for name, tune in (("six_bit", ()), ("bytes", (0, _lib.HB_X_WIRE_64B))):
         ctxs = []
         try:
             for r in range(world):

@@ -29,6 +29,22 @@ def test_header_symbols_all_exported():
     assert _lib.load().hb_abi_version() == 6
 
 
+def test_experiment_switch_names_agree_with_the_python_binding():
+    """Every HB_X_* switch of stract_amd/csrc/hb_experiments.h exists in _lib with the same value, and vice versa; each is one bit of
+    hb_options.tune[1] above the low byte (the gather unroll), and no two share a bit."""
+    text = open(os.path.join(ROOT, "stract_amd", "csrc", "hb_experiments.h")).read()
+    header = {name: int(value, 16) for name, value in re.findall(r"^\s*(HB_X_[A-Z0-9_]+)\s*=\s*(0x[0-9A-Fa-f]+)u?\s*,", text, flags=re.M)}
+    assert len(header) >= 17, sorted(header)
+    binding = {name: getattr(_lib, name) for name in dir(_lib) if name.startswith("HB_X_")}
+    assert header == binding
+    seen = 0
+    for name, value in sorted(header.items()):
+        assert value & (value - 1) == 0 and 0xFF < value <= 0xFFFFFFFF, (name, hex(value))
+        assert not seen & value, "%s shares its bit with another switch" % name
+        seen |= value
+        assert _lib.needs_experiments_build((0, value)), name
+
+
 def test_headers_are_plain_c99_and_struct_sizes_agree(tmp_path):
     """What a cgo / bindgen / JNI binding compiles is C, not C++: every header under include/ must pass a strict C99 compiler on its own,
     and the struct sizes the C compiler sees are the ones the Python binding (and INTEGRATION.md's Rust shim) assume."""

@@ -67,8 +67,8 @@ def one_case(rng, max_nodes, case):
         return None
     ids, row_ptr, src = graphs.dense_from_tuples(edges)
     chunk = int(rng.choice([4, 8, 16, 32, 64, 128, 256]))
-    # (round 5 switches of tune[1]: 0x8000 = a result snapshot after every pass, 0x20000 = only the first one, 0x10000 = a 16-entry final list)
-    tune = (int(rng.choice([0, 0, 1, 2, 7])), int(rng.choice([0, 1, 2, 4])) | int(rng.choice([0, 0, 0x100, 0x800, 0x2000])) | int(rng.choice([0, 0, 0x8000, 0x28000, 0x38000])) | int(rng.choice([0, 0, 0x200000, 0x400000])) | int(rng.choice([0, 0, 0x800000])) | int(rng.choice([0, 0, 0x2000000])),  # (+ the single-workgroup tail kernel: on / on after any pass; round 6: full init, transposition by scatter)
+    # (tune[1] above its low byte: switches of the experiments build, stract_amd/csrc/hb_experiments.h)
+    tune = (int(rng.choice([0, 0, 1, 2, 7])), int(rng.choice([0, 1, 2, 4])) | int(rng.choice([0, 0, _lib.HB_X_TILE_EPILOGUE, _lib.HB_X_SEED_3LAUNCH, _lib.HB_X_BITMAP_SLOTWISE])) | int(rng.choice([0, 0, _lib.HB_X_SNAPSHOT_EVERY_PASS, _lib.HB_X_SNAPSHOT_EVERY_PASS | _lib.HB_X_ONE_SNAPSHOT, _lib.HB_X_SNAPSHOT_EVERY_PASS | _lib.HB_X_SHORT_FINAL_LIST | _lib.HB_X_ONE_SNAPSHOT])) | int(rng.choice([0, 0, _lib.HB_X_TAIL_KERNEL, _lib.HB_X_TAIL_KERNEL_ANY])) | int(rng.choice([0, 0, _lib.HB_X_FULL_INIT])) | int(rng.choice([0, 0, _lib.HB_X_SCATTER_TRANSPOSE])),  # (+ the single-workgroup tail kernel: on / on after any pass; round 6: full init, transposition by scatter)
             int(rng.choice([0, 0, 30, 101])),
             int(rng.integers(4, 17)), int(rng.integers(1, 9)), int(rng.integers(0, chunk + 1)), int(rng.choice([0, 0, 1, 4, 1000000])))
     names = sorted(set(rng.choice(FLAG_POOL, size=int(rng.integers(0, 3))).tolist()))
@@ -136,8 +136,8 @@ def records_case(rng, max_nodes, case):
     how = int(rng.integers(0, 3))
     what = dict(case=case, kind="records", records=int(len(e)), pool=n, how=("batches", "at once", "at once + node list")[how])
     flags_ctx = int(rng.choice([0, 0, _lib.HB_FLAG_HOST_INGEST, _lib.HB_FLAG_HOST_PLAN]))
-    # hb_run: the tail pipeline (default) or one pass at a time (0x100000), results in snapshots (0x8000 / 0x38000) or at the end
-    tune_ctx = (0, int(rng.choice([0, 0, 0x8000, 0x100000, 0x38000, 0x108000])) | int(rng.choice([0, 0, 0x200000, 0x400000])), int(rng.choice([0, 0, 101])), 0, 0, 0,
+    # hb_run: the tail pipeline (default) or one pass at a time (HB_X_NO_TAIL_PIPELINE), results in snapshots (HB_X_SNAPSHOT_EVERY_PASS) or at the end
+    tune_ctx = (0, int(rng.choice([0, 0, _lib.HB_X_SNAPSHOT_EVERY_PASS, _lib.HB_X_NO_TAIL_PIPELINE, _lib.HB_X_SNAPSHOT_EVERY_PASS | _lib.HB_X_SHORT_FINAL_LIST | _lib.HB_X_ONE_SNAPSHOT, _lib.HB_X_SNAPSHOT_EVERY_PASS | _lib.HB_X_NO_TAIL_PIPELINE])) | int(rng.choice([0, 0, _lib.HB_X_TAIL_KERNEL, _lib.HB_X_TAIL_KERNEL_ANY])), int(rng.choice([0, 0, 101])), 0, 0, 0,
                 int(rng.choice([0, 0, 1])))
     what["tune"] = tune_ctx
     with _lib.Context(flags=flags_ctx, chunk=int(rng.choice([8, 64])), tune=tune_ctx) as ctx:
