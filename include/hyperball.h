@@ -392,6 +392,67 @@ int hb_distance_count(hb_ctx *ctx, uint64_t *count);
 int hb_distance_copy(hb_ctx *ctx, hb_u128 *ids, uint8_t *dist, uint64_t cap);
 int hb_distance_all(hb_ctx *ctx, uint8_t *dist, uint64_t cap);
 
+/* ---- exact betweenness centrality: Betweenness (webgraph/centrality/betweenness.rs:29-172) ------------------------------------------ */
+/* Brandes' algorithm ("A Faster Algorithm for Betweenness Centrality") from a set of source nodes over the loaded graph (host- or
+ * page-level).  The loaded graph is already reduced to unique edges, and a self link never lies on a shortest path, so the
+ * ForwardlinksQuery's skip_self_links / de-duplication (betweenness.rs:73-75) need nothing extra here.
+ * Sources: given as ids; duplicates count once, ids that are no node of the graph are counted in unknown_sources.  sources == NULL means
+ * every node when n <= 100000 (.take(100_000), betweenness.rs:34), HB_ERR_INVALID otherwise: the reference takes an arbitrary 100 000
+ * from a hash set, which nothing can reproduce.  S = the distinct known sources, in ascending NodeID order; source i is lane i % 8 of
+ * batch i / 8.
+ * Per source s (betweenness.rs:50-122):
+ *   dist_s(v)  = BFS distance, a u8, 255 = unreached;
+ *   sigma_s(v) = number of shortest s -> v paths, a u64 with SATURATING add (order-independent for non-negative terms, ~0 absorbing);
+ *   delta_s(v) = sum over the out-neighbours w with dist_s(w) == dist_s(v) + 1 of (sigma_s(v) / sigma_s(w)) * (1 + delta_s(w)), in f64
+ *                from +0.0 (:104-115), computed in the algebraic form sigma_s(v) * sum((1 + delta_s(w)) / sigma_s(w)), without FMA
+ *                contraction and without floating-point atomics.  The order of the terms of one (s, v) is not pinned by the reference
+ *                (hash-set and document order decide it there); here the device layout fixes it: two calls give the same bits.
+ * Result (:118-140): sum(v) = delta_s(v) over the sources s != v in ascending order; value(v) = sum(v) / (S * (S - 1)), one f64
+ * division, so S == 1 gives 0 / 0 = NaN and x / 0 = +inf, as the reference does.  HB_BC_RAW returns sum(v) itself: a caller may split
+ * its sources over several calls and add.  v is a result iff it is a source or some source reaches it (:56, :119).
+ * Limits: a walk that still has a frontier after level 254, and any sigma that saturates (the reference's i32 would have wrapped at
+ * 2^31), end the call with HB_ERR_LIMIT and leave NO result: a truncated betweenness would be a wrong one.
+ * Single rank only.  The result lives in buffers of its own until the next hb_betweenness or the next load; hb_result_* of an earlier
+ * run and the last hb_distances result stay readable.  The walk borrows the HyperBall state (registers, partials, changed bitmaps,
+ * sweep scratch) as hb_sampled_harmonic does: hb_step needs a new hb_begin afterwards, and a later hb_run computes what it computed
+ * before.  Refused (HB_ERR_INVALID) between hb_begin and hb_finish, without a loaded graph, with world_size > 1, with both debug flags
+ * set and with sources == NULL on a graph of more than 100000 nodes.  DESIGN.md section 15. */
+#define HB_BC_RAW          0x1u  /* the result is sum(v), not sum(v) / (S (S - 1)) */
+#define HB_BC_DENSE_ONLY   0x2u  /* debug: every forward level is a dense one (same result) */
+#define HB_BC_SPARSE_ONLY  0x4u  /* debug: every forward level is a sweep (bitmap on a context without sweep support; same result) */
+
+typedef struct hb_betweenness_options {
+    uint32_t struct_size, flags;                    /* struct_size = sizeof(hb_betweenness_options); 0 = this version; flags = HB_BC_* */
+    const hb_u128 *sources; uint64_t source_count;  /* NULL = every node (n <= 100000) */
+} hb_betweenness_options;
+
+typedef struct hb_betweenness_stats {
+    uint32_t struct_size;       /* = sizeof(hb_betweenness_stats); 0 = this version */
+    uint32_t max_dist;          /* largest distance over all sources (Betweenness::max_dist) */
+    uint64_t sources;           /* S: distinct known sources */
+    uint64_t unknown_sources;   /* ids not in the loaded graph */
+    uint64_t batches;           /* ceil(S / 8) */
+    uint64_t results;           /* sources and nodes reached from one */
+    uint64_t levels_forward, levels_backward; /* levels run, over all batches */
+    uint64_t levels_mode[3];    /* forward levels per mode: dense, bitmap, sweep */
+    uint64_t edges_gathered;    /* source entries gathered by the forward levels */
+    uint64_t device_bytes;      /* the operator's own buffers */
+    double   ms_total;          /* wall time of the call */
+    double   ms_forward, ms_backward; /* GPU time of the forward / backward levels */
+    double   ms_mode[3];        /* GPU time of the forward levels per mode */
+    double   ms_dense_max;      /* the slowest dense forward level */
+} hb_betweenness_stats;
+
+int hb_betweenness(hb_ctx *ctx, const hb_betweenness_options *opt, hb_betweenness_stats *stats);
+/* The result of the last hb_betweenness.  count = results; copy = those nodes only, ascending NodeID, at most cap entries, ids or vals
+ * may be NULL (only the results are downloaded); all = one f64 per node in ascending-NodeID order, -1.0 = no result, cap >= n. */
+int hb_betweenness_count(hb_ctx *ctx, uint64_t *count);
+int hb_betweenness_copy(hb_ctx *ctx, hb_u128 *ids, double *vals, uint64_t cap);
+int hb_betweenness_all(hb_ctx *ctx, double *vals, uint64_t cap);
+/* Debug: the per-lane state of the LAST batch of the last hb_betweenness, n x 8 entries each in ascending-NodeID order (entry sid * 8 +
+ * lane; lanes beyond the batch's sources: 255 / 0 / +0.0); any of the three may be NULL. */
+int hb_debug_copy_betweenness_batch(hb_ctx *ctx, uint8_t *dist, uint64_t *sigma, double *delta);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) -------------------------------------- */
 /* Rank 0 calls this and distributes the 128 bytes (e.g. torch.distributed broadcast);
  * every rank puts them in hb_options.rccl_id. */

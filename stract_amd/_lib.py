@@ -214,6 +214,47 @@ class HbDistanceStats(ctypes.Structure):
         return d
 
 
+HB_BC_RAW = 0x1
+HB_BC_DENSE_ONLY = 0x2
+HB_BC_SPARSE_ONLY = 0x4
+
+
+class HbBetweennessOptions(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("sources", ctypes.c_void_p),
+        ("source_count", ctypes.c_uint64),
+    ]
+
+
+class HbBetweennessStats(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("max_dist", ctypes.c_uint32),
+        ("sources", ctypes.c_uint64),
+        ("unknown_sources", ctypes.c_uint64),
+        ("batches", ctypes.c_uint64),
+        ("results", ctypes.c_uint64),
+        ("levels_forward", ctypes.c_uint64),
+        ("levels_backward", ctypes.c_uint64),
+        ("levels_mode", ctypes.c_uint64 * 3),
+        ("edges_gathered", ctypes.c_uint64),
+        ("device_bytes", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+        ("ms_forward", ctypes.c_double),
+        ("ms_backward", ctypes.c_double),
+        ("ms_mode", ctypes.c_double * 3),
+        ("ms_dense_max", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        for k in ("levels_mode", "ms_mode"):  # per mode: dense, bitmap, sweep
+            d[k] = list(d[k])
+        return d
+
+
 # every symbol include/hyperball.h declares: (name, restype, argtypes)
 _P = ctypes.c_void_p
 _U64 = ctypes.c_uint64
@@ -308,6 +349,14 @@ _SIGNATURES += [
     ("hb_distance_count", ctypes.c_int, [_P, ctypes.POINTER(_U64)]),
     ("hb_distance_copy", ctypes.c_int, [_P, _P, _P, _U64]),
     ("hb_distance_all", ctypes.c_int, [_P, _P, _U64]),
+]
+# include/hyperball.h: exact betweenness centrality (Betweenness)
+_SIGNATURES += [
+    ("hb_betweenness", ctypes.c_int, [_P, ctypes.POINTER(HbBetweennessOptions), ctypes.POINTER(HbBetweennessStats)]),
+    ("hb_betweenness_count", ctypes.c_int, [_P, ctypes.POINTER(_U64)]),
+    ("hb_betweenness_copy", ctypes.c_int, [_P, _P, _P, _U64]),
+    ("hb_betweenness_all", ctypes.c_int, [_P, _P, _U64]),
+    ("hb_debug_copy_betweenness_batch", ctypes.c_int, [_P, _P, _P, _P]),
 ]
 SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -671,6 +720,60 @@ class Context:
         """The same call; the result as one byte per node (ascending NodeID, 255 = unreached): (dist, stats)."""
         st = self._distances(sources, reversed, max_dist, mode, flags)
         return self.distance_all(), st
+
+    # -- exact betweenness centrality (Betweenness, centrality/betweenness.rs:29-172)
+    _BC_MODES = {None: 0, "auto": 0, "dense": HB_BC_DENSE_ONLY, "sparse": HB_BC_SPARSE_ONLY}
+
+    def _betweenness(self, sources, raw, mode, flags=0):
+        o = HbBetweennessOptions()
+        o.struct_size = ctypes.sizeof(HbBetweennessOptions)
+        o.flags = int(flags) | (HB_BC_RAW if raw else 0) | self._BC_MODES[mode]
+        if sources is not None:
+            count = len(sources)
+            sources = np.ascontiguousarray(sources, dtype=U128) if count else np.zeros(1, dtype=U128)
+            o.sources = sources.ctypes.data
+            o.source_count = count
+        st = HbBetweennessStats()
+        st.struct_size = ctypes.sizeof(HbBetweennessStats)
+        self._check(self.lib.hb_betweenness(self.h, ctypes.byref(o), ctypes.byref(st)))
+        return st.as_dict()
+
+    def betweenness_count(self):
+        k = ctypes.c_uint64(0)
+        self._check(self.lib.hb_betweenness_count(self.h, ctypes.byref(k)))
+        return k.value
+
+    def betweenness_copy(self):
+        """The results of the last betweenness() call: (ids ascending, values float64)."""
+        k = self.betweenness_count()
+        ids = np.zeros(k, dtype=U128)
+        vals = np.zeros(k, dtype=np.float64)
+        self._check(self.lib.hb_betweenness_copy(self.h, _ptr(ids), _ptr(vals), k))
+        return ids, vals
+
+    def betweenness_all(self):
+        """One float64 per node of the last betweenness() call, ascending NodeID; -1.0 = no result."""
+        out = np.full(self.n(), -1.0, dtype=np.float64)
+        self._check(self.lib.hb_betweenness_all(self.h, _ptr(out), len(out)))
+        return out
+
+    def betweenness(self, sources=None, raw=False, mode=None, flags=0):
+        """hb_betweenness from `sources` (U128 array of node ids; None = every node of a graph of at most 100 000): (ids, vals, stats) -
+        the sources and every node one of them reaches, ascending NodeID, with sum / (S (S - 1)) (raw: the sum itself); mode: None /
+        "dense" / "sparse" (forced kind of forward level)."""
+        st = self._betweenness(sources, raw, mode, flags)
+        ids, vals = self.betweenness_copy()
+        return ids, vals, st
+
+    def debug_betweenness_batch(self):
+        """dist (n, 8) uint8, sigma (n, 8) uint64, delta (n, 8) float64 of the LAST batch of the last betweenness() call, ascending NodeID;
+        lane = position of the source within the batch."""
+        n = self.n()
+        dist = np.full((n, 8), 255, dtype=np.uint8)
+        sigma = np.zeros((n, 8), dtype=np.uint64)
+        delta = np.zeros((n, 8), dtype=np.float64)
+        self._check(self.lib.hb_debug_copy_betweenness_batch(self.h, _ptr(dist), _ptr(sigma), _ptr(delta)))
+        return dist, sigma, delta
 
     # -- results
     def results(self):

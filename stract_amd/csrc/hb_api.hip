@@ -22,6 +22,7 @@
 #include "hb_kernels.hip.h"
 #include "hb_sample.hip.h"
 #include "hb_bfs.hip.h"
+#include "hb_betweenness.hip.h"
 #ifdef HB_EXPERIMENTS
 #include "hb_experiments.hip.h"
 #endif
@@ -210,6 +211,33 @@ struct GraphDeviceState {
         uint64_t words_total = 0;            // words of d_vis / d_next
         uint64_t reached = 0;
     } dst;
+    // hb_betweenness (hb_api_betweenness.inc): the per-batch state, the sums and the last result, dev_alloc'ed at the first call after a load
+    struct BetweennessState {
+        bool ready = false; // the buffers below exist
+        bool valid = false; // they hold the result of a finished hb_betweenness
+        uint8_t *d_dist = nullptr;             // n_pad x 8: distance per device row and lane of the current batch, 255 = unreached
+        unsigned long long *d_sigma = nullptr; // n_pad x 8: shortest-path counts
+        double *d_delta = nullptr;             // n_pad x 8: dependencies
+        uint8_t *d_reached = nullptr;          // n_pad: the row is a result
+        double *d_sum = nullptr;               // n_pad: sum(v) over the batches so far
+        unsigned long long *d_cnt = nullptr;   // 257 levels x 4 counters of the current batch
+        uint32_t *d_srcs = nullptr;            // sids of a batch's sources (<= 8)
+        uint32_t *d_heavy = nullptr;           // backward: node rows whose reader list the grid sums
+        unsigned int *d_heavy_cnt = nullptr;
+        uint32_t heavy_cap = 0;                // such rows in the loaded graph (0 = none: no list, no launches)
+        hbk::bc_d2 *d_seg = nullptr;           // ... their per-segment partial sums
+        const uint64_t *d_out_ptr = nullptr;   // the row -> readers transpose: the context's (sweep support), hb_distances', or one of this state's own
+        const uint32_t *d_out_rows = nullptr;
+        double *d_val_sid = nullptr;           // n: value per sid, -1.0 = no result
+        uint8_t *d_flag_sid = nullptr;         // n: 0 = result, 255 = none (the select's input)
+        uint32_t *d_sel_sid = nullptr;         // n: the results' sids, ascending
+        uint8_t *d_sel_flag = nullptr;
+        double *d_sel_val = nullptr;           // n: their values
+        uint64_t *d_sel_cnt = nullptr;
+        uint64_t results = 0;
+        uint64_t bytes = 0;                    // device bytes of the above
+        uint32_t last_lanes = 0;               // sources of the last batch run (0 = none)
+    } btw;
 };
 
 // The timing events of a pass (one set: hb_ctx::ev, or an EvSet), in the order a pass records them; kEvLevel1 lies between kEvStart and
@@ -1488,3 +1516,5 @@ int hb_store_harmonic_results(hb_ctx *c, const char *output, char *err, uint64_t
 #include "hb_api_sample.inc"
 
 #include "hb_api_distance.inc"
+
+#include "hb_api_betweenness.inc"

@@ -279,9 +279,50 @@ def distances_case(rng, max_nodes, case):
     return what
 
 
+def betweenness_case(rng, max_nodes, case):
+    """hb_betweenness: random graph x random source set x forced mode, against the host restatement (tests/betweenness_ref.py: the
+    literal betweenness.rs:50-122) under the comparison rule of tests/test_betweenness.py."""
+    from stract_amd.harmonic import EdgeListGraph
+    from tests import betweenness_ref as bref
+    kind, tuples = graphs.random_graph(rng)
+    if not tuples:
+        return None
+    chunk = int(rng.choice([0, 0, 4, 8, 64]))
+    flags = _lib.HB_FLAG_ALL_RELS | int(rng.choice([0, 0, _lib.HB_FLAG_NO_REORDER, _lib.HB_FLAG_NO_XCD_MAP, _lib.HB_FLAG_NO_SPARSE]))
+    with _lib.Context(flags=flags, chunk=chunk) as ctx:
+        ctx.load_edges(EdgeListGraph.from_tuples(tuples).host_edges())
+        ids, row_ptr, src = ctx.graph()
+        n = len(ids)
+        what = dict(case=case, kind="betweenness:" + kind, n=n, m=int(len(src)), chunk=chunk, flags=flags, passes=0)
+        for _ in range(3):
+            srcs = sorted(set(int(x) for x in rng.integers(0, n, int(rng.integers(1, 20)))))
+            mode = [None, "dense", "sparse"][int(rng.integers(0, 3))]
+            raw = bool(rng.integers(0, 2))
+            run = dict(what, sources=srcs, mode=mode, raw=raw)
+            res = bref.literal(n, row_ptr, src, srcs)
+            if res.max_dist > 254 or max(max(s) for s in res.sigma) >= 2 ** 64 - 1:
+                continue  # (HB_ERR_LIMIT cases: tests/test_betweenness.py)
+            tol = bref.rtol(n, row_ptr, src, res)
+            gids, gvals, st = ctx.betweenness(ids[np.asarray(srcs, dtype=np.int64)], raw=raw, mode=mode)
+            want = res.values(raw)[res.reached]
+            assert np.array_equal(gids, ids[res.reached]) and st["max_dist"] == res.max_dist and st["results"] == len(gids), ("result set / max_dist", run)
+            assert np.array_equal(np.isnan(gvals), np.isnan(want)) and np.array_equal(np.isinf(gvals), np.isinf(want)), ("NaN / inf pattern", run)
+            fin = np.isfinite(want)
+            assert not gvals[fin & (want == 0.0)].view(np.uint64).any(), ("+0.0 values", run)
+            assert (np.abs(gvals[fin] - want[fin]) <= tol * np.abs(want[fin])).all(), ("values", run, tol)
+            dist, sigma, delta = ctx.debug_betweenness_batch()
+            first = (len(srcs) - 1) // 8 * 8
+            for lane, k in enumerate(range(first, len(srcs))):
+                assert np.array_equal(dist[:, lane], np.where(res.dist[k] < 0, 255, res.dist[k]).astype(np.uint8)), ("dist of source %d" % k, run)
+                assert [int(x) for x in sigma[:, lane]] == res.sigma[k], ("sigma of source %d" % k, run)
+                assert (np.abs(delta[:, lane] - res.delta[k]) <= tol * np.abs(res.delta[k])).all(), ("delta of source %d" % k, run)
+            what["passes"] += st["levels_forward"] + st["levels_backward"]
+    return what
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "distances"], default="passes")
+    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "distances", "betweenness"], default="passes")
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-nodes", type=int, default=6000)
@@ -294,6 +335,8 @@ def main():
         try:
             if a.mode == "distances":
                 w = distances_case(rng, a.max_nodes, case)
+            elif a.mode == "betweenness":
+                w = betweenness_case(rng, a.max_nodes, case)
             elif a.mode == "ranks" or (a.mode == "mixed" and case % 6 == 4):
                 w = ranks_case(rng, a.max_nodes, case)
             elif a.mode == "tail" or (a.mode == "mixed" and case % 6 == 5):
