@@ -20,6 +20,7 @@
 #include "hb_internal.h"
 #include "hb_experiments.h" // HB_XBITS: the switches of the experiments build (none in the product library)
 #include "hb_kernels.hip.h"
+#include "hb_walk.hip.h"
 #include "hb_sample.hip.h"
 #include "hb_bfs.hip.h"
 #include "hb_betweenness.hip.h"
@@ -119,7 +120,9 @@ struct GraphDeviceState {
     unsigned long long *d_counters = nullptr; // (max_passes + 1) * kCounterWords, striped (hb_kernels.hip.h)
     double *d_raw = nullptr, *d_bias = nullptr;
     uint8_t *d_lc = nullptr;
-    // sparse (data-driven) tail passes: transposed work-row graph + worklists
+    // sparse (data-driven) tail passes: transposed work-row graph + worklists.  The transpose (row -> readers) is also what hb_distances
+    // and hb_betweenness walk: a context without sweep support gets it at their first call (ensure_transpose, hb_api_walk.inc) -
+    // sparse_ok, not a non-null d_out_ptr, says that the sweep support exists
     uint64_t *d_out_ptr = nullptr;
     uint32_t *d_out_rows = nullptr;
     uint32_t *d_touch = nullptr;
@@ -202,8 +205,6 @@ struct GraphDeviceState {
         unsigned long long *d_cnt = nullptr; // 256 levels x 4 counters
         uint32_t *d_indeg = nullptr;         // rows_total: node sources under every row (reversed switch rule), built at the first reversed call
         bool indeg_valid = false;
-        const uint64_t *d_out_ptr = nullptr; // the row -> readers transpose: the context's (sweep support), or one of this state's own
-        const uint32_t *d_out_rows = nullptr;
         uint8_t *d_by_sid = nullptr;         // n: distance per sid
         uint32_t *d_sel_sid = nullptr;       // n: the reached sids, ascending
         uint8_t *d_sel_dist = nullptr;       // n: their distances
@@ -226,8 +227,6 @@ struct GraphDeviceState {
         unsigned int *d_heavy_cnt = nullptr;
         uint32_t heavy_cap = 0;                // such rows in the loaded graph (0 = none: no list, no launches)
         hbk::bc_d2 *d_seg = nullptr;           // ... their per-segment partial sums
-        const uint64_t *d_out_ptr = nullptr;   // the row -> readers transpose: the context's (sweep support), hb_distances', or one of this state's own
-        const uint32_t *d_out_rows = nullptr;
         double *d_val_sid = nullptr;           // n: value per sid, -1.0 = no result
         uint8_t *d_flag_sid = nullptr;         // n: 0 = result, 255 = none (the select's input)
         uint32_t *d_sel_sid = nullptr;         // n: the results' sids, ascending
@@ -1512,6 +1511,8 @@ int hb_store_harmonic_results(hb_ctx *c, const char *output, char *err, uint64_t
 #include "hb_api_debug.inc"
 
 } // extern "C"
+
+#include "hb_api_walk.inc"
 
 #include "hb_api_sample.inc"
 

@@ -12,7 +12,6 @@ int betweenness_alloc(hb_ctx *c)
     auto &b = c->btw;
     if (b.ready) return HB_OK;
     const Plan &p = c->plan;
-    const uint64_t rows_total = p.n_pad + p.nv;
     const uint64_t before = c->stats.device_bytes;
     int rc;
     if ((rc = dev_alloc(c, &b.d_dist, p.n_pad * 8))) return rc;
@@ -28,25 +27,10 @@ int betweenness_alloc(hb_ctx *c)
     if ((rc = dev_alloc(c, &b.d_sel_flag, p.n))) return rc;
     if ((rc = dev_alloc(c, &b.d_sel_val, p.n))) return rc;
     if ((rc = dev_alloc(c, &b.d_sel_cnt, 8))) return rc;
-    if (c->sparse_ok) { // the sweep passes' transpose
-        b.d_out_ptr = c->d_out_ptr;
-        b.d_out_rows = c->d_out_rows;
-    } else if (c->dst.ready) { // hb_distances built one for the same reason
-        b.d_out_ptr = c->dst.d_out_ptr;
-        b.d_out_rows = c->dst.d_out_rows;
-    } else { // a context without sweep support (HB_FLAG_NO_SPARSE, unfused passes): the same transpose, owned by this state
-        uint64_t *op = nullptr;
-        uint32_t *orow = nullptr;
-        if ((rc = dev_alloc(c, &op, rows_total + 1))) return rc;
-        if ((rc = dev_alloc(c, &orow, c->plan_entries))) return rc;
-        const std::string e = gpu_transpose_rows((void *)c->stream, c->d_row_ptr, c->d_src, rows_total, c->plan_entries, op, orow);
-        if (!e.empty()) return fail(c, e.find("out of memory") != std::string::npos ? HB_ERR_NOMEM : HB_ERR_HIP, "hb_betweenness: " + e);
-        b.d_out_ptr = op;
-        b.d_out_rows = orow;
-    }
+    if ((rc = ensure_transpose(c, "hb_betweenness"))) return rc;
     // node rows whose reader list the grid sums: their number is the capacity of the heavy list (0 = those kernels are never launched)
     HB_HIP(hipMemsetAsync(b.d_cnt, 0, 4 * sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(hbk::bc_count_heavy_kernel, dim3(grid_blocks(c, (p.n_pad + 255) / 256, 8, 1)), dim3(256), 0, c->stream, b.d_out_ptr, p.n_pad, b.d_cnt);
+    hipLaunchKernelGGL(hbk::bc_count_heavy_kernel, dim3(grid_blocks(c, (p.n_pad + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint64_t *)c->d_out_ptr, p.n_pad, b.d_cnt);
     HB_HIP(hipGetLastError());
     unsigned long long heavy = 0;
     HB_HIP(hipMemcpyAsync(&heavy, b.d_cnt, sizeof(heavy), hipMemcpyDeviceToHost, c->stream));
@@ -60,28 +44,6 @@ int betweenness_alloc(hb_ctx *c)
     b.bytes = c->stats.device_bytes - before;
     b.ready = true;
     return HB_OK;
-}
-
-// launch shape of one forward level: a wave per 32-row word, grid-stride; XCD-affine groups for the first hub-chunk level (as the
-// sampled walk's)
-void betweenness_launch(hb_ctx *c, const hbk::BcParams &bp, bool real, int mode)
-{
-    const uint64_t words = (bp.row_hi - bp.row_lo + 31) / 32;
-    if (!words) return;
-    uint64_t blocks = std::min<uint64_t>((words + 3) / 4, (uint64_t)c->num_cu * 8);
-    if (bp.xcd_map) blocks = std::max<uint64_t>((blocks + 7) / 8 * 8, 8);
-    const dim3 grid((unsigned)blocks), blk(256);
-#define HB_BC_LAUNCH(R, M) hipLaunchKernelGGL((hbk::bc_forward_kernel<R, M>), grid, blk, 0, c->stream, bp)
-    if (real) {
-        if (mode == hbk::kBcDense) HB_BC_LAUNCH(true, hbk::kBcDense);
-        else if (mode == hbk::kBcBitmap) HB_BC_LAUNCH(true, hbk::kBcBitmap);
-        else HB_BC_LAUNCH(true, hbk::kBcSweep);
-    } else {
-        if (mode == hbk::kBcDense) HB_BC_LAUNCH(false, hbk::kBcDense);
-        else if (mode == hbk::kBcBitmap) HB_BC_LAUNCH(false, hbk::kBcBitmap);
-        else HB_BC_LAUNCH(false, hbk::kBcSweep);
-    }
-#undef HB_BC_LAUNCH
 }
 
 // the result of the finished batches in sid order, and its compacted form (only the results are downloaded)
@@ -114,18 +76,13 @@ int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_
     const double t0 = now_ms();
     hb_betweenness_options o{};
     copy_in(opt_in, &o);
-    if (multi_rank(c)) return fail(c, HB_ERR_INVALID, "hb_betweenness: single rank only (world_size > 1)");
-    if (!c->loaded) return fail(c, HB_ERR_INVALID, "hb_betweenness: no graph loaded");
+    int rc;
+    if ((rc = walk_prologue(c, "hb_betweenness"))) return rc;
     if ((o.flags & HB_BC_DENSE_ONLY) && (o.flags & HB_BC_SPARSE_ONLY))
         return fail(c, HB_ERR_INVALID, "hb_betweenness: HB_BC_DENSE_ONLY and HB_BC_SPARSE_ONLY exclude each other");
     const Plan &p = c->plan;
     if (!o.sources && p.n > 100000)
         return fail(c, HB_ERR_INVALID, "hb_betweenness: sources == NULL means every node, which the reference limits to 100000 (betweenness.rs:34); name the sources");
-    int rc;
-    if ((rc = plan_rows_word_aligned(c, "hb_betweenness"))) return rc;
-    for (uint64_t lb : p.level_begin)
-        if (lb < p.n_pad || lb > p.n_pad + p.nv) return fail(c, HB_ERR_INVALID, "hb_betweenness: unexpected plan layout (virtual level boundary)");
-    if ((rc = refuse_stale_error(c, "hb_betweenness"))) return rc;
     auto &b = c->btw;
     b.valid = false;
     b.results = 0;
@@ -134,14 +91,7 @@ int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_
     // the sources as distinct ascending sids
     std::vector<uint32_t> sids;
     if (o.sources) {
-        sids.reserve(o.source_count);
-        for (uint64_t i = 0; i < o.source_count; i++) {
-            uint32_t sid;
-            if (find_sid(c, o.sources[i], &sid)) sids.push_back(sid);
-            else st.unknown_sources++;
-        }
-        std::sort(sids.begin(), sids.end());
-        sids.erase(std::unique(sids.begin(), sids.end()), sids.end());
+        resolve_sources(c, o.sources, o.source_count, &sids, &st.unknown_sources);
     } else {
         sids.resize(p.n);
         for (uint64_t i = 0; i < p.n; i++) sids[i] = (uint32_t)i;
@@ -161,8 +111,6 @@ int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_
     if ((rc = betweenness_alloc(c))) return rc;
     const uint64_t n_pad = p.n_pad, rows_total = p.n_pad + p.nv;
     const size_t nlev = p.level_begin.size() > 1 ? p.level_begin.size() - 1 : 0;
-    const bool xcd_ok = p.xcd_groups == 8 && p.level_begin.size() > 1 && p.xcd_begin[0] == p.level_begin[0] && p.xcd_begin[8] == p.level_begin[1] &&
-                        std::all_of(p.xcd_begin, p.xcd_begin + 9, [](uint64_t x) { return x % 32 == 0; });
     HB_HIP(hipMemsetAsync(b.d_sum, 0, n_pad * sizeof(double), c->stream));
     HB_HIP(hipMemsetAsync(b.d_reached, 0, n_pad, c->stream));
     // from here on the HyperBall state is gone: hb_step needs a new hb_begin, the tail kernel's lists describe nothing
@@ -185,23 +133,12 @@ int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_
         HB_HIP(hipMemsetAsync(b.d_cnt, 0, 257 * 4 * sizeof(unsigned long long), c->stream));
         HB_HIP(hipMemcpyAsync(b.d_srcs, sids.data() + b0, count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
         hbk::BcParams bp{};
-        bp.row_ptr = c->d_row_ptr;
-        bp.src = c->d_src;
+        fill_walk_params(c, &bp);
         bp.part = (hbk::bc_u2 *)c->d_part;
-        bp.touch = c->d_touch;
-        bp.out_ptr = b.d_out_ptr;
-        bp.out_rows = b.d_out_rows;
-        bp.outdeg = c->d_outdeg;
         bp.dist = b.d_dist;
         bp.sigma = b.d_sigma;
         bp.reached = b.d_reached;
         bp.cnt = b.d_cnt;
-        bp.n_pad = n_pad;
-        bp.rows_total = rows_total;
-        for (int x = 0; x < 8; x++) {
-            bp.xcd_lo[x] = p.xcd_begin[x];
-            bp.xcd_hi[x] = p.xcd_begin[x + 1];
-        }
         hipLaunchKernelGGL(hbk::bc_seed_kernel, dim3(1), dim3(64), 0, c->stream, (const uint32_t *)b.d_srcs, count, (const uint32_t *)c->d_dev_of,
                            (unsigned long long *)c->d_regs[0], c->d_bits[0], bp);
         HB_HIP(hipGetLastError());
@@ -214,52 +151,26 @@ int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_
         for (uint32_t d = 1; d <= 255 && last_changed; d++) {
             // dense / bitmap / sweep as in hb_run (pass_mode): the A_t rule on the out-degree sum of the rows that changed at d - 1;
             // level 1 of a batch (<= 8 rows changed) is a sweep wherever the sweep support exists
-            static_assert(hbk::kBcDense == kModeDense && hbk::kBcBitmap == kModeBitmap && hbk::kBcSweep == kModeSweep, "one numbering of the modes");
-            int mode = (d == 1 && c->sparse_ok) ? hbk::kBcSweep : (int)pass_mode(c, last_active);
-            if (o.flags & HB_BC_DENSE_ONLY) mode = hbk::kBcDense;
-            if (o.flags & HB_BC_SPARSE_ONLY) mode = c->sparse_ok ? hbk::kBcSweep : hbk::kBcBitmap;
+            PassMode mode = (d == 1 && c->sparse_ok) ? kModeSweep : pass_mode(c, last_active);
+            if (o.flags & HB_BC_DENSE_ONLY) mode = kModeDense;
+            if (o.flags & HB_BC_SPARSE_ONLY) mode = c->sparse_ok ? kModeSweep : kModeBitmap;
             bp.rd = (const hbk::bc_u2 *)c->d_regs[cur];
             bp.wr = (hbk::bc_u2 *)c->d_regs[cur ^ 1];
             bp.bits_rd = c->d_bits[cur];
             bp.bits_wr = c->d_bits[cur ^ 1];
             bp.cnt = b.d_cnt + 4 * (uint64_t)d;
             bp.level = d;
-            HB_HIP(hipEventRecord(c->ev[kEvStart], c->stream));
-            if (mode == hbk::kBcSweep) {
-                // the rows changed at d - 1 -> touch bits of their readers: hb_run's seed / expand kernels, unchanged (launch_sweep_seeding)
-                hbk::PassParams seed_pp{}; // (all the seeding kernels read of it)
-                seed_pp.bits_rd = c->d_bits[cur];
-                seed_pp.n_pad = n_pad;
-                seed_pp.rows_total = rows_total;
-                HB_HIP(hipMemsetAsync(c->d_sparse_counts, 0, 4 * sizeof(unsigned int), c->stream));
-                launch_sweep_seeding(c, make_sweep_params(c, seed_pp, 0, nullptr), last_changed <= 4096);
-                HB_HIP(hipGetLastError());
-            }
-            for (size_t l = 0; l < nlev; l++) { // virtual levels: partials of level d from the rows of level d - 1
-                bp.row_lo = p.level_begin[l];
-                bp.row_hi = p.level_begin[l + 1];
-                bp.xcd_map = (l == 0 && xcd_ok && mode == hbk::kBcDense) ? 1 : 0;
-                betweenness_launch(c, bp, false, mode);
-            }
-            bp.xcd_map = 0;
-            bp.row_lo = 0;
-            bp.row_hi = n_pad;
-            betweenness_launch(c, bp, true, mode);
-            HB_HIP(hipGetLastError());
-            HB_HIP(hipEventRecord(c->ev[kEvEnd], c->stream));
-            HB_HIP(hipMemcpyAsync(h, bp.cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-            HB_HIP(hipStreamSynchronize(c->stream));
-            float ms = 0.f;
-            HB_HIP(hipEventElapsedTime(&ms, c->ev[kEvStart], c->ev[kEvEnd]));
+            WalkLevel lv{};
+            if ((rc = walk_forward_level(c, bp, mode, last_changed, [&](bool real) { launch_walk<BrandesWalk>(c, bp, real, mode); }, &lv))) return rc;
             st.levels_forward++;
             st.levels_mode[mode]++;
-            st.ms_mode[mode] += ms;
-            st.ms_forward += ms;
-            if (mode == hbk::kBcDense) st.ms_dense_max = std::max(st.ms_dense_max, (double)ms);
-            st.edges_gathered += h[2];
-            last_changed = h[0];
-            last_active = h[1];
-            saturated = saturated || h[3] != 0;
+            st.ms_mode[mode] += lv.ms;
+            st.ms_forward += lv.ms;
+            if (mode == kModeDense) st.ms_dense_max = std::max(st.ms_dense_max, (double)lv.ms);
+            st.edges_gathered += lv.cnt[2];
+            last_changed = lv.cnt[0];
+            last_active = lv.cnt[1];
+            saturated = saturated || lv.cnt[3] != 0;
             if (last_changed) L = d;
             cur ^= 1;
         }
@@ -272,8 +183,8 @@ int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_
         HB_HIP(hipMemsetAsync(c->d_bits[0], 0, c->bits_words * 4, c->stream));
         HB_HIP(hipMemsetAsync(c->d_bits[1], 0, c->bits_words * 4, c->stream));
         hbk::BcBackParams kp{};
-        kp.out_ptr = b.d_out_ptr;
-        kp.out_rows = b.d_out_rows;
+        kp.out_ptr = c->d_out_ptr;
+        kp.out_rows = c->d_out_rows;
         kp.cpart = (hbk::bc_d2 *)c->d_part;
         kp.dist = b.d_dist;
         kp.sigma = b.d_sigma;
@@ -329,11 +240,7 @@ int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_
     return finish();
 }
 
-int betweenness_result_ready(hb_ctx *c, const char *who)
-{
-    if (!c->loaded || !c->btw.valid) return fail(c, HB_ERR_INVALID, std::string(who) + ": no betweenness result (call hb_betweenness)");
-    return set_device(c);
-}
+const char *const kNoBetweenness = "no betweenness result (call hb_betweenness)";
 
 } // namespace
 
@@ -345,8 +252,7 @@ int hb_betweenness(hb_ctx *c, const hb_betweenness_options *opt, hb_betweenness_
         if (!c) return HB_ERR_INVALID;
         int rc = set_device(c);
         if (rc) return rc;
-        // between hb_begin and hb_finish the HyperBall state (and the pinned counter words) belong to that run
-        if (c->begun && !c->finished) return fail(c, HB_ERR_INVALID, "hb_betweenness: a HyperBall run is in progress (hb_begin without hb_finish)");
+        if ((rc = run_in_progress(c, "hb_betweenness"))) return rc;
         return betweenness(c, opt, stats);
     });
 }
@@ -355,7 +261,7 @@ int hb_betweenness_count(hb_ctx *c, uint64_t *count)
 {
     return guarded(c, [&]() -> int {
         if (!c || !count) return c ? fail(c, HB_ERR_INVALID, "hb_betweenness_count: count == NULL") : HB_ERR_INVALID;
-        int rc = betweenness_result_ready(c, "hb_betweenness_count");
+        int rc = result_ready(c, c->btw.valid, "hb_betweenness_count", kNoBetweenness);
         if (rc) return rc;
         *count = c->btw.results;
         return HB_OK;
@@ -366,18 +272,13 @@ int hb_betweenness_copy(hb_ctx *c, hb_u128 *ids, double *vals, uint64_t cap)
 {
     return guarded(c, [&]() -> int {
         if (!c) return HB_ERR_INVALID;
-        int rc = betweenness_result_ready(c, "hb_betweenness_copy");
+        int rc = result_ready(c, c->btw.valid, "hb_betweenness_copy", kNoBetweenness);
         if (rc) return rc;
         auto &b = c->btw;
         const uint64_t k = std::min<uint64_t>(cap, b.results);
         if (!k || (!ids && !vals)) return HB_OK;
-        // only the results come down: k sids and k values; the ids are looked up in the host's sorted id array
-        if (ids) {
-            std::vector<uint32_t> sid(k);
-            HB_HIP(hipMemcpyAsync(sid.data(), b.d_sel_sid, k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HB_HIP(hipStreamSynchronize(c->stream));
-            for (uint64_t i = 0; i < k; i++) ids[i] = c->g.ids[sid[i]];
-        }
+        // only the results come down: k sids and k values
+        if (ids && (rc = copy_selected_ids(c, b.d_sel_sid, k, ids))) return rc;
         if (vals) {
             HB_HIP(hipMemcpyAsync(vals, b.d_sel_val, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
             HB_HIP(hipStreamSynchronize(c->stream));
@@ -390,7 +291,7 @@ int hb_betweenness_all(hb_ctx *c, double *vals, uint64_t cap)
 {
     return guarded(c, [&]() -> int {
         if (!c || !vals) return c ? fail(c, HB_ERR_INVALID, "hb_betweenness_all: vals == NULL") : HB_ERR_INVALID;
-        int rc = betweenness_result_ready(c, "hb_betweenness_all");
+        int rc = result_ready(c, c->btw.valid, "hb_betweenness_all", kNoBetweenness);
         if (rc) return rc;
         const uint64_t n = c->plan.n;
         if (cap < n) return fail(c, HB_ERR_INVALID, "hb_betweenness_all: cap < n");
@@ -405,7 +306,7 @@ int hb_debug_copy_betweenness_batch(hb_ctx *c, uint8_t *dist, uint64_t *sigma, d
 {
     return guarded(c, [&]() -> int {
         if (!c) return HB_ERR_INVALID;
-        int rc = betweenness_result_ready(c, "hb_debug_copy_betweenness_batch");
+        int rc = result_ready(c, c->btw.valid, "hb_debug_copy_betweenness_batch", kNoBetweenness);
         if (rc) return rc;
         const Plan &p = c->plan;
         auto &b = c->btw;

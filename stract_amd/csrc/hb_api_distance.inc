@@ -40,19 +40,7 @@ int distance_alloc(hb_ctx *c)
     if ((rc = dev_alloc(c, &d.d_sel_sid, p.n))) return rc;
     if ((rc = dev_alloc(c, &d.d_sel_dist, p.n))) return rc;
     if ((rc = dev_alloc(c, &d.d_sel_cnt, 8))) return rc;
-    if (c->sparse_ok) { // the sweep passes' transpose
-        d.d_out_ptr = c->d_out_ptr;
-        d.d_out_rows = c->d_out_rows;
-    } else { // a context without sweep support (HB_FLAG_NO_SPARSE, unfused passes): the same transpose, owned by this state
-        uint64_t *op = nullptr;
-        uint32_t *orow = nullptr;
-        if ((rc = dev_alloc(c, &op, rows_total + 1))) return rc;
-        if ((rc = dev_alloc(c, &orow, c->plan_entries))) return rc;
-        const std::string e = gpu_transpose_rows((void *)c->stream, c->d_row_ptr, c->d_src, rows_total, c->plan_entries, op, orow);
-        if (!e.empty()) return fail(c, e.find("out of memory") != std::string::npos ? HB_ERR_NOMEM : HB_ERR_HIP, "hb_distances: " + e);
-        d.d_out_ptr = op;
-        d.d_out_rows = orow;
-    }
+    if ((rc = ensure_transpose(c, "hb_distances"))) return rc;
     HB_HIP(hipMemsetAsync(d.d_next, 0, d.words_total * sizeof(uint32_t), c->stream)); // all-zero between levels from here on
     HB_HIP(hipMemsetAsync(d.d_heavy_cnt, 0, 64 * sizeof(unsigned int), c->stream));
     d.ready = true;
@@ -87,18 +75,13 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
     const double t0 = now_ms();
     hb_distance_options o{};
     copy_in(opt_in, &o);
-    if (multi_rank(c)) return fail(c, HB_ERR_INVALID, "hb_distances: single rank only (world_size > 1)");
-    if (!c->loaded) return fail(c, HB_ERR_INVALID, "hb_distances: no graph loaded");
+    int rc;
+    if ((rc = walk_prologue(c, "hb_distances"))) return rc;
     if (!o.sources || !o.source_count) return fail(c, HB_ERR_INVALID, "hb_distances: no sources (source_count == 0)");
     if ((o.flags & HB_DIST_TOP_DOWN_ONLY) && (o.flags & HB_DIST_BOTTOM_UP_ONLY))
         return fail(c, HB_ERR_INVALID, "hb_distances: HB_DIST_TOP_DOWN_ONLY and HB_DIST_BOTTOM_UP_ONLY exclude each other");
     if ((o.flags & HB_DIST_WITH_MAX) && o.max_dist > 255) return fail(c, HB_ERR_INVALID, "hb_distances: max_dist > 255 (the reference's is a u8)");
     const Plan &p = c->plan;
-    int rc;
-    if ((rc = plan_rows_word_aligned(c, "hb_distances"))) return rc;
-    for (uint64_t b : p.level_begin)
-        if (b < p.n_pad || b > p.n_pad + p.nv) return fail(c, HB_ERR_INVALID, "hb_distances: unexpected plan layout (virtual level boundary)");
-    if ((rc = refuse_stale_error(c, "hb_distances"))) return rc;
     auto &d = c->dst;
     d.valid = d.extracted = false;
     d.reached = 0;
@@ -108,16 +91,8 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
         copy_out(st_out, st);
         return HB_OK;
     };
-    // the sources as distinct sids
     std::vector<uint32_t> sids;
-    sids.reserve(o.source_count);
-    for (uint64_t i = 0; i < o.source_count; i++) {
-        uint32_t sid;
-        if (find_sid(c, o.sources[i], &sid)) sids.push_back(sid);
-        else st.unknown_sources++;
-    }
-    std::sort(sids.begin(), sids.end());
-    sids.erase(std::unique(sids.begin(), sids.end()), sids.end());
+    resolve_sources(c, o.sources, o.source_count, &sids, &st.unknown_sources);
     if (p.n == 0) { // an empty graph: every source is unknown
         d.valid = true;
         return finish();
@@ -130,10 +105,10 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
     const uint64_t alpha = dist_env("HB_DIST_ALPHA", kDistAlpha), beta = dist_env("HB_DIST_BETA", kDistBeta);
 
     hbk::BfsParams bp{};
-    bp.push_ptr = reversed ? c->d_row_ptr : d.d_out_ptr;
-    bp.push_idx = reversed ? c->d_src : d.d_out_rows;
-    bp.pull_ptr = reversed ? d.d_out_ptr : c->d_row_ptr;
-    bp.pull_idx = reversed ? d.d_out_rows : c->d_src;
+    bp.push_ptr = reversed ? c->d_row_ptr : c->d_out_ptr;
+    bp.push_idx = reversed ? c->d_src : c->d_out_rows;
+    bp.pull_ptr = reversed ? c->d_out_ptr : c->d_row_ptr;
+    bp.pull_idx = reversed ? c->d_out_rows : c->d_src;
     bp.deg = reversed ? d.d_indeg : c->d_outdeg;
     bp.dist = d.d_dist;
     bp.vis = d.d_vis;
@@ -260,11 +235,7 @@ int distance_extract(hb_ctx *c)
     return HB_OK;
 }
 
-int distance_result_ready(hb_ctx *c, const char *who)
-{
-    if (!c->loaded || !c->dst.valid) return fail(c, HB_ERR_INVALID, std::string(who) + ": no distances (call hb_distances)");
-    return set_device(c);
-}
+const char *const kNoDistances = "no distances (call hb_distances)";
 
 } // namespace
 
@@ -276,8 +247,7 @@ int hb_distances(hb_ctx *c, const hb_distance_options *opt, hb_distance_stats *s
         if (!c) return HB_ERR_INVALID;
         int rc = set_device(c);
         if (rc) return rc;
-        // between hb_begin and hb_finish the pinned counter words (and the stream's event pair) belong to that run
-        if (c->begun && !c->finished) return fail(c, HB_ERR_INVALID, "hb_distances: a HyperBall run is in progress (hb_begin without hb_finish)");
+        if ((rc = run_in_progress(c, "hb_distances"))) return rc;
         return distances(c, opt, stats);
     });
 }
@@ -286,7 +256,7 @@ int hb_distance_count(hb_ctx *c, uint64_t *count)
 {
     return guarded(c, [&]() -> int {
         if (!c || !count) return c ? fail(c, HB_ERR_INVALID, "hb_distance_count: count == NULL") : HB_ERR_INVALID;
-        int rc = distance_result_ready(c, "hb_distance_count");
+        int rc = result_ready(c, c->dst.valid, "hb_distance_count", kNoDistances);
         if (rc) return rc;
         *count = c->dst.reached;
         return HB_OK;
@@ -297,19 +267,14 @@ int hb_distance_copy(hb_ctx *c, hb_u128 *ids, uint8_t *dist, uint64_t cap)
 {
     return guarded(c, [&]() -> int {
         if (!c) return HB_ERR_INVALID;
-        int rc = distance_result_ready(c, "hb_distance_copy");
+        int rc = result_ready(c, c->dst.valid, "hb_distance_copy", kNoDistances);
         if (rc) return rc;
         auto &d = c->dst;
         const uint64_t k = std::min<uint64_t>(cap, d.reached);
         if (!k || (!ids && !dist)) return HB_OK;
         if ((rc = distance_extract(c))) return rc;
-        // only the reached nodes come down: k sids (and k bytes); the ids are looked up in the host's sorted id array
-        if (ids) {
-            std::vector<uint32_t> sid(k);
-            HB_HIP(hipMemcpyAsync(sid.data(), d.d_sel_sid, k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HB_HIP(hipStreamSynchronize(c->stream));
-            for (uint64_t i = 0; i < k; i++) ids[i] = c->g.ids[sid[i]];
-        }
+        // only the reached nodes come down: k sids (and k bytes)
+        if (ids && (rc = copy_selected_ids(c, d.d_sel_sid, k, ids))) return rc;
         if (dist) {
             HB_HIP(hipMemcpyAsync(dist, d.d_sel_dist, k, hipMemcpyDeviceToHost, c->stream));
             HB_HIP(hipStreamSynchronize(c->stream));
@@ -322,7 +287,7 @@ int hb_distance_all(hb_ctx *c, uint8_t *dist, uint64_t cap)
 {
     return guarded(c, [&]() -> int {
         if (!c || !dist) return c ? fail(c, HB_ERR_INVALID, "hb_distance_all: dist == NULL") : HB_ERR_INVALID;
-        int rc = distance_result_ready(c, "hb_distance_all");
+        int rc = result_ready(c, c->dst.valid, "hb_distance_all", kNoDistances);
         if (rc) return rc;
         const uint64_t n = c->plan.n;
         if (cap < n) return fail(c, HB_ERR_INVALID, "hb_distance_all: cap < n");

@@ -465,7 +465,10 @@ int upload_tail_index(hb_ctx *c)
 // source is gathered (no test) - while most nodes still change the frontier test would only cost; bitmap (frontier): every index is read
 // and bit-tested, only active sources are gathered (pays while A_t < ~half of the edges); sweep (sparse): only the work rows that read a
 // changed node are visited at all - the convergence tail.  Every mode gives the same bits (SURVEY App. C-1).
-enum PassMode : uint32_t { kModeDense = 0, kModeBitmap = 1, kModeSweep = 2 }; // (hb_pass_stats::mode; hb_sample.hip.h kSample* are the same numbers)
+using hbk::PassMode; // (hb_walk.hip.h: one numbering for the passes, the walks' levels, their kernels and the statistics)
+using hbk::kModeDense;
+using hbk::kModeBitmap;
+using hbk::kModeSweep;
 // A_t < tune[2] % of the edges (default 50)
 bool below_dense_threshold(const hb_ctx *c, uint64_t active_edges)
 {
@@ -542,7 +545,7 @@ hbk::SweepParams make_sweep_params(const hb_ctx *c, const hbk::PassParams &pp, u
 }
 
 // Sweep mode, first step: the changed node rows -> touch bits of their readers.  `small` (few changed rows): one launch instead of
-// collect + expand + heavy.  Shared by sweep_pass and hb_sampled_harmonic; the caller checks hipGetLastError.
+// collect + expand + heavy.  Shared by sweep_pass and walk_forward_level (hb_api_walk.inc); the caller checks hipGetLastError.
 void launch_sweep_seeding(hb_ctx *c, const hbk::SweepParams &sp, bool small)
 {
     const unsigned sblocks = grid_blocks(c, sp.p.n_pad / 32 / 256, 4, 1);

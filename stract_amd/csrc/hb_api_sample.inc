@@ -87,34 +87,13 @@ int sample_alloc(hb_ctx *c, uint32_t levels)
     return HB_OK;
 }
 
-// launch shape of one level: a wave per 32-row word, grid-stride; XCD-affine groups for the first hub-chunk level (as hb_run's dense pass)
-void sample_launch(hb_ctx *c, hbk::SampleParams sp, bool real, int mode)
-{
-    const uint64_t words = (sp.row_hi - sp.row_lo + 31) / 32;
-    if (!words) return;
-    uint64_t blocks = std::min<uint64_t>((words + 3) / 4, (uint64_t)c->num_cu * 8);
-    if (sp.xcd_map) blocks = std::max<uint64_t>((blocks + 7) / 8 * 8, 8);
-    const dim3 grid((unsigned)blocks), blk(256);
-#define HB_SAMPLE_LAUNCH(R, M) hipLaunchKernelGGL((hbk::sample_level_kernel<R, M>), grid, blk, 0, c->stream, sp)
-    if (real) {
-        if (mode == hbk::kSampleDense) HB_SAMPLE_LAUNCH(true, hbk::kSampleDense);
-        else if (mode == hbk::kSampleBitmap) HB_SAMPLE_LAUNCH(true, hbk::kSampleBitmap);
-        else HB_SAMPLE_LAUNCH(true, hbk::kSampleSweep);
-    } else {
-        if (mode == hbk::kSampleDense) HB_SAMPLE_LAUNCH(false, hbk::kSampleDense);
-        else if (mode == hbk::kSampleBitmap) HB_SAMPLE_LAUNCH(false, hbk::kSampleBitmap);
-        else HB_SAMPLE_LAUNCH(false, hbk::kSampleSweep);
-    }
-#undef HB_SAMPLE_LAUNCH
-}
-
 int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats *st_out)
 {
     const double t0 = now_ms();
     hb_sample_options o{};
     copy_in(opt_in, &o);
-    if (multi_rank(c)) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: single rank only (world_size > 1)");
-    if (!c->loaded) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: no graph loaded");
+    int rc;
+    if ((rc = walk_prologue(c, "hb_sampled_harmonic", ""))) return rc;
     if (c->rs_stream) HB_HIP(hipStreamSynchronize(c->rs_stream)); // (no result snapshot of an earlier run may still be landing in h_out)
     c->rs.valid = false;
     const uint32_t max_dist = o.max_dist ? o.max_dist : 7; // approx_harmonic.rs:62
@@ -126,21 +105,13 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
     if (o.sources && !o.source_count) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: sources given with source_count == 0");
     const uint64_t k_req = o.samples ? o.samples : (o.sources ? o.source_count : sample_count_formula(N, eps));
     if (k_req > 65535 || (o.sources && o.source_count > 65535)) return fail(c, HB_ERR_LIMIT, "hb_sampled_harmonic: more than 65535 sources");
-    if (p.level_begin.size() && p.level_begin.back() > p.n_pad + p.nv) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: unexpected plan layout");
-    int rc;
-    if ((rc = plan_rows_word_aligned(c, "hb_sampled_harmonic"))) return rc;
-    if ((rc = refuse_stale_error(c, "hb_sampled_harmonic"))) return rc;
     // the sources, as ascending sids
     std::vector<uint32_t> sids;
     if (o.sources) {
-        sids.reserve(o.source_count);
-        for (uint64_t i = 0; i < o.source_count; i++) {
-            uint32_t sid;
-            if (!find_sid(c, o.sources[i], &sid)) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: source " + std::to_string(i) + " is not a node of the graph");
-            sids.push_back(sid);
-        }
-        std::sort(sids.begin(), sids.end());
-        if (std::adjacent_find(sids.begin(), sids.end()) != sids.end()) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: duplicate sources");
+        uint64_t unknown = 0, first_unknown = 0;
+        resolve_sources(c, o.sources, o.source_count, &sids, &unknown, &first_unknown);
+        if (unknown) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: source " + std::to_string(first_unknown) + " is not a node of the graph");
+        if (sids.size() != o.source_count) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: duplicate sources");
     } else if ((rc = sample_sids(c, o.seed, k_req, &sids))) {
         return rc;
     }
@@ -150,11 +121,9 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
     for (uint32_t d = 1; d <= D; d++) w[d - 1] = (double)((1.0f / (float)d) * norm);
     if ((rc = sample_alloc(c, D))) return rc;
     auto &sm = c->smp;
-    const uint64_t n_pad = p.n_pad, rows_total = p.n_pad + p.nv;
+    const uint64_t n_pad = p.n_pad;
     HB_HIP(hipMemsetAsync(sm.d_hist.get(), 0, std::max<uint64_t>((uint64_t)D * n_pad, 64) * sizeof(uint16_t), c->stream));
     HB_HIP(hipMemcpyAsync(sm.d_w.get(), w, sizeof(w), hipMemcpyHostToDevice, c->stream));
-    const bool xcd_ok = p.xcd_groups == 8 && p.level_begin.size() > 1 && p.xcd_begin[0] == p.level_begin[0] && p.xcd_begin[8] == p.level_begin[1] &&
-                        std::all_of(p.xcd_begin, p.xcd_begin + 9, [](uint64_t b) { return b % 32 == 0; });
     hb_sample_stats st{};
     st.levels = D;
     st.k_req = k_req;
@@ -180,64 +149,26 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
         HB_HIP(hipMemcpyAsync(h, sm.d_cnt.get(), 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         HB_HIP(hipStreamSynchronize(c->stream));
         uint64_t last_changed = h[0], last_active = h[1];
+        hbk::SampleParams sp{};
+        fill_walk_params(c, &sp);
+        sp.part = c->d_part;
         int cur = 0;
         for (uint32_t d = 1; d <= D && last_changed; d++) {
             // dense / bitmap / sweep as in hb_run (pass_mode): the A_t rule on the out-degree sum of the rows changed at d - 1
-            static_assert(hbk::kSampleDense == kModeDense && hbk::kSampleBitmap == kModeBitmap && hbk::kSampleSweep == kModeSweep, "one numbering of the modes");
-            const int mode = (int)pass_mode(c, last_active);
-            const bool sweep = mode == hbk::kSampleSweep;
-            hbk::SampleParams sp{};
-            sp.row_ptr = c->d_row_ptr;
-            sp.src = c->d_src;
+            const PassMode mode = pass_mode(c, last_active);
             sp.rd = c->d_regs[cur];
             sp.wr = c->d_regs[cur ^ 1];
-            sp.part = c->d_part;
             sp.bits_rd = c->d_bits[cur];
             sp.bits_wr = c->d_bits[cur ^ 1];
-            sp.touch = c->d_touch;
-            sp.out_ptr = c->d_out_ptr;
-            sp.out_rows = c->d_out_rows;
-            sp.outdeg = c->d_outdeg;
             sp.hist = sm.d_hist.get() + (uint64_t)(d - 1) * n_pad;
             sp.cnt = sm.d_cnt.get() + 4 * d;
-            sp.n_pad = n_pad;
-            sp.rows_total = rows_total;
-            HB_HIP(hipEventRecord(c->ev[kEvStart], c->stream));
-            if (sweep) {
-                // the rows changed at d - 1 -> touch bits of their readers: hb_run's seed / expand kernels, unchanged (launch_sweep_seeding)
-                hbk::PassParams seed_pp{}; // (all the seeding kernels read of it)
-                seed_pp.bits_rd = c->d_bits[cur];
-                seed_pp.n_pad = n_pad;
-                seed_pp.rows_total = rows_total;
-                HB_HIP(hipMemsetAsync(c->d_sparse_counts, 0, 4 * sizeof(unsigned int), c->stream));
-                launch_sweep_seeding(c, make_sweep_params(c, seed_pp, 0, nullptr), last_changed <= 4096);
-                HB_HIP(hipGetLastError());
-            }
-            for (size_t l = 0; l + 1 < p.level_begin.size(); l++) { // virtual levels: partials of level d from the rows of level d - 1
-                sp.row_lo = p.level_begin[l];
-                sp.row_hi = p.level_begin[l + 1];
-                sp.xcd_map = (l == 0 && xcd_ok && mode == hbk::kSampleDense) ? 1 : 0;
-                for (int x = 0; x < 8; x++) {
-                    sp.xcd_lo[x] = p.xcd_begin[x];
-                    sp.xcd_hi[x] = p.xcd_begin[x + 1];
-                }
-                sample_launch(c, sp, false, mode);
-            }
-            sp.xcd_map = 0;
-            sp.row_lo = 0;
-            sp.row_hi = n_pad;
-            sample_launch(c, sp, true, mode);
-            HB_HIP(hipGetLastError());
-            HB_HIP(hipEventRecord(c->ev[kEvEnd], c->stream));
-            HB_HIP(hipMemcpyAsync(h, sp.cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-            HB_HIP(hipStreamSynchronize(c->stream));
-            float ms = 0.f;
-            HB_HIP(hipEventElapsedTime(&ms, c->ev[kEvStart], c->ev[kEvEnd]));
-            st.level_changed[d - 1] += h[0];
+            WalkLevel lv{};
+            if ((rc = walk_forward_level(c, sp, mode, last_changed, [&](bool real) { launch_walk<SampleWalk>(c, sp, real, mode); }, &lv))) return rc;
+            st.level_changed[d - 1] += lv.cnt[0];
             st.level_modes[d - 1] |= 1u << mode;
-            st.level_ms[d - 1] += ms;
-            last_changed = h[0]; // no node row grew: nothing can change at d + 1 either (the batch has converged)
-            last_active = h[1];
+            st.level_ms[d - 1] += lv.ms;
+            last_changed = lv.cnt[0]; // no node row grew: nothing can change at d + 1 either (the batch has converged)
+            last_active = lv.cnt[1];
             cur ^= 1;
         }
     }
@@ -275,8 +206,7 @@ int hb_sampled_harmonic(hb_ctx *c, const hb_sample_options *opt, hb_sample_stats
         if (!c) return HB_ERR_INVALID;
         int rc = set_device(c);
         if (rc) return rc;
-        // between hb_begin and hb_finish the HyperBall state (and a result snapshot on its way to h_out) belongs to that run
-        if (c->begun && !c->finished) return fail(c, HB_ERR_INVALID, "hb_sampled_harmonic: a HyperBall run is in progress (hb_begin without hb_finish)");
+        if ((rc = run_in_progress(c, "hb_sampled_harmonic"))) return rc;
         c->finished = false; // (a refusal leaves no result behind)
         c->smp.levels = 0;
         return sampled_harmonic(c, opt, stats);

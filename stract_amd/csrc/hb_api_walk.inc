@@ -1,0 +1,188 @@
+// hb_api_walk.inc - part of the hb_api.hip translation unit (included before the operator files; uses its hb_ctx and helpers).
+// What hb_sampled_harmonic, hb_distances and hb_betweenness share on the host: their refusals, the sources as sids, the row -> readers
+// transpose, the download of a compacted result - and, for the two operators that walk 64-byte rows (device side: hb_walk.hip.h), the
+// launcher and one forward level.
+
+namespace {
+
+// ---- the three operators ---------------------------------------------------------------------------------------------------------------
+// between hb_begin and hb_finish the HyperBall state, the pinned counter words, the stream's event pair and a result snapshot on its way
+// to h_out belong to that run
+int run_in_progress(hb_ctx *c, const char *who)
+{
+    if (c->begun && !c->finished) return fail(c, HB_ERR_INVALID, std::string(who) + ": a HyperBall run is in progress (hb_begin without hb_finish)");
+    return HB_OK;
+}
+
+// what every operator refuses before it looks at its options: more than one rank, no graph, a plan whose node rows or virtual levels do
+// not begin on a 32-row word or lie outside [n_pad, n_pad + nv] (the planner produces neither), an unchecked HIP error of an earlier call
+int walk_prologue(hb_ctx *c, const char *who, const char *boundary_note = " (virtual level boundary)")
+{
+    if (multi_rank(c)) return fail(c, HB_ERR_INVALID, std::string(who) + ": single rank only (world_size > 1)");
+    if (!c->loaded) return fail(c, HB_ERR_INVALID, std::string(who) + ": no graph loaded");
+    const Plan &p = c->plan;
+    int rc;
+    if ((rc = plan_rows_word_aligned(c, who))) return rc;
+    for (uint64_t b : p.level_begin)
+        if (b < p.n_pad || b > p.n_pad + p.nv) return fail(c, HB_ERR_INVALID, std::string(who) + ": unexpected plan layout" + boundary_note);
+    return refuse_stale_error(c, who);
+}
+
+// NodeIDs -> the distinct sids among them, ascending; *unknown = ids that are no node of the graph, *first_unknown = the first such index
+void resolve_sources(const hb_ctx *c, const hb_u128 *ids, uint64_t count, std::vector<uint32_t> *sids, uint64_t *unknown, uint64_t *first_unknown = nullptr)
+{
+    sids->clear();
+    sids->reserve(count);
+    *unknown = 0;
+    for (uint64_t i = 0; i < count; i++) {
+        uint32_t sid;
+        if (find_sid(c, ids[i], &sid)) sids->push_back(sid);
+        else if (!(*unknown)++ && first_unknown) *first_unknown = i;
+    }
+    std::sort(sids->begin(), sids->end());
+    sids->erase(std::unique(sids->begin(), sids->end()), sids->end());
+}
+
+// The row -> readers transpose of the plan (GraphDeviceState::d_out_ptr / d_out_rows): the sweep passes' when the context has sweep
+// support (sparse_ok); else (HB_FLAG_NO_SPARSE, unfused passes) built here at the first call of hb_distances / hb_betweenness after a
+// load, and counted in that call's device bytes.  The pointers are set only once the transpose is complete; sparse_ok, not they, says
+// whether the sweep support exists.
+int ensure_transpose(hb_ctx *c, const char *who)
+{
+    if (c->d_out_ptr) return HB_OK;
+    const uint64_t rows_total = c->plan.n_pad + c->plan.nv;
+    uint64_t *op = nullptr;
+    uint32_t *orow = nullptr;
+    int rc;
+    if ((rc = dev_alloc(c, &op, rows_total + 1))) return rc;
+    if ((rc = dev_alloc(c, &orow, c->plan_entries))) return rc;
+    const std::string e = gpu_transpose_rows((void *)c->stream, c->d_row_ptr, c->d_src, rows_total, c->plan_entries, op, orow);
+    if (!e.empty()) return fail(c, e.find("out of memory") != std::string::npos ? HB_ERR_NOMEM : HB_ERR_HIP, std::string(who) + ": " + e);
+    c->d_out_ptr = op;
+    c->d_out_rows = orow;
+    return HB_OK;
+}
+
+// a result is there to be read: `missing` = what to say when it is not
+int result_ready(hb_ctx *c, bool valid, const char *who, const char *missing)
+{
+    if (!c->loaded || !valid) return fail(c, HB_ERR_INVALID, std::string(who) + ": " + missing);
+    return set_device(c);
+}
+
+// the ids of a compacted result: only its k sids come down, the ids are looked up in the host's sorted id array
+int copy_selected_ids(hb_ctx *c, const uint32_t *d_sel_sid, uint64_t k, hb_u128 *ids)
+{
+    std::vector<uint32_t> sid(k);
+    HB_HIP(hipMemcpyAsync(sid.data(), d_sel_sid, k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HB_HIP(hipStreamSynchronize(c->stream));
+    for (uint64_t i = 0; i < k; i++) ids[i] = c->g.ids[sid[i]];
+    return HB_OK;
+}
+
+// ---- the walks over 64-byte rows (hb_walk.hip.h) -------------------------------------------------------------------------------------
+// A kernel family: its parameter struct and its six instances.  walk_kernel is the only place that names one.
+struct SampleWalk {
+    using Params = hbk::SampleParams;
+    template <bool REAL, int MODE>
+    static constexpr void (*kernel)(const Params) = hbk::sample_level_kernel<REAL, MODE>;
+};
+struct BrandesWalk {
+    using Params = hbk::BcParams;
+    template <bool REAL, int MODE>
+    static constexpr void (*kernel)(const Params) = hbk::bc_forward_kernel<REAL, MODE>;
+};
+
+template <class W, bool REAL>
+auto walk_kernel_of(hbk::PassMode mode) -> void (*)(const typename W::Params)
+{
+    if (mode == hbk::kModeDense) return W::template kernel<REAL, hbk::kModeDense>;
+    if (mode == hbk::kModeBitmap) return W::template kernel<REAL, hbk::kModeBitmap>;
+    return W::template kernel<REAL, hbk::kModeSweep>;
+}
+template <class W>
+auto walk_kernel(bool real, hbk::PassMode mode) -> void (*)(const typename W::Params)
+{
+    return real ? walk_kernel_of<W, true>(mode) : walk_kernel_of<W, false>(mode);
+}
+
+// launch shape of one level: a wave per 32-row word, grid-stride; XCD-affine groups for the first hub-chunk level (as hb_run's dense pass)
+template <class W>
+void launch_walk(hb_ctx *c, const typename W::Params &wp, bool real, hbk::PassMode mode)
+{
+    const uint64_t words = (wp.row_hi - wp.row_lo + 31) / 32;
+    if (!words) return;
+    uint64_t blocks = std::min<uint64_t>((words + 3) / 4, (uint64_t)c->num_cu * 8);
+    if (wp.xcd_map) blocks = std::max<uint64_t>((blocks + 7) / 8 * 8, 8);
+    hipLaunchKernelGGL(walk_kernel<W>(real, mode), dim3((unsigned)blocks), dim3(256), 0, c->stream, wp);
+}
+
+// the first hub-chunk level may run as eight XCD-affine groups: the planner cut it into eight word-aligned groups
+bool walk_xcd_ok(const Plan &p)
+{
+    return p.xcd_groups == 8 && p.level_begin.size() > 1 && p.xcd_begin[0] == p.level_begin[0] && p.xcd_begin[8] == p.level_begin[1] &&
+           std::all_of(p.xcd_begin, p.xcd_begin + 9, [](uint64_t b) { return b % 32 == 0; });
+}
+
+// what a walk's parameters say about the loaded graph (the rest - buffers, bitmaps, counters, rows - changes per level)
+void fill_walk_params(const hb_ctx *c, hbk::WalkParams *wp)
+{
+    const Plan &p = c->plan;
+    wp->row_ptr = c->d_row_ptr;
+    wp->src = c->d_src;
+    wp->touch = c->d_touch;
+    wp->out_ptr = c->d_out_ptr;
+    wp->out_rows = c->d_out_rows;
+    wp->outdeg = c->d_outdeg;
+    wp->n_pad = p.n_pad;
+    wp->rows_total = p.n_pad + p.nv;
+    for (int x = 0; x < 8; x++) {
+        wp->xcd_lo[x] = p.xcd_begin[x];
+        wp->xcd_hi[x] = p.xcd_begin[x + 1];
+    }
+}
+
+struct WalkLevel {
+    unsigned long long cnt[4]; // the level's counters (WalkParams::cnt)
+    float ms;
+};
+
+// One forward level d of a walk, timed: `wp` (the WalkParams of the parameters `launch(real)` launches with) holds this level's bits_rd /
+// bits_wr / cnt; last_changed = node rows whose bit was set at d - 1.  Sweep: those rows -> touch bits of their readers first (hb_run's
+// seed / expand kernels, unchanged).  Then the virtual levels - partials of level d from the rows of level d - 1 -, then the node rows.
+template <class LAUNCH>
+int walk_forward_level(hb_ctx *c, hbk::WalkParams &wp, hbk::PassMode mode, uint64_t last_changed, LAUNCH launch, WalkLevel *out)
+{
+    const Plan &p = c->plan;
+    HB_HIP(hipEventRecord(c->ev[kEvStart], c->stream));
+    if (mode == hbk::kModeSweep) {
+        hbk::PassParams seed_pp{}; // (all the seeding kernels read of it)
+        seed_pp.bits_rd = wp.bits_rd;
+        seed_pp.n_pad = wp.n_pad;
+        seed_pp.rows_total = wp.rows_total;
+        HB_HIP(hipMemsetAsync(c->d_sparse_counts, 0, 4 * sizeof(unsigned int), c->stream));
+        launch_sweep_seeding(c, make_sweep_params(c, seed_pp, 0, nullptr), last_changed <= 4096);
+        HB_HIP(hipGetLastError());
+    }
+    const bool xcd = mode == hbk::kModeDense && walk_xcd_ok(p);
+    for (size_t l = 0; l + 1 < p.level_begin.size(); l++) {
+        wp.row_lo = p.level_begin[l];
+        wp.row_hi = p.level_begin[l + 1];
+        wp.xcd_map = (l == 0 && xcd) ? 1 : 0;
+        launch(false);
+    }
+    wp.xcd_map = 0;
+    wp.row_lo = 0;
+    wp.row_hi = p.n_pad;
+    launch(true);
+    HB_HIP(hipGetLastError());
+    HB_HIP(hipEventRecord(c->ev[kEvEnd], c->stream));
+    unsigned long long *h = c->h_counters; // (pinned words of the context; hb_run rewrites them before it reads them)
+    HB_HIP(hipMemcpyAsync(h, wp.cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HB_HIP(hipStreamSynchronize(c->stream));
+    HB_HIP(hipEventElapsedTime(&out->ms, c->ev[kEvStart], c->ev[kEvEnd]));
+    std::copy(h, h + 4, out->cnt);
+    return HB_OK;
+}
+
+} // namespace

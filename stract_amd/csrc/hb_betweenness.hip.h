@@ -1,20 +1,19 @@
 // hb_betweenness.hip.h - device code of hb_betweenness (Betweenness::calculate, crates/core/src/webgraph/centrality/betweenness.rs:29-146):
 // Brandes' algorithm for eight sources at once over the HyperBall device plan.  Part of the hb_api.hip translation unit (included after
-// hb_bfs.hip.h; uses the plan layout, the quad helpers of hb_regs.hip.h, touch_set of hb_sweep.hip.h and wave_add_counters / kBfsHeavy of
-// its siblings).  Driver: hb_api_betweenness.inc.  Definitions: include/hyperball.h.
+// hb_bfs.hip.h; the forward half is a walk of hb_walk.hip.h, the backward half uses the plan layout, the quad helpers of hb_regs.hip.h and
+// kBfsHeavy).  Driver: hb_api_betweenness.inc.  Definitions: include/hyperball.h.
 //
 // A row of 64 bytes holds one value per source of the batch: eight u64 path counts going forward, eight f64 coefficients going back.
 // Quad per row; lane q of the quad owns bytes 16 q .. 16 q + 15 of every row = the sources 2 q and 2 q + 1 of the batch.
 //
-// Forward level d is a HyperBall-shaped pass with a saturating add as the join.  F_{d-1} holds, per row and source, sigma where
+// Forward level d is a level of hb_walk.hip.h with a saturating add as the join.  F_{d-1} holds, per row and source, sigma where
 // dist == d - 1 and 0 elsewhere; A[w] = sum of F_{d-1} over in(w), through the chunk trees (virtual rows level by level, their partials
 // rebuilt from zero); a source that has no distance for w yet and A > 0 gets dist = d, sigma = A, F_d = A.  A row's changed bit at d =
 // "its F_d row is non-zero".  F is NOT cumulative, so the double buffer needs more care than the sampled walk's: the buffer written at
 // level d still holds F_{d-2}, and every row whose bit is set in the bitmap word being overwritten is rewritten (zeroed unless it is
 // non-zero again).  By induction a buffer holds exactly F of its level in EVERY row, which is what the dense mode (no bit test) reads.
-// Modes as in hb_sample.hip.h: dense; bitmap (every row visited, only sources with a set bit gathered); sweep (only rows a changed row
-// reaches are visited).  Stale partials of rows a sweep level did not visit are never read: their bit is clear and the non-dense modes
-// test it, a dense level rebuilds every partial first.
+// Stale partials of rows a sweep level did not visit are never read: their bit is clear and the non-dense modes test it, a dense level
+// rebuilds every partial first.
 //
 // Backward level d (d = L + 1 .. 1) is a pull over the row -> readers transpose.  C_d holds, per node row and source, (1 + delta) /
 // sigma where dist == d and 0 elsewhere, copied down the chunk trees (a chunk row carries the coefficient of the rows that read it), with
@@ -30,7 +29,6 @@ namespace hbk {
 constexpr uint32_t kBcLanes = 8;       // sources per batch: the u64 / f64 values of one 64-byte row
 constexpr uint64_t kBcWaveList = 256;  // backward: a longer reader list is summed by the whole wave, a shorter one by its quad
 constexpr uint64_t kBcSegment = kBfsHeavy; // backward: a reader list longer than this is summed by the grid, one wave per segment
-constexpr int kBcDense = 0, kBcBitmap = 1, kBcSweep = 2;
 
 struct alignas(16) bc_u2 {
     unsigned long long a, b;
@@ -39,27 +37,14 @@ struct alignas(16) bc_d2 {
     double a, b;
 };
 
-struct BcParams {
-    const uint64_t *row_ptr;
-    const uint32_t *src;
+struct BcParams : WalkParams { // a row's bit = "its F row is non-zero"; cnt[2] = entries gathered, cnt[3] = saturated sigmas
     const bc_u2 *rd;          // node rows: F of level d - 1
-    bc_u2 *wr;                // node rows: F of level d (holds F of level d - 2 on entry)
+    bc_u2 *wr;                // node rows: F of level d (holds F of level d - 2 on entry, and bits_wr the bits of level d - 2)
     bc_u2 *part;              // virtual rows, indexed by vid - n_pad
-    uint32_t *bits_rd;        // non-zero bits: node rows = level d - 1, virtual rows = level d (written by this level's launches)
-    uint32_t *bits_wr;        // node rows: level d - 2 on entry, level d on exit
-    uint32_t *touch;          // sweep: one bit per work row
-    const uint64_t *out_ptr;  // sweep: readers of every work row
-    const uint32_t *out_rows;
-    const uint32_t *outdeg;   // per node row: out-degree
     uint8_t *dist;            // n_pad x 8: distance per row and source, 255 = none
     unsigned long long *sigma; // n_pad x 8
     uint8_t *reached;         // n_pad: the row is a result (a source, or reached from one, in any batch)
-    unsigned long long *cnt;  // this level: [0] node rows with a new distance, [1] their out-degree sum, [2] entries gathered, [3] saturated sigmas
-    uint64_t n_pad, rows_total;
-    uint64_t row_lo, row_hi;  // rows of this launch (row_lo a multiple of 32)
     uint32_t level;
-    int xcd_map;              // as SampleParams::xcd_map
-    uint64_t xcd_lo[8], xcd_hi[8];
 };
 
 __device__ __forceinline__ unsigned long long bc_sat_add(unsigned long long a, unsigned long long b)
@@ -95,10 +80,9 @@ __global__ __launch_bounds__(64) void bc_seed_kernel(const uint32_t *sids, uint3
     wave_add_counters(p.cnt, one, od, 0ull);
 }
 
-// One forward level over the rows [row_lo, row_hi) of one kind.  A wave owns one 32-row word of the bitmaps per iteration (two rounds of
-// 16 rows, a quad per row) and writes that word whole.
+// One forward level over the rows [row_lo, row_hi) of one kind.
 //   !REAL: virtual rows: partial = sum of the sources (dense: all of them; else those with a set bit); sweep: a non-zero partial
-//          touches its readers (higher levels / node rows of this level).
+//          touches its readers.
 //   REAL:  node rows: A = sum; sources without a distance and A > 0 get one.  The row of `wr` is stored when it is non-zero now or was
 //          at level d - 2 (the bit of the word being overwritten).
 template <bool REAL, int MODE>
@@ -106,75 +90,27 @@ __global__ __launch_bounds__(256) void bc_forward_kernel(const BcParams p)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 2, q = lane & 3, qshift = lane & ~3;
-    uint64_t row_lo = p.row_lo, row_hi = p.row_hi;
-    uint64_t wid = (uint64_t)blockIdx.x * 4 + wave, wstride = (uint64_t)gridDim.x * 4;
-    if (!REAL && p.xcd_map) {
-        const int x = blockIdx.x & 7;
-        row_lo = p.xcd_lo[x];
-        row_hi = p.xcd_hi[x];
-        wid = (uint64_t)(blockIdx.x >> 3) * 4 + wave;
-        wstride = (uint64_t)(gridDim.x >> 3) * 4; // the grid is a multiple of 8
-    }
-    const uint64_t w_lo = row_lo >> 5, nwords = (row_hi - row_lo + 31) >> 5;
-    const bc_u2 *vbase = p.part - p.n_pad * 4;
+    const WalkSpan sp = walk_span<REAL>(p, wave);
+    const bc_u2 *vbase = walk_virtual_base<bc_u2>(p.part, p.n_pad);
     unsigned long long c_changed = 0, c_out = 0, c_gath = 0, c_sat = 0;
-    for (uint64_t wi = wid; wi < nwords; wi += wstride) { // wave-uniform trip count
-        const uint64_t w = w_lo + wi;
-        uint32_t tw = 0xFFFFFFFFu;
-        if (MODE == kBcSweep) {
-            tw = __shfl(p.touch[w], 0);
-            if (lane == 0 && tw) p.touch[w] = 0; // consumed: the touch bitmap is all-zero again after the level
-        }
+    const auto sat_add = [](bc_u2 a, bc_u2 b) { return bc_u2{bc_sat_add(a.a, b.a), bc_sat_add(a.b, b.b)}; };
+    for (uint64_t wi = sp.wid; wi < sp.nwords; wi += sp.wstride) { // wave-uniform trip count
+        const uint64_t w = sp.w_lo + wi;
+        const uint32_t tw = walk_take_touch<MODE>(p, w, lane);
         const uint32_t ow = REAL ? p.bits_wr[w] : 0u; // node rows whose `wr` image is a non-zero F of level d - 2
-        if (MODE == kBcSweep && tw == 0 && ow == 0) { // nothing to visit or to zero in this word (a node word of bits_wr is zero already)
-            if (!REAL && lane == 0) p.bits_rd[w] = 0u;
+        if (MODE == kModeSweep && tw == 0 && ow == 0) { // nothing to visit or to zero in this word (a node word of bits_wr is zero already)
+            if (!REAL) walk_store_bits<false>(p, w, 0u, lane);
             continue;
         }
         uint32_t chw = 0;
         for (int h = 0; h < 2; h++) {
             const uint32_t bit = (uint32_t)(h * 16 + g);
             const uint64_t row = (w << 5) + bit;
-            const bool valid = row < row_hi;
+            const bool valid = row < sp.row_hi;
             const bool active = valid && ((tw >> bit) & 1u);
-            bc_u2 acc = {0ull, 0ull};
-            uint64_t beg = 0, end = 0;
-            if (active) {
-                beg = p.row_ptr[row];
-                end = p.row_ptr[row + 1];
-            }
-            for (uint64_t e = beg; e < end; e += 8) { // quad-uniform trip count: 8 gathers in flight per quad
-                uint32_t i0 = (e + q < end) ? p.src[e + q] : kNone;
-                uint32_t i1 = (e + 4 + q < end) ? p.src[e + 4 + q] : kNone;
-                if (MODE != kBcDense) { // only sources with a non-zero row (node rows: at d - 1; virtual rows: at this level)
-                    if (i0 != kNone && !((p.bits_rd[i0 >> 5] >> (i0 & 31u)) & 1u)) i0 = kNone;
-                    if (i1 != kNone && !((p.bits_rd[i1 >> 5] >> (i1 & 31u)) & 1u)) i1 = kNone;
-                }
-                uint32_t s[8];
-                s[0] = quad_bcast<0>(i0);
-                s[1] = quad_bcast<1>(i0);
-                s[2] = quad_bcast<2>(i0);
-                s[3] = quad_bcast<3>(i0);
-                s[4] = quad_bcast<0>(i1);
-                s[5] = quad_bcast<1>(i1);
-                s[6] = quad_bcast<2>(i1);
-                s[7] = quad_bcast<3>(i1);
-                bc_u2 r[8];
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    r[j].a = 0ull;
-                    r[j].b = 0ull;
-                    if (s[j] != kNone) {
-                        HB_DBG_ASSERT(s[j] < p.rows_total);
-                        r[j] = (s[j] < p.n_pad) ? p.rd[(uint64_t)s[j] * 4 + q] : vbase[(uint64_t)s[j] * 4 + q];
-                        if (q == 0) c_gath++;
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    acc.a = bc_sat_add(acc.a, r[j].a);
-                    acc.b = bc_sat_add(acc.b, r[j].b);
-                }
-            }
+            const bc_u2 acc = walk_gather<MODE>(p, p.rd, vbase, row, active, q, bc_u2{0ull, 0ull}, sat_add, [&] {
+                if (q == 0) c_gath++;
+            });
             if (REAL) {
                 bc_u2 f = {0ull, 0ull};
                 if (active && (acc.a | acc.b) != 0ull) { // one writer per byte / word: this lane owns the two sources of this row
@@ -205,18 +141,12 @@ __global__ __launch_bounds__(256) void bc_forward_kernel(const BcParams p)
             } else {
                 const uint64_t bal = __ballot(active && (acc.a | acc.b) != 0ull);
                 const bool changed = ((bal >> qshift) & 0xFull) != 0;
-                if (active && (MODE == kBcDense || changed)) p.part[(row - p.n_pad) * 4 + q] = acc;
-                if (MODE == kBcSweep && changed) {
-                    const uint64_t kb = p.out_ptr[row], ke = p.out_ptr[row + 1];
-                    for (uint64_t k = kb + q; k < ke; k += 4) touch_set(p.touch, p.out_rows[k], p.rows_total);
-                }
+                if (active && (MODE == kModeDense || changed)) p.part[(row - p.n_pad) * 4 + q] = acc;
+                if (MODE == kModeSweep && changed) walk_touch_readers(p, row, q);
                 chw |= pack16(bal) << (16 * h);
             }
         }
-        if (lane == 0) {
-            if (REAL) p.bits_wr[w] = chw;
-            else p.bits_rd[w] = chw; // (dense levels: nobody reads these, written anyway)
-        }
+        walk_store_bits<REAL>(p, w, chw, lane);
     }
     bc_add_counters(p.cnt, c_changed, c_out, c_gath, c_sat);
 }

@@ -110,12 +110,16 @@ def test_layout_variants(gpu_ctx_factory, variant):
              "host_plan": _lib.HB_FLAG_HOST_PLAN, "host_ingest": _lib.HB_FLAG_HOST_INGEST}[variant]
     tuples = graphs.lcg_graph(n=400, m=3000, seed=3) + [(1, v) for v in range(2, 300)] + [(v, 7) for v in range(8, 350)]  # hubs both ways
     g = EdgeListGraph.from_tuples(tuples)
-    hists = []
+    hists, modes = [], []
     for flags, chunk in ((_lib.HB_FLAG_ALL_RELS, 0), (_lib.HB_FLAG_ALL_RELS | extra, 4 if variant == "chunk4" else 0)):
         with _ctx(gpu_ctx_factory, g, flags=flags, chunk=chunk) as ctx:
-            _check(ctx, samples=40, seed=9, tol_check=False)
+            st, _ = _check(ctx, samples=40, seed=9, tol_check=False)
             hists.append(ctx.sample_histogram())
+            modes.append(int(np.bitwise_or.reduce(np.asarray(st["level_modes"], dtype=np.int64))))
     assert np.array_equal(hists[0], hists[1])
+    # the default-flags context has sweep support: on this graph the A_t rule takes the 40 walks through a sweep level (1), dense levels
+    # (2-5) and a bitmap level (6), so all six instances of the level kernel have produced the restatement's histogram
+    assert modes[0] == 0b111
 
 
 # (e) the sampler
