@@ -453,6 +453,74 @@ int hb_betweenness_all(hb_ctx *ctx, double *vals, uint64_t cap);
  * lane; lanes beyond the batch's sources: 255 / 0 / +0.0); any of the three may be NULL. */
 int hb_debug_copy_betweenness_batch(hb_ctx *ctx, uint8_t *dist, uint64_t *sigma, double *delta);
 
+/* ---- inbound similarity: Scorer (ranking/inbound_similarity.rs:61-138) over BitVec (ranking/bitvec_similarity.rs:131-189) ---------- */
+/* The score of EVERY node of the loaded graph against a list of liked and a list of disliked hosts (searcher/api/mod.rs:199-216,
+ * similar_hosts.rs).  in(v) = the in-neighbours of v in the loaded graph.
+ * BitVec of a node (bitvec_similarity.rs:144-163): len = |in(v)|, sqrt_len = sqrt(len as f64), and a bloom of 16 u64 words in which the
+ * low id word x of every in-neighbour sets bit (x * 11400714819323198549 mod 2^64) % 64 of word (the same product) % 16; ones = bits set.
+ * Both indices come from one product and 16 divides 64, so the bloom is kept as ONE u64 mask (bit h & 63): same ones, same intersections.
+ * sim(a, v) (:165-180) = 0.0 if either len is 0; 0.0 if popcount(bloom_a & bloom_v) / max(ones_a, ones_v) < 0.25 (tested as
+ * 4 * intersect_ones < max_ones in integers: the quotient of two integers <= 1024 is never within an ulp of 0.25); else
+ * |in(a) & in(v)| as f64 / (sqrt_len_a * sqrt_len_v) - one multiply, one division, no FMA contraction.
+ * score(v) (Scorer::calculate_score, inbound_similarity.rs:99-118) = max(0.0, s) with s = D + (sum_liked - sum_disliked), divided by
+ * max(L, 1) with HB_SIM_NORMALIZED; L / D = the number of liked / disliked entries; both sums run in entry order from +0.0; an entry
+ * whose id is v contributes self_score (1.0 unless HB_SIM_SELF_SCORE) instead of sim.  Duplicate entries each count.  An entry that is
+ * no node of the graph has an empty BitVec: its sim is 0, it counts in L or D (and in hb_similarity_stats.unknown).
+ * Defined differences: in(v) is the WHOLE in-list of the loaded graph - unique edges, self links as loaded, the relation filter of the
+ * load (HB_SKIPPED_REL_MASK drops NOFOLLOW among others; HB_FLAG_ALL_RELS keeps everything).  The reference takes
+ * EdgeLimit::Limit(512) backlinks in search order before it filters, which nothing can reproduce: the two agree wherever every host
+ * involved has at most 512 inbound records.
+ * Entry 16 b + j (liked entries first, then the disliked ones, in caller order) is slot j of batch b; a batch is one level of the walk
+ * the other operators share (hb_sampled_harmonic, hb_betweenness) with sixteen u32 counts per 64-byte row and a plain add as the join.
+ * Single rank only.  The call borrows the HyperBall state as those walks do: hb_step needs a new hb_begin afterwards, a later hb_run
+ * computes what it computed before, the results of hb_run / hb_distances / hb_betweenness stay readable.  The per-graph state (one
+ * position byte, one in-degree and one u64 bloom per row) is built at the first call after a load and freed by the next load; the
+ * scores live in buffers of their own until the next hb_inbound_similarity or the next load.  Refused (HB_ERR_INVALID) between hb_begin
+ * and hb_finish, without a loaded graph, with world_size > 1, with both debug flags set and with no entry at all.  DESIGN.md section 16. */
+#define HB_SIM_NORMALIZED   0x1u  /* Scorer::new(.., normalized = true): s / max(L, 1) */
+#define HB_SIM_DENSE_ONLY   0x2u  /* debug: every count level is a dense one (same result) */
+#define HB_SIM_SPARSE_ONLY  0x4u  /* debug: every count level is a sweep (bitmap on a context without sweep support; same result) */
+#define HB_SIM_SELF_SCORE   0x8u  /* Scorer::set_self_score(self_score); without it self_score = 1.0 */
+#define HB_SIM_TOP_SKIP_ANCHORS 0x1u /* hb_similarity_top: leave the liked / disliked hosts out (similar_hosts.rs:163) */
+
+typedef struct hb_similarity_options {
+    uint32_t struct_size, flags;                    /* struct_size = sizeof(hb_similarity_options); 0 = this version; flags = HB_SIM_* */
+    const hb_u128 *liked;    uint64_t liked_count;
+    const hb_u128 *disliked; uint64_t disliked_count;
+    double self_score;                              /* used only with HB_SIM_SELF_SCORE */
+} hb_similarity_options;
+
+typedef struct hb_similarity_stats {
+    uint32_t struct_size;       /* = sizeof(hb_similarity_stats); 0 = this version */
+    uint32_t reserved;
+    uint64_t liked, disliked;   /* L, D: entries as given (duplicates and unknown ids included) */
+    uint64_t unknown;           /* entries that are no node of the graph */
+    uint64_t batches;           /* ceil((L + D) / 16) */
+    uint64_t rows_nonzero;      /* node rows with a non-zero count, summed over the batches */
+    uint64_t levels_mode[3];    /* count levels per mode: dense, bitmap, sweep (a batch without a known anchor runs none) */
+    uint64_t edges_gathered;    /* source entries gathered by the count levels */
+    uint64_t device_bytes;      /* the operator's own buffers */
+    double   ms_total;          /* wall time of the call */
+    double   ms_bloom;          /* GPU time of the per-graph state (0 when it existed) */
+    double   ms_count;          /* GPU time of the count levels */
+    double   ms_score;          /* GPU time of seed + accumulate + score */
+    double   ms_mode[3];        /* GPU time of the count levels per mode */
+} hb_similarity_stats;
+
+int hb_inbound_similarity(hb_ctx *ctx, const hb_similarity_options *opt, hb_similarity_stats *stats);
+/* The result of the last hb_inbound_similarity.  all = one f64 per node in ascending-NodeID order, cap >= n.  lookup = Scorer::score of
+ * the given hosts; an id that is no node of the graph gets the score of an empty BitVec (its only possible terms are the self_score of
+ * the entries equal to it).  top = the first min(k, candidates) nodes in the order of sorted_k(Reverse((SortableFloat(score), node)))
+ * (similar_hosts.rs:182-191): score descending, ties by NodeID descending; selection and sort run on the device, only those entries are
+ * downloaded; ids or vals may be NULL; flags = HB_SIM_TOP_*. */
+int hb_similarity_all(hb_ctx *ctx, double *vals, uint64_t cap);
+int hb_similarity_lookup(hb_ctx *ctx, const hb_u128 *ids, uint64_t count, double *vals);
+int hb_similarity_top(hb_ctx *ctx, uint64_t k, uint32_t flags, hb_u128 *ids, double *vals, uint64_t *written);
+/* Debug: the counts of the LAST batch of the last hb_inbound_similarity (n x 16, entry sid * 16 + slot: |in(v) & in(anchor)|; slots
+ * without a known anchor are 0), and the per-graph bloom masks and in-degrees (n each), ascending-NodeID order; any of the three may be
+ * NULL.  The counts lie in the borrowed HyperBall state: refused once another call has used that state. */
+int hb_debug_copy_similarity_batch(hb_ctx *ctx, uint32_t *counts, uint64_t *bloom, uint32_t *len);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) -------------------------------------- */
 /* Rank 0 calls this and distributes the 128 bytes (e.g. torch.distributed broadcast);
  * every rank puts them in hb_options.rccl_id. */

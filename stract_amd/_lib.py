@@ -255,6 +255,51 @@ class HbBetweennessStats(ctypes.Structure):
         return d
 
 
+HB_SIM_NORMALIZED = 0x1
+HB_SIM_DENSE_ONLY = 0x2
+HB_SIM_SPARSE_ONLY = 0x4
+HB_SIM_SELF_SCORE = 0x8
+HB_SIM_TOP_SKIP_ANCHORS = 0x1
+
+
+class HbSimilarityOptions(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("liked", ctypes.c_void_p),
+        ("liked_count", ctypes.c_uint64),
+        ("disliked", ctypes.c_void_p),
+        ("disliked_count", ctypes.c_uint64),
+        ("self_score", ctypes.c_double),
+    ]
+
+
+class HbSimilarityStats(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("liked", ctypes.c_uint64),
+        ("disliked", ctypes.c_uint64),
+        ("unknown", ctypes.c_uint64),
+        ("batches", ctypes.c_uint64),
+        ("rows_nonzero", ctypes.c_uint64),
+        ("levels_mode", ctypes.c_uint64 * 3),
+        ("edges_gathered", ctypes.c_uint64),
+        ("device_bytes", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+        ("ms_bloom", ctypes.c_double),
+        ("ms_count", ctypes.c_double),
+        ("ms_score", ctypes.c_double),
+        ("ms_mode", ctypes.c_double * 3),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        for k in ("levels_mode", "ms_mode"):  # per mode: dense, bitmap, sweep
+            d[k] = list(d[k])
+        return d
+
+
 # every symbol include/hyperball.h declares: (name, restype, argtypes)
 _P = ctypes.c_void_p
 _U64 = ctypes.c_uint64
@@ -357,6 +402,14 @@ _SIGNATURES += [
     ("hb_betweenness_copy", ctypes.c_int, [_P, _P, _P, _U64]),
     ("hb_betweenness_all", ctypes.c_int, [_P, _P, _U64]),
     ("hb_debug_copy_betweenness_batch", ctypes.c_int, [_P, _P, _P, _P]),
+]
+# include/hyperball.h: inbound similarity (Scorer over BitVec)
+_SIGNATURES += [
+    ("hb_inbound_similarity", ctypes.c_int, [_P, ctypes.POINTER(HbSimilarityOptions), ctypes.POINTER(HbSimilarityStats)]),
+    ("hb_similarity_all", ctypes.c_int, [_P, _P, _U64]),
+    ("hb_similarity_lookup", ctypes.c_int, [_P, _P, _U64, _P]),
+    ("hb_similarity_top", ctypes.c_int, [_P, _U64, ctypes.c_uint32, _P, _P, ctypes.POINTER(_U64)]),
+    ("hb_debug_copy_similarity_batch", ctypes.c_int, [_P, _P, _P, _P]),
 ]
 SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -774,6 +827,63 @@ class Context:
         delta = np.zeros((n, 8), dtype=np.float64)
         self._check(self.lib.hb_debug_copy_betweenness_batch(self.h, _ptr(dist), _ptr(sigma), _ptr(delta)))
         return dist, sigma, delta
+
+    # -- inbound similarity (Scorer, ranking/inbound_similarity.rs:61-138)
+    _SIM_MODES = {None: 0, "auto": 0, "dense": HB_SIM_DENSE_ONLY, "sparse": HB_SIM_SPARSE_ONLY}
+
+    def inbound_similarity(self, liked=(), disliked=(), normalized=False, self_score=None, mode=None, flags=0):
+        """hb_inbound_similarity: scores every node against `liked` / `disliked` (U128 arrays of node ids, duplicates and unknown ids
+        allowed); returns the stats.  mode: None / "dense" / "sparse" (forced kind of count level)."""
+        o = HbSimilarityOptions()
+        o.struct_size = ctypes.sizeof(HbSimilarityOptions)
+        o.flags = int(flags) | (HB_SIM_NORMALIZED if normalized else 0) | self._SIM_MODES[mode]
+        if self_score is not None:
+            o.flags |= HB_SIM_SELF_SCORE
+            o.self_score = float(self_score)
+        liked = np.ascontiguousarray(liked, dtype=U128) if len(liked) else np.zeros(0, dtype=U128)
+        disliked = np.ascontiguousarray(disliked, dtype=U128) if len(disliked) else np.zeros(0, dtype=U128)
+        if len(liked):
+            o.liked = liked.ctypes.data
+            o.liked_count = len(liked)
+        if len(disliked):
+            o.disliked = disliked.ctypes.data
+            o.disliked_count = len(disliked)
+        st = HbSimilarityStats()
+        st.struct_size = ctypes.sizeof(HbSimilarityStats)
+        self._check(self.lib.hb_inbound_similarity(self.h, ctypes.byref(o), ctypes.byref(st)))
+        return st.as_dict()
+
+    def similarity_all(self):
+        """One float64 per node of the last inbound_similarity() call, ascending NodeID."""
+        out = np.zeros(self.n(), dtype=np.float64)
+        self._check(self.lib.hb_similarity_all(self.h, _ptr(out), len(out)))
+        return out
+
+    def similarity_lookup(self, ids):
+        """Scorer::score of the given hosts (U128 array); an id that is no node gets the score of an empty BitVec."""
+        ids = np.ascontiguousarray(ids, dtype=U128)
+        out = np.zeros(len(ids), dtype=np.float64)
+        self._check(self.lib.hb_similarity_lookup(self.h, _ptr(ids) if len(ids) else None, len(ids), _ptr(out) if len(ids) else None))
+        return out
+
+    def similarity_top(self, k, skip_anchors=False):
+        """The k best nodes of the last inbound_similarity() call: (ids, scores), score descending, ties by NodeID descending."""
+        k = int(k)
+        ids = np.zeros(k, dtype=U128)
+        vals = np.zeros(k, dtype=np.float64)
+        w = ctypes.c_uint64(0)
+        self._check(self.lib.hb_similarity_top(self.h, k, HB_SIM_TOP_SKIP_ANCHORS if skip_anchors else 0, _ptr(ids), _ptr(vals), ctypes.byref(w)))
+        return ids[:w.value], vals[:w.value]
+
+    def debug_similarity_batch(self):
+        """counts (n, 16) uint32 of the LAST batch of the last inbound_similarity() call, and the per-graph bloom masks (n) uint64 and
+        in-degrees (n) uint32, ascending NodeID."""
+        n = self.n()
+        counts = np.zeros((n, 16), dtype=np.uint32)
+        bloom = np.zeros(n, dtype=np.uint64)
+        length = np.zeros(n, dtype=np.uint32)
+        self._check(self.lib.hb_debug_copy_similarity_batch(self.h, _ptr(counts), _ptr(bloom), _ptr(length)))
+        return counts, bloom, length
 
     # -- results
     def results(self):

@@ -24,6 +24,7 @@
 #include "hb_sample.hip.h"
 #include "hb_bfs.hip.h"
 #include "hb_betweenness.hip.h"
+#include "hb_similarity.hip.h"
 #ifdef HB_EXPERIMENTS
 #include "hb_experiments.hip.h"
 #endif
@@ -237,6 +238,29 @@ struct GraphDeviceState {
         uint64_t bytes = 0;                    // device bytes of the above
         uint32_t last_lanes = 0;               // sources of the last batch run (0 = none)
     } btw;
+    // hb_inbound_similarity (hb_api_similarity.inc): the per-graph state (position bytes, blooms; the in-degrees are dst.d_indeg), the
+    // sums and the last result, dev_alloc'ed at the first call after a load
+    struct SimilarityState {
+        bool ready = false;      // the buffers below exist and the per-graph state is built
+        bool valid = false;      // they hold the result of a finished hb_inbound_similarity
+        bool batch_live = false; // d_regs[1] / d_bits[1] still hold the last batch's counts (hb_begin and the other walks clear this)
+        uint8_t *d_pos = nullptr;              // n_pad: h & 63 of the row's low id word
+        uint64_t *d_bloom = nullptr;           // rows_total: OR of 1 << pos over the in-list (chunk rows: their partial)
+        uint32_t *d_vmask = nullptr;           // nv: seed: the anchor slots whose in-list runs through the chunk row
+        double *d_acc = nullptr;               // n_pad x 2: sum of the liked / disliked terms so far
+        uint32_t *d_anchor_rows = nullptr;     // 16: device rows of the batch's anchors, kNone = no node
+        uint32_t *d_anchor_sids = nullptr;     // 16: ... their sids, kNone = no node
+        unsigned long long *d_cnt = nullptr;   // 2 x 4 counters: the seed's, the count level's
+        double *d_score = nullptr;             // n: score per sid
+        uint8_t *d_anchor = nullptr;           // n: 1 = the sid is a liked / disliked host
+        uint64_t *d_key = nullptr;             // n: hb_similarity_top's sort keys
+        uint8_t *d_keep = nullptr;             // n: ... and which sids take part
+        std::vector<hb_u128> liked, disliked;  // the entries of the last call (hb_similarity_lookup of ids that are no node)
+        bool normalized = false;
+        double self_score = 1.0;
+        uint32_t last_slots = 0;               // slots of the last batch
+        uint64_t bytes = 0;                    // device bytes of the above (and of dst.d_indeg when this operator built it)
+    } sim;
 };
 
 // The timing events of a pass (one set: hb_ctx::ev, or an EvSet), in the order a pass records them; kEvLevel1 lies between kEvStart and
@@ -1200,6 +1224,7 @@ int hb_begin(hb_ctx *c)
         c->begun = true;
         c->finished = false;
         c->res_count = 0;
+        c->sim.batch_live = false; // (the counts of hb_inbound_similarity's last batch lay in the registers)
         return HB_OK;
     });
 }
@@ -1519,3 +1544,5 @@ int hb_store_harmonic_results(hb_ctx *c, const char *output, char *err, uint64_t
 #include "hb_api_distance.inc"
 
 #include "hb_api_betweenness.inc"
+
+#include "hb_api_similarity.inc"

@@ -1,5 +1,5 @@
 // hb_api_walk.inc - part of the hb_api.hip translation unit (included before the operator files; uses its hb_ctx and helpers).
-// What hb_sampled_harmonic, hb_distances and hb_betweenness share on the host: their refusals, the sources as sids, the row -> readers
+// What hb_sampled_harmonic, hb_distances, hb_betweenness and hb_inbound_similarity share on the host: their refusals, the sources as sids, the row -> readers
 // transpose, the download of a compacted result - and, for the two operators that walk 64-byte rows (device side: hb_walk.hip.h), the
 // launcher and one forward level.
 
@@ -25,6 +25,7 @@ int walk_prologue(hb_ctx *c, const char *who, const char *boundary_note = " (vir
     if ((rc = plan_rows_word_aligned(c, who))) return rc;
     for (uint64_t b : p.level_begin)
         if (b < p.n_pad || b > p.n_pad + p.nv) return fail(c, HB_ERR_INVALID, std::string(who) + ": unexpected plan layout" + boundary_note);
+    c->sim.batch_live = false; // (every operator here rewrites the rows hb_inbound_similarity left its last counts in)
     return refuse_stale_error(c, who);
 }
 
@@ -91,6 +92,12 @@ struct BrandesWalk {
     using Params = hbk::BcParams;
     template <bool REAL, int MODE>
     static constexpr void (*kernel)(const Params) = hbk::bc_forward_kernel<REAL, MODE>;
+};
+
+struct SimilarityWalk {
+    using Params = hbk::SimParams;
+    template <bool REAL, int MODE>
+    static constexpr void (*kernel)(const Params) = hbk::sim_count_kernel<REAL, MODE>;
 };
 
 template <class W, bool REAL>

@@ -263,6 +263,10 @@ std::string device_offsets(void *stream, uint32_t *d_counts, uint64_t count, uin
 std::string device_prefix(void *stream, const uint32_t *d_counts, uint64_t count, uint64_t *d_offsets);
 // the reached nodes of a distance run (hb_api_distance.inc): (sid, distance) of every sid with d_by_sid[sid] != 255, ascending sid
 std::string gpu_select_reached(void *stream, const uint8_t *d_by_sid, uint64_t n, uint32_t *d_sids, uint8_t *d_dist, uint64_t *d_count);
+// hb_similarity_top (hb_api_similarity.inc): the first `top` (sid, key) pairs in the order key descending, ties sid descending, over
+// the sids whose d_keep byte is non-zero; h_sid / h_key hold `top` entries, *written = how many were filled
+std::string gpu_similarity_top(void *stream, const uint64_t *d_key, const uint8_t *d_keep, uint64_t n, uint64_t top, uint32_t *h_sid, uint64_t *h_key,
+                               uint64_t *written);
 // the transposed work-row graph (out_ptr: rows_total + 1 offsets, out_rows: `entries` reader rows) by one stable radix sort of
 // (source, row) keys; "" or an error text - "out of memory ..." = the caller may fall back to the scatter kernels
 std::string gpu_transpose_rows(void *stream, const uint64_t *d_row_ptr, const uint32_t *d_src, uint64_t rows_total, uint64_t entries, uint64_t *d_out_ptr,

@@ -604,6 +604,63 @@ std::string gpu_select_reached(void *stream_v, const uint8_t *d_by_sid, uint64_t
     return "";
 }
 
+// hb_similarity_top: the first `top` entries of the order "key descending, ties by sid descending" over the sids whose d_keep byte is
+// set - sorted_k(Reverse((SortableFloat(score), node))), similar_hosts.rs:182-191.  One order-preserving select of (sid, key), one stable
+// ascending radix sort of the pairs (equal keys keep ascending sid), and the LAST entries of it read backwards: only they come down.
+std::string gpu_similarity_top(void *stream_v, const uint64_t *d_key, const uint8_t *d_keep, uint64_t n, uint64_t top, uint32_t *h_sid, uint64_t *h_key,
+                               uint64_t *written)
+{
+    hipStream_t stream = (hipStream_t)stream_v;
+    *written = 0;
+    if (!n || !top) return "";
+    struct Scratch { // freed on every way out
+        void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Scratch()
+        {
+            for (void *q : p)
+                if (q) (void)hipFree(q);
+        }
+    } mem;
+    uint32_t *d_sid = nullptr, *d_sid_s = nullptr;
+    uint64_t *d_k = nullptr, *d_k_s = nullptr, *d_cnt = nullptr;
+    PL_HIP(hipMalloc(&mem.p[0], std::max<size_t>(n * sizeof(uint32_t), 256)));
+    PL_HIP(hipMalloc(&mem.p[1], std::max<size_t>(n * sizeof(uint32_t), 256)));
+    PL_HIP(hipMalloc(&mem.p[2], std::max<size_t>(n * sizeof(uint64_t), 256)));
+    PL_HIP(hipMalloc(&mem.p[3], std::max<size_t>(n * sizeof(uint64_t), 256)));
+    PL_HIP(hipMalloc(&mem.p[4], 256));
+    d_sid = (uint32_t *)mem.p[0];
+    d_sid_s = (uint32_t *)mem.p[1];
+    d_k = (uint64_t *)mem.p[2];
+    d_k_s = (uint64_t *)mem.p[3];
+    d_cnt = (uint64_t *)mem.p[4];
+    auto iota = rocprim::make_counting_iterator<uint32_t>(0);
+    size_t b0 = 0, b1 = 0, b2 = 0;
+    PL_HIP(rocprim::select(nullptr, b0, iota, d_keep, d_sid, d_cnt, (size_t)n, stream));
+    PL_HIP(rocprim::select(nullptr, b1, d_key, d_keep, d_k, d_cnt, (size_t)n, stream));
+    PL_HIP(rocprim::radix_sort_pairs(nullptr, b2, (const uint64_t *)d_k, d_k_s, (const uint32_t *)d_sid, d_sid_s, (size_t)n, 0, 64, stream));
+    const size_t bytes = std::max<size_t>(std::max(b0, std::max(b1, b2)), 256);
+    PL_HIP(hipMalloc(&mem.p[5], bytes));
+    size_t b = bytes;
+    PL_HIP(rocprim::select(mem.p[5], b, iota, d_keep, d_sid, d_cnt, (size_t)n, stream));
+    b = bytes;
+    PL_HIP(rocprim::select(mem.p[5], b, d_key, d_keep, d_k, d_cnt, (size_t)n, stream));
+    uint64_t kept = 0;
+    PL_HIP(hipMemcpyAsync(&kept, d_cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    PL_HIP(hipStreamSynchronize(stream));
+    if (kept > n) return "gpu_similarity_top: select count out of range";
+    const uint64_t k = std::min(top, kept);
+    if (!k) return "";
+    b = bytes;
+    PL_HIP(rocprim::radix_sort_pairs(mem.p[5], b, (const uint64_t *)d_k, d_k_s, (const uint32_t *)d_sid, d_sid_s, (size_t)kept, 0, 64, stream));
+    PL_HIP(hipMemcpyAsync(h_sid, d_sid_s + (kept - k), k * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    PL_HIP(hipMemcpyAsync(h_key, d_k_s + (kept - k), k * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    PL_HIP(hipStreamSynchronize(stream));
+    std::reverse(h_sid, h_sid + k);
+    std::reverse(h_key, h_key + k);
+    *written = k;
+    return "";
+}
+
 // ---- the transposed work-row graph by SORTING [r6] ----------------------------------------------------------------------------------
 // out_rows / out_ptr (who reads each node or virtual row: the sweep passes' expansion) used to be built by scattering: one atomic
 // cursor bump and one 4-byte store at a random place per entry - 126 bytes of HBM traffic per entry at C4 (266 GB for 2.1 G entries,

@@ -1,0 +1,321 @@
+"""hb_inbound_similarity (Scorer, crates/core/src/ranking/inbound_similarity.rs:61-138, over BitVec, ranking/bitvec_similarity.rs) against
+the host restatement in tests/inbound_similarity_ref.py.
+
+Comparison rule: EVERYTHING is exact.  The counts of the last batch, the in-degrees and the blooms (the device's one u64 against the
+restatement's sixteen words folded) are compared as integers; every score bit for bit, zeros as +0.0."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+from stract_amd import _lib, synth
+from stract_amd.harmonic import EdgeListGraph, ids_from_ints
+from tests import distance_ref as dref
+from tests import graphs
+from tests import inbound_similarity_ref as sref
+
+pytestmark = pytest.mark.gpu
+
+MODES = (None, "dense", "sparse")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "similarity_cases.json")
+_REF = {}  # the restatement's BitVecs, once per graph
+
+
+def _ctx(factory, graph, flags=_lib.HB_FLAG_ALL_RELS, **kw):
+    ctx = factory(flags=flags, **kw)
+    ctx.load_edges(graph.host_edges())
+    return ctx
+
+
+def _bitvecs(key, graph):
+    if key not in _REF:
+        _REF[key] = sref.bitvecs(*graph)
+    return _REF[key]
+
+
+def _bits(a):
+    return np.asarray(a, dtype=np.float64).view(np.uint64)
+
+
+def _assert_exact(got, want, what):
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    assert got.shape == want.shape, what
+    bad = np.flatnonzero(_bits(got) != _bits(want))
+    assert not len(bad), (what, bad[:5], got[bad[:5]], want[bad[:5]])
+
+
+def _check(ctx, graph, bv, liked, disliked, normalized=False, self_score=None, modes=MODES, want=None):
+    """the default run and the two forced modes against the restatement: scores, and the last batch's counts / bloom / len"""
+    ids = graph[0]
+    ints = sref.id_ints(ids)
+    if want is None:
+        want = sref.literal(*graph, liked, disliked, normalized, 1.0 if self_score is None else self_score, bv=bv)
+    entries = list(liked) + list(disliked)
+    last = entries[(len(entries) - 1) // 16 * 16:]
+    stats = []
+    for mode in modes:
+        st = ctx.inbound_similarity(ids_from_ints(liked), ids_from_ints(disliked), normalized=normalized, self_score=self_score, mode=mode)
+        _assert_exact(ctx.similarity_all(), want, "scores (%s)" % mode)
+        known = sum(1 for e in entries if e in bv) if bv is not None else None
+        assert st["liked"] == len(liked) and st["disliked"] == len(disliked) and st["batches"] == (len(entries) + 15) // 16
+        assert known is None or st["unknown"] == len(entries) - known
+        assert sum(st["levels_mode"]) <= st["batches"] and st["device_bytes"] > 0
+        if mode == "dense":
+            assert st["levels_mode"][1] == 0 and st["levels_mode"][2] == 0
+        if mode == "sparse":
+            assert st["levels_mode"][0] == 0
+        if bv is not None:
+            counts, bloom, length = ctx.debug_similarity_batch()
+            assert np.array_equal(counts[:, :len(last)], sref.counts(bv, ids, last)), mode
+            assert not counts[:, len(last):].any()
+            assert [int(x) for x in bloom] == [bv[v].fold() for v in ints] and [int(x) for x in length] == [len(bv[v].ranks) for v in ints]
+        stats.append(st)
+    return want, stats
+
+
+def _entries(ints, L, D):
+    """L liked and D disliked entries over the nodes `ints`: spread over the graph, with an unknown id and a duplicate in both lists
+    and one id both liked and disliked"""
+    pool = ints[::max(1, len(ints) // 41)] + ints[1::7]
+    pool = pool * ((L + D) // len(pool) + 1)  # (a graph smaller than the lists: its nodes again and again)
+    liked = pool[:L]
+    if L > 3:
+        liked[3] = 1 << 100  # no node of the graph
+    if L > 5:
+        liked[5] = liked[0]  # a duplicate: a slot of its own
+    disliked = pool[L:L + D]
+    if D and L:
+        disliked[0] = liked[0]  # the same id liked and disliked
+    if D > 2:
+        disliked[2] = (1 << 100) + 1
+    if D > 4:
+        disliked[4] = disliked[1]
+    return liked, disliked
+
+
+def _star(leaves=100_000):
+    """hub 1 has `leaves` in-edges, hub 2 has `leaves` out-edges, 1 -> 2 (tests/test_betweenness.py)"""
+    t = [(v, 1) for v in range(3, leaves + 3)] + [(2, v) for v in range(3, leaves + 3)] + [(1, 2)]
+    return EdgeListGraph.from_tuples(t)
+
+
+# (1) the hand-made known answer: shared in-neighbours, the bloom gate, no in-links, the self score
+def test_known_answer(gpu_ctx_factory):
+    with open(GOLDEN) as f:
+        g = json.load(f)
+    with _ctx(gpu_ctx_factory, EdgeListGraph.from_tuples([tuple(e) for e in g["edges"]])) as ctx:
+        graph = ctx.graph()
+        ints = sref.id_ints(graph[0])
+        bv = _bitvecs("golden", graph)
+        for case in g["cases"]:
+            want = np.array([case["expect"][str(v)] for v in ints], dtype=np.float64)
+            _check(ctx, graph, bv, case["liked"], case["disliked"], case["normalized"], case["self_score"], want=want)
+        from stract_amd.inbound_similarity import Scorer
+        s = Scorer.new(ctx, [100], [])
+        assert s.score([101, 100, 555]).tolist() == [0.5, 1.0, 0.0]
+        s.set_self_score(0.25)
+        assert s.score([100]).tolist() == [0.25] and s.top(2)[0] == [103, 101]
+        all_ids, all_scores = s.score_all()
+        assert all_scores[all_ids.index(101)] == 0.5 and len(all_ids) == len(ints)
+
+
+# (2) slot packing across batches, both lists, duplicates, the same id in both, unknown ids, L = 0
+@pytest.mark.parametrize("L,D", [(L, D) for L in (0, 1, 15, 16, 17, 33) for D in (0, 1, 17) if L + D])
+def test_lcg_entry_counts(gpu_ctx_factory, L, D):
+    with _ctx(gpu_ctx_factory, EdgeListGraph.from_tuples(graphs.lcg_graph())) as ctx:
+        graph = ctx.graph()
+        bv = _bitvecs("lcg", graph)
+        liked, disliked = _entries(sref.id_ints(graph[0]), L, D)
+        _check(ctx, graph, bv, liked, disliked, normalized=False)
+        _check(ctx, graph, bv, liked, disliked, normalized=True, self_score=0.5, modes=(None,))
+
+
+@pytest.mark.parametrize("name", ["fixture", "host_fixture"])
+def test_fixture_graphs(gpu_ctx_factory, name):
+    g = {"fixture": graphs.fixture_graph, "host_fixture": lambda: graphs.host_fixture()[0]}[name]()
+    with _ctx(gpu_ctx_factory, g) as ctx:
+        graph = ctx.graph()
+        bv = _bitvecs(name, graph)
+        ints = sref.id_ints(graph[0])
+        for L, D, normalized in ((1, 0, False), (0, 1, True), (17, 17, True), (33, 1, False)):
+            liked, disliked = _entries(ints, L, D)
+            _check(ctx, graph, bv, liked, disliked, normalized=normalized)
+
+
+# (3) chunk trees: an anchor's in-list seeded through the tree (hub 1) and a count summed through it (hub 1 against itself)
+def test_star_hubs_through_chunk_trees(gpu_ctx_factory):
+    leaves = 100_000
+    with _ctx(gpu_ctx_factory, _star(leaves)) as ctx:
+        graph = ctx.graph()
+        n = len(graph[0])
+        assert ctx.plan()["nv"] > 0 and sref.id_ints(graph[0][:3]) == [1, 2, 3]
+        for mode in MODES:  # anchors: hub 1 (in = the leaves), leaf 3 (in = {2}), hub 2 (in = {1})
+            st = ctx.inbound_similarity(ids_from_ints([1, 3, 2]), mode=mode)
+            # every leaf's in-set is {2} = in(3): sim 1; the hubs and leaf 3 only score themselves
+            _assert_exact(ctx.similarity_all(), np.ones(n), "star (%s)" % mode)
+            counts, bloom, length = ctx.debug_similarity_batch()
+            want = np.zeros((n, 16), dtype=np.uint32)
+            want[0, 0] = leaves  # |in(1) & in(1)|: summed through the chunk tree
+            want[2:, 1] = 1      # the leaves against leaf 3
+            want[1, 2] = 1       # |in(2) & in(2)|
+            assert np.array_equal(counts, want), mode
+            assert length.tolist()[:3] == [leaves, 1, 1] and (length[2:] == 1).all() and st["rows_nonzero"] == leaves + 2
+        want = sref.numpy_scores(*graph, [1], [3, 50], True)
+        assert want[0] == 3.0 and want[1] == 2.0 and not _bits(want[2:]).any()  # every leaf: 2 + (0 - (1 + 1)) = +0.0
+        for mode in MODES:
+            ctx.inbound_similarity(ids_from_ints([1]), ids_from_ints([3, 50]), normalized=True, mode=mode)
+            _assert_exact(ctx.similarity_all(), want, "star, disliked leaves (%s)" % mode)
+
+
+# (4) the three kinds of level give the same bits, and each is taken
+def test_modes_on_the_tailed_graph(gpu_ctx_factory):
+    with _ctx(gpu_ctx_factory, EdgeListGraph.from_tuples(graphs.tailed_graph())) as ctx:
+        graph = ctx.graph()
+        bv = _bitvecs("tailed", graph)
+        ints = sref.id_ints(graph[0])
+        indeg = np.diff(np.asarray(graph[1], dtype=np.int64))
+        liked = [ints[i] for i in np.argsort(-indeg, kind="stable")[:20]] + ints[-3:]
+        _, (auto, dense, sparse) = _check(ctx, graph, bv, liked, ints[5:8], normalized=True)
+        assert dense["levels_mode"][0] == dense["batches"] and sparse["levels_mode"][1] + sparse["levels_mode"][2] == sparse["batches"]
+        assert sum(auto["levels_mode"]) == auto["batches"] and dense["edges_gathered"] >= sparse["edges_gathered"] > 0
+        _, (one,) = _check(ctx, graph, bv, ints[-1:], [], modes=(None,))  # one in-neighbour marked: the A_t rule leaves the dense mode
+        assert one["levels_mode"][0] == 0 and sum(one["levels_mode"]) == 1
+
+
+# (5) 128-bit ids: the bloom takes the low word only (insert_u128, bitvec_similarity.rs:43-45)
+def test_wide_ids_with_colliding_low_words(gpu_ctx_factory):
+    rng = np.random.default_rng(17)
+    lows = [5, 5 + 64, 5 + 128, 7, 7, 7, 1 << 40, (1 << 40) + 64, 9, 73]
+    nodes = [(int(hi) << 64) | lo for hi, lo in zip(range(1, 41), lows * 4)]
+    edges = sorted({(nodes[int(a)], nodes[int(b)]) for a, b in rng.integers(0, 40, (260, 2))})
+    with _ctx(gpu_ctx_factory, EdgeListGraph.from_tuples(edges)) as ctx:
+        graph = ctx.graph()
+        bv = _bitvecs("wide", graph)
+        assert any(v.ones < len(v.ranks) for v in bv.values())  # collisions happen
+        _check(ctx, graph, bv, nodes[:17] + [nodes[3] & ((1 << 64) - 1)], nodes[30:33], normalized=True)
+
+
+# (6) top and lookup
+def test_top_and_lookup(gpu_ctx_factory):
+    with _ctx(gpu_ctx_factory, EdgeListGraph.from_tuples(graphs.lcg_graph())) as ctx:
+        graph = ctx.graph()
+        ids = graph[0]
+        n = len(ids)
+        bv = _bitvecs("lcg", graph)
+        liked, disliked = [3, 50, 1 << 90, 3], [120, (1 << 90) + 1]
+        want, _ = _check(ctx, graph, bv, liked, disliked, modes=(None,))
+        assert len(set(want.tolist())) < n  # ties in score
+        for k in (1, 10, n, n + 7):
+            for skip in (False, True):
+                got_ids, got_vals = ctx.similarity_top(k, skip_anchors=skip)
+                order = sref.top_order(ids, want, k, skip=liked + disliked if skip else ())
+                assert sref.id_ints(got_ids) == [v for _, v in order], (k, skip)
+                _assert_exact(got_vals, [s for s, _ in order], "top %d" % k)
+        assert len(ctx.similarity_top(n + 7)[0]) == n and len(ctx.similarity_top(n + 7, skip_anchors=True)[0]) == n - 3
+        assert len(ctx.similarity_top(0)[0]) == 0
+        # lookup: nodes, ids that are no node, and an unknown id that is an entry (it meets itself: self_score)
+        asked = [50, 777777, 3, 1 << 90, (1 << 90) + 1, 120, 50]
+        _assert_exact(ctx.similarity_lookup(ids_from_ints(asked)), sref.lookup(bv, liked, disliked, False, 1.0, asked), "lookup")
+        ctx.inbound_similarity(ids_from_ints(liked), ids_from_ints(disliked), normalized=True, self_score=0.25)
+        _assert_exact(ctx.similarity_lookup(ids_from_ints(asked)), sref.lookup(bv, liked, disliked, True, 0.25, asked), "lookup, normalized")
+        assert len(ctx.similarity_lookup(ids_from_ints([]))) == 0
+
+
+# (7) state: results, distances, betweenness and a later hb_run are untouched; a reload drops the per-graph state
+def test_state_of_the_other_operators_and_reload(gpu_ctx_factory):
+    g = synth.RmatGraph(12, 30_000)
+    graph = (g.ids, g.row_ptr, g.src)
+    with gpu_ctx_factory() as ctx:
+        ctx.load_dense(g.ids, g.row_ptr, g.src)
+        ctx.run()
+        h0 = ctx.state_hash()
+        r0 = ctx.results()
+        dist_want = dref.bfs(g.n, g.row_ptr, g.src, [11, 500])
+        ctx.distances(g.ids[[11, 500]])
+        b0 = ctx.betweenness(g.ids[[3, 11, 500]])
+        before = ctx.stats()["device_bytes"]
+        liked, disliked = sref.id_ints(g.ids[[7, 11, 500, 1000]]), sref.id_ints(g.ids[[2000]])
+        want = sref.numpy_scores(*graph, liked, disliked, True)
+        st = ctx.inbound_similarity(ids_from_ints(liked), ids_from_ints(disliked), normalized=True)
+        _assert_exact(ctx.similarity_all(), want, "scores")
+        assert st["device_bytes"] > 0 and ctx.stats()["device_bytes"] == before + st["device_bytes"]
+        st2 = ctx.inbound_similarity(ids_from_ints(liked), ids_from_ints(disliked), normalized=True)
+        assert st2["device_bytes"] == st["device_bytes"] and ctx.stats()["device_bytes"] == before + st["device_bytes"] and st2["ms_bloom"] == 0.0
+        assert np.array_equal(ctx.distance_all(), dist_want)
+        b1 = ctx.betweenness_copy()
+        assert b0[0].tobytes() == b1[0].tobytes() and b0[1].tobytes() == b1[1].tobytes()
+        r1 = ctx.results()
+        assert r0[0].tobytes() == r1[0].tobytes() and r0[1].tobytes() == r1[1].tobytes()
+        with pytest.raises(_lib.HyperballError):  # the HyperBall state was borrowed: hb_step needs a new hb_begin
+            ctx.step()
+        ctx.run()
+        assert ctx.state_hash() == h0
+        r2 = ctx.results()
+        assert r0[0].tobytes() == r2[0].tobytes() and r0[1].tobytes() == r2[1].tobytes()
+        _assert_exact(ctx.similarity_all(), want, "scores after hb_run")  # the scores live in buffers of their own ...
+        with pytest.raises(_lib.HyperballError) as e:  # ... the last batch's counts did not
+            ctx.debug_similarity_batch()
+        assert e.value.code == _lib.HB_ERR_INVALID
+        # a smaller graph on the same context: nothing of the first one answers for it
+        small = EdgeListGraph.from_tuples(graphs.lcg_graph(n=70, m=300, seed=3))
+        ctx.load_edges(small.host_edges())
+        fresh = ctx.stats()["device_bytes"]
+        with pytest.raises(_lib.HyperballError) as e:
+            ctx.similarity_all()
+        assert e.value.code == _lib.HB_ERR_INVALID
+        sgraph = ctx.graph()
+        want2 = sref.literal(*sgraph, [1, 2, 3], [4])
+        st3 = ctx.inbound_similarity(ids_from_ints([1, 2, 3]), ids_from_ints([4]))
+        _assert_exact(ctx.similarity_all(), want2, "scores after the reload")
+        assert 0 < st3["device_bytes"] < st["device_bytes"] and ctx.stats()["device_bytes"] == fresh + st3["device_bytes"] and st3["ms_bloom"] > 0.0
+
+
+# (7b) refusals
+def test_refusals(gpu_ctx_factory):
+    def refused(fn, who="hb_inbound_similarity"):
+        with pytest.raises(_lib.HyperballError) as e:
+            fn()
+        assert e.value.code == _lib.HB_ERR_INVALID and who in str(e.value)
+
+    one = ids_from_ints([1])
+    with gpu_ctx_factory(flags=_lib.HB_FLAG_ALL_RELS) as ctx:
+        refused(lambda: ctx.inbound_similarity(one))  # no graph loaded
+        refused(lambda: ctx.similarity_all(), "hb_similarity_all")
+        ctx.load_edges(np.zeros(0, dtype=_lib.EDGE))  # an empty graph: nothing to score, unknown hosts still answer
+        st = ctx.inbound_similarity(one, one)
+        assert st["unknown"] == 2 and st["batches"] == 0 and len(ctx.similarity_top(5)[0]) == 0
+        assert ctx.similarity_lookup(ids_from_ints([1, 2])).tolist() == [1.0, 1.0]  # D + (self - self), D + (0 - 0)
+    with _ctx(gpu_ctx_factory, graphs.fixture_graph()) as ctx:
+        refused(lambda: ctx.similarity_top(3), "hb_similarity_top")  # no result yet
+        refused(lambda: ctx.similarity_lookup(one), "hb_similarity_lookup")
+        refused(lambda: ctx.debug_similarity_batch(), "hb_debug_copy_similarity_batch")
+        refused(lambda: ctx.inbound_similarity())  # L + D == 0
+        refused(lambda: ctx.inbound_similarity(one, flags=_lib.HB_SIM_DENSE_ONLY | _lib.HB_SIM_SPARSE_ONLY))
+        ctx.begin()
+        ctx.step()
+        refused(lambda: ctx.inbound_similarity(one))  # between hb_begin and hb_finish
+        ctx.finish()
+        st = ctx.inbound_similarity(ids_from_ints([77, 78]))  # every entry unknown: succeeds, every score is D + 0
+        assert st["unknown"] == 2 and sum(st["levels_mode"]) == 0 and not _bits(ctx.similarity_all()).any()
+    with gpu_ctx_factory(world_size=2, rank=0, flags=_lib.HB_FLAG_NO_RCCL) as ctx:
+        refused(lambda: ctx.inbound_similarity(one))
+
+
+# (8) C2 size against the numpy restatement (GPU only)
+def test_c2_against_numpy(gpu_ctx_factory):
+    g = synth.RmatGraph(20, 20_000_000)
+    graph = (g.ids, g.row_ptr, g.src)
+    indeg = np.diff(np.asarray(g.row_ptr, dtype=np.int64))
+    rng = np.random.default_rng(5)
+    liked = sref.id_ints(g.ids[np.argsort(-indeg, kind="stable")[:3]]) + sref.id_ints(g.ids[rng.choice(np.flatnonzero(indeg > 0), 6, replace=False)])
+    disliked = sref.id_ints(g.ids[rng.choice(np.flatnonzero(indeg > 0), 1, replace=False)])
+    want = sref.numpy_scores(*graph, liked, disliked, True)
+    with gpu_ctx_factory() as ctx:
+        ctx.load_dense(g.ids, g.row_ptr, g.src)
+        st = ctx.inbound_similarity(ids_from_ints(liked), ids_from_ints(disliked), normalized=True)
+        _assert_exact(ctx.similarity_all(), want, "C2")
+        assert st["batches"] == 1 and st["levels_mode"][0] == 1 and np.count_nonzero(want != 1.0) > 1000
+        length, bloom, _ = sref.numpy_state(*graph)
+        _, dev_bloom, dev_len = ctx.debug_similarity_batch()
+        assert np.array_equal(dev_bloom, bloom) and np.array_equal(dev_len, length.astype(np.uint32))

@@ -5,7 +5,7 @@ Runs against whatever library HB_LIB_PATH names: the gfx950 library on a GPU box
 interpreted test build of the device sources (tests/simt, with HB_ALLOW_SIMT_INTERPRETER=1; add the AddressSanitizer preload
 for the `make asan` build).  A failure prints the seed and case that reproduce it and makes the exit code non-zero.
 
-usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|distances] [--seconds S] [--seed N] [--max-nodes N]"""
+usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|distances|betweenness|similarity] [--seconds S] [--seed N] [--max-nodes N]"""
 import argparse
 import json
 import os
@@ -320,9 +320,62 @@ def betweenness_case(rng, max_nodes, case):
     return what
 
 
+def similarity_case(rng, max_nodes, case):
+    """hb_inbound_similarity: random graph x random entry lists (duplicates, unknown ids, an entry equal to a scored node - every known
+    entry is one) x the three mode settings, against the host restatement (tests/inbound_similarity_ref.py), bit for bit."""
+    from stract_amd.harmonic import EdgeListGraph, ids_from_ints
+    from tests import inbound_similarity_ref as sref
+    kind, tuples = graphs.random_graph(rng)
+    if not tuples:
+        return None
+    chunk = int(rng.choice([0, 0, 4, 8, 64]))
+    flags = _lib.HB_FLAG_ALL_RELS | int(rng.choice([0, 0, _lib.HB_FLAG_NO_REORDER, _lib.HB_FLAG_NO_XCD_MAP, _lib.HB_FLAG_NO_SPARSE]))
+    with _lib.Context(flags=flags, chunk=chunk) as ctx:
+        ctx.load_edges(EdgeListGraph.from_tuples(tuples).host_edges())
+        graph = ctx.graph()
+        ids = graph[0]
+        ints = sref.id_ints(ids)
+        n = len(ints)
+        bv = sref.bitvecs(*graph)
+        what = dict(case=case, kind="similarity:" + kind, n=n, m=int(len(graph[2])), chunk=chunk, flags=flags, passes=0)
+
+        def entries(k):
+            e = [ints[int(x)] for x in rng.integers(0, n, k)]
+            if k > 2:
+                e[int(rng.integers(0, k))] = (1 << 100) + int(rng.integers(0, 3))  # no node of the graph
+                e[int(rng.integers(0, k))] = e[0]  # a duplicate
+            return e
+
+        for _ in range(2):
+            liked, disliked = entries(int(rng.integers(0, 40))), entries(int(rng.integers(0, 20)))
+            if not liked and not disliked:
+                continue
+            normalized = bool(rng.integers(0, 2))
+            self_score = [None, 0.25, 3.0][int(rng.integers(0, 3))]
+            want = sref.literal(*graph, liked, disliked, normalized, 1.0 if self_score is None else self_score, bv=bv)
+            last = (liked + disliked)[(len(liked) + len(disliked) - 1) // 16 * 16:]
+            for mode in (None, "dense", "sparse"):
+                run = dict(what, liked=liked, disliked=disliked, normalized=normalized, self_score=self_score, mode=mode)
+                st = ctx.inbound_similarity(ids_from_ints(liked), ids_from_ints(disliked), normalized=normalized, self_score=self_score, mode=mode)
+                assert ctx.similarity_all().tobytes() == want.tobytes(), ("scores", run)
+                counts, bloom, length = ctx.debug_similarity_batch()
+                assert np.array_equal(counts[:, :len(last)], sref.counts(bv, ids, last)), ("counts of the last batch", run)
+                assert [int(x) for x in bloom] == [bv[v].fold() for v in ints], ("bloom", run)
+                assert [int(x) for x in length] == [len(bv[v].ranks) for v in ints], ("len", run)
+                what["passes"] += sum(st["levels_mode"])
+            asked = liked[:3] + [1 << 100, 5]
+            assert ctx.similarity_lookup(ids_from_ints(asked)).tobytes() == \
+                sref.lookup(bv, liked, disliked, normalized, 1.0 if self_score is None else self_score, asked).tobytes(), ("lookup", what)
+            k = int(rng.integers(1, n + 3))
+            tids, tvals = ctx.similarity_top(k)
+            order = sref.top_order(ids, want, k)
+            assert sref.id_ints(tids) == [v for _, v in order] and tvals.tolist() == [x for x, _ in order], ("top", what, k)
+    return what
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "distances", "betweenness"], default="passes")
+    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "distances", "betweenness", "similarity"], default="passes")
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-nodes", type=int, default=6000)
@@ -337,6 +390,8 @@ def main():
                 w = distances_case(rng, a.max_nodes, case)
             elif a.mode == "betweenness":
                 w = betweenness_case(rng, a.max_nodes, case)
+            elif a.mode == "similarity":
+                w = similarity_case(rng, a.max_nodes, case)
             elif a.mode == "ranks" or (a.mode == "mixed" and case % 6 == 4):
                 w = ranks_case(rng, a.max_nodes, case)
             elif a.mode == "tail" or (a.mode == "mixed" and case % 6 == 5):
