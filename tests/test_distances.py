@@ -217,6 +217,22 @@ def test_star_hubs_through_chunk_trees(gpu_ctx_factory, reversed):
         _check(ctx, [0, 1, leaf], reversed, modes=(None,))
 
 
+# the switch rule's constants can be overridden from the environment (read at every call): another sequence of steps, the same distances
+def test_switch_rule_overrides_from_the_environment(gpu_ctx_factory, monkeypatch):
+    with _ctx(gpu_ctx_factory, EdgeListGraph.from_tuples(graphs.lcg_graph())) as ctx:
+        ids, row_ptr, src = ctx.graph()
+        want = dref.bfs(len(ids), row_ptr, src, [5])
+        st = _run(ctx, ids, want, ids[[5]], False, None, None)
+        assert st["step"][1] == 0  # one frontier node against 1200 edges: top-down
+        monkeypatch.setenv("HB_DIST_ALPHA", "1000000000")
+        monkeypatch.setenv("HB_DIST_BETA", "1000000000")  # n_f * beta < n never holds
+        eager = _run(ctx, ids, want, ids[[5]], False, None, None)
+        assert all(eager["step"][1:]) and eager["levels"] == st["levels"]  # bottom-up from the first level on, and it never switches back
+        monkeypatch.setenv("HB_DIST_ALPHA", "0")  # not a number the rule can use: the built-in constant
+        monkeypatch.setenv("HB_DIST_BETA", "")
+        assert _run(ctx, ids, want, ids[[5]], False, None, None)["step"] == st["step"]
+
+
 # (6) layout variants give identical output
 @pytest.mark.parametrize("variant", ["chunk4", "no_reorder", "no_xcd_map", "host_plan", "host_ingest", "no_sparse"])
 def test_layout_variants(gpu_ctx_factory, variant):
@@ -305,6 +321,10 @@ def test_refusals(gpu_ctx_factory):
     with gpu_ctx_factory(flags=_lib.HB_FLAG_ALL_RELS) as ctx:
         refused(lambda: ctx.distances(_u128([graphs.A])))  # no graph loaded
         refused(lambda: ctx.distance_count())
+        ctx.load_edges(np.zeros(0, dtype=_lib.EDGE))  # an empty graph: every source is unknown, nothing is reached
+        ids, dist, st = ctx.distances(_u128([graphs.A, graphs.B]))
+        assert len(ids) == 0 and len(dist) == 0 and st["reached"] == 0 and st["unknown_sources"] == 2 and st["levels"] == 0
+        assert ctx.distance_count() == 0
     with _ctx(gpu_ctx_factory, graphs.fixture_graph()) as ctx:
         refused(lambda: ctx.distance_copy())  # no distances yet
         refused(lambda: ctx.distances(_u128([])))  # source_count == 0

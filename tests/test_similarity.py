@@ -3,6 +3,7 @@ the host restatement in tests/inbound_similarity_ref.py.
 
 Comparison rule: EVERYTHING is exact.  The counts of the last batch, the in-degrees and the blooms (the device's one u64 against the
 restatement's sixteen words folded) are compared as integers; every score bit for bit, zeros as +0.0."""
+import ctypes
 import json
 import os
 
@@ -291,6 +292,16 @@ def test_refusals(gpu_ctx_factory):
         refused(lambda: ctx.similarity_lookup(one), "hb_similarity_lookup")
         refused(lambda: ctx.debug_similarity_batch(), "hb_debug_copy_similarity_batch")
         refused(lambda: ctx.inbound_similarity())  # L + D == 0
+
+        def count_without_list(field):  # the C ABI itself: liked_count = 1 with liked == NULL (the Python layer never builds that)
+            o = _lib.HbSimilarityOptions()
+            o.struct_size = ctypes.sizeof(_lib.HbSimilarityOptions)
+            setattr(o, field, 1)
+            st = _lib.HbSimilarityStats()
+            st.struct_size = ctypes.sizeof(_lib.HbSimilarityStats)
+            ctx._check(ctx.lib.hb_inbound_similarity(ctx.h, ctypes.byref(o), ctypes.byref(st)))
+        refused(lambda: count_without_list("liked_count"))
+        refused(lambda: count_without_list("disliked_count"))
         refused(lambda: ctx.inbound_similarity(one, flags=_lib.HB_SIM_DENSE_ONLY | _lib.HB_SIM_SPARSE_ONLY))
         ctx.begin()
         ctx.step()

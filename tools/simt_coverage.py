@@ -3,7 +3,7 @@
 against the coverage build of the interpreted library (tests/simt, `make cov`: -fsanitize-coverage=trace-pc-guard,pc-table), every
 process leaves a <pid>.cov file, this tool merges them and maps the instrumented blocks to source lines through the DWARF line table (llvm-dwarfdump).
 
-usage: tools/simt_coverage.py [--select PYTEST_K_EXPRESSION] [--out FILE] [--list FILE.hip.h ...]
+usage: tools/simt_coverage.py [--tests TEST_FILE ...] [--select PYTEST_K_EXPRESSION] [--out FILE] [--list FILE.hip.h ...]
 prints, per source file under stract_amd/csrc, source lines reached / lines with code, and (--list) the lines no test reached."""
 import argparse
 import collections
@@ -22,6 +22,7 @@ DWARFDUMP = "/opt/rocm/lib/llvm/bin/llvm-dwarfdump"
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--select", default="not test_c2 and not test_caching_allocator_under_memory_pressure")
+    ap.add_argument("--tests", nargs="+", default=["tests/test_gpu.py"], help="test files to run, relative to the repository (default: tests/test_gpu.py)")
     ap.add_argument("--out", default="")
     ap.add_argument("--list", nargs="*", default=[])
     ap.add_argument("--extra", nargs="*", default=[], help="more commands to run under the coverage build (each one string)")
@@ -29,7 +30,7 @@ def main():
     subprocess.check_call(["make", "-s", "-j8", "-C", SIMT, "cov"])
     cov_dir = tempfile.mkdtemp(prefix="hb_cov_")
     env = dict(os.environ, HB_LIB_PATH=LIB, HB_ALLOW_SIMT_INTERPRETER="1", PYTHONPATH=ROOT, HB_SIMT_COV_DIR=cov_dir)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu.py"), "-m", "gpu", "-q", "-k", a.select, "-p", "no:cacheprovider"],
+    r = subprocess.run([sys.executable, "-m", "pytest"] + [os.path.join(ROOT, t) for t in a.tests] + ["-m", "gpu", "-q", "-k", a.select, "-p", "no:cacheprovider"],
                        env=env, cwd=ROOT, capture_output=True, text=True)
     summary = (r.stdout.strip().splitlines() or ["?"])[-1]
     for cmd in a.extra:
@@ -80,7 +81,7 @@ def main():
         seen[name].add(line)
         if ran[k]:
             reached[name].add(line)
-    out = ["tests: %s   (%s)" % (summary, a.select),
+    out = ["tests: %s   (%s; -k %s)" % (summary, " ".join(a.tests), a.select),
            "source lines with code, by file: reached by some test / all (a line counts as reached if any instantiation or inlined copy of it ran)",
            "%-24s %8s %8s %7s" % ("file", "reached", "lines", "share")]
     tot = [0, 0]
