@@ -13,7 +13,10 @@
 // lock step, here the fence is where the other lanes catch up), __syncthreads - and waits there.  When every live lane of a
 // wave waits, the lanes at the LOWEST code address are served together, as ONE operation with exactly those lanes active
 // ("min-PC" re-convergence: lanes that left a loop early wait at the code behind it until the others arrive, lanes inside
-// the loop keep being served), and continue.  Atomics are plain operations (one OS thread per launch).
+// the loop keep being served), and continue.  One exception: a quad whose live lanes all wait at the same DPP is served first,
+// whatever its address - a quad permutation needs its quad only, and the body of a quad-uniform branch inside a loop lies
+// BEHIND the loop's first wave-wide operation, where the lanes that skipped the branch already wait (simt_core.cpp).
+// Atomics are plain operations (one OS thread per launch).
 #pragma once
 #include <cstdint>
 #include <functional>

@@ -121,19 +121,42 @@ bool serve_wave(int w0, int w1)
         if (L.st == WAIT && L.kind != K_BLOCK_SYNC && (!site || L.site < site)) site = L.site;
     }
     if (!site) return false;
+    // A quad permutation needs the lanes of its quad only.  Where every live lane of a quad waits at the same DPP, that quad is served
+    // before anything else (the lowest such address first): the body of a quad-uniform branch inside a loop - hll_fold_quad behind
+    // `if (big)` in the tile loop of pass_kernel - lies at a HIGHER address than the loop's first wave-wide operation, where the lanes
+    // that skipped the branch already wait for the next iteration; min-PC alone would serve their ballot without the others, while
+    // on the machine the branch re-joins before the wave goes on.
+    const void *quad_site = nullptr;
+    bool quad_ok[16] = {};
+    for (int q0 = w0; q0 < w1; q0 += 4) {
+        const void *s = nullptr;
+        bool ok = true;
+        for (int i = q0; i < std::min(q0 + 4, w1) && ok; i++) {
+            const Lane &L = g.lanes[i];
+            if (L.st == DONE) continue;
+            if (L.st != WAIT || L.kind != K_DPP || (s && L.site != s)) ok = false;
+            else s = L.site;
+        }
+        if (ok && s) {
+            quad_ok[(q0 - w0) >> 2] = true;
+            if (!quad_site || s < quad_site) quad_site = s;
+        }
+    }
+    const bool quads_first = quad_site && quad_site != site;
+    if (quads_first) site = quad_site;
     bool in[64];
     int kind = 0, members = 0, live = 0;
     for (int i = w0; i < w1; i++) {
         const Lane &L = g.lanes[i];
         live += L.st != DONE;
-        in[i - w0] = L.st == WAIT && L.kind != K_BLOCK_SYNC && L.site == site;
+        in[i - w0] = L.st == WAIT && L.kind != K_BLOCK_SYNC && L.site == site && (!quads_first || quad_ok[(i - w0) >> 2]);
         if (in[i - w0]) {
             if (kind && kind != L.kind) die("lanes wait at one address with different operations");
             kind = L.kind;
             members++;
         }
     }
-    if (members < live) __atomic_fetch_add(&g_stats.partial_groups, 1, __ATOMIC_RELAXED);
+    if (members < live && !quads_first) __atomic_fetch_add(&g_stats.partial_groups, 1, __ATOMIC_RELAXED);
     __atomic_fetch_add(&g_stats.collectives, 1, __ATOMIC_RELAXED);
     uint64_t ballot = 0;
     if (kind == K_BALLOT)

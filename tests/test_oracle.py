@@ -569,3 +569,86 @@ def test_reference_bloom_filter_test():
         bf.insert(v)
     assert all(bf.contains(v) for v in (1, 2, 3, 4, 5))
     assert not any(bf.contains(v) for v in (6, 7, 8, 9, 10))
+
+
+# ---- the estimator at the register values only built ids reach (48..58, 65) -----------------------------------------------------
+def test_crafted_ids_set_the_register_they_name():
+    """graphs.crafted_id_low inverts FastHasher's multiplication: every register index x every value add() can give (1..58 and 65),
+    with random bits below the leading one, through the C oracle's add and the Python restatement's."""
+    rng = np.random.default_rng(17)
+    lows = set()
+    for index in range(64):
+        for value in list(range(1, 59)) + [65]:
+            low = graphs.crafted_id_low(index, value, int(rng.integers(0, 1 << 62)))
+            assert 0 <= low < 1 << 64
+            lows.add(low)
+            want = [0] * 64
+            want[index] = value
+            c = np.zeros(64, np.uint8)
+            hbo.hll_add(c, (int(rng.integers(1, 1 << 60)) << 64) | low)  # the high half is not hashed
+            py = pyref.hll_new()
+            pyref.hll_add(py, low)
+            assert c.tolist() == want and py == want, (index, value)
+    assert len(lows) == 64 * 59
+    assert graphs.crafted_id_low(0, 65) == 0 and graphs.crafted_id_low(39, 1, (1 << 57) - 1) != graphs.crafted_id_low(39, 1, 0)
+    for bad in (0, 59, 60, 63, 64, 66, -1):
+        with pytest.raises(ValueError):
+            graphs.crafted_id_low(3, bad)
+    with pytest.raises(ValueError):
+        graphs.crafted_id_low(64, 5)
+
+
+def _exact_size(reg):
+    """HyperLogLog<64>::size() of a counter without zero register whose estimate is above 320 (no linear counting, no bias table:
+    hyperloglog.rs:4494-4515), from exact rational arithmetic: float(Fraction) rounds correctly, as each f64 operation does."""
+    from fractions import Fraction
+    total = Fraction(0)
+    s = 0.0
+    for r in reg:  # the reference's left fold in f64, each step checked against the exactly rounded exact sum so far
+        total += Fraction(1, 1 << int(r))
+        s = float(Fraction(s) + Fraction(1, 1 << int(r)))
+    z = float(1 / Fraction(s))
+    e = float(Fraction(0.709 * 4096.0) * Fraction(z))
+    assert e > 320.0
+    return ((1 << 64) - 1 if e >= 2.0 ** 64 else int(e)), s == float(total)
+
+
+def test_estimator_matches_exact_arithmetic_at_extreme_registers():
+    """hbo.hll_sizes - the reference of every GPU comparison - on 2000 counters whose registers are all at least 30, against exact
+    arithmetic (fractions.Fraction) rounded once per f64 operation, Rust's saturating `as usize` included: exact match.  The left
+    fold's f64 sum equals the correctly rounded exact sum on every one of them (64 terms within 41 bits: exact in any order)."""
+    rng = np.random.default_rng(23)
+    regs = np.zeros((2000, 64), dtype=np.uint8)
+    values = np.array(list(range(30, 59)) + [65], dtype=np.uint8)
+    regs[0], regs[1], regs[2], regs[3] = 58, 65, 30, 48
+    regs[4] = 65
+    regs[4, 63] = 30
+    regs[5] = 58
+    regs[5, 0] = 65
+    regs[6:500] = rng.choice(values, (494, 64))                                      # anything add() can give from 30 up
+    regs[500:1000] = rng.choice(np.array([47, 48, 51, 55, 58, 65], np.uint8), (500, 64))  # around the device's `big` switch
+    regs[1000:1500] = rng.choice(np.array([58, 65], np.uint8), (500, 64))            # either side of 2^64
+    regs[1500:] = 65
+    for i in range(1500, 2000):                                                      # a few registers below an all-65 counter
+        regs[i, rng.choice(64, int(rng.integers(1, 6)), replace=False)] = rng.integers(52, 59, 1)[0]
+    got = hbo.hll_sizes(regs).tolist()
+    saturated = 0
+    for i, reg in enumerate(regs):
+        want, fold_is_exact = _exact_size(reg)
+        assert got[i] == want, (i, reg.tolist())
+        assert pyref.hll_size(reg.tolist()) == want, i
+        assert fold_is_exact, i
+        saturated += want == (1 << 64) - 1
+    assert got[1] == (1 << 64) - 1 and got[0] < (1 << 64) - 1 and 100 < saturated < 1500
+
+
+def test_extreme_register_graph_meets_its_conditions():
+    """tests/graphs.py extreme_register_graph (the graph of tests/test_extreme_registers.py), on the oracle alone: after pass 0 the
+    values above 47 are exactly 48, 51, 55, 58 and 65, at least 100 counters have one and no zero register, a size is 2^64 - 1 and
+    more are later, a Kahan sum reaches 2^63, the default plan has virtual rows, 40..50 passes, tiles that mix every kind of row."""
+    ref = graphs.extreme_reference()
+    assert ref.T == len(ref.passes) and not ref.passes[-1]["has"] and all(p["has"] for p in ref.passes[:-1])
+    assert 850 <= len(ref.ids) <= 1050
+    assert min(p["moved_big"] for p in ref.passes[:-1]) >= 1  # every pass but the last moves a counter with a register above 47
+    ids2 = graphs.extreme_register_graph(1)[0]
+    assert np.array_equal(ids2, ref.ids) and not np.array_equal(graphs.extreme_register_graph(2)[0]["lo"], ref.ids["lo"])

@@ -5,7 +5,11 @@ Runs against whatever library HB_LIB_PATH names: the gfx950 library on a GPU box
 interpreted test build of the device sources (tests/simt, with HB_ALLOW_SIMT_INTERPRETER=1; add the AddressSanitizer preload
 for the `make asan` build).  A failure prints the seed and case that reproduce it and makes the exit code non-zero.
 
-usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|distances|betweenness|similarity] [--seconds S] [--seed N] [--max-nodes N]"""
+--ids extreme relabels a random 10 to 50 % of each case's nodes (passes, ranks, records) with ids whose hash sets a chosen register to a chosen
+value, weighted towards 40..58 and 65 (tests/graphs.py crafted_id_low): the estimator's sequential fold, saturated sizes and the six-bit
+wire codes above 47, which ids 1..n never reach; mixed alternates between plain and extreme.
+
+usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|distances|betweenness|similarity] [--ids plain|extreme|mixed] [--seconds S] [--seed N] [--max-nodes N]"""
 import argparse
 import json
 import os
@@ -58,13 +62,35 @@ def big_graph(rng, max_nodes):
     return kind, sorted((a, b) for a, b in e if a != b)
 
 
-def one_case(rng, max_nodes, case):
+def crafted_low(rng):
+    """Low id half for a random register index and a value weighted towards 40..58 and 65."""
+    u = rng.random()
+    value = 65 if u < 0.2 else int(rng.integers(40, 59)) if u < 0.7 else int(rng.integers(1, 59))
+    return graphs.crafted_id_low(int(rng.integers(0, 64)), value, int(rng.integers(0, 1 << 62)))
+
+
+def relabel_extreme(rng, edges):
+    """The same graph with a random 10 to 50 % of its nodes under crafted ids; the high half tells apart ids whose low halves collide."""
+    nodes = sorted({x for e in edges for x in e})
+    picked = rng.choice(len(nodes), max(1, int(len(nodes) * rng.uniform(0.1, 0.5))), replace=False).tolist()
+    new, used = {}, set(nodes)
+    for k in picked:
+        low = crafted_low(rng)
+        new[nodes[k]] = low if low not in used else ((nodes[k] + 1) << 64) | low
+        used.add(low)
+    assert len(set(new.values())) == len(new)
+    return sorted((new.get(a, a), new.get(b, b)) for a, b in edges)
+
+
+def one_case(rng, max_nodes, case, extreme=False):
     if rng.random() < 0.5:
         kind, edges = graphs.random_graph(rng)
     else:
         kind, edges = big_graph(rng, max_nodes)
     if not edges:
         return None
+    if extreme:
+        edges = relabel_extreme(rng, edges)
     ids, row_ptr, src = graphs.dense_from_tuples(edges)
     chunk = int(rng.choice([4, 8, 16, 32, 64, 128, 256]))
     # (tune[1] above its low byte: switches of the experiments build, stract_amd/csrc/hb_experiments.h)
@@ -75,7 +101,7 @@ def one_case(rng, max_nodes, case):
     flags = 0
     for nm in names:
         flags |= getattr(_lib, "HB_FLAG_" + nm)
-    what = dict(case=case, kind=kind, n=int(len(ids)), m=int(len(src)), chunk=chunk, tune=tune, flags=names)
+    what = dict(case=case, kind=kind, n=int(len(ids)), m=int(len(src)), chunk=chunk, tune=tune, flags=names, extreme_ids=extreme)
     o = hbo.Dense(ids["lo"].copy(), row_ptr, src)
     with _lib.Context(flags=flags, chunk=chunk, tune=tune) as ctx:
         ctx.load_dense(ids, row_ptr, src)
@@ -105,7 +131,7 @@ SKIPPED_BITS = [8, 10, 11, 13, 14, 15, 16, 17, 18, 19, 21, 22]  # HB_SKIPPED_REL
 HARMLESS_BITS = [0, 1, 2, 3, 4, 5, 6, 7, 9, 12, 20]
 
 
-def records_case(rng, max_nodes, case):
+def records_case(rng, max_nodes, case, extreme=False):
     """The record boundary: a random stream of SmallEdge records - 128-bit ids (equal low halves, different high halves among them),
     duplicates of a pair with other flags before and after it, skipped and harmless rel flags, self links - handed over in random
     batches (hb_append_edges ... hb_finalize, the device ingest: hash table of provisional ids, one stable sort) or at once, with and
@@ -116,6 +142,14 @@ def records_case(rng, max_nodes, case):
     pool_hi = rng.integers(0, 3, n, dtype=np.uint64) if rng.random() < 0.5 else rng.integers(0, 1 << 63, n, dtype=np.uint64)
     if rng.random() < 0.3:
         pool_lo[: n // 2] = pool_lo[n // 2: n // 2 + n // 2]  # same low half, told apart only by the high half
+    if extreme:
+        used = set(pool_lo.tolist())
+        for k in rng.choice(n, max(1, int(n * rng.uniform(0.1, 0.5))), replace=False).tolist():
+            low = crafted_low(rng)
+            pool_lo[k] = low
+            if low in used:
+                pool_hi[k] = (1 << 40) + k
+            used.add(low)
     e = np.zeros(m, dtype=_lib.EDGE)
     a, b = rng.integers(0, n, m), rng.integers(0, n, m)
     if rng.random() < 0.5:  # a hub destination
@@ -134,7 +168,7 @@ def records_case(rng, max_nodes, case):
         e = e[rng.permutation(len(e))]
     fids, fvals, fst = hbo.faithful_run(e)
     how = int(rng.integers(0, 3))
-    what = dict(case=case, kind="records", records=int(len(e)), pool=n, how=("batches", "at once", "at once + node list")[how])
+    what = dict(case=case, kind="records", records=int(len(e)), pool=n, how=("batches", "at once", "at once + node list")[how], extreme_ids=extreme)
     flags_ctx = int(rng.choice([0, 0, _lib.HB_FLAG_HOST_INGEST, _lib.HB_FLAG_HOST_PLAN]))
     # hb_run: the tail pipeline (default) or one pass at a time (HB_X_NO_TAIL_PIPELINE), results in snapshots (HB_X_SNAPSHOT_EVERY_PASS) or at the end
     tune_ctx = (0, int(rng.choice([0, 0, _lib.HB_X_SNAPSHOT_EVERY_PASS, _lib.HB_X_NO_TAIL_PIPELINE, _lib.HB_X_SNAPSHOT_EVERY_PASS | _lib.HB_X_SHORT_FINAL_LIST | _lib.HB_X_ONE_SNAPSHOT, _lib.HB_X_SNAPSHOT_EVERY_PASS | _lib.HB_X_NO_TAIL_PIPELINE])) | int(rng.choice([0, 0, _lib.HB_X_TAIL_KERNEL, _lib.HB_X_TAIL_KERNEL_ANY])), int(rng.choice([0, 0, 101])), 0, 0, 0,
@@ -198,7 +232,7 @@ def tail_case(rng, case):
     return what
 
 
-def ranks_case(rng, max_nodes, case):
+def ranks_case(rng, max_nodes, case, extreme=False):
     """The multi-rank decompositions with R = 2..5 LOGICAL ranks on one device (the collective emulated by hb_debug_exchange): edge
     partition (all-reduce(max)), its changed-only form, destination partition (all-gather of the owned slices), its changed-only form;
     random graphs and layout knobs; after every pass all ranks must hold the oracle's registers, at the end the oracle's final list."""
@@ -206,13 +240,15 @@ def ranks_case(rng, max_nodes, case):
     kind, edges = graphs.random_graph(rng) if rng.random() < 0.5 else big_graph(rng, max(200, max_nodes // 3))
     if not edges:
         return None
+    if extreme:
+        edges = relabel_extreme(rng, edges)
     ids, row_ptr, src = graphs.dense_from_tuples(edges)
     world = int(rng.integers(2, 6))
     mode = str(rng.choice(["edge", "edge_changed", "dest", "dest_changed"]))
     flags = _lib.HB_FLAG_NO_RCCL | (_lib.HB_FLAG_DEST_PARTITION if mode.startswith("dest") else 0) | (_lib.HB_FLAG_CHANGED_ONLY if mode.endswith("_changed") else 0)
     chunk = int(rng.choice([8, 16, 64]))
     tune = (0, 0, int(rng.choice([0, 101])), int(rng.integers(4, 9)), int(rng.integers(1, 9)))
-    what = dict(case=case, kind="ranks:" + kind, n=int(len(ids)), m=int(len(src)), world=world, mode=mode, chunk=chunk, tune=tune)
+    what = dict(case=case, kind="ranks:" + kind, n=int(len(ids)), m=int(len(src)), world=world, mode=mode, chunk=chunk, tune=tune, extreme_ids=extreme)
     o = hbo.Dense(ids["lo"].copy(), row_ptr, src)
     split = dist.partition_dense_by_dest if mode.startswith("dest") else dist.partition_dense
     ctxs = []
@@ -376,6 +412,7 @@ def similarity_case(rng, max_nodes, case):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "distances", "betweenness", "similarity"], default="passes")
+    ap.add_argument("--ids", choices=["plain", "extreme", "mixed"], default="plain")
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-nodes", type=int, default=6000)
@@ -385,6 +422,7 @@ def main():
     done, edges, passes = 0, 0, 0
     case = 0
     while time.time() - t0 < a.seconds:
+        extreme = a.ids == "extreme" or (a.ids == "mixed" and case % 2 == 1)
         try:
             if a.mode == "distances":
                 w = distances_case(rng, a.max_nodes, case)
@@ -393,13 +431,13 @@ def main():
             elif a.mode == "similarity":
                 w = similarity_case(rng, a.max_nodes, case)
             elif a.mode == "ranks" or (a.mode == "mixed" and case % 6 == 4):
-                w = ranks_case(rng, a.max_nodes, case)
+                w = ranks_case(rng, a.max_nodes, case, extreme)
             elif a.mode == "tail" or (a.mode == "mixed" and case % 6 == 5):
                 w = tail_case(rng, case)
             elif a.mode == "records" or (a.mode == "mixed" and case % 3 == 2):
-                w = records_case(rng, a.max_nodes, case)
+                w = records_case(rng, a.max_nodes, case, extreme)
             else:
-                w = one_case(rng, a.max_nodes, case)
+                w = one_case(rng, a.max_nodes, case, extreme)
         except AssertionError as e:
             print(json.dumps({"failed": str(e.args[0] if e.args else e), "seed": a.seed, "cases_before": done}))
             sys.exit(1)
@@ -408,7 +446,7 @@ def main():
             done += 1
             edges += w["m"]
             passes += w["passes"]
-    print(json.dumps({"library": _lib.LIB_PATH, "mode": a.mode, "seed": a.seed, "seconds": round(time.time() - t0, 1), "cases": done, "edges": edges, "passes_compared": passes, "failed": None}))
+    print(json.dumps({"library": _lib.LIB_PATH, "mode": a.mode, "ids": a.ids, "seed": a.seed, "seconds": round(time.time() - t0, 1), "cases": done, "edges": edges, "passes_compared": passes, "failed": None}))
 
 
 if __name__ == "__main__":
