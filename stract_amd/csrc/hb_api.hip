@@ -242,8 +242,8 @@ struct GraphDeviceState {
     // sums and the last result, dev_alloc'ed at the first call after a load
     struct SimilarityState {
         bool ready = false;      // the buffers below exist and the per-graph state is built
-        bool valid = false;      // they hold the result of a finished hb_inbound_similarity
-        bool batch_live = false; // d_regs[1] / d_bits[1] still hold the last batch's counts (hb_begin and the other walks clear this)
+        bool valid = false;      // they hold the result of a finished hb_inbound_similarity (its last batch's counts lie in d_regs[1] / d_bits[1]
+                                 // while rows == RowsOf::Similarity)
         uint8_t *d_pos = nullptr;              // n_pad: h & 63 of the row's low id word
         uint64_t *d_bloom = nullptr;           // rows_total: OR of 1 << pos over the in-list (chunk rows: their partial)
         uint32_t *d_vmask = nullptr;           // nv: seed: the anchor slots whose in-list runs through the chunk row
@@ -275,6 +275,9 @@ enum PassEvent {
     kEvLevel1,     // the first hub-chunk level is done (sweep passes: seed collection + expansion)
     kEvSlots
 };
+
+enum class RowsOf : uint8_t { Nobody, HyperBall, Sampled, Brandes, Similarity }; // hb_ctx::rows
+enum class Image : uint8_t { None, HyperBall, Sampled };                        // hb_ctx::image
 
 struct hb_ctx : GraphDeviceState {
     // ---- context lifetime: hb_create .. hb_destroy ------------------------------------------------------------------------------------
@@ -321,7 +324,13 @@ struct hb_ctx : GraphDeviceState {
     IngestStream app;
     DenseGraph g;                  // ids kept; row_ptr/src kept only for hb_debug_copy_graph
     Plan plan;
-    bool loaded = false, begun = false, finished = false;
+    bool loaded = false;
+    // who wrote d_regs / d_part / d_bits / the touch bitmap / the sweep scratch last, what d_out / h_out / res_count hold, and whether a
+    // HyperBall run is open (hb_begin .. hb_finish).  Written by hb_begin, hb_finish, claim_rows and take_image (hb_api_walk.inc) and by
+    // a load, by nobody else; DESIGN.md section 18 has the table of calls and states
+    RowsOf rows = RowsOf::Nobody;
+    Image image = Image::None;
+    bool run_open = false;
     std::vector<DevBuf> allocs;   // what dev_alloc / adopt gave the graph state above; hb_stats.device_bytes is their sum
     uint64_t m_global = 0;        // edges of the whole graph (all ranks)
     uint64_t plan_entries = 0; // entries of all work rows' source lists
@@ -1167,6 +1176,10 @@ int hb_begin(hb_ctx *c)
         const Plan &p = c->plan;
         if (p.n_pad * 4 >= 0xFFFFFFFFull) return fail(c, HB_ERR_LIMIT, "more than 2^30 nodes: init_kernel is one quad per node in one dispatch");
         if ((rc = refuse_stale_error(c, "hb_begin"))) return rc;
+        // the rows are nobody's until the initial state is complete (an error return below leaves them so)
+        c->rows = RowsOf::Nobody;
+        c->run_open = false;
+        c->tl_valid = c->tl_declined = false;
         // d_part needs no clearing: pass 0 is always dense, and a dense pass overwrites every partial without
         // reading it (hb_kernels.hip.h)
         HB_HIP(hipMemsetAsync(c->d_bits[0], 0, c->bits_words * 4, c->stream));
@@ -1220,11 +1233,10 @@ int hb_begin(hb_ctx *c)
         c->pending_times.clear();
         c->pipelined_passes = 0;
         c->tail_kernel_passes = 0;
-        c->tl_valid = c->tl_declined = false;
-        c->begun = true;
-        c->finished = false;
+        c->rows = RowsOf::HyperBall;
+        c->run_open = true;
+        c->image = Image::None;
         c->res_count = 0;
-        c->sim.batch_live = false; // (the counts of hb_inbound_similarity's last batch lay in the registers)
         return HB_OK;
     });
 }
@@ -1272,7 +1284,7 @@ int hb_finish(hb_ctx *c)
 {
     return guarded(c, [&]() -> int {
         if (!c) return HB_ERR_INVALID;
-        if (!c->begun) return fail(c, HB_ERR_INVALID, "hb_finish: call hb_begin first");
+        if (c->rows != RowsOf::HyperBall) return fail(c, HB_ERR_INVALID, "hb_finish: call hb_begin first");
         int rc = set_device(c);
         if (rc) return rc;
         const Plan &p = c->plan;
@@ -1358,7 +1370,8 @@ int hb_finish(hb_ctx *c)
         c->stats.ms_loop_gpu = g;
         c->stats.ms_collective = coll;
         c->stats.wire_bytes = c->wire_bytes;
-        c->finished = true;
+        c->run_open = false;
+        c->image = Image::HyperBall;
         return HB_OK;
     });
 }
@@ -1425,7 +1438,7 @@ int hb_result_count(hb_ctx *c, uint64_t *count)
 {
     return guarded(c, [&]() -> int {
         if (!c || !count) return HB_ERR_INVALID;
-        if (!c->finished) return fail(c, HB_ERR_INVALID, "no results: hb_run / hb_finish not called");
+        if (c->image == Image::None) return fail(c, HB_ERR_INVALID, "no results: hb_run / hb_finish not called");
         *count = c->res_count;
         return HB_OK;
     });
@@ -1435,7 +1448,7 @@ int hb_result_copy(hb_ctx *c, hb_u128 *ids, double *vals, uint64_t cap)
 {
     return guarded(c, [&]() -> int {
         if (!c) return HB_ERR_INVALID;
-        if (!c->finished) return fail(c, HB_ERR_INVALID, "no results: hb_run / hb_finish not called");
+        if (c->image == Image::None) return fail(c, HB_ERR_INVALID, "no results: hb_run / hb_finish not called");
         // compaction of the per-node array (absent = negative) into the caller's buffers, on the host cores the process may use
         // (C4: 99 M nodes -> 79 M results = 1.9 GB written; one thread took 1.3 s of the 15 s chain store -> load -> run -> store)
         host_compact_results(c->h_out, c->g.ids.data(), c->plan.n, ids, vals, cap, c->h_in_bits.empty() ? nullptr : c->h_in_bits.data());
@@ -1447,7 +1460,7 @@ int hb_result_ranks(hb_ctx *c, uint64_t *ranks, uint64_t cap)
 {
     return guarded(c, [&]() -> int {
         if (!c || (cap && !ranks)) return HB_ERR_INVALID;
-        if (!c->finished) return fail(c, HB_ERR_INVALID, "no results: hb_run / hb_finish not called");
+        if (c->image == Image::None) return fail(c, HB_ERR_INVALID, "no results: hb_run / hb_finish not called");
         if (cap < c->res_count) return fail(c, HB_ERR_INVALID, "hb_result_ranks: cap < hb_result_count");
         int rc = set_device(c);
         if (rc) return rc;
@@ -1461,7 +1474,7 @@ int hb_result_top(hb_ctx *c, uint64_t k, hb_u128 *ids, double *vals, uint64_t *w
 {
     return guarded(c, [&]() -> int {
         if (!c) return HB_ERR_INVALID;
-        if (!c->finished) return fail(c, HB_ERR_INVALID, "no results: hb_run / hb_finish not called");
+        if (c->image == Image::None) return fail(c, HB_ERR_INVALID, "no results: hb_run / hb_finish not called");
         int rc = set_device(c);
         if (rc) return rc;
         const uint64_t top = std::min<uint64_t>(k, c->res_count);
@@ -1500,7 +1513,7 @@ int hb_store_harmonic_results(hb_ctx *c, const char *output, char *err, uint64_t
     if (err && err_len) err[0] = 0;
     const int rc = guarded(c, [&]() -> int {
         if (!c || !output || !*output) return c ? fail(c, HB_ERR_INVALID, "hb_store_harmonic_results: output is empty") : HB_ERR_INVALID;
-        if (!c->finished) return fail(c, HB_ERR_INVALID, "no results: hb_run / hb_finish not called");
+        if (c->image == Image::None) return fail(c, HB_ERR_INVALID, "no results: hb_run / hb_finish not called");
         int rc2 = set_device(c);
         if (rc2) return rc2;
         const uint64_t k = c->res_count;

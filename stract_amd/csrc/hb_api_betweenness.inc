@@ -1,8 +1,8 @@
 // hb_api_betweenness.inc - part of the hb_api.hip translation unit (included at its end; uses its hb_ctx and helpers).
 // hb_betweenness: Betweenness::calculate (crates/core/src/webgraph/centrality/betweenness.rs:29-146) on the loaded graph - Brandes'
 // algorithm, eight sources per batch in the 64-byte rows of the HyperBall plan (kernels: hb_betweenness.hip.h).  Definitions:
-// include/hyperball.h.  The walk borrows d_regs / d_part / the changed bitmaps / the sweep scratch as hb_sampled_harmonic does (hb_begin
-// rewrites them); everything it keeps - the per-batch state, the sums, the result - lives in buffers of its own.
+// include/hyperball.h.  The walk borrows d_regs / d_part / the changed bitmaps / the sweep scratch as hb_sampled_harmonic does
+// (claim_rows); everything it keeps - the per-batch state, the sums, the result - lives in buffers of its own.
 
 namespace {
 
@@ -77,7 +77,6 @@ int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_
     hb_betweenness_options o{};
     copy_in(opt_in, &o);
     int rc;
-    if ((rc = walk_prologue(c, "hb_betweenness"))) return rc;
     if ((o.flags & HB_BC_DENSE_ONLY) && (o.flags & HB_BC_SPARSE_ONLY))
         return fail(c, HB_ERR_INVALID, "hb_betweenness: HB_BC_DENSE_ONLY and HB_BC_SPARSE_ONLY exclude each other");
     const Plan &p = c->plan;
@@ -110,12 +109,9 @@ int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_
     }
     if ((rc = betweenness_alloc(c))) return rc;
     const uint64_t n_pad = p.n_pad, rows_total = p.n_pad + p.nv;
-    const size_t nlev = p.level_begin.size() > 1 ? p.level_begin.size() - 1 : 0;
     HB_HIP(hipMemsetAsync(b.d_sum, 0, n_pad * sizeof(double), c->stream));
     HB_HIP(hipMemsetAsync(b.d_reached, 0, n_pad, c->stream));
-    // from here on the HyperBall state is gone: hb_step needs a new hb_begin, the tail kernel's lists describe nothing
-    c->begun = false;
-    c->tl_valid = false;
+    claim_rows(c, RowsOf::Brandes);
     unsigned long long *h = c->h_counters; // (pinned words of the context; hb_run rewrites them before it reads them)
     auto virt_grid = [&](uint64_t lo, uint64_t hi) { return dim3(grid_blocks(c, ((hi - lo + 31) / 32 + 3) / 4, 8, 1)); };
     for (uint64_t b0 = 0; b0 < S; b0 += hbk::kBcLanes) {
@@ -212,14 +208,11 @@ int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_
                 hipLaunchKernelGGL(hbk::bc_back_heavy_finish_kernel, dim3((kp.heavy_cap * 4 + 255) / 256), dim3(256), 0, c->stream, kp);
             }
             if (d > 1) { // the coefficients of level d - 1 down the chunk trees: the highest virtual level first
-                for (size_t k = 0; k < nlev; k++) {
-                    const size_t l = nlev - 1 - k;
-                    kp.row_lo = p.level_begin[l];
-                    kp.row_hi = p.level_begin[l + 1];
-                    if (kp.row_hi > kp.row_lo)
-                        hipLaunchKernelGGL(hbk::bc_back_virt_kernel, virt_grid(kp.row_lo, kp.row_hi), dim3(256), 0, c->stream, kp, (const hbk::bc_d2 *)c->d_regs[cb ^ 1],
-                                           c->d_bits[cb ^ 1]);
-                }
+                for_each_virtual_level(p, false, [&](uint64_t lo, uint64_t hi) {
+                    kp.row_lo = lo;
+                    kp.row_hi = hi;
+                    hipLaunchKernelGGL(hbk::bc_back_virt_kernel, virt_grid(lo, hi), dim3(256), 0, c->stream, kp, (const hbk::bc_d2 *)c->d_regs[cb ^ 1], c->d_bits[cb ^ 1]);
+                });
             }
             HB_HIP(hipGetLastError());
             st.levels_backward++;
@@ -248,23 +241,14 @@ extern "C" {
 
 int hb_betweenness(hb_ctx *c, const hb_betweenness_options *opt, hb_betweenness_stats *stats)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        int rc = set_device(c);
-        if (rc) return rc;
-        if ((rc = run_in_progress(c, "hb_betweenness"))) return rc;
-        return betweenness(c, opt, stats);
-    });
+    return operator_entry(c, "hb_betweenness", [&]() { return betweenness(c, opt, stats); });
 }
 
 int hb_betweenness_count(hb_ctx *c, uint64_t *count)
 {
     return guarded(c, [&]() -> int {
-        if (!c || !count) return c ? fail(c, HB_ERR_INVALID, "hb_betweenness_count: count == NULL") : HB_ERR_INVALID;
-        int rc = result_ready(c, c->btw.valid, "hb_betweenness_count", kNoBetweenness);
-        if (rc) return rc;
-        *count = c->btw.results;
-        return HB_OK;
+        if (!c) return HB_ERR_INVALID;
+        return result_count(c, c->btw.valid, "hb_betweenness_count", kNoBetweenness, count, c->btw.results);
     });
 }
 
@@ -290,15 +274,8 @@ int hb_betweenness_copy(hb_ctx *c, hb_u128 *ids, double *vals, uint64_t cap)
 int hb_betweenness_all(hb_ctx *c, double *vals, uint64_t cap)
 {
     return guarded(c, [&]() -> int {
-        if (!c || !vals) return c ? fail(c, HB_ERR_INVALID, "hb_betweenness_all: vals == NULL") : HB_ERR_INVALID;
-        int rc = result_ready(c, c->btw.valid, "hb_betweenness_all", kNoBetweenness);
-        if (rc) return rc;
-        const uint64_t n = c->plan.n;
-        if (cap < n) return fail(c, HB_ERR_INVALID, "hb_betweenness_all: cap < n");
-        if (!n) return HB_OK;
-        HB_HIP(hipMemcpyAsync(vals, c->btw.d_val_sid, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HB_HIP(hipStreamSynchronize(c->stream));
-        return HB_OK;
+        if (!c) return HB_ERR_INVALID;
+        return result_all<double>(c, c->btw.valid, "hb_betweenness_all", "vals", kNoBetweenness, vals, cap, c->btw.d_val_sid);
     });
 }
 

@@ -5,7 +5,7 @@ int hb_debug_copy_registers(hb_ctx *c, uint8_t *out)
 {
     return guarded(c, [&]() -> int {
         if (!c || !out) return HB_ERR_INVALID;
-        if (!c->begun) return fail(c, HB_ERR_INVALID, "call hb_begin first");
+        if (c->rows != RowsOf::HyperBall) return fail(c, HB_ERR_INVALID, "call hb_begin first");
         int rc = set_device(c);
         if (rc) return rc;
         if ((rc = ensure_initial_state(c))) return rc;
@@ -26,7 +26,7 @@ int hb_debug_copy_kahan(hb_ctx *c, double *sum, double *err)
 {
     return guarded(c, [&]() -> int {
         if (!c) return HB_ERR_INVALID;
-        if (!c->begun) return fail(c, HB_ERR_INVALID, "call hb_begin first");
+        if (c->rows != RowsOf::HyperBall) return fail(c, HB_ERR_INVALID, "call hb_begin first");
         int rc = set_device(c);
         if (rc) return rc;
         if ((rc = ensure_initial_state(c))) return rc;
@@ -48,7 +48,7 @@ int hb_debug_copy_sizes(hb_ctx *c, uint64_t *out)
 {
     return guarded(c, [&]() -> int {
         if (!c || !out) return HB_ERR_INVALID;
-        if (!c->begun) return fail(c, HB_ERR_INVALID, "call hb_begin first");
+        if (c->rows != RowsOf::HyperBall) return fail(c, HB_ERR_INVALID, "call hb_begin first");
         int rc = set_device(c);
         if (rc) return rc;
         if ((rc = ensure_initial_state(c))) return rc;
@@ -100,7 +100,7 @@ int hb_debug_state_hash(hb_ctx *c, uint64_t out[2])
 {
     return guarded(c, [&]() -> int {
         if (!c || !out) return HB_ERR_INVALID;
-        if (!c->begun) return fail(c, HB_ERR_INVALID, "call hb_begin first");
+        if (c->rows != RowsOf::HyperBall) return fail(c, HB_ERR_INVALID, "call hb_begin first");
         int rc = set_device(c);
         if (rc) return rc;
         if ((rc = ensure_initial_state(c))) return rc;

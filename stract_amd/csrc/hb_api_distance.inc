@@ -58,13 +58,12 @@ int distance_indegrees(hb_ctx *c)
     if (!d.d_indeg && (rc = dev_alloc(c, &d.d_indeg, rows_total))) return rc;
     HB_HIP(hipMemsetAsync(d.d_indeg, 0, std::max<uint64_t>(rows_total, 1) * sizeof(uint32_t), c->stream));
     auto launch = [&](uint64_t lo, uint64_t hi) {
-        if (hi <= lo) return;
         const unsigned blocks = grid_blocks(c, (hi - lo + 255) / 256, 8);
         hipLaunchKernelGGL(hbk::bfs_indegree_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr, (const uint32_t *)c->d_src, d.d_indeg,
                            p.n_pad, rows_total, lo, hi);
     };
-    for (size_t l = 0; l + 1 < p.level_begin.size(); l++) launch(p.level_begin[l], p.level_begin[l + 1]);
-    launch(0, p.n_pad);
+    for_each_virtual_level(p, true, launch); // ascending: a chunk row sums the counts of the chunk rows below it
+    if (p.n_pad) launch(0, p.n_pad);
     HB_HIP(hipGetLastError());
     d.indeg_valid = true;
     return HB_OK;
@@ -76,7 +75,6 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
     hb_distance_options o{};
     copy_in(opt_in, &o);
     int rc;
-    if ((rc = walk_prologue(c, "hb_distances"))) return rc;
     if (!o.sources || !o.source_count) return fail(c, HB_ERR_INVALID, "hb_distances: no sources (source_count == 0)");
     if ((o.flags & HB_DIST_TOP_DOWN_ONLY) && (o.flags & HB_DIST_BOTTOM_UP_ONLY))
         return fail(c, HB_ERR_INVALID, "hb_distances: HB_DIST_TOP_DOWN_ONLY and HB_DIST_BOTTOM_UP_ONLY exclude each other");
@@ -150,7 +148,6 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
         const uint64_t words = (hi - lo + 31) / 32;
         return dim3(grid_blocks(c, (words + words_per_block - 1) / words_per_block, 8, 1));
     };
-    const size_t nlev = p.level_begin.size() > 1 ? p.level_begin.size() - 1 : 0;
     HB_HIP(hipEventRecord(c->ev[kEvStart], c->stream));
     for (uint32_t lvl = 1; lvl <= d_max && n_f; lvl++) {
         // the step: Beamer's rule, with hysteresis (a bottom-up phase ends only when the frontier is small AND shrinking)
@@ -170,20 +167,18 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
             hipLaunchKernelGGL((hbk::bfs_push_kernel<false>), grid_words(0, n_pad, 256), dim3(256), 0, c->stream, bp);
             if (bp.heavy_cap) hipLaunchKernelGGL(hbk::bfs_push_heavy_kernel, dim3((unsigned)c->num_cu * 4), dim3(256), 0, c->stream, bp);
             bp.heavy_cap = 0;
-            for (size_t k = 0; k < nlev; k++) {
-                const size_t l = reversed ? nlev - 1 - k : k;
-                bp.row_lo = p.level_begin[l];
-                bp.row_hi = p.level_begin[l + 1];
-                if (bp.row_hi > bp.row_lo) hipLaunchKernelGGL((hbk::bfs_push_kernel<true>), grid_words(bp.row_lo, bp.row_hi, 256), dim3(256), 0, c->stream, bp);
-            }
+            for_each_virtual_level(p, !reversed, [&](uint64_t lo, uint64_t hi) {
+                bp.row_lo = lo;
+                bp.row_hi = hi;
+                hipLaunchKernelGGL((hbk::bfs_push_kernel<true>), grid_words(lo, hi, 256), dim3(256), 0, c->stream, bp);
+            });
         } else {
             // the virtual rows' bits first (ascending forward: a chunk looks at its sources; descending reversed: at its readers)
-            for (size_t k = 0; k < nlev; k++) {
-                const size_t l = reversed ? nlev - 1 - k : k;
-                bp.row_lo = p.level_begin[l];
-                bp.row_hi = p.level_begin[l + 1];
-                if (bp.row_hi > bp.row_lo) hipLaunchKernelGGL((hbk::bfs_pull_kernel<true>), grid_words(bp.row_lo, bp.row_hi, 4), dim3(256), 0, c->stream, bp);
-            }
+            for_each_virtual_level(p, !reversed, [&](uint64_t lo, uint64_t hi) {
+                bp.row_lo = lo;
+                bp.row_hi = hi;
+                hipLaunchKernelGGL((hbk::bfs_pull_kernel<true>), grid_words(lo, hi, 4), dim3(256), 0, c->stream, bp);
+            });
             bp.row_lo = 0;
             bp.row_hi = n_pad;
             hipLaunchKernelGGL((hbk::bfs_pull_kernel<false>), grid_words(0, n_pad, 4), dim3(256), 0, c->stream, bp);
@@ -243,23 +238,14 @@ extern "C" {
 
 int hb_distances(hb_ctx *c, const hb_distance_options *opt, hb_distance_stats *stats)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        int rc = set_device(c);
-        if (rc) return rc;
-        if ((rc = run_in_progress(c, "hb_distances"))) return rc;
-        return distances(c, opt, stats);
-    });
+    return operator_entry(c, "hb_distances", [&]() { return distances(c, opt, stats); });
 }
 
 int hb_distance_count(hb_ctx *c, uint64_t *count)
 {
     return guarded(c, [&]() -> int {
-        if (!c || !count) return c ? fail(c, HB_ERR_INVALID, "hb_distance_count: count == NULL") : HB_ERR_INVALID;
-        int rc = result_ready(c, c->dst.valid, "hb_distance_count", kNoDistances);
-        if (rc) return rc;
-        *count = c->dst.reached;
-        return HB_OK;
+        if (!c) return HB_ERR_INVALID;
+        return result_count(c, c->dst.valid, "hb_distance_count", kNoDistances, count, c->dst.reached);
     });
 }
 
@@ -286,16 +272,8 @@ int hb_distance_copy(hb_ctx *c, hb_u128 *ids, uint8_t *dist, uint64_t cap)
 int hb_distance_all(hb_ctx *c, uint8_t *dist, uint64_t cap)
 {
     return guarded(c, [&]() -> int {
-        if (!c || !dist) return c ? fail(c, HB_ERR_INVALID, "hb_distance_all: dist == NULL") : HB_ERR_INVALID;
-        int rc = result_ready(c, c->dst.valid, "hb_distance_all", kNoDistances);
-        if (rc) return rc;
-        const uint64_t n = c->plan.n;
-        if (cap < n) return fail(c, HB_ERR_INVALID, "hb_distance_all: cap < n");
-        if (!n) return HB_OK;
-        if ((rc = distance_extract(c))) return rc;
-        HB_HIP(hipMemcpyAsync(dist, c->dst.d_by_sid, n, hipMemcpyDeviceToHost, c->stream));
-        HB_HIP(hipStreamSynchronize(c->stream));
-        return HB_OK;
+        if (!c) return HB_ERR_INVALID;
+        return result_all<uint8_t>(c, c->dst.valid, "hb_distance_all", "dist", kNoDistances, dist, cap, c->dst.d_by_sid, distance_extract);
     });
 }
 

@@ -115,7 +115,9 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
 {
     const uint64_t n = c->g.ids.size();
     c->loaded = false;
-    c->begun = c->finished = false;
+    c->rows = RowsOf::Nobody;
+    c->image = Image::None;
+    c->run_open = false;
     free_graph_buffers(c);
     c->stats.n = n;
     c->stats.m_input = c->g.m_input;

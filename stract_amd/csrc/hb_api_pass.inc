@@ -659,7 +659,7 @@ int bloom_frontier_prelude(hb_ctx *c)
 
 int step_local(hb_ctx *c)
 {
-    if (!c->begun || c->finished) return fail(c, HB_ERR_INVALID, "hb_step*: call hb_begin first");
+    if (!c->run_open) return fail(c, HB_ERR_INVALID, "hb_step*: call hb_begin first");
     c->tl_valid = false;    // (the bitmaps are about to be rewritten by other kernels: the tail kernel's lists no longer describe them)
     c->tl_declined = false;
     if (c->pending_local) return fail(c, HB_ERR_INVALID, "hb_step_local called twice");
@@ -881,7 +881,7 @@ int tail_kernel_run(hb_ctx *, uint32_t, uint32_t *ran)
 bool tail_kernel_ready(const hb_ctx *c)
 {
     // (last_active = A_{t+1} = the out-degree sum of the changed nodes = the entries of their reader lists: every edge sits in one work row)
-    return c->begun && !c->finished && c->has_changes && c->t > 0 && c->last_changed <= hbk::kTailSeeds && c->last_active <= hbk::kTailReaders &&
+    return c->run_open && c->has_changes && c->t > 0 && c->last_changed <= hbk::kTailSeeds && c->last_active <= hbk::kTailReaders &&
            c->sparse_ok && !c->tl_declined &&
            c->d_tl_count && !multi_rank(c) && !linked(c) && !unfused(c) && !ref_tail(c) && !(c->opt.flags & (HB_FLAG_PASS_STATS | HB_FLAG_NO_FRONTIER)) &&
            xbit(c, HB_X_TAIL_KERNEL | HB_X_TAIL_KERNEL_ANY) && // OFF by default (measured: no faster than the launches it replaces, DESIGN.md §3)
@@ -979,7 +979,7 @@ int tail_kernel_run(hb_ctx *c, uint32_t budget, uint32_t *ran)
 // `last_changed <= 4096` kernel choice of the queued pass come from pass q - 1; every choice gives the same bits (SURVEY App. C-1).
 bool tail_pipeline_ready(const hb_ctx *c)
 {
-    return c->begun && !c->finished && c->has_changes && c->t > 0 && c->cur_mode == 2 && c->last_changed <= 4096 && c->sparse_ok && !multi_rank(c) &&
+    return c->run_open && c->has_changes && c->t > 0 && c->cur_mode == 2 && c->last_changed <= 4096 && c->sparse_ok && !multi_rank(c) &&
            !linked(c) && !unfused(c) && !ref_tail(c) && !(c->opt.flags & HB_FLAG_PASS_STATS) && !xbit(c, HB_X_NO_TAIL_PIPELINE) &&
            c->t + 2 < c->max_passes;
 }

@@ -93,9 +93,7 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
     hb_sample_options o{};
     copy_in(opt_in, &o);
     int rc;
-    if ((rc = walk_prologue(c, "hb_sampled_harmonic", ""))) return rc;
-    if (c->rs_stream) HB_HIP(hipStreamSynchronize(c->rs_stream)); // (no result snapshot of an earlier run may still be landing in h_out)
-    c->rs.valid = false;
+    c->smp.levels = 0; // (no histogram while this call runs, and none after a refusal; an earlier result image stays until take_image)
     const uint32_t max_dist = o.max_dist ? o.max_dist : 7; // approx_harmonic.rs:62
     if (max_dist > hbk::kSampleMaxLevels - 1) return fail(c, HB_ERR_LIMIT, "hb_sampled_harmonic: max_dist > 15");
     const uint32_t D = sample_levels(max_dist);
@@ -115,6 +113,7 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
     } else if ((rc = sample_sids(c, o.seed, k_req, &sids))) {
         return rc;
     }
+    if ((rc = take_image(c))) return rc; // (every refusal lies above: a refused call leaves the earlier result where it is)
     // weights, f32 exactly as approx_harmonic.rs:57,69 writes them (norm from the REQUESTED sample count)
     const float norm = (float)N / ((float)k_req * ((float)N - 1.0f));
     double w[hbk::kSampleMaxLevels] = {0};
@@ -130,6 +129,7 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
     st.sources = sids.size();
     const uint64_t S = sids.size();
     unsigned long long *h = c->h_counters; // (pinned words of the context; hb_run rewrites them before it reads them)
+    claim_rows(c, RowsOf::Sampled);
     for (uint64_t b0 = 0; b0 < S; b0 += hbk::kSampleBatch) {
         const uint32_t count = (uint32_t)std::min<uint64_t>(hbk::kSampleBatch, S - b0);
         st.batches++;
@@ -188,8 +188,7 @@ int sampled_harmonic(hb_ctx *c, const hb_sample_options *opt_in, hb_sample_stats
         c->res_count = 0;
     }
     sm.levels = D;
-    c->begun = false; // (the HyperBall state is gone: hb_step needs a new hb_begin)
-    c->finished = true;
+    c->image = Image::Sampled;
     st.results = c->res_count;
     st.ms_total = now_ms() - t0;
     copy_out(st_out, st);
@@ -202,15 +201,7 @@ extern "C" {
 
 int hb_sampled_harmonic(hb_ctx *c, const hb_sample_options *opt, hb_sample_stats *stats)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        int rc = set_device(c);
-        if (rc) return rc;
-        if ((rc = run_in_progress(c, "hb_sampled_harmonic"))) return rc;
-        c->finished = false; // (a refusal leaves no result behind)
-        c->smp.levels = 0;
-        return sampled_harmonic(c, opt, stats);
-    });
+    return operator_entry(c, "hb_sampled_harmonic", [&]() { return sampled_harmonic(c, opt, stats); }, "");
 }
 
 int hb_sample_sources(hb_ctx *c, uint64_t seed, uint64_t k, hb_u128 *out, uint64_t *written)
@@ -233,7 +224,7 @@ int hb_debug_sample_histogram(hb_ctx *c, uint16_t *out)
 {
     return guarded(c, [&]() -> int {
         if (!c || !out) return HB_ERR_INVALID;
-        if (!c->finished || !c->smp.levels) return fail(c, HB_ERR_INVALID, "hb_debug_sample_histogram: no sampled result (call hb_sampled_harmonic)");
+        if (!c->smp.levels) return fail(c, HB_ERR_INVALID, "hb_debug_sample_histogram: no sampled result (call hb_sampled_harmonic)");
         int rc = set_device(c);
         if (rc) return rc;
         const Plan &p = c->plan;

@@ -2,7 +2,7 @@
 // hb_inbound_similarity: Scorer (crates/core/src/ranking/inbound_similarity.rs:61-138) over BitVec (ranking/bitvec_similarity.rs:131-189)
 // for every node of the loaded graph - sixteen liked / disliked hosts per batch in the 64-byte rows of the HyperBall plan, one level of
 // the shared walk per batch (kernels: hb_similarity.hip.h).  Definitions: include/hyperball.h.  The walk borrows d_regs / d_part / the
-// changed bitmaps / the sweep scratch as hb_betweenness does (hb_begin rewrites them); the per-graph state, the sums and the result live
+// changed bitmaps / the sweep scratch as hb_betweenness does (claim_rows); the per-graph state, the sums and the result live
 // in buffers of their own.
 
 namespace {
@@ -32,12 +32,11 @@ int similarity_alloc(hb_ctx *c, double *ms_out)
     hipLaunchKernelGGL(hbk::sim_pos_kernel, dim3(grid_blocks(c, (p.n_pad + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint64_t *)c->d_idlow,
                        (const uint32_t *)c->d_sid_of, p.n_pad, s.d_pos);
     auto bloom = [&](uint64_t lo, uint64_t hi) { // a quad per row
-        if (hi <= lo) return;
         hipLaunchKernelGGL(hbk::sim_bloom_kernel, dim3(grid_blocks(c, (hi - lo + 63) / 64, 8, 1)), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr,
                            (const uint32_t *)c->d_src, (const uint8_t *)s.d_pos, s.d_bloom, p.n_pad, rows_total, lo, hi);
     };
-    for (size_t l = 0; l + 1 < p.level_begin.size(); l++) bloom(p.level_begin[l], p.level_begin[l + 1]);
-    bloom(0, p.n_pad);
+    for_each_virtual_level(p, true, bloom); // ascending: a chunk row ORs the partials of the chunk rows below it
+    if (p.n_pad) bloom(0, p.n_pad);
     HB_HIP(hipGetLastError());
     HB_HIP(hipEventRecord(c->ev[kEvCollective], c->stream));
     HB_HIP(hipStreamSynchronize(c->stream));
@@ -69,7 +68,6 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
     hb_similarity_options o{};
     copy_in(opt_in, &o);
     int rc;
-    if ((rc = walk_prologue(c, "hb_inbound_similarity"))) return rc;
     if ((o.flags & HB_SIM_DENSE_ONLY) && (o.flags & HB_SIM_SPARSE_ONLY))
         return fail(c, HB_ERR_INVALID, "hb_inbound_similarity: HB_SIM_DENSE_ONLY and HB_SIM_SPARSE_ONLY exclude each other");
     if ((o.liked_count && !o.liked) || (o.disliked_count && !o.disliked))
@@ -103,12 +101,9 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
     }
     if ((rc = similarity_alloc(c, &st.ms_bloom))) return rc;
     const uint64_t n_pad = p.n_pad, rows_total = p.n_pad + p.nv;
-    const size_t nlev = p.level_begin.size() > 1 ? p.level_begin.size() - 1 : 0;
     HB_HIP(hipMemsetAsync(s.d_acc, 0, n_pad * 2 * sizeof(double), c->stream));
     HB_HIP(hipMemsetAsync(s.d_anchor, 0, p.n, c->stream));
-    // from here on the HyperBall state is gone: hb_step needs a new hb_begin, the tail kernel's lists describe nothing
-    c->begun = false;
-    c->tl_valid = false;
+    claim_rows(c, RowsOf::Similarity);
     unsigned long long *h = c->h_counters; // (pinned words of the context; hb_run rewrites them before it reads them)
     float ms = 0.f;
     for (uint64_t b0 = 0; b0 < E; b0 += hbk::kSimSlots) {
@@ -130,13 +125,11 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
                                s.d_anchor_rows, s.d_anchor);
             hipLaunchKernelGGL(hbk::sim_seed_node_kernel, dim3(count), dim3(256), 0, c->stream, (const uint32_t *)s.d_anchor_rows, count, (const uint64_t *)c->d_row_ptr,
                                (const uint32_t *)c->d_src, (uint32_t *)c->d_regs[0], c->d_bits[0], s.d_vmask, (const uint32_t *)c->d_outdeg, n_pad, rows_total, s.d_cnt);
-            for (size_t k = 0; k < nlev; k++) { // the chunk rows of the anchors' lists, the highest virtual level first
-                const uint64_t lo = p.level_begin[nlev - 1 - k], hi = p.level_begin[nlev - k];
-                if (hi > lo)
-                    hipLaunchKernelGGL(hbk::sim_seed_virt_kernel, dim3(grid_blocks(c, (hi - lo + 3) / 4, 8, 1)), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr,
-                                       (const uint32_t *)c->d_src, (uint32_t *)c->d_regs[0], c->d_bits[0], s.d_vmask, (const uint32_t *)c->d_outdeg, n_pad, rows_total,
-                                       lo, hi, s.d_cnt);
-            }
+            for_each_virtual_level(p, false, [&](uint64_t lo, uint64_t hi) { // the chunk rows of the anchors' lists, the highest virtual level first
+                hipLaunchKernelGGL(hbk::sim_seed_virt_kernel, dim3(grid_blocks(c, (hi - lo + 3) / 4, 8, 1)), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr,
+                                   (const uint32_t *)c->d_src, (uint32_t *)c->d_regs[0], c->d_bits[0], s.d_vmask, (const uint32_t *)c->d_outdeg, n_pad, rows_total, lo,
+                                   hi, s.d_cnt);
+            });
             HB_HIP(hipGetLastError());
             HB_HIP(hipMemcpyAsync(h, s.d_cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         }
@@ -200,7 +193,6 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
     HB_HIP(hipEventElapsedTime(&ms, c->ev[kEvMerge], c->ev[kEvCollective]));
     st.ms_score += ms;
     s.valid = true;
-    s.batch_live = true;
     return finish();
 }
 
@@ -212,27 +204,14 @@ extern "C" {
 
 int hb_inbound_similarity(hb_ctx *c, const hb_similarity_options *opt, hb_similarity_stats *stats)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        int rc = set_device(c);
-        if (rc) return rc;
-        if ((rc = run_in_progress(c, "hb_inbound_similarity"))) return rc;
-        return inbound_similarity(c, opt, stats);
-    });
+    return operator_entry(c, "hb_inbound_similarity", [&]() { return inbound_similarity(c, opt, stats); });
 }
 
 int hb_similarity_all(hb_ctx *c, double *vals, uint64_t cap)
 {
     return guarded(c, [&]() -> int {
-        if (!c || !vals) return c ? fail(c, HB_ERR_INVALID, "hb_similarity_all: vals == NULL") : HB_ERR_INVALID;
-        int rc = result_ready(c, c->sim.valid, "hb_similarity_all", kNoSimilarity);
-        if (rc) return rc;
-        const uint64_t n = c->plan.n;
-        if (cap < n) return fail(c, HB_ERR_INVALID, "hb_similarity_all: cap < n");
-        if (!n) return HB_OK;
-        HB_HIP(hipMemcpyAsync(vals, c->sim.d_score, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HB_HIP(hipStreamSynchronize(c->stream));
-        return HB_OK;
+        if (!c) return HB_ERR_INVALID;
+        return result_all<double>(c, c->sim.valid, "hb_similarity_all", "vals", kNoSimilarity, vals, cap, c->sim.d_score);
     });
 }
 
@@ -301,14 +280,15 @@ int hb_debug_copy_similarity_batch(hb_ctx *c, uint32_t *counts, uint64_t *bloom,
         const Plan &p = c->plan;
         auto &s = c->sim;
         if (!p.n) return HB_OK;
-        if (counts && !s.batch_live)
+        const bool counts_live = c->rows == RowsOf::Similarity; // (s.valid holds: d_regs[1] / d_bits[1] still hold the last batch's counts)
+        if (counts && !counts_live)
             return fail(c, HB_ERR_INVALID, "hb_debug_copy_similarity_batch: the counts of the last batch are gone (another call has used the HyperBall state)");
         DevPtr<uint32_t> d_counts, d_len;
         DevPtr<uint64_t> d_bloom;
         HB_HIP(d_counts.alloc(p.n * hbk::kSimSlots));
         HB_HIP(d_len.alloc(p.n));
         HB_HIP(d_bloom.alloc(p.n));
-        const uint32_t *bits = s.batch_live ? c->d_bits[1] : nullptr; // (bloom / len alone: no counts are read)
+        const uint32_t *bits = counts_live ? c->d_bits[1] : nullptr; // (bloom / len alone: no counts are read)
         hipLaunchKernelGGL(hbk::sim_export_kernel, dim3(grid_blocks(c, (p.n + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint32_t *)c->d_regs[1], bits,
                            (const uint64_t *)s.d_bloom, (const uint32_t *)c->dst.d_indeg, (const uint32_t *)c->d_dev_of, p.n, d_counts.get(), d_bloom.get(), d_len.get());
         HB_HIP(hipGetLastError());

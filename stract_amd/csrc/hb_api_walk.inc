@@ -1,32 +1,64 @@
 // hb_api_walk.inc - part of the hb_api.hip translation unit (included before the operator files; uses its hb_ctx and helpers).
-// What hb_sampled_harmonic, hb_distances, hb_betweenness and hb_inbound_similarity share on the host: their refusals, the sources as sids, the row -> readers
-// transpose, the download of a compacted result - and, for the two operators that walk 64-byte rows (device side: hb_walk.hip.h), the
-// launcher and one forward level.
+// What hb_sampled_harmonic, hb_distances, hb_betweenness and hb_inbound_similarity share on the host: who holds the shared rows and the
+// result image, their entry and its refusals, the virtual levels in order, the sources as sids, the row -> readers transpose, the download
+// of a result - and, for the operators that walk 64-byte rows (device side: hb_walk.hip.h), the launcher and one forward level.
 
 namespace {
 
-// ---- the three operators ---------------------------------------------------------------------------------------------------------------
-// between hb_begin and hb_finish the HyperBall state, the pinned counter words, the stream's event pair and a result snapshot on its way
-// to h_out belong to that run
-int run_in_progress(hb_ctx *c, const char *who)
+// ---- the four operators --------------------------------------------------------------------------------------------------------------
+// The only place outside hb_begin that changes hb_ctx::rows (DESIGN.md section 18): an operator calls it immediately before its first
+// write to d_regs / d_part / d_bits / the touch bitmap / the sweep scratch, so an error return after that never leaves its rows marked
+// as HyperBall state for hb_step, hb_finish or the debug exports.  The tail kernel's lists describe the bitmaps no longer.
+void claim_rows(hb_ctx *c, RowsOf who)
 {
-    if (c->begun && !c->finished) return fail(c, HB_ERR_INVALID, std::string(who) + ": a HyperBall run is in progress (hb_begin without hb_finish)");
+    c->rows = who;
+    c->tl_valid = false;
+}
+
+// the result image (d_out / h_out / res_count) is about to be rewritten by somebody who is not hb_finish: no result snapshot of an earlier
+// run may still be landing in h_out, and nothing is served from it until the writer says what it holds
+int take_image(hb_ctx *c)
+{
+    if (c->rs_stream) HB_HIP(hipStreamSynchronize(c->rs_stream));
+    c->rs.valid = false;
+    c->image = Image::None;
     return HB_OK;
 }
 
-// what every operator refuses before it looks at its options: more than one rank, no graph, a plan whose node rows or virtual levels do
-// not begin on a 32-row word or lie outside [n_pad, n_pad + nv] (the planner produces neither), an unchecked HIP error of an earlier call
-int walk_prologue(hb_ctx *c, const char *who, const char *boundary_note = " (virtual level boundary)")
+// The entry of hb_sampled_harmonic, hb_distances, hb_betweenness and hb_inbound_similarity: the context's device, then what each of them
+// refuses before it looks at its options - an open run (between hb_begin and hb_finish the HyperBall state, the pinned counter words, the
+// stream's event pair and a result snapshot on its way to h_out belong to that run), more than one rank, no graph, a plan whose node rows
+// or virtual levels do not begin on a 32-row word or lie outside [n_pad, n_pad + nv] (the planner produces neither), an unchecked HIP error
+// of an earlier call - then the body
+template <class BODY>
+int operator_entry(hb_ctx *c, const char *who, BODY body, const char *boundary_note = " (virtual level boundary)")
 {
-    if (multi_rank(c)) return fail(c, HB_ERR_INVALID, std::string(who) + ": single rank only (world_size > 1)");
-    if (!c->loaded) return fail(c, HB_ERR_INVALID, std::string(who) + ": no graph loaded");
-    const Plan &p = c->plan;
-    int rc;
-    if ((rc = plan_rows_word_aligned(c, who))) return rc;
-    for (uint64_t b : p.level_begin)
-        if (b < p.n_pad || b > p.n_pad + p.nv) return fail(c, HB_ERR_INVALID, std::string(who) + ": unexpected plan layout" + boundary_note);
-    c->sim.batch_live = false; // (every operator here rewrites the rows hb_inbound_similarity left its last counts in)
-    return refuse_stale_error(c, who);
+    return guarded(c, [&]() -> int {
+        if (!c) return HB_ERR_INVALID;
+        int rc = set_device(c);
+        if (rc) return rc;
+        if (c->run_open) return fail(c, HB_ERR_INVALID, std::string(who) + ": a HyperBall run is in progress (hb_begin without hb_finish)");
+        if (multi_rank(c)) return fail(c, HB_ERR_INVALID, std::string(who) + ": single rank only (world_size > 1)");
+        if (!c->loaded) return fail(c, HB_ERR_INVALID, std::string(who) + ": no graph loaded");
+        if ((rc = plan_rows_word_aligned(c, who))) return rc;
+        for (uint64_t b : c->plan.level_begin)
+            if (b < c->plan.n_pad || b > c->plan.n_pad + c->plan.nv) return fail(c, HB_ERR_INVALID, std::string(who) + ": unexpected plan layout" + boundary_note);
+        if ((rc = refuse_stale_error(c, who))) return rc;
+        return body();
+    });
+}
+
+// The virtual levels of the plan in order, fn(lo, hi) for every level that has rows.  The order is part of each caller's correctness: a
+// chunk row feeds the higher levels (and its hub), so values that flow from the sources to the readers need `ascending`, values that
+// flow from a hub down its chunk tree need the highest level first.
+template <class FN>
+void for_each_virtual_level(const Plan &p, bool ascending, FN fn)
+{
+    const size_t nlev = p.level_begin.size() > 1 ? p.level_begin.size() - 1 : 0;
+    for (size_t k = 0; k < nlev; k++) {
+        const size_t l = ascending ? k : nlev - 1 - k;
+        if (p.level_begin[l + 1] > p.level_begin[l]) fn(p.level_begin[l], p.level_begin[l + 1]);
+    }
 }
 
 // NodeIDs -> the distinct sids among them, ascending; *unknown = ids that are no node of the graph, *first_unknown = the first such index
@@ -69,6 +101,31 @@ int result_ready(hb_ctx *c, bool valid, const char *who, const char *missing)
 {
     if (!c->loaded || !valid) return fail(c, HB_ERR_INVALID, std::string(who) + ": " + missing);
     return set_device(c);
+}
+
+// hb_*_count: the number of entries of a compacted result
+int result_count(hb_ctx *c, bool valid, const char *who, const char *missing, uint64_t *count, uint64_t value)
+{
+    if (!count) return fail(c, HB_ERR_INVALID, std::string(who) + ": count == NULL");
+    const int rc = result_ready(c, valid, who, missing);
+    if (!rc) *count = value;
+    return rc;
+}
+
+// hb_*_all: one value per node in sid order, from d_by_sid (`prepare`, if given, fills it first); `arg` = the caller's name of `out`
+template <class T>
+int result_all(hb_ctx *c, bool valid, const char *who, const char *arg, const char *missing, T *out, uint64_t cap, const T *d_by_sid, int (*prepare)(hb_ctx *) = nullptr)
+{
+    if (!out) return fail(c, HB_ERR_INVALID, std::string(who) + ": " + arg + " == NULL");
+    int rc = result_ready(c, valid, who, missing);
+    if (rc) return rc;
+    const uint64_t n = c->plan.n;
+    if (cap < n) return fail(c, HB_ERR_INVALID, std::string(who) + ": cap < n");
+    if (!n) return HB_OK;
+    if (prepare && (rc = prepare(c))) return rc;
+    HB_HIP(hipMemcpyAsync(out, d_by_sid, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    HB_HIP(hipStreamSynchronize(c->stream));
+    return HB_OK;
 }
 
 // the ids of a compacted result: only its k sids come down, the ids are looked up in the host's sorted id array
@@ -172,12 +229,12 @@ int walk_forward_level(hb_ctx *c, hbk::WalkParams &wp, hbk::PassMode mode, uint6
         HB_HIP(hipGetLastError());
     }
     const bool xcd = mode == hbk::kModeDense && walk_xcd_ok(p);
-    for (size_t l = 0; l + 1 < p.level_begin.size(); l++) {
-        wp.row_lo = p.level_begin[l];
-        wp.row_hi = p.level_begin[l + 1];
-        wp.xcd_map = (l == 0 && xcd) ? 1 : 0;
+    for_each_virtual_level(p, true, [&](uint64_t lo, uint64_t hi) { // ascending: a level's partials are built from the levels below it
+        wp.row_lo = lo;
+        wp.row_hi = hi;
+        wp.xcd_map = (xcd && lo == p.xcd_begin[0] && hi == p.xcd_begin[8]) ? 1 : 0; // (the first hub-chunk level, walk_xcd_ok)
         launch(false);
-    }
+    });
     wp.xcd_map = 0;
     wp.row_lo = 0;
     wp.row_hi = p.n_pad;

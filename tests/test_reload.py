@@ -1,8 +1,8 @@
-"""A second (and third) load on a context that has used all three operators - hb_run, hb_sampled_harmonic, hb_distances.  Everything
-the first graph left on the context (device buffers, sizes, row indices, the sampler's candidates, the operators' results) must be gone
-after hb_load_*: graph A is the larger one, so every size kept from it is too large for graph B and every row index out of range.
-The comparisons are the sibling tests' own (tests/test_gpu.py, test_sampled_harmonic.py, test_distances.py): bit-exact lists, equal
-distance arrays."""
+"""A second (and third) load on a context that has used all five operators - hb_run, hb_sampled_harmonic, hb_distances, hb_betweenness,
+hb_inbound_similarity.  Everything the first graph left on the context (device buffers, sizes, row indices, the sampler's candidates, the
+operators' results) must be gone after hb_load_*: graph A is the larger one, so every size kept from it is too large for graph B and
+every row index out of range.  The comparisons are the sibling tests' own (tests/test_gpu.py, test_sampled_harmonic.py,
+test_distances.py, test_betweenness.py, test_similarity.py): bit-exact lists, equal distance arrays, betweenness within its rule."""
 import functools
 
 import numpy as np
@@ -13,9 +13,12 @@ from stract_amd import _lib
 from stract_amd.harmonic import EdgeListGraph
 from tests import distance_ref as dref
 from tests import graphs
+from tests import inbound_similarity_ref as sref
 from tests import sample_ref as ref
+from tests import test_betweenness as tb
 from tests import test_distances as td
 from tests import test_sampled_harmonic as ts
+from tests import test_similarity as tsim
 
 pytestmark = pytest.mark.gpu
 
@@ -35,6 +38,11 @@ def _oracle(name):
     T = o.run()
     vals, keep, _ = o.finish()
     return (ids, row_ptr, src), (T, vals, keep)
+
+
+@functools.lru_cache(maxsize=None)
+def _bitvecs(name):
+    return sref.bitvecs(*_oracle(name)[0])
 
 
 def _sources(row_ptr, src):
@@ -65,6 +73,11 @@ def _check_operators(ctx, name):
     for srcs, reversed in ((forward, False), (backward, True)):
         st = td._check(ctx, srcs, reversed, modes=(None,), ref=dref.bfs)
         assert st["reached"] > len(srcs)
+    res, _ = tb._check(ctx, sampled, modes=(None,))  # against tests/betweenness_ref.py
+    assert res.reached.sum() > len(sampled)
+    ints = sref.id_ints(ids)
+    want, _ = tsim._check(ctx, (ids, row_ptr, src), _bitvecs(name), [ints[s] for s in sampled], [ints[s] for s in backward], modes=(None,))
+    assert want.any()  # against tests/inbound_similarity_ref.py
 
 
 def _refused(fn):
@@ -74,7 +87,7 @@ def _refused(fn):
 
 
 @pytest.mark.parametrize("variant", ["default", "no_sparse"])
-def test_reload_after_all_three_operators(gpu_ctx_factory, variant):
+def test_reload_after_all_five_operators(gpu_ctx_factory, variant):
     # no_sparse: hb_distances owns its transpose, the sampled operator takes the dense / bitmap modes
     flags = _lib.HB_FLAG_ALL_RELS | (_lib.HB_FLAG_NO_SPARSE if variant == "no_sparse" else 0)
     with gpu_ctx_factory(flags=flags) as ctx:
@@ -83,9 +96,11 @@ def test_reload_after_all_three_operators(gpu_ctx_factory, variant):
         cand_a = td._ints(ctx.sample_sources(5, 10))
 
         ctx.load_edges(_edges("B"))
-        # nothing of A answers for B: no distances, no histogram, and the sampler draws from B's candidates
+        # nothing of A answers for B: no distances, no histogram, no betweenness, no scores, and the sampler draws from B's candidates
         _refused(ctx.distance_count)
         _refused(ctx.sample_histogram)
+        _refused(ctx.betweenness_count)
+        _refused(ctx.similarity_all)
         (ids, row_ptr, src), _ = _oracle("B")
         cand_b = td._ints(ctx.sample_sources(5, 10))
         assert cand_b == td._ints(ids[ref.sample_sids(len(ids), row_ptr, src, 5, 10)]) and cand_b != cand_a
