@@ -521,6 +521,76 @@ int hb_similarity_top(hb_ctx *ctx, uint64_t k, uint32_t flags, hb_u128 *ids, dou
  * NULL.  The counts lie in the borrowed HyperBall state: refused once another call has used that state. */
 int hb_debug_copy_similarity_batch(hb_ctx *ctx, uint32_t *counts, uint64_t *bloom, uint32_t *len);
 
+/* ---- nearest-seed centrality: HarmonicNearestSeed (entrypoint/centrality.rs:126-201, `stract centrality harmonic-nearest-seed`) ------ */
+/* Completes a centrality that covers only some nodes (ApproxHarmonic: hb_sampled_harmonic): for EVERY node v of the loaded graph
+ * (stream_page_node_ids, entrypoint/webgraph.rs:113-160) - if the original centrality has a value for v, v gets it unchanged
+ * (centrality.rs:153-156; Some(0.0) is a value); otherwise v gets original(seed(v)) * discount_factor, one f64 multiply (:158-176,
+ * default discount_factor 0.5: config/defaults.rs:230), and nothing when v has no seed or the seed has no value - there is no fallback
+ * to a second backlink.
+ * seed(v) = the `from` of the first result of BacklinksQuery::new(v).with_limit(Limit(1)) (query/backlink.rs:96-209): the in-neighbour
+ * u != v of v (self links are skipped, LinksQuery.skip_self_links, query/raw/links.rs:31-49,194) that minimises (key[u], NodeID u), where
+ * key is the caller's per-node order key - the harmonic rank of the node's host, which is what sort_score = from_host_rank
+ * .saturating_add(to_host_rank) orders one node's backlinks by (ascending: query/collector/top_docs.rs:394-400, query/document_scorer/
+ * mod.rs).  A node that is not in the key list has key u64::MAX, which is an ordinary key: a node whose only in-neighbour is unlisted
+ * still has that seed.  seed(v) is defined for every node, those with an original value included; none if v has no in-neighbour other
+ * than itself.
+ * Defined differences (each is something the reference leaves to chance): ties in the key go to the smaller NodeID; keys are compared
+ * unsaturated, which is the reference's order whenever from_rank + to_rank < 2^64 (with a destination rank of u64::MAX every backlink
+ * ties there); the in-list is that of the loaded graph, whatever relation filter the load applied - the reference applies none, so load
+ * with HB_FLAG_ALL_RELS; edges are unique in the loaded graph (the reference de-duplicates by `from`).
+ * Rounds: val_0 = the original values.  Round r = 1 .. rounds: a node without a value after round r - 1 whose seed has one gets
+ * val_(r-1)(seed) * discount_factor; synchronous (the state after r - 1 is read, the state after r written), one multiply per hop.
+ * rounds = 1 (or 0) is the reference; more rounds follow the chain of best-rank backlinks further (an extension).  The loop stops after
+ * the first round that fills nothing.
+ * The orig list is the original_centrality Db: duplicate ids - the last one wins (Db::insert); ids that are no node of the graph are
+ * ignored and counted; a NaN or a value with its sign bit set is refused (HB_ERR_INVALID).  Presence is a flag of its own, not val > 0.
+ * HB_SEED_FROM_IMAGE: the original is the context's live result (hb_run / hb_sampled_harmonic, as hb_result_copy lists it), read on the
+ * device; refused without one.
+ * Single rank only.  The operator borrows nothing: hb_run / hb_step, hb_result_*, hb_distances, hb_betweenness and
+ * hb_inbound_similarity results are untouched, and its own result lives in buffers of its own until the next successful
+ * hb_nearest_seed or the next load - a refused call leaves it as it was.  Refused (HB_ERR_INVALID) between hb_begin and hb_finish,
+ * without a loaded graph, with world_size > 1, with opt == NULL, a discount_factor that is not finite or negative, rounds > 255,
+ * HB_SEED_FROM_IMAGE together with an orig list, and an orig or key pointer NULL with a non-zero count.  DESIGN.md section 19. */
+#define HB_SEED_FROM_IMAGE 0x1u  /* original = the context's live result (hb_run / hb_sampled_harmonic); orig_* must be NULL / 0 */
+
+typedef struct hb_nearest_seed_options {
+    uint32_t struct_size, flags;                    /* struct_size = sizeof(hb_nearest_seed_options); 0 = this version; flags = HB_SEED_* */
+    double   discount_factor;                       /* finite, >= 0; no default: 0.0 means 0.0 */
+    uint32_t rounds;                                /* 0 = 1 = the reference; at most 255 */
+    uint32_t reserved;
+    const hb_u128 *orig_ids; const double *orig_vals; uint64_t orig_count;  /* the original_centrality Db */
+    const hb_u128 *key_ids;  const uint64_t *keys;    uint64_t key_count;   /* per-node order key (the host's harmonic rank); a node not
+                                                                                listed has u64::MAX; NULL / 0 = none */
+} hb_nearest_seed_options;
+
+typedef struct hb_nearest_seed_stats {
+    uint32_t struct_size;         /* = sizeof(hb_nearest_seed_stats); 0 = this version */
+    uint32_t rounds_run;          /* rounds executed (the first one that fills nothing is the last) */
+    uint64_t with_original;       /* nodes with an original value */
+    uint64_t filled[16];          /* nodes filled by round 1, 2, ...; rounds beyond the 16th are summed into the last entry */
+    uint64_t unknown_orig;        /* entries of the orig list that are no node of the graph */
+    uint64_t unknown_keys;        /* entries of the key list that are no node of the graph */
+    uint64_t no_seed;             /* nodes that end without a value and have no seed */
+    uint64_t seed_without_value;  /* nodes that end without a value although they have a seed */
+    uint64_t results;             /* nodes with a value: with_original + the sum of filled[] */
+    uint64_t device_bytes;        /* the operator's own buffers */
+    double   ms_total;            /* wall time of the call */
+    double   ms_seed;             /* GPU time of the seed level (candidates, chunk rows, node rows) */
+    double   ms_fill;             /* GPU time of round 0, the rounds and the result in NodeID order */
+} hb_nearest_seed_stats;
+
+int hb_nearest_seed(hb_ctx *ctx, const hb_nearest_seed_options *opt, hb_nearest_seed_stats *stats);
+/* The result of the last hb_nearest_seed.  count = results; copy = those nodes only, ascending NodeID, at most cap entries, ids or vals
+ * may be NULL (only the results are downloaded); all = one f64 per node in ascending-NodeID order, -1.0 = no result, cap >= n; top =
+ * the first min(k, results) rows of harmonic.csv (centrality.rs:186-195): value descending, ties by NodeID ASCENDING (hb_similarity_top
+ * breaks ties the other way), selected and sorted on the device, only those pairs are downloaded; seeds = seed(v) of EVERY node in
+ * ascending-NodeID order, has_seed[v] = 0 (and a zero id) where there is none, cap >= n, either array may be NULL. */
+int hb_nearest_seed_count(hb_ctx *ctx, uint64_t *count);
+int hb_nearest_seed_copy(hb_ctx *ctx, hb_u128 *ids, double *vals, uint64_t cap);
+int hb_nearest_seed_all(hb_ctx *ctx, double *vals, uint64_t cap);
+int hb_nearest_seed_top(hb_ctx *ctx, uint64_t k, hb_u128 *ids, double *vals, uint64_t *written);
+int hb_nearest_seed_seeds(hb_ctx *ctx, hb_u128 *seed, uint8_t *has_seed, uint64_t cap);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) -------------------------------------- */
 /* Rank 0 calls this and distributes the 128 bytes (e.g. torch.distributed broadcast);
  * every rank puts them in hb_options.rccl_id. */

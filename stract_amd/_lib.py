@@ -300,6 +300,48 @@ class HbSimilarityStats(ctypes.Structure):
         return d
 
 
+HB_SEED_FROM_IMAGE = 0x1
+
+
+class HbNearestSeedOptions(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("discount_factor", ctypes.c_double),
+        ("rounds", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("orig_ids", ctypes.c_void_p),
+        ("orig_vals", ctypes.c_void_p),
+        ("orig_count", ctypes.c_uint64),
+        ("key_ids", ctypes.c_void_p),
+        ("keys", ctypes.c_void_p),
+        ("key_count", ctypes.c_uint64),
+    ]
+
+
+class HbNearestSeedStats(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("rounds_run", ctypes.c_uint32),
+        ("with_original", ctypes.c_uint64),
+        ("filled", ctypes.c_uint64 * 16),
+        ("unknown_orig", ctypes.c_uint64),
+        ("unknown_keys", ctypes.c_uint64),
+        ("no_seed", ctypes.c_uint64),
+        ("seed_without_value", ctypes.c_uint64),
+        ("results", ctypes.c_uint64),
+        ("device_bytes", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+        ("ms_seed", ctypes.c_double),
+        ("ms_fill", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["filled"] = list(d["filled"])  # per round; the 16th entry holds every later round
+        return d
+
+
 # every symbol include/hyperball.h declares: (name, restype, argtypes)
 _P = ctypes.c_void_p
 _U64 = ctypes.c_uint64
@@ -410,6 +452,15 @@ _SIGNATURES += [
     ("hb_similarity_lookup", ctypes.c_int, [_P, _P, _U64, _P]),
     ("hb_similarity_top", ctypes.c_int, [_P, _U64, ctypes.c_uint32, _P, _P, ctypes.POINTER(_U64)]),
     ("hb_debug_copy_similarity_batch", ctypes.c_int, [_P, _P, _P, _P]),
+]
+# include/hyperball.h: nearest-seed centrality (HarmonicNearestSeed)
+_SIGNATURES += [
+    ("hb_nearest_seed", ctypes.c_int, [_P, ctypes.POINTER(HbNearestSeedOptions), ctypes.POINTER(HbNearestSeedStats)]),
+    ("hb_nearest_seed_count", ctypes.c_int, [_P, ctypes.POINTER(_U64)]),
+    ("hb_nearest_seed_copy", ctypes.c_int, [_P, _P, _P, _U64]),
+    ("hb_nearest_seed_all", ctypes.c_int, [_P, _P, _U64]),
+    ("hb_nearest_seed_top", ctypes.c_int, [_P, _U64, _P, _P, ctypes.POINTER(_U64)]),
+    ("hb_nearest_seed_seeds", ctypes.c_int, [_P, _P, _P, _U64]),
 ]
 SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -884,6 +935,69 @@ class Context:
         length = np.zeros(n, dtype=np.uint32)
         self._check(self.lib.hb_debug_copy_similarity_batch(self.h, _ptr(counts), _ptr(bloom), _ptr(length)))
         return counts, bloom, length
+
+    # -- nearest-seed centrality (HarmonicNearestSeed, entrypoint/centrality.rs:126-201)
+    def nearest_seed(self, orig_ids=None, orig_vals=None, key_ids=None, keys=None, discount_factor=0.5, rounds=0, from_image=False, flags=0):
+        """hb_nearest_seed: every node without an original value takes discount_factor x the value of its seed (the in-neighbour with
+        the smallest (key, NodeID)); returns the stats.  orig_ids / orig_vals: the original centralities (U128 / float64 arrays), or
+        from_image=True for the context's live result; key_ids / keys: the order keys (U128 / uint64), unlisted nodes have 2^64 - 1."""
+        o = HbNearestSeedOptions()
+        o.struct_size = ctypes.sizeof(HbNearestSeedOptions)
+        o.flags = int(flags) | (HB_SEED_FROM_IMAGE if from_image else 0)
+        o.discount_factor = float(discount_factor)
+        o.rounds = int(rounds)
+        if orig_ids is not None and len(orig_ids):
+            orig_ids = np.ascontiguousarray(orig_ids, dtype=U128)
+            orig_vals = np.ascontiguousarray(orig_vals, dtype=np.float64)
+            if len(orig_ids) != len(orig_vals):
+                raise ValueError("orig_ids and orig_vals differ in length")
+            o.orig_ids, o.orig_vals, o.orig_count = orig_ids.ctypes.data, orig_vals.ctypes.data, len(orig_ids)
+        if key_ids is not None and len(key_ids):
+            key_ids = np.ascontiguousarray(key_ids, dtype=U128)
+            keys = np.ascontiguousarray(keys, dtype=np.uint64)
+            if len(key_ids) != len(keys):
+                raise ValueError("key_ids and keys differ in length")
+            o.key_ids, o.keys, o.key_count = key_ids.ctypes.data, keys.ctypes.data, len(key_ids)
+        st = HbNearestSeedStats()
+        st.struct_size = ctypes.sizeof(HbNearestSeedStats)
+        self._check(self.lib.hb_nearest_seed(self.h, ctypes.byref(o), ctypes.byref(st)))
+        return st.as_dict()
+
+    def nearest_seed_count(self):
+        k = ctypes.c_uint64(0)
+        self._check(self.lib.hb_nearest_seed_count(self.h, ctypes.byref(k)))
+        return k.value
+
+    def nearest_seed_copy(self):
+        """The results of the last nearest_seed() call: (ids ascending, values float64)."""
+        k = self.nearest_seed_count()
+        ids = np.zeros(k, dtype=U128)
+        vals = np.zeros(k, dtype=np.float64)
+        self._check(self.lib.hb_nearest_seed_copy(self.h, _ptr(ids), _ptr(vals), k))
+        return ids, vals
+
+    def nearest_seed_all(self):
+        """One float64 per node of the last nearest_seed() call, ascending NodeID; -1.0 = no result."""
+        out = np.full(self.n(), -1.0, dtype=np.float64)
+        self._check(self.lib.hb_nearest_seed_all(self.h, _ptr(out), len(out)))
+        return out
+
+    def nearest_seed_top(self, k):
+        """The k best results of the last nearest_seed() call: (ids, values), value descending, ties by NodeID ASCENDING."""
+        k = int(k)
+        ids = np.zeros(k, dtype=U128)
+        vals = np.zeros(k, dtype=np.float64)
+        w = ctypes.c_uint64(0)
+        self._check(self.lib.hb_nearest_seed_top(self.h, k, _ptr(ids), _ptr(vals), ctypes.byref(w)))
+        return ids[:w.value], vals[:w.value]
+
+    def nearest_seed_seeds(self):
+        """seed(v) of every node of the last nearest_seed() call, ascending NodeID: (ids U128, has_seed bool)."""
+        n = self.n()
+        seed = np.zeros(n, dtype=U128)
+        has = np.zeros(n, dtype=np.uint8)
+        self._check(self.lib.hb_nearest_seed_seeds(self.h, _ptr(seed), _ptr(has), n))
+        return seed, has.astype(bool)
 
     # -- results
     def results(self):

@@ -25,6 +25,7 @@
 #include "hb_bfs.hip.h"
 #include "hb_betweenness.hip.h"
 #include "hb_similarity.hip.h"
+#include "hb_nearest_seed.hip.h"
 #ifdef HB_EXPERIMENTS
 #include "hb_experiments.hip.h"
 #endif
@@ -261,6 +262,32 @@ struct GraphDeviceState {
         uint32_t last_slots = 0;               // slots of the last batch
         uint64_t bytes = 0;                    // device bytes of the above (and of dst.d_indeg when this operator built it)
     } sim;
+    // hb_nearest_seed (hb_api_nearest_seed.inc): the candidates, the seeds, the double-buffered values and the last result, dev_alloc'ed at
+    // the first call after a load.  The operator borrows nothing of the HyperBall state
+    struct NearestSeedState {
+        bool ready = false; // the buffers below exist
+        bool valid = false; // they hold the result of a finished hb_nearest_seed
+        uint4 *d_cand = nullptr;                 // n_pad: {key, sid} of the row's node, {~0, kNone} for padding rows
+        uint4 *d_part = nullptr;                 // nv x 2: the two best distinct candidates under a chunk row
+        uint32_t *d_seed_row = nullptr;          // n_pad: device row of the seed, kNone = none
+        double *d_val[2] = {nullptr, nullptr};   // n_pad: the value after the previous / this round
+        uint8_t *d_has[2] = {nullptr, nullptr};  // n_pad: ... and whether there is one
+        unsigned long long *d_up_key = nullptr;  // n: the caller's keys by sid, ~0 = not listed
+        double *d_up_val = nullptr;              // n: the caller's original values by sid
+        uint8_t *d_up_has = nullptr;             // n: ... and which sids have one
+        unsigned long long *d_cnt = nullptr;     // kCounterWords striped words of a round + 4 plain counters
+        double *d_val_sid = nullptr;             // n: value per sid, -1.0 = no result
+        uint8_t *d_flag_sid = nullptr;           // n: 0 = result, 255 = none (the select's input)
+        uint32_t *d_seed_sid = nullptr;          // n: the seed of every sid as a sid, kNone = none
+        uint32_t *d_sel_sid = nullptr;           // n: the results' sids, ascending
+        uint8_t *d_sel_flag = nullptr;
+        double *d_sel_val = nullptr;             // n: their values
+        uint64_t *d_sel_cnt = nullptr;
+        uint64_t *d_top_key = nullptr;           // n: hb_nearest_seed_top's sort keys, reversed sid order
+        uint8_t *d_top_keep = nullptr;           // n: ... and which entries are results
+        uint64_t results = 0;
+        uint64_t bytes = 0;                      // device bytes of the above
+    } nst;
 };
 
 // The timing events of a pass (one set: hb_ctx::ev, or an EvSet), in the order a pass records them; kEvLevel1 lies between kEvStart and
@@ -1559,3 +1586,5 @@ int hb_store_harmonic_results(hb_ctx *c, const char *output, char *err, uint64_t
 #include "hb_api_betweenness.inc"
 
 #include "hb_api_similarity.inc"
+
+#include "hb_api_nearest_seed.inc"

@@ -786,6 +786,15 @@ void host_gather_id_lo(const hb_u128 *ids, uint64_t n, uint64_t *lo)
     for (int64_t s = 0; s < (int64_t)n; s++) lo[s] = ids[s].lo;
 }
 
+void host_find_sids(const hb_u128 *ids, uint64_t n, const hb_u128 *query, uint64_t count, uint32_t *sids)
+{
+#pragma omp parallel for num_threads(count >= (1u << 14) ? std::min(host_threads(), 16) : 1) schedule(static)
+    for (int64_t i = 0; i < (int64_t)count; i++) {
+        const hb_u128 *it = std::lower_bound(ids, ids + n, query[i], u128_less);
+        sids[i] = (it != ids + n && u128_eq(*it, query[i])) ? (uint32_t)(it - ids) : kNone;
+    }
+}
+
 void host_compact_results(const double *src, const hb_u128 *idsrc, uint64_t n, hb_u128 *ids, double *vals, uint64_t cap, const uint64_t *in_bits)
 {
     const int want = n >= (1u << 18) ? std::min(host_threads(), 16) : 1;

@@ -285,6 +285,8 @@ double now_ms();
 void host_scatter_f64(double *out, const uint32_t *idx, const double *val, uint64_t n);
 // lo[s] = ids[s].lo (the half of a NodeID HyperLogLog::add_u128 hashes), on the OpenMP team
 void host_gather_id_lo(const hb_u128 *ids, uint64_t n, uint64_t *lo);
+// sids[i] = the sid of query[i] in the ascending id array, kNone = no node of the graph; long lists on the OpenMP team
+void host_find_sids(const hb_u128 *ids, uint64_t n, const hb_u128 *query, uint64_t count, uint32_t *sids);
 //   the (id, value) pairs with src[sid] >= 0.0 in ascending sid order, at most cap of them; ids / vals may be NULL
 // in_bits != NULL [r6]: src is the COMPACT image - one entry per sid whose bit is set, in sid order (hb_aux.hip.h "the compact result image")
 void host_compact_results(const double *src, const hb_u128 *idsrc, uint64_t n, hb_u128 *ids, double *vals, uint64_t cap, const uint64_t *in_bits = nullptr);

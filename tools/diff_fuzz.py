@@ -9,7 +9,7 @@ for the `make asan` build).  A failure prints the seed and case that reproduce i
 value, weighted towards 40..58 and 65 (tests/graphs.py crafted_id_low): the estimator's sequential fold, saturated sizes and the six-bit
 wire codes above 47, which ids 1..n never reach; mixed alternates between plain and extreme.
 
-usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|distances|betweenness|similarity] [--ids plain|extreme|mixed] [--seconds S] [--seed N] [--max-nodes N]"""
+usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|distances|betweenness|similarity|nearest_seed] [--ids plain|extreme|mixed] [--seconds S] [--seed N] [--max-nodes N]"""
 import argparse
 import json
 import os
@@ -409,9 +409,58 @@ def similarity_case(rng, max_nodes, case):
     return what
 
 
+def nearest_seed_case(rng, max_nodes, case):
+    """hb_nearest_seed: random graph (self links added) x random original / key lists (duplicates, unknown ids, 0.0, few distinct keys so
+    that ties are common, u64::MAX) x rounds x discount, against the host restatement (tests/nearest_seed_ref.py): the seed of every
+    node, every value bit for bit, every counter, the top order."""
+    from stract_amd.harmonic import EdgeListGraph, ids_from_ints
+    from tests import inbound_similarity_ref as sref
+    from tests import nearest_seed_ref as nref
+    kind, tuples = graphs.random_graph(rng)
+    if not tuples:
+        return None
+    nodes_in = sorted({x for e in tuples for x in e[:2]})
+    tuples = list(tuples) + [(v, v) for v in nodes_in if rng.random() < 0.1]
+    chunk = int(rng.choice([0, 0, 4, 8, 64]))
+    flags = _lib.HB_FLAG_ALL_RELS | int(rng.choice([0, 0, _lib.HB_FLAG_NO_REORDER, _lib.HB_FLAG_NO_XCD_MAP, _lib.HB_FLAG_NO_SPARSE]))
+    with _lib.Context(flags=flags, chunk=chunk) as ctx:
+        ctx.load_edges(EdgeListGraph.from_tuples(tuples).host_edges())
+        graph = ctx.graph()
+        ints = sref.id_ints(graph[0])
+        n = len(ints)
+        what = dict(case=case, kind="nearest_seed:" + kind, n=n, m=int(len(graph[2])), chunk=chunk, flags=flags, passes=0)
+        for _ in range(3):
+            share = [0.02, 0.1, 0.5][int(rng.integers(0, 3))]
+            orig = [(ints[int(x)], [0.0, float(rng.random()), float(rng.integers(0, 4)) / 4.0][int(rng.integers(0, 3))])
+                    for x in rng.integers(0, n, max(1, int(n * share)))]
+            orig += [((1 << 100) + 1, 0.5), orig[0]]
+            spread = int(rng.choice([1, 3, 1 << 62]))
+            keys = [(v, int(rng.integers(0, spread)) if rng.random() < 0.9 else nref.U64_MAX) for v in ints if rng.random() < 0.8]
+            keys += [((1 << 100) + 2, 0)] + keys[:2]
+            discount = [0.5, 0.3, 0.0, 1.0][int(rng.integers(0, 4))]
+            rounds = int(rng.choice([0, 1, 2, 5, 255]))
+            run = dict(what, discount=discount, rounds=rounds, orig=len(orig), keys=len(keys), spread=spread)
+            seeds, vals, want = nref.literal(*graph, orig, keys, discount, rounds)
+            st = ctx.nearest_seed(ids_from_ints([v for v, _ in orig]), np.array([x for _, x in orig]), ids_from_ints([v for v, _ in keys]),
+                                  np.array([k for _, k in keys], dtype=np.uint64), discount_factor=discount, rounds=rounds)
+            got_seed, got_has = ctx.nearest_seed_seeds()
+            assert {v: s for v, s, h in zip(ints, sref.id_ints(got_seed), got_has.tolist()) if h} == seeds, ("seeds", run)
+            want_all = np.array([vals.get(v, -1.0) for v in ints], dtype=np.float64)
+            assert ctx.nearest_seed_all().tobytes() == want_all.tobytes(), ("values", run)
+            cids, cvals = ctx.nearest_seed_copy()
+            assert sref.id_ints(cids) == [v for v in ints if v in vals] and cvals.tobytes() == want_all[want_all >= 0.0].tobytes(), ("copy", run)
+            assert {k: st[k] for k in nref.STAT_KEYS} == want, ("stats", run, {k: st[k] for k in nref.STAT_KEYS}, want)
+            k = int(rng.integers(1, n + 3))
+            tids, tvals = ctx.nearest_seed_top(k)
+            order = nref.top_order(vals, k)
+            assert sref.id_ints(tids) == [v for v, _ in order] and tvals.tolist() == [x for _, x in order], ("top", run, k)
+            what["passes"] += st["rounds_run"]
+    return what
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "distances", "betweenness", "similarity"], default="passes")
+    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "distances", "betweenness", "similarity", "nearest_seed"], default="passes")
     ap.add_argument("--ids", choices=["plain", "extreme", "mixed"], default="plain")
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--seed", type=int, default=1)
@@ -430,6 +479,8 @@ def main():
                 w = betweenness_case(rng, a.max_nodes, case)
             elif a.mode == "similarity":
                 w = similarity_case(rng, a.max_nodes, case)
+            elif a.mode == "nearest_seed":
+                w = nearest_seed_case(rng, a.max_nodes, case)
             elif a.mode == "ranks" or (a.mode == "mixed" and case % 6 == 4):
                 w = ranks_case(rng, a.max_nodes, case, extreme)
             elif a.mode == "tail" or (a.mode == "mixed" and case % 6 == 5):
