@@ -1,18 +1,29 @@
 /*
- * hb_ampc.h - a GPU-resident shard of the AMPC harmonic-centrality counter table.
+ * hb_ampc.h - a GPU-resident shard of the AMPC table store: what the harmonic-centrality and the shortest-path job of the
+ * reference's distributed variant keep per shard.
  *
- * The reference's distributed variant keeps `counters: DefaultDhtTable<NodeID, HyperLogLog<64>>`
- * (crates/core/src/entrypoint/ampc/harmonic_centrality/mod.rs:47-53) in a raft-replicated key-value store and
- * drives it with three batch operations per shard (mapper.rs:52-118):
- *     batch_set     setup_counters                                   dht/store.rs (insert / overwrite)
- *     batch_get     get_old_counters (edge.from of a batch)
- *     batch_upsert  update_counters with `HyperLogLog64Upsert`       dht/upsert.rs:43-54,67-89, dht/store.rs:159-190
- * batch_upsert applies the pairs IN ORDER: an absent key is inserted (`Inserted`); otherwise old.merge(&new)
- * (register-wise max, hyperloglog.rs:4531-4535) and the action is `Merged` iff the stored value changed, else
- * `NoChange`.  This header is the C ABI a GPU worker would put behind those three calls: the counters of a shard
- * live in HBM as one 64-byte block each, the merge / changed detection runs in a HIP kernel (one quad per key,
- * the key's pairs applied in batch order), the key -> slot index is a device hash table (hb_table.hip.h) since round 5.
- * Raft replication, the network protocol and the other upsert operators are out of scope.
+ * The harmonic job keeps `counters: DefaultDhtTable<NodeID, HyperLogLog<64>>` and `centrality: DefaultDhtTable<NodeID, KahanSum>`
+ * (crates/core/src/entrypoint/ampc/harmonic_centrality/mod.rs:47-53), the shortest-path job `distances: DefaultDhtTable<NodeID, u64>`
+ * (shortest_path/mod.rs:51-55), in a raft-replicated key-value store driven by batch operations (harmonic_centrality/mapper.rs:52-209,
+ * shortest_path/mapper.rs:57-103):
+ *     batch_set     setup_counters, update_centralities                  dht/store.rs (insert / overwrite)
+ *     batch_get     get_old_counters, get_old_distances
+ *     batch_upsert  update_counters (`HyperLogLog64Upsert`), update_distances (`U64Min`)   dht/upsert.rs, dht/store.rs:159-190
+ *     clone_table   init_from at the start of every round                dht/store.rs:192-195, ampc/dht_conn.rs:271-277
+ * batch_upsert applies the pairs IN ORDER: an absent key is inserted (`Inserted`, the pair's value verbatim); otherwise
+ * merged = op(old, new) and the action is `Merged` iff merged != old (Rust's derived PartialEq: an IEEE comparison for the float kinds,
+ * so a NaN result is always `Merged` and -0.0 turning into +0.0 is `NoChange` although the merged bits are stored), else `NoChange`.
+ * This header is the C ABI a GPU worker would put behind those calls.  A table lives in HBM: the key -> slot index is a device hash
+ * table (hb_table.hip.h), the values one array of 64 / 8 / 4 / 8 / 16 bytes each.  A batch is grouped by key with its order kept and
+ * every group is folded by one writer in that order (HyperLogLog: one quad per key; the scalar kinds: one thread per key, one wave for
+ * a key with many pairs).  hbu_update_centralities is CentralityMapper::update_centralities (mapper.rs:157-209) as one device call:
+ * no counter and no size crosses the link.
+ * In: HyperLogLog<64> with HyperLogLog64Upsert; u64 with U64Add / U64Min; f32 with F32Add; f64 with F64Add; KahanSum with KahanSumAdd
+ * (upsert.rs:92-152); the copy of a table; update_centralities.  Still out: HyperLogLog<8/16/32/128> (no job uses them), the String,
+ * meta and bloom-valued tables and UpdatedNodes (a handful of values per shard: host work on the actions array), raft replication,
+ * the network protocol, shards that span ranks.
+ * Defined differences: U64Add wraps at 2^64 (the reference panics in a debug build and wraps in a release build); an operator that
+ * does not belong to the table's kind is refused with HB_ERR_INVALID and changes nothing (the reference panics).
  *
  * extern "C", never unwinds, 0 = ok, negative = HB_ERR_* of hyperball.h; needs a gfx950 device (no CPU fallback).
  */
@@ -33,8 +44,23 @@ typedef struct hbu_table hbu_table;
 #define HBU_MERGED    1 /* UpsertAction::Merged                          */
 #define HBU_INSERTED  2 /* UpsertAction::Inserted                        */
 
+#define HBU_KIND_HLL64 0 /* 64 B: HyperLogLog<64>::registers; what hbu_create makes */
+#define HBU_KIND_U64   1 /*  8 B                                                    */
+#define HBU_KIND_F32   2 /*  4 B                                                    */
+#define HBU_KIND_F64   3 /*  8 B                                                    */
+#define HBU_KIND_KAHAN 4 /* 16 B: {double sum, err}  (kahan_sum.rs:30-33)           */
+
+#define HBU_OP_HLL64     0 /* register-wise max                                      upsert.rs:67-89   */
+#define HBU_OP_U64_ADD   1 /* old + new, wrapping                                    upsert.rs:92-103  */
+#define HBU_OP_U64_MIN   2 /* min(old, new)                                          upsert.rs:105-116 */
+#define HBU_OP_F32_ADD   3 /* old + new: one f32 addition per pair, in batch order   upsert.rs:118-129 */
+#define HBU_OP_F64_ADD   4 /* old + new: one f64 addition per pair, in batch order   upsert.rs:131-142 */
+#define HBU_OP_KAHAN_ADD 5 /* old += new.sum (kahan_sum.rs:47-54); new.err ignored   upsert.rs:143-152 */
+
 /* device < 0: current device.  capacity_hint: expected number of keys (the table grows as needed). */
 int hbu_create(int32_t device, uint64_t capacity_hint, hbu_table **out);
+int hbu_create_kind(int32_t device, uint64_t capacity_hint, uint32_t kind, hbu_table **out);
+int hbu_kind(const hbu_table *t, uint32_t *kind, uint32_t *value_bytes);
 void hbu_destroy(hbu_table *t);
 const char *hbu_last_error(const hbu_table *t);
 int hbu_len(const hbu_table *t, uint64_t *keys);
@@ -45,6 +71,29 @@ int hbu_batch_set(hbu_table *t, const hb_u128 *keys, const uint8_t *counters, ui
 int hbu_batch_get(hbu_table *t, const hb_u128 *keys, uint64_t count, uint8_t *counters_out, uint8_t *found);
 /* HyperLogLog64Upsert over the pairs in order; actions[i] = HBU_* for pair i. */
 int hbu_batch_upsert(hbu_table *t, const hb_u128 *keys, const uint8_t *counters, uint64_t count, uint8_t *actions);
+
+
+/* ---- any kind.  values: count x value_bytes, in the table's kind.  On an HBU_KIND_HLL64 table these are the three calls above (op =
+ * HBU_OP_HLL64); the three calls above are refused (HB_ERR_INVALID, table untouched) on a table of another kind, and so is an
+ * operator that does not belong to the table's kind. */
+int hbu_batch_set_values(hbu_table *t, const hb_u128 *keys, const void *values, uint64_t count);
+/* an absent key: found[i] = 0 and zero bytes (0 / 0.0 / KahanSum::default()) */
+int hbu_batch_get_values(hbu_table *t, const hb_u128 *keys, uint64_t count, void *values_out, uint8_t *found);
+int hbu_batch_upsert_values(hbu_table *t, uint32_t op, const hb_u128 *keys, const void *values, uint64_t count, uint8_t *actions);
+/* pairs of one key up to this many are folded by one thread, more by one wave (tests place groups at this length) */
+uint32_t hbu_wave_group_length(void);
+
+/* clone_table: a new table of the same kind on the same device with the same keys and values; independent afterwards.
+ * Device-to-device copies only. */
+int hbu_clone(hbu_table *from, hbu_table **out);
+
+/* CentralityMapper::update_centralities (mapper.rs:157-209) for `count` nodes, all four tables on one device: a node found in BOTH
+ * counter tables with d = next.size() saturating-minus prev.size() != 0 gets
+ *     next_centrality[node] = (prev_centrality[node] or KahanSum::default()) + d as f64 / (round + 1) as f64
+ * SET (not upserted; may insert the key).  *written = the number of distinct nodes set (a node listed twice counts once, as in the
+ * reference's BTreeMap).  Refused with HB_ERR_INVALID: wrong kinds, tables on different devices, prev_centrality == next_centrality. */
+int hbu_update_centralities(hbu_table *prev_counters, hbu_table *next_counters, hbu_table *prev_centrality, hbu_table *next_centrality,
+                            const hb_u128 *nodes, uint64_t count, uint64_t round, uint64_t *written);
 
 #ifdef __cplusplus
 }

@@ -417,6 +417,14 @@ _SIGNATURES += [
     ("hbu_batch_set", ctypes.c_int, [_P, _P, _P, _U64]),
     ("hbu_batch_get", ctypes.c_int, [_P, _P, _U64, _P, _P]),
     ("hbu_batch_upsert", ctypes.c_int, [_P, _P, _P, _U64, _P]),
+    ("hbu_create_kind", ctypes.c_int, [ctypes.c_int32, _U64, ctypes.c_uint32, ctypes.POINTER(_P)]),
+    ("hbu_kind", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    ("hbu_batch_set_values", ctypes.c_int, [_P, _P, _P, _U64]),
+    ("hbu_batch_get_values", ctypes.c_int, [_P, _P, _U64, _P, _P]),
+    ("hbu_batch_upsert_values", ctypes.c_int, [_P, ctypes.c_uint32, _P, _P, _U64, _P]),
+    ("hbu_wave_group_length", ctypes.c_uint32, []),
+    ("hbu_clone", ctypes.c_int, [_P, ctypes.POINTER(_P)]),
+    ("hbu_update_centralities", ctypes.c_int, [_P, _P, _P, _P, _P, _U64, _U64, ctypes.POINTER(_U64)]),
 ]
 # include/hb_store.h
 _SIGNATURES += [

@@ -1,6 +1,9 @@
-"""ctypes binding of include/hb_ampc.h: a GPU-resident shard of the AMPC harmonic-centrality counter table
-(`DefaultDhtTable<NodeID, HyperLogLog<64>>`, crates/core/src/entrypoint/ampc/harmonic_centrality/mod.rs:47-53) with the
-three batch operations its mappers use (mapper.rs:52-118): batch_set, batch_get, batch_upsert(HyperLogLog64Upsert)."""
+"""ctypes binding of include/hb_ampc.h: a GPU-resident shard of the AMPC table store.  CounterTable is the harmonic-centrality
+counter table (`DefaultDhtTable<NodeID, HyperLogLog<64>>`, crates/core/src/entrypoint/ampc/harmonic_centrality/mod.rs:47-53) with the
+three batch operations its mappers use (mapper.rs:52-118): batch_set, batch_get, batch_upsert(HyperLogLog64Upsert).  ValueTable is a
+table of one of the scalar kinds (u64, f32, f64, KahanSum) with the scalar upsert operators (dht/upsert.rs:92-152): the `centrality`
+table of that job and the `distances` table of the shortest-path job (shortest_path/mod.rs:51-55).  Both have clone() (clone_table,
+dht/store.rs:192-195); update_centralities is mapper.rs:157-209 as one device call."""
 import ctypes
 
 import numpy as np
@@ -8,16 +11,24 @@ import numpy as np
 from . import _lib
 
 NO_CHANGE, MERGED, INSERTED = 0, 1, 2  # UpsertAction, dht/upsert.rs:24-28
+KIND_HLL64, KIND_U64, KIND_F32, KIND_F64, KIND_KAHAN = range(5)  # HBU_KIND_*
+OP_HLL64, OP_U64_ADD, OP_U64_MIN, OP_F32_ADD, OP_F64_ADD, OP_KAHAN_ADD = range(6)  # HBU_OP_*
+KAHAN = np.dtype([("sum", "<f8"), ("err", "<f8")])  # KahanSum, kahan_sum.rs:30-33
+DTYPES = {KIND_U64: np.dtype(np.uint64), KIND_F32: np.dtype(np.float32), KIND_F64: np.dtype(np.float64), KIND_KAHAN: KAHAN}
+OPS = {KIND_HLL64: (OP_HLL64,), KIND_U64: (OP_U64_ADD, OP_U64_MIN), KIND_F32: (OP_F32_ADD,), KIND_F64: (OP_F64_ADD,), KIND_KAHAN: (OP_KAHAN_ADD,)}
 
 
-class CounterTable:
-    def __init__(self, device=-1, capacity_hint=0):
-        self.lib = _lib.load()
+class _Table:
+    """What the two table classes share: the handle, its length, clone()."""
+
+    def clone(self):
+        """clone_table: a new table with the same kind, keys and values (device-to-device copies), independent afterwards"""
         h = ctypes.c_void_p()
-        rc = self.lib.hbu_create(device, capacity_hint, ctypes.byref(h))
-        if rc != _lib.HB_OK:
-            raise _lib.HyperballError(rc, (self.lib.hbu_last_error(None) or b"").decode())
-        self.h = h
+        self._check(self.lib.hbu_clone(self.h, ctypes.byref(h)))
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        new.h = h
+        return new
 
     def close(self):
         if getattr(self, "h", None):
@@ -45,6 +56,18 @@ class CounterTable:
         self._check(self.lib.hbu_len(self.h, ctypes.byref(n)))
         return n.value
 
+
+class CounterTable(_Table):
+    kind = KIND_HLL64
+
+    def __init__(self, device=-1, capacity_hint=0):
+        self.lib = _lib.load()
+        h = ctypes.c_void_p()
+        rc = self.lib.hbu_create(device, capacity_hint, ctypes.byref(h))
+        if rc != _lib.HB_OK:
+            raise _lib.HyperballError(rc, (self.lib.hbu_last_error(None) or b"").decode())
+        self.h = h
+
     @staticmethod
     def _args(keys, counters):
         keys = np.ascontiguousarray(keys, dtype=_lib.U128)
@@ -67,3 +90,61 @@ class CounterTable:
         actions = np.zeros(len(keys), dtype=np.uint8)
         self._check(self.lib.hbu_batch_upsert(self.h, _lib._ptr(keys), _lib._ptr(counters), len(keys), _lib._ptr(actions)))
         return actions
+
+
+class ValueTable(_Table):
+    """A table of one scalar kind; values are numpy arrays of DTYPES[kind] (KIND_KAHAN: the (sum, err) structured dtype)."""
+
+    def __init__(self, kind, device=-1, capacity_hint=0):
+        self.lib = _lib.load()
+        if kind not in DTYPES:
+            raise ValueError("ValueTable kinds: KIND_U64, KIND_F32, KIND_F64, KIND_KAHAN (counters: CounterTable)")
+        self.kind, self.dtype = kind, DTYPES[kind]
+        h = ctypes.c_void_p()
+        rc = self.lib.hbu_create_kind(device, capacity_hint, kind, ctypes.byref(h))
+        if rc != _lib.HB_OK:
+            raise _lib.HyperballError(rc, (self.lib.hbu_last_error(None) or b"").decode())
+        self.h = h
+
+    def _args(self, keys, values):
+        keys = np.ascontiguousarray(keys, dtype=_lib.U128)
+        values = np.ascontiguousarray(values, dtype=self.dtype)
+        if values.shape != (len(keys),):
+            raise ValueError("one value per key")
+        return keys, values
+
+    def batch_set(self, keys, values):
+        keys, values = self._args(keys, values)
+        self._check(self.lib.hbu_batch_set_values(self.h, _lib._ptr(keys), _lib._ptr(values), len(keys)))
+
+    def batch_get(self, keys):
+        """(values, found): an absent key reads as 0 / 0.0 / KahanSum::default()"""
+        keys = np.ascontiguousarray(keys, dtype=_lib.U128)
+        out = np.zeros(len(keys), dtype=self.dtype)
+        found = np.zeros(len(keys), dtype=np.uint8)
+        self._check(self.lib.hbu_batch_get_values(self.h, _lib._ptr(keys), len(keys), _lib._ptr(out), _lib._ptr(found)))
+        return out, found.astype(bool)
+
+    def batch_upsert(self, op, keys, values):
+        """The pairs in order under operator `op` (OP_*); returns the action of every pair."""
+        keys, values = self._args(keys, values)
+        actions = np.zeros(len(keys), dtype=np.uint8)
+        self._check(self.lib.hbu_batch_upsert_values(self.h, op, _lib._ptr(keys), _lib._ptr(values), len(keys), _lib._ptr(actions)))
+        return actions
+
+
+def wave_group_length():
+    """Pairs of one key in a batch up to this many are folded by one thread of the upsert kernel, more by a whole wave."""
+    return int(_lib.load().hbu_wave_group_length())
+
+
+def update_centralities(prev_counters, next_counters, prev_centrality, next_centrality, nodes, round):
+    """CentralityMapper::update_centralities (mapper.rs:157-209) on four resident tables: every node of `nodes` found in both
+    counter tables whose size grew gets next_centrality[node] = prev_centrality[node] + growth / (round + 1).  Returns the number of
+    distinct nodes written."""
+    nodes = np.ascontiguousarray(nodes, dtype=_lib.U128)
+    written = ctypes.c_uint64(0)
+    rc = next_centrality.lib.hbu_update_centralities(prev_counters.h, next_counters.h, prev_centrality.h, next_centrality.h, _lib._ptr(nodes), len(nodes),
+                                                     round, ctypes.byref(written))
+    next_centrality._check(rc)
+    return written.value

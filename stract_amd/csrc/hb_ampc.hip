@@ -1,17 +1,22 @@
-// hb_ampc.hip - GPU-resident shard of the AMPC counter table with HyperLogLog64Upsert semantics
-// (include/hb_ampc.h cites the reference operations this serves).
+// hb_ampc.hip - GPU-resident shard of the AMPC tables: the HyperLogLog<64> counter table with HyperLogLog64Upsert semantics, the
+// scalar value tables with the five scalar upsert operators, a device copy of a table and the update_centralities step
+// (include/hb_ampc.h cites the reference operations this serves; the scalar kernels live in hb_ampc_values.hip.h).
 #include "hb_guard_alloc.h" // FIRST: no-op unless built with -DHB_GUARD_ALLOC=<mode> (debug allocators: guard pages / poison / red zones)
 #include "hb_pool.h"        // then: every hipMalloc / hipFree below goes through the caching device allocator (shipped build)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include <rocprim/rocprim.hpp>
 
 #include "../../include/hb_ampc.h"
+#include "hb_ampc_values.hip.h"
+#include "hb_internal.h"
 #include "hb_regs.hip.h"
 #include "hb_table.hip.h"
 
@@ -127,8 +132,10 @@ struct hbu_table {
     unsigned long long *h_word = nullptr; // pinned: read-backs of the counter / the group count
     uint64_t committed = 0;               // keys visible to the caller (= d_next outside a failed batch)
     bool broken = false;                  // a failed batch could not be undone: every further call is refused
-    uint4 *d_table = nullptr;
-    uint64_t cap = 0; // counters allocated
+    uint32_t kind = HBU_KIND_HLL64;
+    uint32_t vbytes = 64; // bytes of one value of that kind
+    void *d_table = nullptr; // cap x vbytes, value of slot s at s * vbytes
+    uint64_t cap = 0;        // values allocated
     std::string err;
     // work memory of one batch, kept between calls (a mapper sends thousands of equally sized batches)
     void *d_work = nullptr;
@@ -162,15 +169,15 @@ int guarded(hbu_table *t, F &&f)
 unsigned grid_for(uint64_t items) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + 255) / 256, 1), 1u << 16); }
 Table table_of(const hbu_table *t) { return Table{t->d_keys, t->d_pids, t->slots - 1, t->d_next}; }
 
-// counters for `need` keys
+// values for `need` keys
 int reserve(hbu_table *t, uint64_t need)
 {
     if (need <= t->cap) return HB_OK;
     const uint64_t cap = std::max<uint64_t>(need, std::max<uint64_t>(2 * t->cap, 1024));
-    uint4 *n = nullptr;
-    if (hipMalloc((void **)&n, cap * 64) != hipSuccess) return fail(t, HB_ERR_NOMEM, "hipMalloc(counter table) failed");
-    hipError_t e = hipMemsetAsync(n, 0, cap * 64, t->stream);
-    if (e == hipSuccess && t->cap) e = hipMemcpyAsync(n, t->d_table, t->cap * 64, hipMemcpyDeviceToDevice, t->stream);
+    void *n = nullptr;
+    if (hipMalloc((void **)&n, cap * t->vbytes) != hipSuccess) return fail(t, HB_ERR_NOMEM, "hipMalloc(value table) failed");
+    hipError_t e = hipMemsetAsync(n, 0, cap * t->vbytes, t->stream);
+    if (e == hipSuccess && t->cap) e = hipMemcpyAsync(n, t->d_table, t->cap * t->vbytes, hipMemcpyDeviceToDevice, t->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(t->stream);
     if (e != hipSuccess) {
         (void)hipFree(n);
@@ -243,18 +250,55 @@ struct Carve { // consecutive 256-byte aligned pieces of the work buffer
     }
 };
 
-// shared body of batch_set / batch_upsert
-int apply(hbu_table *t, const hb_u128 *keys, const uint8_t *counters, uint64_t count, uint8_t *actions, bool upsert)
+constexpr uint32_t kOpSet = 0xFFFFFFFFu; // batch_set: no operator, the last pair of a key wins
+uint32_t bytes_of_kind(uint32_t kind)
 {
-    if (!t || (count && (!keys || !counters)) || (upsert && count && !actions)) return t ? fail(t, HB_ERR_INVALID, "NULL argument") : HB_ERR_INVALID;
-    if (t->broken) return fail(t, HB_ERR_INVALID, "the table is unusable: an earlier failed batch could not be undone");
+    switch (kind) {
+    case HBU_KIND_HLL64: return 64;
+    case HBU_KIND_U64: return 8;
+    case HBU_KIND_F32: return 4;
+    case HBU_KIND_F64: return 8;
+    case HBU_KIND_KAHAN: return 16;
+    default: return 0;
+    }
+}
+uint32_t kind_of_op(uint32_t op)
+{
+    switch (op) {
+    case HBU_OP_HLL64: return HBU_KIND_HLL64;
+    case HBU_OP_U64_ADD:
+    case HBU_OP_U64_MIN: return HBU_KIND_U64;
+    case HBU_OP_F32_ADD: return HBU_KIND_F32;
+    case HBU_OP_F64_ADD: return HBU_KIND_F64;
+    case HBU_OP_KAHAN_ADD: return HBU_KIND_KAHAN;
+    default: return 0xFFFFFFFFu;
+    }
+}
+const char *const kBrokenMsg = "the table is unusable: an earlier failed batch could not be undone";
+
+// the pairs of a batch: in host memory (they cross the link once), or already in device memory and complete with respect to the
+// table's stream (update_centralities hands its compacted result over this way)
+struct Pairs {
+    const hb_u128 *keys;
+    const void *values;
+    bool on_device;
+};
+
+// shared body of batch_set (op = kOpSet) / batch_upsert; *distinct = the number of distinct keys of the batch
+int apply(hbu_table *t, uint32_t op, Pairs in, uint64_t count, uint8_t *actions, uint64_t *distinct = nullptr)
+{
+    const bool upsert = op != kOpSet;
+    if (!t || (count && (!in.keys || !in.values)) || (upsert && count && !actions)) return t ? fail(t, HB_ERR_INVALID, "NULL argument") : HB_ERR_INVALID;
+    if (t->broken) return fail(t, HB_ERR_INVALID, kBrokenMsg);
+    if (upsert && kind_of_op(op) != t->kind) return fail(t, HB_ERR_INVALID, "the upsert operator does not belong to the table's kind");
     // the kernels index 4 threads per pair / group with 32-bit thread ids
     if (count >= (1ull << 30)) return fail(t, HB_ERR_LIMIT, "batch too large (< 2^30 pairs per call)");
+    if (distinct) *distinct = 0;
     if (!count) return HB_OK;
     HBU_HIP(hipSetDevice(t->device));
     if (t->committed + count >= 0xFFFFFFFEull) return fail(t, HB_ERR_LIMIT, "too many keys in one table (< 2^32)");
     // ---- everything that can fail for lack of memory comes BEFORE the index changes: room for count new keys (every pair might
-    // bring one), their counters, the batch's work memory
+    // bring one), their values, the batch's work memory
     int rc;
     // (slots = the power of two >= 2 x keys: the rounding is what makes repeated growth geometric)
     if (2 * (t->committed + count) > t->slots && (rc = rebuild_index(t, t->committed + count, t->committed))) return rc;
@@ -269,10 +313,11 @@ int apply(hbu_table *t, const hb_u128 *keys, const uint8_t *counters, uint64_t c
         HBU_HIP(rocprim::select(nullptr, select_bytes, iota, flags, nul, nul, (size_t)count, t->stream));
     }
     const size_t tmp_bytes = std::max(sort_bytes, select_bytes);
-    auto layout = [&](Carve &c, hb_u128 *&dk, uint4 *&dv, uint32_t *&slot, uint32_t *&slot_s, uint32_t *&perm, uint32_t *&heads, uint32_t *&groups,
+    const uint64_t staged = in.on_device ? 0 : count; // pairs that need room in the work memory
+    auto layout = [&](Carve &c, hb_u128 *&dk, char *&dv, uint32_t *&slot, uint32_t *&slot_s, uint32_t *&perm, uint32_t *&heads, uint32_t *&groups,
                       uint8_t *&act, char *&tmp) {
-        dk = c.take<hb_u128>(count);
-        dv = c.take<uint4>(count * 4);
+        dk = c.take<hb_u128>(staged);
+        dv = c.take<char>(staged * t->vbytes);
         slot = c.take<uint32_t>(count);
         slot_s = c.take<uint32_t>(count);
         perm = c.take<uint32_t>(count);
@@ -282,7 +327,7 @@ int apply(hbu_table *t, const hb_u128 *keys, const uint8_t *counters, uint64_t c
         tmp = c.take<char>(tmp_bytes);
     };
     hb_u128 *d_k;
-    uint4 *d_v;
+    char *d_v;
     uint32_t *d_slot, *d_slot_s, *d_perm, *d_heads, *d_groups;
     uint8_t *d_act;
     char *d_tmp;
@@ -293,14 +338,40 @@ int apply(hbu_table *t, const hb_u128 *keys, const uint8_t *counters, uint64_t c
     }
     Carve carve{(char *)t->d_work};
     layout(carve, d_k, d_v, d_slot, d_slot_s, d_perm, d_heads, d_groups, d_act, d_tmp);
+    const hb_u128 *keys_d = in.on_device ? in.keys : d_k;
+    const void *vals_d = in.on_device ? in.values : d_v;
     // ---- from here on a failure is a HIP error; the keys this batch may have put into the index are taken out again
     // (the index is rebuilt from the entries below `committed`) before the error is returned: the batch is transactional
     const uint32_t first_new = (uint32_t)t->committed;
+    auto launch_values = [&]() {
+        const uint32_t *ss = d_slot_s, *hd = d_heads, *gr = d_groups, *pm = d_perm;
+        const dim3 grid((unsigned)std::min<uint64_t>((count + 255) / 256, 1u << 16)), block(256);
+#define HBU_SET(RAW) hipLaunchKernelGGL(hbv::group_set_kernel<RAW>, grid, block, 0, t->stream, (RAW *)t->d_table, ss, hd, gr, n32, pm, (const RAW *)vals_d)
+#define HBU_UPSERT(OP) \
+    hipLaunchKernelGGL(hbv::group_apply_kernel<hbv::OP>, grid, block, 0, t->stream, (hbv::OP::V *)t->d_table, ss, hd, gr, n32, first_new, pm, (const hbv::OP::V *)vals_d, d_act)
+        switch (op) {
+        case kOpSet:
+            if (t->vbytes == 4) HBU_SET(uint32_t);
+            else if (t->vbytes == 8) HBU_SET(uint64_t);
+            else HBU_SET(uint4);
+            break;
+        case HBU_OP_U64_ADD: HBU_UPSERT(OpU64Add); break;
+        case HBU_OP_U64_MIN: HBU_UPSERT(OpU64Min); break;
+        case HBU_OP_F32_ADD: HBU_UPSERT(OpF32Add); break;
+        case HBU_OP_F64_ADD: HBU_UPSERT(OpF64Add); break;
+        default: HBU_UPSERT(OpKahanAdd); break;
+        }
+#undef HBU_SET
+#undef HBU_UPSERT
+    };
     auto run = [&]() -> hipError_t {
-        hipError_t e = hipMemcpyAsync(d_k, keys, count * sizeof(hb_u128), hipMemcpyHostToDevice, t->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_v, counters, count * 64, hipMemcpyHostToDevice, t->stream);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(slots_insert_kernel, dim3(grid_for(count)), dim3(256), 0, t->stream, (const hb_u128 *)d_k, n32, table_of(t), d_slot);
+        hipError_t e = hipSuccess;
+        if (!in.on_device) {
+            e = hipMemcpyAsync(d_k, in.keys, count * sizeof(hb_u128), hipMemcpyHostToDevice, t->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_v, in.values, count * t->vbytes, hipMemcpyHostToDevice, t->stream);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(slots_insert_kernel, dim3(grid_for(count)), dim3(256), 0, t->stream, keys_d, n32, table_of(t), d_slot);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         auto iota = rocprim::make_counting_iterator<uint32_t>(0);
         size_t b = tmp_bytes;
@@ -309,15 +380,19 @@ int apply(hbu_table *t, const hb_u128 *keys, const uint8_t *counters, uint64_t c
         b = tmp_bytes;
         if ((e = rocprim::select(d_tmp, b, iota, flags, d_heads, d_groups, (size_t)count, t->stream)) != hipSuccess) return e;
         const unsigned blocks = (unsigned)std::min<uint64_t>((count + 63) / 64, 1u << 16);
-        if (upsert)
-            hipLaunchKernelGGL(upsert_kernel<0>, dim3(blocks), dim3(256), 0, t->stream, t->d_table, (const uint32_t *)d_slot_s, (const uint32_t *)d_heads,
-                               (const uint32_t *)d_groups, n32, first_new, (const uint32_t *)d_perm, (const uint4 *)d_v, d_act);
+        if (t->kind != HBU_KIND_HLL64)
+            launch_values();
+        else if (upsert)
+            hipLaunchKernelGGL(upsert_kernel<0>, dim3(blocks), dim3(256), 0, t->stream, (uint4 *)t->d_table, (const uint32_t *)d_slot_s, (const uint32_t *)d_heads,
+                               (const uint32_t *)d_groups, n32, first_new, (const uint32_t *)d_perm, (const uint4 *)vals_d, d_act);
         else
-            hipLaunchKernelGGL(upsert_kernel<1>, dim3(blocks), dim3(256), 0, t->stream, t->d_table, (const uint32_t *)d_slot_s, (const uint32_t *)d_heads,
-                               (const uint32_t *)d_groups, n32, first_new, (const uint32_t *)d_perm, (const uint4 *)d_v, d_act);
+            hipLaunchKernelGGL(upsert_kernel<1>, dim3(blocks), dim3(256), 0, t->stream, (uint4 *)t->d_table, (const uint32_t *)d_slot_s, (const uint32_t *)d_heads,
+                               (const uint32_t *)d_groups, n32, first_new, (const uint32_t *)d_perm, (const uint4 *)vals_d, d_act);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if (upsert && (e = hipMemcpyAsync(actions, d_act, count, hipMemcpyDeviceToHost, t->stream)) != hipSuccess) return e;
         if ((e = hipMemcpyAsync(t->h_word, t->d_next, sizeof(unsigned long long), hipMemcpyDeviceToHost, t->stream)) != hipSuccess) return e;
+        t->h_word[1] = 0;
+        if (distinct && (e = hipMemcpyAsync(&t->h_word[1], d_groups, sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream)) != hipSuccess) return e;
         return hipStreamSynchronize(t->stream);
     };
     const hipError_t e = run();
@@ -328,8 +403,123 @@ int apply(hbu_table *t, const hb_u128 *keys, const uint8_t *counters, uint64_t c
         return fail(t, e == hipErrorOutOfMemory ? HB_ERR_NOMEM : HB_ERR_HIP, why);
     }
     t->committed = *t->h_word;
+    if (distinct) *distinct = t->h_word[1];
     return HB_OK;
 }
+
+// shared body of the two batch_get calls
+int get(hbu_table *t, const hb_u128 *keys, uint64_t count, void *values_out, uint8_t *found)
+{
+    if (!t || (count && (!keys || !values_out))) return t ? fail(t, HB_ERR_INVALID, "NULL argument") : HB_ERR_INVALID;
+    if (count >= (1ull << 30)) return fail(t, HB_ERR_LIMIT, "batch too large (< 2^30 keys per call)"); // 4 threads per key, 32-bit ids
+    if (!count) return HB_OK;
+    if (t->broken) return fail(t, HB_ERR_INVALID, kBrokenMsg);
+    HBU_HIP(hipSetDevice(t->device));
+    Carve probe{nullptr};
+    (void)probe.take<hb_u128>(count);
+    (void)probe.take<uint32_t>(count);
+    (void)probe.take<char>(count * t->vbytes);
+    (void)probe.take<uint8_t>(count);
+    int rc = work_memory(t, probe.used);
+    if (rc) return rc;
+    Carve carve{(char *)t->d_work};
+    hb_u128 *d_k = carve.take<hb_u128>(count);
+    uint32_t *d_slots = carve.take<uint32_t>(count);
+    char *d_out = carve.take<char>(count * t->vbytes);
+    uint8_t *d_found = carve.take<uint8_t>(count);
+    HBU_HIP(hipMemcpyAsync(d_k, keys, count * sizeof(hb_u128), hipMemcpyHostToDevice, t->stream));
+    hipLaunchKernelGGL(slots_find_kernel, dim3(grid_for(count)), dim3(256), 0, t->stream, (const hb_u128 *)d_k, (uint32_t)count, table_of(t),
+                       (uint32_t)t->committed, d_slots, d_found);
+#define HBU_GET(RAW) \
+    hipLaunchKernelGGL(hbv::get_values_kernel<RAW>, dim3(grid_for(count)), dim3(256), 0, t->stream, (const RAW *)t->d_table, (const uint32_t *)d_slots, (uint32_t)count, (RAW *)d_out)
+    if (t->vbytes == 64)
+        hipLaunchKernelGGL(get_kernel, dim3((unsigned)((count * 4 + 255) / 256)), dim3(256), 0, t->stream, (const uint4 *)t->d_table, (const uint32_t *)d_slots,
+                           (uint32_t)count, (uint4 *)d_out);
+    else if (t->vbytes == 4) HBU_GET(uint32_t);
+    else if (t->vbytes == 8) HBU_GET(uint64_t);
+    else HBU_GET(uint4);
+#undef HBU_GET
+    HBU_HIP(hipGetLastError());
+    HBU_HIP(hipMemcpyAsync(values_out, d_out, count * t->vbytes, hipMemcpyDeviceToHost, t->stream));
+    if (found) HBU_HIP(hipMemcpyAsync(found, d_found, count, hipMemcpyDeviceToHost, t->stream));
+    HBU_HIP(hipStreamSynchronize(t->stream));
+    return HB_OK;
+}
+
+// an empty table of `kind` with an index for index_keys keys and room for value_keys values
+int create(int32_t device, uint32_t kind, uint64_t index_keys, uint64_t value_keys, hbu_table **out)
+{
+    hbu_table *t = nullptr;
+    if (!out) return fail(t, HB_ERR_INVALID, "out == NULL");
+    *out = nullptr;
+    if (!bytes_of_kind(kind)) return fail(t, HB_ERR_INVALID, "unknown table kind");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(t, HB_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU fallback");
+    int dev = device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (dev >= ndev) return fail(t, HB_ERR_INVALID, "device ordinal out of range");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return fail(t, HB_ERR_NO_DEVICE, "kernels are built for gfx950 only");
+    hbu_table *tab = new hbu_table();
+    tab->device = dev;
+    tab->kind = kind;
+    tab->vbytes = bytes_of_kind(kind);
+    if (hipSetDevice(dev) != hipSuccess || hipStreamCreateWithFlags(&tab->stream, hipStreamNonBlocking) != hipSuccess) {
+        delete tab;
+        return fail(t, HB_ERR_HIP, "stream creation failed");
+    }
+    int rc = HB_OK;
+    if (hipMalloc((void **)&tab->d_next, 2 * sizeof(unsigned long long)) != hipSuccess || hipHostMalloc((void **)&tab->h_word, 2 * sizeof(unsigned long long)) != hipSuccess) {
+        (void)hipGetLastError();
+        rc = fail(tab, HB_ERR_NOMEM, "allocation of the index counter failed");
+    }
+    if (!rc) rc = rebuild_index(tab, std::max<uint64_t>(index_keys, 1), 0);
+    if (!rc) rc = reserve(tab, std::max<uint64_t>(value_keys, 1));
+    if (rc) {
+        g_hbu_error = tab->err;
+        hbu_destroy(tab);
+        return rc;
+    }
+    *out = tab;
+    return HB_OK;
+}
+
+// HyperLogLog<64>::size()'s tables on a device (hll64_tables.inc + the linear-counting table of hb_internal.h): they go up once
+// per device and process and stay
+struct EstimatorTables {
+    double *raw = nullptr, *bias = nullptr;
+    uint8_t *lc = nullptr;
+};
+std::mutex g_estimator_mu;
+std::map<int, EstimatorTables> g_estimator;
+int estimator_tables(hbu_table *t, EstimatorTables *out)
+{
+    std::lock_guard<std::mutex> lock(g_estimator_mu);
+    auto it = g_estimator.find(t->device);
+    if (it == g_estimator.end()) {
+        uint8_t lc[68];
+        if (!hb::build_lc_table(lc)) return fail(t, HB_ERR_INVALID, "host libm log() too close to a rounding boundary for the linear-counting table");
+        EstimatorTables n;
+        hipError_t e = hipMalloc((void **)&n.raw, sizeof(HLL64_RAW_ESTIMATE));
+        if (e == hipSuccess) e = hipMalloc((void **)&n.bias, sizeof(HLL64_BIAS));
+        if (e == hipSuccess) e = hipMalloc((void **)&n.lc, 68);
+        if (e == hipSuccess) e = hipMemcpy(n.raw, HLL64_RAW_ESTIMATE, sizeof(HLL64_RAW_ESTIMATE), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(n.bias, HLL64_BIAS, sizeof(HLL64_BIAS), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(n.lc, lc, 68, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            for (void *p : {(void *)n.raw, (void *)n.bias, (void *)n.lc})
+                if (p) (void)hipFree(p);
+            return fail(t, e == hipErrorOutOfMemory ? HB_ERR_NOMEM : HB_ERR_HIP, std::string("estimator tables: ") + hipGetErrorString(e));
+        }
+        it = g_estimator.emplace(t->device, n).first;
+    }
+    *out = it->second;
+    return HB_OK;
+}
+template <class V>
+hbv::Side<V> side_of(const hbu_table *t) { return hbv::Side<V>{table_of(t), (uint32_t)t->committed, (const V *)t->d_table}; }
 } // namespace
 
 extern "C" {
@@ -338,40 +528,23 @@ const char *hbu_last_error(const hbu_table *t) { return t ? t->err.c_str() : g_h
 
 int hbu_create(int32_t device, uint64_t capacity_hint, hbu_table **out)
 {
-    return guarded(nullptr, [&]() -> int {
-        hbu_table *t = nullptr;
-        if (!out) return fail(t, HB_ERR_INVALID, "out == NULL");
-        *out = nullptr;
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(t, HB_ERR_NO_DEVICE, "no HIP device visible: this library has no CPU fallback");
-        int dev = device;
-        if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-        if (dev >= ndev) return fail(t, HB_ERR_INVALID, "device ordinal out of range");
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) != hipSuccess || std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            return fail(t, HB_ERR_NO_DEVICE, "kernels are built for gfx950 only");
-        hbu_table *tab = new hbu_table();
-        tab->device = dev;
-        if (hipSetDevice(dev) != hipSuccess || hipStreamCreateWithFlags(&tab->stream, hipStreamNonBlocking) != hipSuccess) {
-            delete tab;
-            return fail(t, HB_ERR_HIP, "stream creation failed");
-        }
-        int rc = HB_OK;
-        if (hipMalloc((void **)&tab->d_next, 2 * sizeof(unsigned long long)) != hipSuccess || hipHostMalloc((void **)&tab->h_word, 2 * sizeof(unsigned long long)) != hipSuccess) {
-            (void)hipGetLastError();
-            rc = fail(tab, HB_ERR_NOMEM, "allocation of the index counter failed");
-        }
-        if (!rc) rc = rebuild_index(tab, std::max<uint64_t>(capacity_hint, 1), 0);
-        if (!rc) rc = reserve(tab, std::max<uint64_t>(capacity_hint, 1));
-        if (rc) {
-            g_hbu_error = tab->err;
-            hbu_destroy(tab);
-            return rc;
-        }
-        *out = tab;
-        return HB_OK;
-    });
+    return guarded(nullptr, [&]() -> int { return create(device, HBU_KIND_HLL64, capacity_hint, capacity_hint, out); });
 }
+
+int hbu_create_kind(int32_t device, uint64_t capacity_hint, uint32_t kind, hbu_table **out)
+{
+    return guarded(nullptr, [&]() -> int { return create(device, kind, capacity_hint, capacity_hint, out); });
+}
+
+int hbu_kind(const hbu_table *t, uint32_t *kind, uint32_t *value_bytes)
+{
+    if (!t) return HB_ERR_INVALID;
+    if (kind) *kind = t->kind;
+    if (value_bytes) *value_bytes = t->vbytes;
+    return HB_OK;
+}
+
+uint32_t hbu_wave_group_length(void) { return hbv::kWaveGroupLen; }
 
 void hbu_destroy(hbu_table *t)
 {
@@ -392,45 +565,132 @@ int hbu_len(const hbu_table *t, uint64_t *keys)
     return HB_OK;
 }
 
+// the three calls of the counter table: refused on a table of another kind
+#define HBU_COUNTERS_ONLY(t) \
+    if ((t) && (t)->kind != HBU_KIND_HLL64) return fail((t), HB_ERR_INVALID, "not a HyperLogLog<64> table: use the _values calls")
+
 int hbu_batch_set(hbu_table *t, const hb_u128 *keys, const uint8_t *counters, uint64_t count)
 {
-    return guarded(t, [&]() -> int { return apply(t, keys, counters, count, nullptr, false); });
+    return guarded(t, [&]() -> int {
+        HBU_COUNTERS_ONLY(t);
+        return apply(t, kOpSet, Pairs{keys, counters, false}, count, nullptr);
+    });
 }
 
 int hbu_batch_upsert(hbu_table *t, const hb_u128 *keys, const uint8_t *counters, uint64_t count, uint8_t *actions)
 {
-    return guarded(t, [&]() -> int { return apply(t, keys, counters, count, actions, true); });
+    return guarded(t, [&]() -> int {
+        HBU_COUNTERS_ONLY(t);
+        return apply(t, HBU_OP_HLL64, Pairs{keys, counters, false}, count, actions);
+    });
 }
 
 int hbu_batch_get(hbu_table *t, const hb_u128 *keys, uint64_t count, uint8_t *counters_out, uint8_t *found)
 {
     return guarded(t, [&]() -> int {
-        if (!t || (count && (!keys || !counters_out))) return t ? fail(t, HB_ERR_INVALID, "NULL argument") : HB_ERR_INVALID;
-        if (count >= (1ull << 30)) return fail(t, HB_ERR_LIMIT, "batch too large (< 2^30 keys per call)"); // 4 threads per key, 32-bit ids
+        HBU_COUNTERS_ONLY(t);
+        return get(t, keys, count, counters_out, found);
+    });
+}
+
+int hbu_batch_set_values(hbu_table *t, const hb_u128 *keys, const void *values, uint64_t count)
+{
+    return guarded(t, [&]() -> int { return apply(t, kOpSet, Pairs{keys, values, false}, count, nullptr); });
+}
+
+int hbu_batch_upsert_values(hbu_table *t, uint32_t op, const hb_u128 *keys, const void *values, uint64_t count, uint8_t *actions)
+{
+    return guarded(t, [&]() -> int {
+        if (t && kind_of_op(op) == 0xFFFFFFFFu) return fail(t, HB_ERR_INVALID, "unknown upsert operator");
+        return apply(t, op, Pairs{keys, values, false}, count, actions);
+    });
+}
+
+int hbu_batch_get_values(hbu_table *t, const hb_u128 *keys, uint64_t count, void *values_out, uint8_t *found)
+{
+    return guarded(t, [&]() -> int { return get(t, keys, count, values_out, found); });
+}
+
+int hbu_clone(hbu_table *from, hbu_table **out)
+{
+    return guarded(from, [&]() -> int {
+        hbu_table *t = from;
+        if (!t || !out) return t ? fail(t, HB_ERR_INVALID, "NULL argument") : HB_ERR_INVALID;
+        *out = nullptr;
+        if (t->broken) return fail(t, HB_ERR_INVALID, kBrokenMsg);
+        hbu_table *tab = nullptr;
+        // (slots / 2 keys give an index of exactly `slots` entries: the copy keeps every entry where it is)
+        int rc = create(t->device, t->kind, t->slots / 2, t->committed, &tab);
+        if (rc) return fail(t, rc, g_hbu_error);
+        // everything of `from` is complete on return of every call; the synchronise covers a caller that used another thread
+        hipError_t e = tab->slots == t->slots ? hipStreamSynchronize(t->stream) : hipErrorInvalidValue;
+        if (e == hipSuccess) e = hipMemcpyAsync(tab->d_keys, t->d_keys, t->slots * sizeof(u128), hipMemcpyDeviceToDevice, tab->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(tab->d_pids, t->d_pids, t->slots * sizeof(uint32_t), hipMemcpyDeviceToDevice, tab->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(tab->d_next, t->d_next, sizeof(unsigned long long), hipMemcpyDeviceToDevice, tab->stream);
+        if (e == hipSuccess && t->committed) e = hipMemcpyAsync(tab->d_table, t->d_table, t->committed * t->vbytes, hipMemcpyDeviceToDevice, tab->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(tab->stream);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            hbu_destroy(tab);
+            return fail(t, HB_ERR_HIP, std::string("copy of the table: ") + hipGetErrorString(e));
+        }
+        tab->committed = t->committed;
+        *out = tab;
+        return HB_OK;
+    });
+}
+
+int hbu_update_centralities(hbu_table *prev_counters, hbu_table *next_counters, hbu_table *prev_centrality, hbu_table *next_centrality, const hb_u128 *nodes,
+                            uint64_t count, uint64_t round, uint64_t *written)
+{
+    hbu_table *t = next_centrality; // the table that changes: its stream runs the step, its error text reports it
+    return guarded(t, [&]() -> int {
+        if (written) *written = 0;
+        if (!prev_counters || !next_counters || !prev_centrality || !t || (count && !nodes)) return t ? fail(t, HB_ERR_INVALID, "NULL argument") : HB_ERR_INVALID;
+        if (prev_counters->kind != HBU_KIND_HLL64 || next_counters->kind != HBU_KIND_HLL64 || prev_centrality->kind != HBU_KIND_KAHAN || t->kind != HBU_KIND_KAHAN)
+            return fail(t, HB_ERR_INVALID, "update_centralities needs two HyperLogLog<64> tables and two KahanSum tables");
+        if (prev_centrality == t) return fail(t, HB_ERR_INVALID, "prev_centrality and next_centrality are the same table");
+        hbu_table *const others[3] = {prev_counters, next_counters, prev_centrality};
+        for (hbu_table *o : others) {
+            if (o->device != t->device) return fail(t, HB_ERR_INVALID, "the four tables are not on one device");
+            if (o->broken) return fail(t, HB_ERR_INVALID, kBrokenMsg);
+        }
+        if (t->broken) return fail(t, HB_ERR_INVALID, kBrokenMsg);
+        if (count >= (1ull << 30)) return fail(t, HB_ERR_LIMIT, "batch too large (< 2^30 nodes per call)");
         if (!count) return HB_OK;
-        if (t->broken) return fail(t, HB_ERR_INVALID, "the table is unusable: an earlier failed batch could not be undone");
         HBU_HIP(hipSetDevice(t->device));
+        EstimatorTables est;
+        int rc = estimator_tables(t, &est);
+        if (rc) return rc;
+        // staging lives in next_counters' work memory (apply() below may replace next_centrality's own): the nodes, the compacted
+        // (node, value) pairs, their count
+        hbu_table *const w = next_counters;
         Carve probe{nullptr};
         (void)probe.take<hb_u128>(count);
-        (void)probe.take<uint32_t>(count);
-        (void)probe.take<uint4>(count * 4);
-        (void)probe.take<uint8_t>(count);
-        int rc = work_memory(t, probe.used);
-        if (rc) return rc;
-        Carve carve{(char *)t->d_work};
-        hb_u128 *d_k = carve.take<hb_u128>(count);
-        uint32_t *d_slots = carve.take<uint32_t>(count);
-        uint4 *d_out = carve.take<uint4>(count * 4);
-        uint8_t *d_found = carve.take<uint8_t>(count);
-        HBU_HIP(hipMemcpyAsync(d_k, keys, count * sizeof(hb_u128), hipMemcpyHostToDevice, t->stream));
-        hipLaunchKernelGGL(slots_find_kernel, dim3(grid_for(count)), dim3(256), 0, t->stream, (const hb_u128 *)d_k, (uint32_t)count, table_of(t),
-                           (uint32_t)t->committed, d_slots, d_found);
-        hipLaunchKernelGGL(get_kernel, dim3((unsigned)((count * 4 + 255) / 256)), dim3(256), 0, t->stream, (const uint4 *)t->d_table,
-                           (const uint32_t *)d_slots, (uint32_t)count, d_out);
+        (void)probe.take<hb_u128>(count);
+        (void)probe.take<hbv::Kahan>(count);
+        (void)probe.take<unsigned long long>(2);
+        if ((rc = work_memory(w, probe.used))) return fail(t, rc, w->err);
+        Carve carve{(char *)w->d_work};
+        hb_u128 *d_nodes = carve.take<hb_u128>(count);
+        hb_u128 *d_keys = carve.take<hb_u128>(count);
+        hbv::Kahan *d_vals = carve.take<hbv::Kahan>(count);
+        unsigned long long *d_count = carve.take<unsigned long long>(2);
+        // every table has its own stream: the three that are only read are idle before this one's stream touches them
+        for (hbu_table *o : others) HBU_HIP(hipStreamSynchronize(o->stream));
+        HBU_HIP(hipMemcpyAsync(d_nodes, nodes, count * sizeof(hb_u128), hipMemcpyHostToDevice, t->stream));
+        HBU_HIP(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned long long), t->stream));
+        const unsigned blocks = (unsigned)std::min<uint64_t>((count + 63) / 64, 1u << 16);
+        hipLaunchKernelGGL(hbv::update_centralities_kernel, dim3(blocks), dim3(256), 0, t->stream, (const hb_u128 *)d_nodes, (uint32_t)count, side_of<uint4>(prev_counters),
+                           side_of<uint4>(next_counters), side_of<hbv::Kahan>(prev_centrality), (const double *)est.raw, (const double *)est.bias,
+                           (const uint8_t *)est.lc, (double)(round + 1), d_keys, d_vals, d_count);
         HBU_HIP(hipGetLastError());
-        HBU_HIP(hipMemcpyAsync(counters_out, d_out, count * 64, hipMemcpyDeviceToHost, t->stream));
-        if (found) HBU_HIP(hipMemcpyAsync(found, d_found, count, hipMemcpyDeviceToHost, t->stream));
+        HBU_HIP(hipMemcpyAsync(t->h_word, d_count, sizeof(unsigned long long), hipMemcpyDeviceToHost, t->stream));
         HBU_HIP(hipStreamSynchronize(t->stream));
+        const uint64_t pairs = *t->h_word; // (a count, not a counter or a size: what apply() must know to size its sort)
+        uint64_t distinct = 0;
+        if ((rc = apply(t, kOpSet, Pairs{d_keys, d_vals, true}, pairs, nullptr, &distinct))) return rc;
+        if (written) *written = distinct;
         return HB_OK;
     });
 }

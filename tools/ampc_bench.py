@@ -4,7 +4,14 @@ at 10 M keys"): batch_set of K distinct keys (every pair inserts), batch_upsert 
 its slot, the pairs of one key applied in batch order), batch_get; from pageable numpy buffers (what the ctypes mirror hands
 over) and from page-locked ones (hb_pinned_alloc: what a worker that owns its receive buffers would use).  Semantics:
 crates/core/src/ampc/dht/upsert.rs:66-89, dht/store.rs:159-190; driver: entrypoint/ampc/harmonic_centrality/mapper.rs:52-118.
-usage: tools/ampc_bench.py [keys, default 10000000] [pairs per batch, default 1000000]"""
+--values adds the scalar value tables in the same process (the counter table's rate above is their comparator): per kind / operator (or
+the one of --kind / --op) the set, get and upsert rates on uniformly drawn keys and the time of a HOT-KEY batch - one key takes half of
+every batch, the shape a shortest-path round sends to a hub - over the time of a uniform one.  --centralities adds
+hbu_update_centralities on four tables of that many keys against the host route it replaces: two batch_gets of counters,
+HyperLogLog::size() on the host (the CPU oracle's, called per counter from Python: its time is reported on its own), the Kahan sums,
+one batch_set.  --out FILE also writes the JSON line there.
+usage: tools/ampc_bench.py [keys, default 10000000] [pairs per batch, default 1000000] [--values] [--kind K] [--op OP] [--centralities] [--out FILE]"""
+import argparse
 import json
 import os
 import sys
@@ -16,9 +23,136 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from stract_amd import _lib, ampc  # noqa: E402
 
 
+KINDS = {"u64": ampc.KIND_U64, "f32": ampc.KIND_F32, "f64": ampc.KIND_F64, "kahan": ampc.KIND_KAHAN}
+OP_NAMES = {"u64_add": ampc.OP_U64_ADD, "u64_min": ampc.OP_U64_MIN, "f32_add": ampc.OP_F32_ADD, "f64_add": ampc.OP_F64_ADD, "kahan_add": ampc.OP_KAHAN_ADD}
+
+
+def random_values(rng, kind, n):
+    if kind == ampc.KIND_U64:
+        return rng.integers(0, 1 << 40, n, dtype=np.uint64)
+    if kind == ampc.KIND_KAHAN:
+        v = np.zeros(n, dtype=ampc.KAHAN)
+        v["sum"] = rng.random(n) * 1e6
+        return v
+    return (rng.random(n) * 1e6).astype(ampc.DTYPES[kind])
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    fn()  # (every call of the table ends in a stream synchronise)
+    return time.perf_counter() - t0
+
+
+def values_mode(rng, keys, K, B, kind, op):
+    """set / get / upsert rates of one scalar kind and operator from page-locked buffers, uniform and hot-key batches alternating"""
+    dtype = ampc.DTYPES[kind]
+    kb, vb = _lib.PinnedRecords(B, dtype=_lib.U128), _lib.PinnedRecords(B, dtype=dtype)
+    kbuf, vbuf = kb.array, vb.array
+    vbuf[:] = random_values(rng, kind, B)
+    acts, found, gout = np.zeros(B, dtype=np.uint8), np.zeros(B, dtype=np.uint8), np.zeros(B, dtype=dtype)
+    rounds = max(K // B, 1)
+    with ampc.ValueTable(kind, capacity_hint=K) as tab:
+        lib, h = tab.lib, tab.h
+        t_set = t_up = t_hot = t_get = 0.0
+        for b in range(0, K, B):
+            n = min(B, K - b)
+            kbuf[:n] = keys[b:b + n]
+            t_set += timed(lambda: tab._check(lib.hbu_batch_set_values(h, _lib._ptr(kbuf), _lib._ptr(vbuf), n)))
+        assert len(tab) == K
+        for shape in ["warm_uniform", "warm_hot"] + ["uniform", "hot"] * rounds:  # alternating: both see the same machine
+            idx = rng.integers(0, K, B)
+            if shape.endswith("hot"):
+                idx[rng.random(B) < 0.5] = 12345 % K  # one key takes half of the batch, spread over it
+            kbuf[:] = keys[idx]
+            t = timed(lambda: tab._check(lib.hbu_batch_upsert_values(h, op, _lib._ptr(kbuf), _lib._ptr(vbuf), B, _lib._ptr(acts))))
+            if shape == "uniform":
+                t_up += t
+            elif shape == "hot":
+                t_hot += t
+        for r in range(rounds):
+            kbuf[:] = keys[rng.integers(0, K, B)]
+            t_get += timed(lambda: tab._check(lib.hbu_batch_get_values(h, _lib._ptr(kbuf), B, _lib._ptr(gout), _lib._ptr(found))))
+        assert found.all() and len(tab) == K
+    kb.close()
+    vb.close()
+    pair_bytes = 16 + dtype.itemsize + 1
+    return {"bytes_per_pair": pair_bytes, "batch_set_inserting_Mpairs_per_s": round(K / t_set / 1e6, 2),
+            "batch_upsert_Mpairs_per_s": round(rounds * B / t_up / 1e6, 2), "batch_upsert_hot_key_Mpairs_per_s": round(rounds * B / t_hot / 1e6, 2),
+            "hot_over_uniform_batch_time": round(t_hot / t_up, 3), "upsert_link_GBs": round(rounds * B * pair_bytes / t_up / 1e9, 2),
+            "batch_get_Mkeys_per_s": round(rounds * B / t_get / 1e6, 2)}
+
+
+def centralities_mode(rng, keys, K, B, host_batches=2):
+    """hbu_update_centralities over four tables of K keys in batches of B nodes, and the host route for the first host_batches of them"""
+    from oracle import hbo
+    regs = rng.integers(0, 30, (B, 64), dtype=np.uint8)
+    more = rng.integers(0, 32, (B, 64), dtype=np.uint8)
+    acts = np.zeros(B, dtype=np.uint8)
+    res = {}
+    with ampc.CounterTable(capacity_hint=K) as prev_c, ampc.ValueTable(ampc.KIND_KAHAN, capacity_hint=K) as prev_v:
+        for b in range(0, K, B):
+            n = min(B, K - b)
+            prev_c.batch_set(keys[b:b + n], regs[:n])
+            prev_v.batch_set(keys[b:b + n], random_values(rng, ampc.KIND_KAHAN, n))
+        t_clone = timed(lambda: res.setdefault("t", (prev_c.clone(), prev_v.clone())))
+        next_c, next_v = res.pop("t")
+        res["clone_counters_and_centrality_s"] = round(t_clone, 4)
+        res["clone_GBs"] = round(K * (64 + 16 + 2 * 2 * 20) / t_clone / 1e9, 1)  # values + the index (2 x 20 B per key at load factor 1/2)
+        for b in range(0, K, B):                      # a round's update_counters: about half of the counters grow
+            n = min(B, K - b)
+            next_c.batch_upsert(keys[b:b + n], more[:n])
+        with next_c, next_v:
+            ampc.update_centralities(prev_c, next_c, prev_v, next_v, keys[:B], 0)  # warm-up (the estimator tables go up here)
+            t_dev, written = 0.0, 0
+            for b in range(0, K, B):
+                nodes = keys[b:b + B]
+                t0 = time.perf_counter()
+                written += ampc.update_centralities(prev_c, next_c, prev_v, next_v, nodes, 1)
+                t_dev += time.perf_counter() - t0
+            res["update_centralities_Mnodes_per_s"] = round(K / t_dev / 1e6, 2)
+            res["written_share"] = round(written / K, 3)
+            t_link = t_size = t_kahan = 0.0
+            done = 0
+            for b in range(0, min(K, host_batches * B), B):
+                nodes = keys[b:b + B]
+                t0 = time.perf_counter()
+                old_c, _ = prev_c.batch_get(nodes)
+                new_c, _ = next_c.batch_get(nodes)
+                old_v, _ = prev_v.batch_get(nodes)
+                t1 = time.perf_counter()
+                d = hbo.hll_sizes(new_c).astype(np.int64) - hbo.hll_sizes(old_c).astype(np.int64)
+                t2 = time.perf_counter()
+                sel = d > 0
+                rhs = d[sel].astype(np.float64) / 2.0
+                y = rhs - old_v["err"][sel]
+                t = old_v["sum"][sel] + y
+                val = np.zeros(int(sel.sum()), dtype=ampc.KAHAN)
+                val["sum"], val["err"] = t, (t - old_v["sum"][sel]) - y
+                t3 = time.perf_counter()
+                next_v.batch_set(nodes[sel], val)
+                t4 = time.perf_counter()
+                t_link += (t1 - t0) + (t4 - t3)
+                t_size += t2 - t1
+                t_kahan += t3 - t2
+                done += len(nodes)
+            res["host_route_Mnodes_per_s"] = round(done / (t_link + t_size + t_kahan) / 1e6, 3)
+            res["host_route_link_only_Mnodes_per_s"] = round(done / t_link / 1e6, 2)  # the gets and the set alone: 64 + 64 + 16 B down, 32 B up per node
+            res["host_route_seconds_per_Mnodes"] = {"gets_and_set": round(t_link / done * 1e6, 3), "sizes_on_host": round(t_size / done * 1e6, 3),
+                                                    "kahan_on_host": round(t_kahan / done * 1e6, 3)}
+    return res
+
+
 def main():
-    K = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
-    B = int(sys.argv[2]) if len(sys.argv) > 2 else 1_000_000
+    ap = argparse.ArgumentParser()
+    ap.add_argument("keys", nargs="?", type=int, default=10_000_000)
+    ap.add_argument("batch", nargs="?", type=int, default=1_000_000)
+    ap.add_argument("--values", action="store_true", help="also the scalar value tables (every kind / operator unless --kind / --op)")
+    ap.add_argument("--kind", choices=sorted(KINDS))
+    ap.add_argument("--op", choices=sorted(OP_NAMES))
+    ap.add_argument("--centralities", action="store_true", help="also hbu_update_centralities against the host route")
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    K, B = args.keys, args.batch
     rng = np.random.default_rng(1)
     keys = np.zeros(K, dtype=_lib.U128)
     keys["lo"] = rng.permutation(K).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)
@@ -69,7 +203,22 @@ def main():
             if x:
                 x.close()
         out[label] = res
-    print(json.dumps(out))
+        print(label, res, file=sys.stderr, flush=True)
+    if args.values or args.kind or args.op:
+        out["values_pinned"] = {}
+        for name, op in OP_NAMES.items():
+            kind = name.split("_")[0]
+            if (args.kind and kind != args.kind) or (args.op and name != args.op):
+                continue
+            out["values_pinned"][name] = values_mode(rng, keys, K, B, KINDS[kind], op)
+            print(name, out["values_pinned"][name], file=sys.stderr, flush=True)
+    if args.centralities:
+        out["update_centralities"] = centralities_mode(rng, keys, K, B)
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":
