@@ -17,13 +17,19 @@
  * table (hb_table.hip.h), the values one array of 64 / 8 / 4 / 8 / 16 bytes each.  A batch is grouped by key with its order kept and
  * every group is folded by one writer in that order (HyperLogLog: one quad per key; the scalar kinds: one thread per key, one wave for
  * a key with many pairs).  hbu_update_centralities is CentralityMapper::update_centralities (mapper.rs:157-209) as one device call:
- * no counter and no size crosses the link.
+ * no counter and no size crosses the link.  The two steps that walk the EDGES are device calls between two resident tables as well:
+ *     hbu_update_counters   CentralityMapper::update_counters (mapper.rs:89-111): batch_get of edge.from, add_u128(edge.from),
+ *                           batch_upsert(HyperLogLog64Upsert) into edge.to - 32 B of ids up and one action byte back per edge
+ *     hbu_update_distances  ShortestPathMapper::update_distances (shortest_path/mapper.rs:64-86): batch_get of edge.from, + 1, the
+ *                           batch's own minimum per destination, batch_upsert(U64Min) - ids up, one (key, action) per destination back
+ * so that clone -> edge step -> update_centralities -> swap is a whole round of either job with no counter on the link.
  * In: HyperLogLog<64> with HyperLogLog64Upsert; u64 with U64Add / U64Min; f32 with F32Add; f64 with F64Add; KahanSum with KahanSumAdd
- * (upsert.rs:92-152); the copy of a table; update_centralities.  Still out: HyperLogLog<8/16/32/128> (no job uses them), the String,
+ * (upsert.rs:92-152); the copy of a table; update_centralities; update_counters; update_distances.  Still out: HyperLogLog<8/16/32/128> (no job uses them), the String,
  * meta and bloom-valued tables and UpdatedNodes (a handful of values per shard: host work on the actions array), raft replication,
  * the network protocol, shards that span ranks.
- * Defined differences: U64Add wraps at 2^64 (the reference panics in a debug build and wraps in a release build); an operator that
- * does not belong to the table's kind is refused with HB_ERR_INVALID and changes nothing (the reference panics).
+ * Defined differences: U64Add wraps at 2^64 (the reference panics in a debug build and wraps in a release build), and so does the
+ * `+ 1` of hbu_update_distances; an operator that does not belong to the table's kind is refused with HB_ERR_INVALID and changes
+ * nothing (the reference panics).
  *
  * extern "C", never unwinds, 0 = ok, negative = HB_ERR_* of hyperball.h; needs a gfx950 device (no CPU fallback).
  */
@@ -94,6 +100,30 @@ int hbu_clone(hbu_table *from, hbu_table **out);
  * reference's BTreeMap).  Refused with HB_ERR_INVALID: wrong kinds, tables on different devices, prev_centrality == next_centrality. */
 int hbu_update_centralities(hbu_table *prev_counters, hbu_table *next_counters, hbu_table *prev_centrality, hbu_table *next_centrality,
                             const hb_u128 *nodes, uint64_t count, uint64_t round, uint64_t *written);
+
+/* ---- the edge steps: `prev` is only read, `next` changes; both of one kind on one device.  Everything is visible on return (the call
+ * runs on next's stream after a synchronise of prev's).  Refused with HB_ERR_INVALID, or HB_ERR_LIMIT for count >= 2^30 (checked before
+ * an edge is read), both tables untouched and hbu_last_error set on next: NULL with a count, a wrong kind on either table, tables on
+ * different devices, prev == next, a broken table.  count == 0: HB_OK, nothing touched.  Transactional like every batch call: after a
+ * HIP error next holds the keys it held before. */
+
+/* CentralityMapper::update_counters (mapper.rs:89-111) for `count` edges (from[i], to[i]), both tables HBU_KIND_HLL64: pair i =
+ * (to[i], (prev[from[i]] or HyperLogLog::default() - unwrap_or_default, mapper.rs:98: an absent source is NOT a skipped edge) with
+ * add_u128(from[i]): only the low 64 bits of from[i] are hashed, hyperloglog.rs:4398-4400, while the table key is all 128), upserted
+ * into `next` with HyperLogLog64Upsert in edge order (an absent destination: Inserted, the pair's counter verbatim); actions[i] = HBU_*
+ * of pair i.  Tables and actions equal, bit for bit, those of hbu_batch_get(prev, from) + add_u128 on the host +
+ * hbu_batch_upsert(next, to, ...) for the same batch. */
+int hbu_update_counters(hbu_table *prev_counters, hbu_table *next_counters, const hb_u128 *from, const hb_u128 *to, uint64_t count, uint8_t *actions);
+
+/* ShortestPathMapper::update_distances (shortest_path/mapper.rs:64-86), both tables HBU_KIND_U64: an edge whose source has no distance
+ * in `prev` is skipped (and inserts nothing: a destination all of whose edges were skipped is neither in the output nor in `next`); the
+ * others give to[i] the candidate prev[from[i]] + 1 (2^64 - 1 wraps to 0); every distinct destination with a candidate is upserted ONCE
+ * with U64Min and its smallest candidate: Inserted for an absent destination, Merged iff that candidate is below the stored value,
+ * NoChange otherwise.  keys_out / actions_out (room for `count` entries each): one entry per such destination, *written of them, every
+ * destination exactly once; their order is unspecified (the reference's is a hash map's iteration order), the set of entries is the
+ * same for the same inputs. */
+int hbu_update_distances(hbu_table *prev_distances, hbu_table *next_distances, const hb_u128 *from, const hb_u128 *to, uint64_t count,
+                         hb_u128 *keys_out, uint8_t *actions_out, uint64_t *written);
 
 #ifdef __cplusplus
 }

@@ -425,6 +425,8 @@ _SIGNATURES += [
     ("hbu_wave_group_length", ctypes.c_uint32, []),
     ("hbu_clone", ctypes.c_int, [_P, ctypes.POINTER(_P)]),
     ("hbu_update_centralities", ctypes.c_int, [_P, _P, _P, _P, _P, _U64, _U64, ctypes.POINTER(_U64)]),
+    ("hbu_update_counters", ctypes.c_int, [_P, _P, _P, _P, _U64, _P]),
+    ("hbu_update_distances", ctypes.c_int, [_P, _P, _P, _P, _U64, _P, _P, ctypes.POINTER(_U64)]),
 ]
 # include/hb_store.h
 _SIGNATURES += [

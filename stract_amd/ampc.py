@@ -3,7 +3,8 @@ counter table (`DefaultDhtTable<NodeID, HyperLogLog<64>>`, crates/core/src/entry
 three batch operations its mappers use (mapper.rs:52-118): batch_set, batch_get, batch_upsert(HyperLogLog64Upsert).  ValueTable is a
 table of one of the scalar kinds (u64, f32, f64, KahanSum) with the scalar upsert operators (dht/upsert.rs:92-152): the `centrality`
 table of that job and the `distances` table of the shortest-path job (shortest_path/mod.rs:51-55).  Both have clone() (clone_table,
-dht/store.rs:192-195); update_centralities is mapper.rs:157-209 as one device call."""
+dht/store.rs:192-195); update_centralities is mapper.rs:157-209 as one device call, update_counters (mapper.rs:89-111) and
+update_distances (shortest_path/mapper.rs:64-86) are the two jobs' edge steps between two resident tables: edge ids go up, actions come back."""
 import ctypes
 
 import numpy as np
@@ -148,3 +149,34 @@ def update_centralities(prev_counters, next_counters, prev_centrality, next_cent
                                                      round, ctypes.byref(written))
     next_centrality._check(rc)
     return written.value
+
+
+def _edges(from_ids, to_ids):
+    from_ids = np.ascontiguousarray(from_ids, dtype=_lib.U128)
+    to_ids = np.ascontiguousarray(to_ids, dtype=_lib.U128)
+    if from_ids.shape != to_ids.shape or from_ids.ndim != 1:
+        raise ValueError("one source and one destination per edge")
+    return from_ids, to_ids
+
+
+def update_counters(prev, next, from_ids, to_ids):
+    """CentralityMapper::update_counters (mapper.rs:89-111) on two resident counter tables: for every edge in order, the counter of
+    `from` in `prev` (or the default one) with `from` itself added is upserted into `to` of `next` with HyperLogLog64Upsert.  Returns
+    the action of every edge (uint8 array)."""
+    from_ids, to_ids = _edges(from_ids, to_ids)
+    actions = np.zeros(len(from_ids), dtype=np.uint8)
+    next._check(next.lib.hbu_update_counters(prev.h, next.h, _lib._ptr(from_ids), _lib._ptr(to_ids), len(from_ids), _lib._ptr(actions)))
+    return actions
+
+
+def update_distances(prev, next, from_ids, to_ids):
+    """ShortestPathMapper::update_distances (shortest_path/mapper.rs:64-86) on two resident u64 tables: an edge whose source has no
+    distance in `prev` is skipped; every other destination is upserted once into `next` with U64Min and the smallest `prev[from] + 1`
+    of its edges.  Returns (keys, actions): one entry per such destination, in no particular order."""
+    from_ids, to_ids = _edges(from_ids, to_ids)
+    keys = np.zeros(len(from_ids), dtype=_lib.U128)
+    actions = np.zeros(len(from_ids), dtype=np.uint8)
+    written = ctypes.c_uint64(0)
+    next._check(next.lib.hbu_update_distances(prev.h, next.h, _lib._ptr(from_ids), _lib._ptr(to_ids), len(from_ids), _lib._ptr(keys), _lib._ptr(actions),
+                                              ctypes.byref(written)))
+    return keys[:written.value].copy(), actions[:written.value].copy()

@@ -1,6 +1,7 @@
 // hb_ampc.hip - GPU-resident shard of the AMPC tables: the HyperLogLog<64> counter table with HyperLogLog64Upsert semantics, the
-// scalar value tables with the five scalar upsert operators, a device copy of a table and the update_centralities step
-// (include/hb_ampc.h cites the reference operations this serves; the scalar kernels live in hb_ampc_values.hip.h).
+// scalar value tables with the five scalar upsert operators, a device copy of a table, the update_centralities step and the two edge
+// steps update_counters / update_distances (include/hb_ampc.h cites the reference operations this serves; the scalar kernels live in
+// hb_ampc_values.hip.h, those of the edge steps in hb_ampc_edges.hip.h).
 #include "hb_guard_alloc.h" // FIRST: no-op unless built with -DHB_GUARD_ALLOC=<mode> (debug allocators: guard pages / poison / red zones)
 #include "hb_pool.h"        // then: every hipMalloc / hipFree below goes through the caching device allocator (shipped build)
 #include <hip/hip_runtime.h>
@@ -16,6 +17,7 @@
 
 #include "../../include/hb_ampc.h"
 #include "hb_ampc_values.hip.h"
+#include "hb_ampc_edges.hip.h"
 #include "hb_internal.h"
 #include "hb_regs.hip.h"
 #include "hb_table.hip.h"
@@ -282,13 +284,22 @@ struct Pairs {
     const hb_u128 *keys;
     const void *values;
     bool on_device;
+    // update_counters: `values` is NULL and the counter of pair i is gathered from another table while the pair is folded
+    const hbe::CounterSource *gather = nullptr;
+};
+// update_distances: what comes back is one (key, action) per key GROUP of the batch instead of one action per pair (host memory,
+// room for `count` entries each; the number of groups is *distinct)
+struct GroupOut {
+    hb_u128 *keys;
+    uint8_t *actions;
 };
 
 // shared body of batch_set (op = kOpSet) / batch_upsert; *distinct = the number of distinct keys of the batch
-int apply(hbu_table *t, uint32_t op, Pairs in, uint64_t count, uint8_t *actions, uint64_t *distinct = nullptr)
+int apply(hbu_table *t, uint32_t op, Pairs in, uint64_t count, uint8_t *actions, uint64_t *distinct = nullptr, const GroupOut *per_group = nullptr)
 {
     const bool upsert = op != kOpSet;
-    if (!t || (count && (!in.keys || !in.values)) || (upsert && count && !actions)) return t ? fail(t, HB_ERR_INVALID, "NULL argument") : HB_ERR_INVALID;
+    if (!t || (count && (!in.keys || (!in.values && !in.gather))) || (upsert && count && !actions && !per_group))
+        return t ? fail(t, HB_ERR_INVALID, "NULL argument") : HB_ERR_INVALID;
     if (t->broken) return fail(t, HB_ERR_INVALID, kBrokenMsg);
     if (upsert && kind_of_op(op) != t->kind) return fail(t, HB_ERR_INVALID, "the upsert operator does not belong to the table's kind");
     // the kernels index 4 threads per pair / group with 32-bit thread ids
@@ -314,6 +325,9 @@ int apply(hbu_table *t, uint32_t op, Pairs in, uint64_t count, uint8_t *actions,
     }
     const size_t tmp_bytes = std::max(sort_bytes, select_bytes);
     const uint64_t staged = in.on_device ? 0 : count; // pairs that need room in the work memory
+    const uint64_t grouped = per_group ? count : 0; // (key, action) of every group
+    hb_u128 *d_gkeys;
+    uint8_t *d_gact;
     auto layout = [&](Carve &c, hb_u128 *&dk, char *&dv, uint32_t *&slot, uint32_t *&slot_s, uint32_t *&perm, uint32_t *&heads, uint32_t *&groups,
                       uint8_t *&act, char *&tmp) {
         dk = c.take<hb_u128>(staged);
@@ -325,6 +339,8 @@ int apply(hbu_table *t, uint32_t op, Pairs in, uint64_t count, uint8_t *actions,
         groups = c.take<uint32_t>(2);
         act = c.take<uint8_t>(count);
         tmp = c.take<char>(tmp_bytes);
+        d_gkeys = c.take<hb_u128>(grouped);
+        d_gact = c.take<uint8_t>(grouped);
     };
     hb_u128 *d_k;
     char *d_v;
@@ -382,6 +398,9 @@ int apply(hbu_table *t, uint32_t op, Pairs in, uint64_t count, uint8_t *actions,
         const unsigned blocks = (unsigned)std::min<uint64_t>((count + 63) / 64, 1u << 16);
         if (t->kind != HBU_KIND_HLL64)
             launch_values();
+        else if (in.gather)
+            hipLaunchKernelGGL(hbe::upsert_edges_kernel, dim3(blocks), dim3(256), 0, t->stream, (uint4 *)t->d_table, (const uint32_t *)d_slot_s, (const uint32_t *)d_heads,
+                               (const uint32_t *)d_groups, n32, first_new, (const uint32_t *)d_perm, *in.gather, d_act);
         else if (upsert)
             hipLaunchKernelGGL(upsert_kernel<0>, dim3(blocks), dim3(256), 0, t->stream, (uint4 *)t->d_table, (const uint32_t *)d_slot_s, (const uint32_t *)d_heads,
                                (const uint32_t *)d_groups, n32, first_new, (const uint32_t *)d_perm, (const uint4 *)vals_d, d_act);
@@ -389,10 +408,21 @@ int apply(hbu_table *t, uint32_t op, Pairs in, uint64_t count, uint8_t *actions,
             hipLaunchKernelGGL(upsert_kernel<1>, dim3(blocks), dim3(256), 0, t->stream, (uint4 *)t->d_table, (const uint32_t *)d_slot_s, (const uint32_t *)d_heads,
                                (const uint32_t *)d_groups, n32, first_new, (const uint32_t *)d_perm, (const uint4 *)vals_d, d_act);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        if (upsert && (e = hipMemcpyAsync(actions, d_act, count, hipMemcpyDeviceToHost, t->stream)) != hipSuccess) return e;
+        if (per_group) {
+            hipLaunchKernelGGL(hbe::group_actions_kernel, dim3(grid_for(count)), dim3(256), 0, t->stream, (const uint32_t *)d_heads, (const uint32_t *)d_groups, n32,
+                               (const uint32_t *)d_perm, keys_d, (const uint8_t *)d_act, d_gkeys, d_gact);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+        } else if (upsert && (e = hipMemcpyAsync(actions, d_act, count, hipMemcpyDeviceToHost, t->stream)) != hipSuccess) {
+            return e;
+        }
         if ((e = hipMemcpyAsync(t->h_word, t->d_next, sizeof(unsigned long long), hipMemcpyDeviceToHost, t->stream)) != hipSuccess) return e;
         t->h_word[1] = 0;
-        if (distinct && (e = hipMemcpyAsync(&t->h_word[1], d_groups, sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream)) != hipSuccess) return e;
+        if ((distinct || per_group) && (e = hipMemcpyAsync(&t->h_word[1], d_groups, sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream)) != hipSuccess) return e;
+        if ((e = hipStreamSynchronize(t->stream)) != hipSuccess || !per_group) return e;
+        // the group count is known only now: exactly that many (key, action) entries cross the link
+        const uint64_t groups = t->h_word[1];
+        if ((e = hipMemcpyAsync(per_group->keys, d_gkeys, groups * sizeof(hb_u128), hipMemcpyDeviceToHost, t->stream)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(per_group->actions, d_gact, groups, hipMemcpyDeviceToHost, t->stream)) != hipSuccess) return e;
         return hipStreamSynchronize(t->stream);
     };
     const hipError_t e = run();
@@ -691,6 +721,119 @@ int hbu_update_centralities(hbu_table *prev_counters, hbu_table *next_counters, 
         uint64_t distinct = 0;
         if ((rc = apply(t, kOpSet, Pairs{d_keys, d_vals, true}, pairs, nullptr, &distinct))) return rc;
         if (written) *written = distinct;
+        return HB_OK;
+    });
+}
+
+// what the two edge steps refuse before they look at an edge; t = the table that changes
+static int edge_step_refusal(hbu_table *prev, hbu_table *t, uint32_t kind, const hb_u128 *from, const hb_u128 *to, uint64_t count, const char *kinds_msg)
+{
+    if (!prev || !t) return t ? fail(t, HB_ERR_INVALID, "NULL argument") : HB_ERR_INVALID;
+    if (count >= (1ull << 30)) return fail(t, HB_ERR_LIMIT, "batch too large (< 2^30 edges per call)"); // 32-bit positions, 4 threads per group
+    if (count && (!from || !to)) return fail(t, HB_ERR_INVALID, "NULL argument");
+    if (prev->kind != kind || t->kind != kind) return fail(t, HB_ERR_INVALID, kinds_msg);
+    if (prev == t) return fail(t, HB_ERR_INVALID, "prev and next are the same table");
+    if (prev->device != t->device) return fail(t, HB_ERR_INVALID, "the two tables are not on one device");
+    if (prev->broken || t->broken) return fail(t, HB_ERR_INVALID, kBrokenMsg);
+    return HB_OK;
+}
+
+int hbu_update_counters(hbu_table *prev_counters, hbu_table *next_counters, const hb_u128 *from, const hb_u128 *to, uint64_t count, uint8_t *actions)
+{
+    hbu_table *t = next_counters; // the table that changes: its stream runs the step, its error text reports it
+    return guarded(t, [&]() -> int {
+        int rc = edge_step_refusal(prev_counters, t, HBU_KIND_HLL64, from, to, count, "update_counters needs two HyperLogLog<64> tables");
+        if (rc) return rc;
+        if (count && !actions) return fail(t, HB_ERR_INVALID, "NULL argument");
+        if (!count) return HB_OK;
+        HBU_HIP(hipSetDevice(t->device));
+        // staging lives in prev's work memory (apply() below may replace next's own): both ends of every edge, the source's slot, the
+        // register its add sets.  No counter is staged.
+        hbu_table *const w = prev_counters;
+        Carve probe{nullptr};
+        (void)probe.take<hb_u128>(count);
+        (void)probe.take<hb_u128>(count);
+        (void)probe.take<uint32_t>(count);
+        (void)probe.take<uint16_t>(count);
+        if ((rc = work_memory(w, probe.used))) return fail(t, rc, w->err);
+        Carve carve{(char *)w->d_work};
+        hb_u128 *d_from = carve.take<hb_u128>(count);
+        hb_u128 *d_to = carve.take<hb_u128>(count);
+        uint32_t *d_src = carve.take<uint32_t>(count);
+        uint16_t *d_jp = carve.take<uint16_t>(count);
+        HBU_HIP(hipStreamSynchronize(w->stream)); // prev is only read: idle before this table's stream touches it
+        HBU_HIP(hipMemcpyAsync(d_from, from, count * sizeof(hb_u128), hipMemcpyHostToDevice, t->stream));
+        HBU_HIP(hipMemcpyAsync(d_to, to, count * sizeof(hb_u128), hipMemcpyHostToDevice, t->stream));
+        hipLaunchKernelGGL(hbe::counter_sources_kernel, dim3(grid_for(count)), dim3(256), 0, t->stream, (const hb_u128 *)d_from, (uint32_t)count,
+                           side_of<uint4>(prev_counters), d_src, d_jp);
+        HBU_HIP(hipGetLastError());
+        const hbe::CounterSource src{(const uint4 *)prev_counters->d_table, d_src, d_jp};
+        Pairs pairs{d_to, nullptr, true};
+        pairs.gather = &src;
+        return apply(t, HBU_OP_HLL64, pairs, count, actions);
+    });
+}
+
+int hbu_update_distances(hbu_table *prev_distances, hbu_table *next_distances, const hb_u128 *from, const hb_u128 *to, uint64_t count, hb_u128 *keys_out,
+                         uint8_t *actions_out, uint64_t *written)
+{
+    hbu_table *t = next_distances;
+    return guarded(t, [&]() -> int {
+        if (written) *written = 0;
+        int rc = edge_step_refusal(prev_distances, t, HBU_KIND_U64, from, to, count, "update_distances needs two u64 tables");
+        if (rc) return rc;
+        if (count && (!keys_out || !actions_out || !written)) return fail(t, HB_ERR_INVALID, "NULL argument");
+        if (!count) return HB_OK;
+        HBU_HIP(hipSetDevice(t->device));
+        // staging lives in prev's work memory, as above: the edges, a candidate and a flag per edge, the compacted (destination,
+        // candidate) pairs of the edges that have one, their count
+        hbu_table *const w = prev_distances;
+        size_t select_bytes = 0, select_bytes_v = 0;
+        {
+            const uint8_t *nul = nullptr;
+            HBU_HIP(rocprim::select(nullptr, select_bytes, (const hb_u128 *)nullptr, nul, (hb_u128 *)nullptr, (uint32_t *)nullptr, (size_t)count, t->stream));
+            HBU_HIP(rocprim::select(nullptr, select_bytes_v, (const uint64_t *)nullptr, nul, (uint64_t *)nullptr, (uint32_t *)nullptr, (size_t)count, t->stream));
+            select_bytes = std::max(select_bytes, select_bytes_v);
+        }
+        hb_u128 *d_from, *d_to, *d_keys;
+        uint64_t *d_cand, *d_vals;
+        uint8_t *d_has;
+        uint32_t *d_count;
+        char *d_tmp;
+        auto layout = [&](Carve &c) {
+            d_from = c.take<hb_u128>(count);
+            d_to = c.take<hb_u128>(count);
+            d_cand = c.take<uint64_t>(count);
+            d_has = c.take<uint8_t>(count);
+            d_keys = c.take<hb_u128>(count);
+            d_vals = c.take<uint64_t>(count);
+            d_count = c.take<uint32_t>(2);
+            d_tmp = c.take<char>(select_bytes);
+        };
+        Carve probe{nullptr};
+        layout(probe);
+        if ((rc = work_memory(w, probe.used))) return fail(t, rc, w->err);
+        Carve carve{(char *)w->d_work};
+        layout(carve);
+        HBU_HIP(hipStreamSynchronize(w->stream));
+        HBU_HIP(hipMemcpyAsync(d_from, from, count * sizeof(hb_u128), hipMemcpyHostToDevice, t->stream));
+        HBU_HIP(hipMemcpyAsync(d_to, to, count * sizeof(hb_u128), hipMemcpyHostToDevice, t->stream));
+        hipLaunchKernelGGL(hbe::distance_candidates_kernel, dim3(grid_for(count)), dim3(256), 0, t->stream, (const hb_u128 *)d_from, (uint32_t)count,
+                           side_of<uint64_t>(prev_distances), d_cand, d_has);
+        HBU_HIP(hipGetLastError());
+        // the edges that have a candidate, batch order kept; only their destinations ever reach next's index
+        size_t b = select_bytes;
+        HBU_HIP(rocprim::select(d_tmp, b, (const hb_u128 *)d_to, (const uint8_t *)d_has, d_keys, d_count, (size_t)count, t->stream));
+        b = select_bytes;
+        HBU_HIP(rocprim::select(d_tmp, b, (const uint64_t *)d_cand, (const uint8_t *)d_has, d_vals, d_count + 1, (size_t)count, t->stream));
+        *t->h_word = 0; // (the copy fills its low half)
+        HBU_HIP(hipMemcpyAsync(t->h_word, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, t->stream));
+        HBU_HIP(hipStreamSynchronize(t->stream));
+        const uint64_t pairs = *t->h_word; // (a count: what apply() must know to size its sort)
+        const GroupOut out{keys_out, actions_out};
+        uint64_t groups = 0;
+        if ((rc = apply(t, HBU_OP_U64_MIN, Pairs{d_keys, d_vals, true}, pairs, nullptr, &groups, &out))) return rc;
+        *written = groups;
         return HB_OK;
     });
 }

@@ -70,4 +70,23 @@ __device__ __forceinline__ bool u4_ne(const uint4 &a, const uint4 &b)
     return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) != 0;
 }
 
+// the one register HyperLogLog::default(); add_u128(id) sets (hyperloglog.rs:4385-4400 with FastHasher :4311-4313; only the low 64 bits of
+// the id are hashed), as index | value << 8 - the entry format of src_jp / self_jp
+__device__ __forceinline__ uint16_t initial_register_jp(uint64_t id_low)
+{
+    const uint64_t hash = id_low * 11400714819323198549ull;
+    const uint32_t j = (uint32_t)(hash >> 58);
+    const uint64_t w = hash << 6;
+    const uint32_t pval = (w == 0 ? 64u : (uint32_t)__clzll((long long)w)) + 1u;
+    return (uint16_t)(j | (pval << 8));
+}
+// lane q's quarter (registers 16 q .. 16 q + 15) of the counter that entry describes
+__device__ __forceinline__ uint4 counter_quarter_of_jp(uint32_t jp, int q)
+{
+    const uint32_t j = jp & 63u, pval = jp >> 8;
+    uint32_t ww[4] = {0, 0, 0, 0};
+    if (pval && (int)(j >> 4) == q) ww[(j & 15u) >> 2] = pval << (8 * (j & 3u));
+    return make_uint4(ww[0], ww[1], ww[2], ww[3]);
+}
+
 } // namespace hbk

@@ -9,8 +9,13 @@ the one of --kind / --op) the set, get and upsert rates on uniformly drawn keys 
 every batch, the shape a shortest-path round sends to a hub - over the time of a uniform one.  --centralities adds
 hbu_update_centralities on four tables of that many keys against the host route it replaces: two batch_gets of counters,
 HyperLogLog::size() on the host (the CPU oracle's, called per counter from Python: its time is reported on its own), the Kahan sums,
-one batch_set.  --out FILE also writes the JSON line there.
-usage: tools/ampc_bench.py [keys, default 10000000] [pairs per batch, default 1000000] [--values] [--kind K] [--op OP] [--centralities] [--out FILE]"""
+one batch_set.  --edges adds the two edge steps, hbu_update_counters and hbu_update_distances, between two tables of that many keys
+against the host route built from the calls that were there before them - batch_get + batch_upsert for the counters, batch_get_values +
+batch_upsert_values(U64_MIN) on the per-destination minima for the distances; the host's own add / minimum is NOT timed, so the
+comparator is its link-and-device part alone - on uniformly drawn destinations and on batches half of which go to one destination,
+both sides alternating, median / minimum / maximum of --reps batches each.  --out FILE also writes the JSON line there.
+usage: tools/ampc_bench.py [keys, default 10000000] [pairs per batch, default 1000000] [--values] [--kind K] [--op OP] [--centralities]
+                           [--edges] [--reps N, default 5] [--out FILE]"""
 import argparse
 import json
 import os
@@ -142,6 +147,103 @@ def centralities_mode(rng, keys, K, B, host_batches=2):
     return res
 
 
+def spread(times):
+    t = sorted(times)
+    return {"median_s": round(t[len(t) // 2] if len(t) % 2 else (t[len(t) // 2 - 1] + t[len(t) // 2]) / 2, 6), "min_s": round(t[0], 6), "max_s": round(t[-1], 6)}
+
+
+def edges_mode(rng, keys, K, B, reps):
+    """hbu_update_counters / hbu_update_distances against the host route (see the module's docstring); every buffer that crosses the link
+    is page-locked on both sides"""
+    fb, tb, ub = (_lib.PinnedRecords(B, dtype=_lib.U128) for _ in range(3))
+    cb = _lib.PinnedRecords(B * 64, dtype=np.uint8)
+    vb = _lib.PinnedRecords(B, dtype=np.uint64)
+    ab, db = _lib.PinnedRecords(B, dtype=np.uint8), _lib.PinnedRecords(B, dtype=np.uint8)
+    fbuf, tbuf, ubuf, cbuf, vbuf, acts, found = fb.array, tb.array, ub.array, cb.array, vb.array, ab.array, db.array
+    written = np.zeros(1, dtype=np.uint64)
+    shapes = ["warm_uniform", "warm_hot"] + ["uniform", "hot"] * reps  # alternating: both shapes and both sides see the same machine
+
+    def draw(shape):
+        fi, ti = rng.integers(0, K, B), rng.integers(0, K, B)
+        if shape.endswith("hot"):
+            ti[rng.random(B) < 0.5] = 12345 % K  # one destination takes half of the batch, spread over it
+        return fi, ti
+
+    def summary(times, link_dev, link_host):
+        out = {}
+        for shape in ("uniform", "hot"):
+            dev, host = spread(times[shape, "device"]), spread(times[shape, "host"])
+            gap = max(dev["max_s"] - dev["min_s"], host["max_s"] - host["min_s"])
+            out[shape] = {"device_call": dev, "host_route": host, "host_over_device_median": round(host["median_s"] / dev["median_s"], 3),
+                          "median_gain_s": round(host["median_s"] - dev["median_s"], 6), "larger_spread_s": round(gap, 6),
+                          "device_Medges_per_s": round(B / dev["median_s"] / 1e6, 2), "host_route_Medges_per_s": round(B / host["median_s"] / 1e6, 2)}
+        out["hot_over_uniform_batch_time"] = {side: round(out["hot"][name]["median_s"] / out["uniform"][name]["median_s"], 3)
+                                              for side, name in (("device", "device_call"), ("host", "host_route"))}
+        out["link_bytes_per_edge"] = {"device": link_dev, "host_route": link_host}
+        return out
+
+    res = {"edges_per_batch": B, "repetitions": reps}
+    # ---- the counter job: 32 B up + 1 B down per edge against 16 up + 64 down, 80 up + 1 down
+    regs = rng.integers(0, 30, (B, 64), dtype=np.uint8)
+    with ampc.CounterTable(capacity_hint=K) as prev:
+        for b in range(0, K, B):
+            n = min(B, K - b)
+            prev.batch_set(keys[b:b + n], regs[:n])
+        with prev.clone() as next_d, prev.clone() as next_h:
+            lib = prev.lib
+            times = {(s, side): [] for s in ("uniform", "hot") for side in ("device", "host")}
+            for shape in shapes:
+                fi, ti = draw(shape)
+                fbuf[:], tbuf[:] = keys[fi], keys[ti]
+                t_dev = timed(lambda: next_d._check(lib.hbu_update_counters(prev.h, next_d.h, _lib._ptr(fbuf), _lib._ptr(tbuf), B, _lib._ptr(acts))))
+                t_host = timed(lambda: prev._check(lib.hbu_batch_get(prev.h, _lib._ptr(fbuf), B, _lib._ptr(cbuf), _lib._ptr(found))))
+                # (here the worker adds edge.from to every counter: host work, not timed)
+                t_host += timed(lambda: next_h._check(lib.hbu_batch_upsert(next_h.h, _lib._ptr(tbuf), _lib._ptr(cbuf), B, _lib._ptr(acts))))
+                if not shape.startswith("warm"):
+                    times[shape, "device"].append(t_dev)
+                    times[shape, "host"].append(t_host)
+            assert len(next_d) == K and len(next_h) == K
+            res["update_counters"] = summary(times, 33, 161)
+    # ---- the distance job: 32 B up per edge + 17 B down per destination against 16 + 8 per distinct source, 24 + 1 per destination
+    with ampc.ValueTable(ampc.KIND_U64, capacity_hint=K) as prev:
+        for b in range(0, K, B):
+            n = min(B, K - b)
+            prev.batch_set(keys[b:b + n], rng.integers(0, 1 << 20, n, dtype=np.uint64))
+        with prev.clone() as next_d, prev.clone() as next_h:
+            lib = prev.lib
+            times = {(s, side): [] for s in ("uniform", "hot") for side in ("device", "host")}
+            sources = dests = 0
+            for shape in shapes:
+                fi, ti = draw(shape)
+                fbuf[:], tbuf[:] = keys[fi], keys[ti]
+                t_dev = timed(lambda: next_d._check(lib.hbu_update_distances(prev.h, next_d.h, _lib._ptr(fbuf), _lib._ptr(tbuf), B, _lib._ptr(ubuf), _lib._ptr(acts),
+                                                                             written.ctypes.data_as(lib.hbu_update_distances.argtypes[7]))))
+                us, inv = np.unique(fi, return_inverse=True)  # the worker asks for every source once
+                ubuf[:len(us)] = keys[us]
+                ns = len(us)
+                t_host = timed(lambda: prev._check(lib.hbu_batch_get_values(prev.h, _lib._ptr(ubuf), ns, _lib._ptr(vbuf), _lib._ptr(found))))
+                cand = vbuf[:ns][inv] + np.uint64(1)          # host work, not timed: the candidates and their minimum per destination
+                ud, dinv = np.unique(ti, return_inverse=True)
+                best = np.full(len(ud), np.iinfo(np.uint64).max, dtype=np.uint64)
+                np.minimum.at(best, dinv, cand)
+                nd = len(ud)
+                assert nd == int(written[0])
+                ubuf[:nd], vbuf[:nd] = keys[ud], best
+                t_host += timed(lambda: next_h._check(lib.hbu_batch_upsert_values(next_h.h, ampc.OP_U64_MIN, _lib._ptr(ubuf), _lib._ptr(vbuf), nd, _lib._ptr(acts))))
+                if not shape.startswith("warm"):
+                    times[shape, "device"].append(t_dev)
+                    times[shape, "host"].append(t_host)
+                    sources, dests = sources + ns, dests + nd
+            res["update_distances"] = summary(times, round(32 + 17 * dests / (2 * reps * B), 1), round((24 * sources + 25 * dests) / (2 * reps * B), 1))
+            res["update_distances"]["distinct_sources_per_edge"] = round(sources / (2 * reps * B), 3)
+            res["update_distances"]["distinct_destinations_per_edge"] = round(dests / (2 * reps * B), 3)
+            check = keys[rng.integers(0, K, min(B, 100000))]   # both routes leave the same table
+            assert np.array_equal(next_d.batch_get(check)[0], next_h.batch_get(check)[0])
+    for x in (fb, tb, ub, cb, vb, ab, db):
+        x.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("keys", nargs="?", type=int, default=10_000_000)
@@ -150,6 +252,8 @@ def main():
     ap.add_argument("--kind", choices=sorted(KINDS))
     ap.add_argument("--op", choices=sorted(OP_NAMES))
     ap.add_argument("--centralities", action="store_true", help="also hbu_update_centralities against the host route")
+    ap.add_argument("--edges", action="store_true", help="also hbu_update_counters / hbu_update_distances against the host route")
+    ap.add_argument("--reps", type=int, default=5, help="timed batches per shape and side of --edges (at least 5)")
     ap.add_argument("--out")
     args = ap.parse_args()
     K, B = args.keys, args.batch
@@ -214,6 +318,9 @@ def main():
             print(name, out["values_pinned"][name], file=sys.stderr, flush=True)
     if args.centralities:
         out["update_centralities"] = centralities_mode(rng, keys, K, B)
+    if args.edges:
+        out["edges"] = edges_mode(rng, keys, K, B, max(args.reps, 5))
+        print("edges", out["edges"], file=sys.stderr, flush=True)
     line = json.dumps(out)
     print(line)
     if args.out:
