@@ -24,9 +24,11 @@
  *                           batch's own minimum per destination, batch_upsert(U64Min) - ids up, one (key, action) per destination back
  * so that clone -> edge step -> update_centralities -> swap is a whole round of either job with no counter on the link.
  * In: HyperLogLog<64> with HyperLogLog64Upsert; u64 with U64Add / U64Min; f32 with F32Add; f64 with F64Add; KahanSum with KahanSumAdd
- * (upsert.rs:92-152); the copy of a table; update_centralities; update_counters; update_distances.  Still out: HyperLogLog<8/16/32/128> (no job uses them), the String,
- * meta and bloom-valued tables and UpdatedNodes (a handful of values per shard: host work on the actions array), raft replication,
- * the network protocol, shards that span ranks.
+ * (upsert.rs:92-152); the copy of a table; update_centralities; update_counters; update_distances; a worker's graph and its changed-node
+ * filter (U64BloomFilter, the Exact arm of UpdatedNodes) resident next to the tables, with one call per mapper step (setup_counters,
+ * map_cardinalities, RelaxEdges, map_centralities).  Still out: HyperLogLog<8/16/32/128> (no job uses them), the String, meta and
+ * bloom-valued tables (a handful of values per shard), the Exact -> Sketch policy of UpdatedNodes and the serde envelopes of the filters
+ * (the caller's), a compressed edge layout, raft replication, the network protocol, shards that span ranks.
  * Defined differences: U64Add wraps at 2^64 (the reference panics in a debug build and wraps in a release build), and so does the
  * `+ 1` of hbu_update_distances; an operator that does not belong to the table's kind is refused with HB_ERR_INVALID and changes
  * nothing (the reference panics).
@@ -124,6 +126,83 @@ int hbu_update_counters(hbu_table *prev_counters, hbu_table *next_counters, cons
  * same for the same inputs. */
 int hbu_update_distances(hbu_table *prev_distances, hbu_table *next_distances, const hb_u128 *from, const hb_u128 *to, uint64_t count,
                          hb_u128 *keys_out, uint8_t *actions_out, uint64_t *written);
+
+/* ---- the resident worker: its graph and its changed-node filter next to the tables ------------------------------------------------
+ * In the reference a worker walks ALL of its edges every round and keeps those whose source passes its changed-nodes filter
+ * (CentralityMapper::map_cardinalities, harmonic_centrality/mapper.rs:253-296, with a U64BloomFilter; ShortestPathMapper::relax_all_edges /
+ * relax_exact_edges, shortest_path/mapper.rs:105-190, with an UpdatedNodes), then turns the returned actions into the next round's filter
+ * (update_changed_nodes, mapper.rs:114-125; map_batch, shortest_path/mapper.rs:88-103).  With the calls below the graph and the filter
+ * live on the device of the tables and one call per mapper step works between them: a round moves a few counts over the link, no ids.
+ * Errors of the graph and filter calls are read with hbu_last_error(NULL) (the calling thread's last message); the round steps report
+ * on the table that changes, as the edge steps do. */
+typedef struct hbu_graph hbu_graph;
+typedef struct hbu_filter hbu_filter;
+
+#define HBU_FILTER_BLOOM 0 /* U64BloomFilter, crates/bloom/src/lib.rs:60-130                                       */
+#define HBU_FILTER_EXACT 1 /* InnerUpdatedNodes::Exact, shortest_path/updated_nodes.rs:27-44: a set of whole 128-bit ids */
+
+/* What worker.graph() yields (worker.rs:77-79), resident on one device: the nodes in host_nodes() order, the edges (from[i], to[i]) in the
+ * worker's iteration order, edges with SKIPPED_REL flags already dropped by the caller (rel flags stay the worker's business).  Uploaded
+ * once: 16 B per node, 32 B per edge.  Either list may be empty.  chunk_edges: the most edges (or nodes) one internal pass of a round
+ * call handles, 0 = the library's default, >= 2^30 is HB_ERR_LIMIT.  The staging of a chunk (about 50 B per edge) is allocated by the
+ * first round call that needs it, not here: a chunk the device has no room for is that call's HB_ERR_NOMEM, with nothing changed.  Chunking is invisible in tables and filters: the upserts apply
+ * pairs in order, so consecutive chunks equal one batch for the counters, and a minimum is associative for the distances.  A graph keeps
+ * the staging of one chunk: it serves one round call at a time. */
+int hbu_graph_create(int32_t device, const hb_u128 *nodes, uint64_t n_nodes, const hb_u128 *from, const hb_u128 *to, uint64_t n_edges, uint64_t chunk_edges,
+                     hbu_graph **out);
+int hbu_graph_len(const hbu_graph *g, uint64_t *n_nodes, uint64_t *n_edges);
+void hbu_graph_destroy(hbu_graph *g);
+
+/* num_bits() of the bloom crate (lib.rs:40-42): ceil(items * ln(fp) / (-8 * ln(2)^2)) in that operation order, `as u64`.  Host only. */
+uint64_t hbu_bloom_num_bits(uint64_t estimated_items, double fp);
+
+/* HBU_FILTER_BLOOM: num_bits bits, 1 .. 2^32 - 1 (0: HB_ERR_INVALID, more: HB_ERR_LIMIT; a table holds fewer than 2^32 keys); the bit of
+ * an id is (low 64 bits of the id * 11400714819323198549 mod 2^64) % num_bits, the high half is ignored as in insert_u128 /
+ * contains_u128 (lib.rs:95-106).  HBU_FILTER_EXACT: num_bits is ignored. */
+int hbu_filter_create(int32_t device, uint32_t kind, uint64_t num_bits, hbu_filter **out);
+void hbu_filter_destroy(hbu_filter *f);
+int hbu_filter_clear(hbu_filter *f);  /* empty_from (lib.rs:73-77, updated_nodes.rs:152-157) */
+int hbu_filter_fill(hbu_filter *f);   /* fill() (lib.rs:79-83); bloom only */
+int hbu_filter_insert(hbu_filter *f, const hb_u128 *ids, uint64_t count);
+int hbu_filter_contains(hbu_filter *f, const hb_u128 *ids, uint64_t count, uint8_t *out_bytes);
+/* dst |= src.  The kinds must match and, for blooms, num_bits too (the reference debug-asserts it, lib.rs:126): else HB_ERR_INVALID.
+ * The Exact -> Sketch policy of UpdatedNodes::union / add (updated_nodes.rs:46-106) stays with the caller. */
+int hbu_filter_union(hbu_filter *dst, hbu_filter *src);
+int hbu_filter_count(hbu_filter *f, uint64_t *n); /* count_ones() of a bloom, len() of an exact set */
+/* bloom only: the bit vector's data words, bit i = bit i % 64 of little-endian 64-bit word i / 64, ceil(num_bits / 64) words.  An import
+ * whose tail bits above num_bits are not zero is refused.  The serde envelope stays with the caller. */
+int hbu_filter_export_bits(hbu_filter *f, uint64_t *words_out);
+int hbu_filter_import_bits(hbu_filter *f, const uint64_t *words);
+/* exact only: the members, order unspecified; *written of them (HB_ERR_INVALID and nothing written if capacity is too small) */
+int hbu_filter_export_ids(hbu_filter *f, hb_u128 *out, uint64_t capacity, uint64_t *written);
+
+/* ---- the round steps.  All objects on one device; a call runs on next's stream and everything is visible on return.  Each call walks
+ * the graph's lists in stored order, in chunks of at most chunk_edges.  Refused, nothing changed, hbu_last_error set on the table that
+ * changes: NULL where an object is required, wrong table kinds, objects on different devices, prev == next, changed == new_changed, a
+ * broken table.  An empty graph or a filter that selects nothing: HB_OK, zero counts, nothing touched.  A HIP error in the middle of a
+ * multi-chunk call leaves each table as the batch calls leave it (the keys it held before the failing chunk, earlier chunks applied); the
+ * error is reported and the caller redoes the round from its clone and a cleared new_changed. */
+
+/* map_setup_counters (mapper.rs:211-242): prev and next both get batch_set(node, HyperLogLog::default() + add_u128(node)) for every
+ * node of g, the counter derived on the device; every node is inserted into `changed` if that is not NULL. */
+int hbu_setup_counters(hbu_table *prev_counters, hbu_table *next_counters, const hbu_graph *g, hbu_filter *changed);
+/* map_cardinalities (mapper.rs:253-296): the edges whose from[e] `changed` contains, in stored order, applied exactly as
+ * hbu_update_counters(prev, next, ...) applies them as one batch; the `to` of every pair whose action is Merged is inserted into
+ * new_changed (mapper.rs:120-124: an Inserted destination is NOT).  *selected / *merged / *inserted: the selected edges and the pairs with
+ * those actions; round_had_changes is merged + inserted > 0 (mapper.rs:141-147).  new_changed may be NULL, else it differs from changed. */
+int hbu_round_counters(hbu_table *prev_counters, hbu_table *next_counters, const hbu_graph *g, hbu_filter *changed, hbu_filter *new_changed, uint64_t *selected,
+                       uint64_t *merged, uint64_t *inserted);
+/* RelaxEdges for the edges of g (shortest_path/mapper.rs:105-190): the same selection; each chunk's selected edges are applied as
+ * hbu_update_distances applies them; every destination whose action is_changed() (Merged OR Inserted, upsert.rs:31-33, mapper.rs:97-101)
+ * is inserted into new_changed.  *changed_nodes: the (destination, chunk) answers that were changed, > 0 iff the round had changes.  With
+ * an HBU_FILTER_EXACT `changed` this selects exactly the edges relax_exact_edges reaches through
+ * ForwardlinksQuery ... skip_self_links(false).deduplicate(false). */
+int hbu_round_distances(hbu_table *prev_distances, hbu_table *next_distances, const hbu_graph *g, hbu_filter *changed, hbu_filter *new_changed, uint64_t *selected,
+                        uint64_t *changed_nodes);
+/* map_centralities (mapper.rs:298-333): the nodes of g that `changed` contains go through hbu_update_centralities, a chunk at a time;
+ * *written sums the chunks' distinct nodes (the reference's batches are as separate). */
+int hbu_round_centralities(hbu_table *prev_counters, hbu_table *next_counters, hbu_table *prev_centrality, hbu_table *next_centrality, const hbu_graph *g,
+                           hbu_filter *changed, uint64_t round, uint64_t *selected, uint64_t *written);
 
 #ifdef __cplusplus
 }

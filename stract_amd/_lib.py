@@ -427,6 +427,25 @@ _SIGNATURES += [
     ("hbu_update_centralities", ctypes.c_int, [_P, _P, _P, _P, _P, _U64, _U64, ctypes.POINTER(_U64)]),
     ("hbu_update_counters", ctypes.c_int, [_P, _P, _P, _P, _U64, _P]),
     ("hbu_update_distances", ctypes.c_int, [_P, _P, _P, _P, _U64, _P, _P, ctypes.POINTER(_U64)]),
+    ("hbu_graph_create", ctypes.c_int, [ctypes.c_int32, _P, _U64, _P, _P, _U64, _U64, ctypes.POINTER(_P)]),
+    ("hbu_graph_len", ctypes.c_int, [_P, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("hbu_graph_destroy", None, [_P]),
+    ("hbu_bloom_num_bits", _U64, [_U64, ctypes.c_double]),
+    ("hbu_filter_create", ctypes.c_int, [ctypes.c_int32, ctypes.c_uint32, _U64, ctypes.POINTER(_P)]),
+    ("hbu_filter_destroy", None, [_P]),
+    ("hbu_filter_clear", ctypes.c_int, [_P]),
+    ("hbu_filter_fill", ctypes.c_int, [_P]),
+    ("hbu_filter_insert", ctypes.c_int, [_P, _P, _U64]),
+    ("hbu_filter_contains", ctypes.c_int, [_P, _P, _U64, _P]),
+    ("hbu_filter_union", ctypes.c_int, [_P, _P]),
+    ("hbu_filter_count", ctypes.c_int, [_P, ctypes.POINTER(_U64)]),
+    ("hbu_filter_export_bits", ctypes.c_int, [_P, _P]),
+    ("hbu_filter_import_bits", ctypes.c_int, [_P, _P]),
+    ("hbu_filter_export_ids", ctypes.c_int, [_P, _P, _U64, ctypes.POINTER(_U64)]),
+    ("hbu_setup_counters", ctypes.c_int, [_P, _P, _P, _P]),
+    ("hbu_round_counters", ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("hbu_round_distances", ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("hbu_round_centralities", ctypes.c_int, [_P, _P, _P, _P, _P, _P, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
 ]
 # include/hb_store.h
 _SIGNATURES += [

@@ -4,7 +4,10 @@ three batch operations its mappers use (mapper.rs:52-118): batch_set, batch_get,
 table of one of the scalar kinds (u64, f32, f64, KahanSum) with the scalar upsert operators (dht/upsert.rs:92-152): the `centrality`
 table of that job and the `distances` table of the shortest-path job (shortest_path/mod.rs:51-55).  Both have clone() (clone_table,
 dht/store.rs:192-195); update_centralities is mapper.rs:157-209 as one device call, update_counters (mapper.rs:89-111) and
-update_distances (shortest_path/mapper.rs:64-86) are the two jobs' edge steps between two resident tables: edge ids go up, actions come back."""
+update_distances (shortest_path/mapper.rs:64-86) are the two jobs' edge steps between two resident tables: edge ids go up, actions come back.
+WorkerGraph and ChangedFilter keep a worker's edges and its changed-node filter (U64BloomFilter, or the Exact arm of UpdatedNodes) on the
+device as well; setup_counters, round_counters, round_distances and round_centralities are the mapper steps between them and the tables
+(only counts cross the link), run_harmonic_job and run_shortest_path_job the coordinator's loop over one resident shard."""
 import ctypes
 
 import numpy as np
@@ -180,3 +183,336 @@ def update_distances(prev, next, from_ids, to_ids):
     next._check(next.lib.hbu_update_distances(prev.h, next.h, _lib._ptr(from_ids), _lib._ptr(to_ids), len(from_ids), _lib._ptr(keys), _lib._ptr(actions),
                                               ctypes.byref(written)))
     return keys[:written.value].copy(), actions[:written.value].copy()
+
+
+# ---- a worker's graph and changed-node filter on the device, the mapper steps, the two jobs' loops ----------------------------------
+FILTER_BLOOM, FILTER_EXACT = 0, 1  # HBU_FILTER_*
+SKETCH_THRESHOLD = 16_384  # shortest_path/updated_nodes.rs:22
+
+
+def _raise_thread_error(lib, rc):
+    if rc != _lib.HB_OK:
+        raise _lib.HyperballError(rc, (lib.hbu_last_error(None) or b"").decode())
+
+
+class _Handle:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WorkerGraph(_Handle):
+    """What worker.graph() yields, resident on one device (hbu_graph): `nodes` in host_nodes() order, the edges (from_ids[i], to_ids[i])
+    in the worker's iteration order, edges with skipped rel flags already dropped.  chunk_edges: edges per internal pass of a round call
+    (0 = the library's default).  `nodes` stays available on the host for reading results back."""
+
+    def __init__(self, nodes, from_ids, to_ids, chunk_edges=0, device=-1):
+        self.lib = _lib.load()
+        self.nodes = np.ascontiguousarray(nodes, dtype=_lib.U128)
+        from_ids, to_ids = _edges(from_ids, to_ids)
+        h = ctypes.c_void_p()
+        _raise_thread_error(self.lib, self.lib.hbu_graph_create(device, _lib._ptr(self.nodes), len(self.nodes), _lib._ptr(from_ids), _lib._ptr(to_ids), len(from_ids),
+                                                                int(chunk_edges), ctypes.byref(h)))
+        self.h = h
+        self.n_nodes, self.n_edges = len(self.nodes), len(from_ids)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.hbu_graph_destroy(self.h)
+            self.h = None
+
+    def __len__(self):
+        n, m = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _raise_thread_error(self.lib, self.lib.hbu_graph_len(self.h, ctypes.byref(n), ctypes.byref(m)))
+        assert (n.value, m.value) == (self.n_nodes, self.n_edges)
+        return m.value
+
+
+class ChangedFilter(_Handle):
+    """The changed-node filter on the device (hbu_filter): ChangedFilter.bloom(num_bits) is U64BloomFilter (crates/bloom/src/lib.rs:60-130),
+    ChangedFilter.exact() the Exact arm of UpdatedNodes (shortest_path/updated_nodes.rs:27-44), a set of whole 128-bit ids."""
+
+    def __init__(self, kind, num_bits=0, device=-1):
+        self.lib = _lib.load()
+        h = ctypes.c_void_p()
+        _raise_thread_error(self.lib, self.lib.hbu_filter_create(device, kind, int(num_bits), ctypes.byref(h)))
+        self.h, self.kind, self.num_bits, self.device = h, kind, (int(num_bits) if kind == FILTER_BLOOM else 0), device
+
+    @classmethod
+    def bloom(cls, num_bits, device=-1):
+        return cls(FILTER_BLOOM, num_bits, device)
+
+    @classmethod
+    def exact(cls, device=-1):
+        return cls(FILTER_EXACT, 0, device)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.hbu_filter_destroy(self.h)
+            self.h = None
+
+    def _check(self, rc):
+        _raise_thread_error(self.lib, rc)
+
+    def clear(self):
+        """empty_from"""
+        self._check(self.lib.hbu_filter_clear(self.h))
+
+    def fill(self):
+        self._check(self.lib.hbu_filter_fill(self.h))
+
+    def insert(self, ids):
+        ids = np.ascontiguousarray(ids, dtype=_lib.U128)
+        self._check(self.lib.hbu_filter_insert(self.h, _lib._ptr(ids), len(ids)))
+
+    def contains(self, ids):
+        ids = np.ascontiguousarray(ids, dtype=_lib.U128)
+        out = np.zeros(len(ids), dtype=np.uint8)
+        self._check(self.lib.hbu_filter_contains(self.h, _lib._ptr(ids), len(ids), _lib._ptr(out)))
+        return out.astype(bool)
+
+    def union(self, other):
+        """self |= other (one kind, one size)"""
+        self._check(self.lib.hbu_filter_union(self.h, other.h))
+
+    def count(self):
+        """count_ones() of a bloom filter, len() of an exact set"""
+        n = ctypes.c_uint64(0)
+        self._check(self.lib.hbu_filter_count(self.h, ctypes.byref(n)))
+        return n.value
+
+    def export_bits(self):
+        """the bit vector's data words (uint64, bit i = bit i % 64 of word i // 64); bloom only"""
+        words = np.zeros((self.num_bits + 63) // 64 if self.kind == FILTER_BLOOM else 1, dtype=np.uint64)
+        self._check(self.lib.hbu_filter_export_bits(self.h, _lib._ptr(words)))
+        return words
+
+    def import_bits(self, words):
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        if self.kind == FILTER_BLOOM and len(words) != (self.num_bits + 63) // 64:
+            raise ValueError("ceil(num_bits / 64) words")
+        self._check(self.lib.hbu_filter_import_bits(self.h, _lib._ptr(words)))
+
+    def export_ids(self):
+        """the members of an exact set (U128 array, no particular order)"""
+        cap = self.count() if self.kind == FILTER_EXACT else 1
+        out = np.zeros(max(cap, 1), dtype=_lib.U128)
+        written = ctypes.c_uint64(0)
+        self._check(self.lib.hbu_filter_export_ids(self.h, _lib._ptr(out), len(out), ctypes.byref(written)))
+        return out[:written.value].copy()
+
+
+def bloom_num_bits(estimated_items, fp):
+    """num_bits() of the bloom crate (lib.rs:40-42)"""
+    return int(_lib.load().hbu_bloom_num_bits(int(estimated_items), float(fp)))
+
+
+def _h(x):
+    return x.h if x is not None else None
+
+
+def setup_counters(prev, next, graph, changed=None):
+    """map_setup_counters (mapper.rs:211-242): both tables get HyperLogLog::default() + add_u128(node) for every node of the graph; every
+    node is inserted into `changed` if given."""
+    next._check(next.lib.hbu_setup_counters(prev.h, next.h, graph.h, _h(changed)))
+
+
+def round_counters(prev, next, graph, changed, new_changed=None):
+    """map_cardinalities (mapper.rs:253-296): the edges whose source `changed` contains go through update_counters; the destinations of
+    the Merged pairs are inserted into new_changed.  Returns (selected, merged, inserted)."""
+    s, m, i = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    next._check(next.lib.hbu_round_counters(prev.h, next.h, graph.h, _h(changed), _h(new_changed), ctypes.byref(s), ctypes.byref(m), ctypes.byref(i)))
+    return s.value, m.value, i.value
+
+
+def round_distances(prev, next, graph, changed, new_changed=None):
+    """RelaxEdges for the graph's edges (shortest_path/mapper.rs:105-190): the edges whose source `changed` contains go through
+    update_distances, a chunk at a time; every Merged or Inserted destination is inserted into new_changed.  Returns (selected,
+    changed_nodes)."""
+    s, c = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    next._check(next.lib.hbu_round_distances(prev.h, next.h, graph.h, _h(changed), _h(new_changed), ctypes.byref(s), ctypes.byref(c)))
+    return s.value, c.value
+
+
+def round_centralities(prev_counters, next_counters, prev_centrality, next_centrality, graph, changed, round):
+    """map_centralities (mapper.rs:298-333): the graph's nodes that `changed` contains go through update_centralities.  Returns (selected,
+    written)."""
+    s, w = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    next_centrality._check(next_centrality.lib.hbu_round_centralities(prev_counters.h, next_counters.h, prev_centrality.h, next_centrality.h, graph.h, _h(changed),
+                                                                      round, ctypes.byref(s), ctypes.byref(w)))
+    return s.value, w.value
+
+
+def run_harmonic_job(graphs, device=-1, on_round=None):
+    """The harmonic-centrality coordinator's loop (harmonic_centrality/coordinator.rs:122-135, ampc/coordinator.rs:151-213) over one resident
+    shard and the workers `graphs` (WorkerGraph each): per round clone, then SetupCounters (round 0), SetupBloom (round 0: every filter
+    filled, num_bits = bloom_num_bits(sum of the workers' node counts, 0.05), worker.rs:49-71), Cardinalities, SaveBloom / UpdateBloom
+    (every worker's filter becomes the union of all of them), Centralities, swap - until a round neither merged nor inserted.  Returns
+    {node id as int: f64::from(centrality) / (num_keys - 1)} (coordinator.rs:204-211).  on_round(state): called at the end of every round
+    with the live tables, filters and counts (tests)."""
+    graphs = list(graphs)
+    total_nodes = sum(g.n_nodes for g in graphs)
+    if not total_nodes:
+        return {}
+    num_bits = bloom_num_bits(total_nodes, 0.05)
+    prev_c, prev_v = CounterTable(device), ValueTable(KIND_KAHAN, device)
+    changed = [ChangedFilter.bloom(num_bits, device) for _ in graphs]
+    spare = [ChangedFilter.bloom(num_bits, device) for _ in graphs]
+    union = ChangedFilter.bloom(num_bits, device)
+    open_tables = []  # the clones of the round under way: closed if the round does not end
+    try:
+        for f in changed:
+            f.fill()
+        had_changes, worker_round = True, 0  # Meta.round_had_changes of prev (forced for the first round), CentralityWorker::round
+        while had_changes:  # CentralityFinish::is_finished
+            next_c = prev_c.clone()
+            open_tables.append(next_c)
+            next_v = prev_v.clone()
+            open_tables.append(next_v)
+            now, counts = False, []
+            if worker_round == 0:
+                for g in graphs:
+                    setup_counters(prev_c, next_c, g)
+            for w, g in enumerate(graphs):  # Cardinalities
+                spare[w].clear()
+                selected, merged, inserted = round_counters(prev_c, next_c, g, changed[w], spare[w])
+                changed[w], spare[w] = spare[w], changed[w]
+                now |= merged + inserted > 0
+                counts.append((selected, merged, inserted))
+            union.clear()  # SaveBloom, UpdateBloom
+            for f in changed:
+                union.union(f)
+            for f in changed:
+                f.union(union)
+            written = [round_centralities(prev_c, next_c, prev_v, next_v, g, changed[w], worker_round) for w, g in enumerate(graphs)]  # Centralities
+            worker_round += 1
+            if on_round:
+                on_round(dict(round=worker_round - 1, prev_counters=prev_c, next_counters=next_c, prev_centrality=prev_v, next_centrality=next_v, filters=changed,
+                              counts=counts, written=written, had_changes=now))
+            prev_c.close()
+            prev_v.close()
+            prev_c, prev_v, had_changes = next_c, next_v, now
+            open_tables.clear()
+        nodes = np.unique(np.concatenate([g.nodes for g in graphs]))
+        vals, found = prev_v.batch_get(nodes)
+        with np.errstate(all="ignore"):
+            scaled = vals["sum"] / np.float64(len(prev_c) - 1)
+        return {(int(k["hi"]) << 64) | int(k["lo"]): float(v) for k, v, f in zip(nodes, scaled, found) if f}
+    finally:
+        for f in changed + spare + [union] + open_tables:
+            f.close()
+        prev_c.close()
+        prev_v.close()
+
+
+class _UpdatedNodes:
+    """UpdatedNodes (shortest_path/updated_nodes.rs) around device filters: the Exact -> Sketch policy the C ABI leaves to its caller."""
+
+    def __init__(self, total_nodes, device, filt=None):
+        self.total_nodes, self.device = total_nodes, device
+        self.f = filt if filt is not None else ChangedFilter.exact(device)
+
+    def _sketch(self):
+        return ChangedFilter.bloom(bloom_num_bits(self.total_nodes, 0.01), self.device)
+
+    def settle(self):
+        """what add() does as soon as an exact set exceeds the threshold (updated_nodes.rs:89-103): a sketch of ALL of its ids"""
+        if self.f.kind == FILTER_EXACT and self.f.count() > SKETCH_THRESHOLD:
+            sketch = self._sketch()
+            sketch.insert(self.f.export_ids())
+            self.f.close()
+            self.f = sketch
+        return self
+
+    def add(self, node_ids):
+        self.f.insert(node_ids)
+        return self.settle()
+
+    def union(self, other):
+        """updated_nodes.rs:46-87; returns a new _UpdatedNodes"""
+        a, b = self.f, other.f
+        if a.kind == FILTER_EXACT and b.kind == FILTER_EXACT:
+            both = ChangedFilter.exact(self.device)
+            both.union(a)
+            both.union(b)
+            if both.count() <= SKETCH_THRESHOLD:
+                return _UpdatedNodes(self.total_nodes, self.device, both)
+            # Exact u Exact over the threshold: the reference builds the sketch from the LEFT set only (updated_nodes.rs:48-58, `for node in
+            # nodes`, not new_nodes); restated as it is
+            both.close()
+            sketch = self._sketch()
+            sketch.insert(a.export_ids())
+            return _UpdatedNodes(self.total_nodes, self.device, sketch)
+        sketch = self._sketch()
+        for f in (a, b):
+            if f.kind == FILTER_BLOOM:
+                sketch.union(f)
+            else:
+                sketch.insert(f.export_ids())
+        return _UpdatedNodes(self.total_nodes, self.device, sketch)
+
+    def close(self):
+        self.f.close()
+
+
+def run_shortest_path_job(graphs, source, max_distance=None, device=-1, on_round=None):
+    """The shortest-path coordinator's loop (shortest_path/coordinator.rs:73-133) over one resident shard and the workers `graphs`: the
+    source gets distance 0; per round clone, RelaxEdges on every worker (its changed set, with the source added, selects the edges; the
+    changed destinations form its new set), UpdateChangedNodes (every worker's set becomes the union of all new sets, folded from an empty
+    exact set in worker order), until a round changed nothing or `max_distance` rounds ran.  A set is exact up to 16 384 ids, then a bloom
+    filter of bloom_num_bits(total_nodes, 0.01) bits.  round_had_changes is the OR over the workers (the reference stores the flag of
+    whichever worker wrote last).  Returns the distance table (ValueTable of KIND_U64); the caller closes it."""
+    graphs = list(graphs)
+    total_nodes = max(sum(g.n_nodes for g in graphs), 1)
+    src = np.zeros(1, dtype=_lib.U128)
+    src["lo"], src["hi"] = int(source) & ((1 << 64) - 1), int(source) >> 64
+    prev = ValueTable(KIND_U64, device)
+    changed = [_UpdatedNodes(total_nodes, device) for _ in graphs]
+    saved, nxt = [], None  # nxt: the clone of the round under way, closed if the round does not end
+    try:
+        prev.batch_set(src, np.zeros(1, dtype=np.uint64))
+        rounds, had_changes = 0, True
+        while had_changes and not (max_distance is not None and rounds >= max_distance):  # ShortestPathFinish::is_finished
+            nxt = prev.clone()
+            now, counts, saved = False, [], []
+            for w, g in enumerate(graphs):  # RelaxEdges
+                changed[w].add(src)
+                new = _UpdatedNodes(total_nodes, device)
+                saved.append(new)
+                selected, changed_nodes = round_distances(prev, nxt, g, changed[w].f, new.f)
+                new.settle()
+                now |= changed_nodes > 0
+                counts.append((selected, changed_nodes))
+            for w in range(len(graphs)):  # UpdateChangedNodes
+                acc = _UpdatedNodes(total_nodes, device)
+                for other in saved:
+                    merged = acc.union(other)
+                    acc.close()
+                    acc = merged
+                changed[w].close()
+                changed[w] = acc
+            rounds += 1
+            if on_round:
+                on_round(dict(round=rounds - 1, prev=prev, next=nxt, filters=[c.f for c in changed], saved=[s.f for s in saved], counts=counts, had_changes=now))
+            for s_ in saved:
+                s_.close()
+            saved = []
+            prev.close()
+            prev, had_changes, nxt = nxt, now, None
+        return prev
+    except BaseException:
+        prev.close()
+        if nxt is not None:
+            nxt.close()
+        raise
+    finally:
+        for c in changed + saved:
+            c.close()

@@ -1,6 +1,7 @@
 // hb_aux.hip.h - helpers, the changed-only exchanges, the reference-tail mode, normalisation and state checksums.
 // Part of the device code of stract_amd/csrc/hb_kernels.hip.h (included from there).
 #pragma once
+#include "hb_bloom.hip.h"
 
 namespace hbk {
 
@@ -219,8 +220,7 @@ __global__ __launch_bounds__(256) void unpack_changed_kernel(uint4 *wr, const ui
 
 // ---- reference-tail mode (HB_FLAG_REFERENCE_TAIL): the changed-node machinery of the reference as written -----------
 // U64BloomFilter::insert_u128 (bloom/src/lib.rs:85-98): slot = (low 64 bits of the id * LARGE_PRIME) % num_bits.
-constexpr unsigned long long kBloomPrime = 11400714819323198549ull;
-__device__ __forceinline__ uint64_t bloom_slot(uint64_t id_low, uint64_t num_bits) { return (id_low * kBloomPrime) % num_bits; }
+// (kBloomPrime / bloom_slot: hb_bloom.hip.h, shared with the AMPC shard's changed-node filter)
 
 // new_changed_nodes of one pass: a bit per slot of every changed node (harmonic.rs:145,103)
 __global__ __launch_bounds__(256) void bloom_insert_kernel(const uint32_t *bits, const uint64_t *id_low, uint64_t n_pad, uint64_t num_bits,

@@ -13,9 +13,16 @@ one batch_set.  --edges adds the two edge steps, hbu_update_counters and hbu_upd
 against the host route built from the calls that were there before them - batch_get + batch_upsert for the counters, batch_get_values +
 batch_upsert_values(U64_MIN) on the per-destination minima for the distances; the host's own add / minimum is NOT timed, so the
 comparator is its link-and-device part alone - on uniformly drawn destinations and on batches half of which go to one destination,
-both sides alternating, median / minimum / maximum of --reps batches each.  --out FILE also writes the JSON line there.
+both sides alternating, median / minimum / maximum of --reps batches each.  --rounds adds the resident worker: a graph of
+--round-edges R-MAT edges (stract_amd/synth.py, stream order) and a bloom filter next to tables of that many keys, one
+hbu_round_counters, hbu_round_distances and hbu_round_centralities per repetition at three filter densities (filled, about 10 % and
+about 0.1 % of the nodes inserted) against the route of the calls that were there before - hbu_update_counters / hbu_update_distances /
+hbu_update_centralities fed from page-locked host ids in batches of `pairs per batch`; only the time inside those calls counts for the
+comparator, the host's own filtering and filter update are timed once per density and reported beside it.  --only-rounds skips the
+counter-table section.  --out FILE also writes the JSON line there.
 usage: tools/ampc_bench.py [keys, default 10000000] [pairs per batch, default 1000000] [--values] [--kind K] [--op OP] [--centralities]
-                           [--edges] [--reps N, default 5] [--out FILE]"""
+                           [--edges] [--rounds] [--round-edges N, default 100000000] [--round-scale S] [--only-rounds] [--reps N, default 5]
+                           [--out FILE]"""
 import argparse
 import json
 import os
@@ -244,6 +251,126 @@ def edges_mode(rng, keys, K, B, reps):
     return res
 
 
+def rounds_mode(rng, K, B, reps, total_edges, scale):
+    """the resident worker's round calls against the host-fed route of the parent's calls (see the module's docstring)"""
+    from stract_amd import synth
+    t0 = time.perf_counter()
+    g = synth.RmatGraph(scale, total_edges)
+    E = g.stream_len(0)
+    from_ids, to_ids = np.zeros(E, dtype=_lib.U128), np.zeros(E, dtype=_lib.U128)
+    at = 0
+    for slab in g.stream():
+        from_ids[at:at + len(slab)], to_ids[at:at + len(slab)] = slab["from"], slab["to"]
+        at += len(slab)
+    nodes = np.array(g.ids)
+    n = len(nodes)
+    g.close()
+    keys = nodes
+    if n < K:  # the shard holds K keys: the graph's nodes and others
+        extra = np.zeros(K - n, dtype=_lib.U128)
+        extra["lo"], extra["hi"] = rng.integers(0, 1 << 63, K - n, dtype=np.uint64), np.uint64(1 << 62)
+        keys = np.concatenate([nodes, extra])
+    print("graph: %d nodes, %d edges, %.1f s" % (n, E, time.perf_counter() - t0), file=sys.stderr, flush=True)
+    num_bits = ampc.bloom_num_bits(n, 0.05)
+    prime = np.uint64(11400714819323198549)
+
+    def slots(ids):
+        return (ids["lo"] * prime) % np.uint64(num_bits)
+
+    fb, tb, ub = (_lib.PinnedRecords(B, dtype=_lib.U128) for _ in range(3))
+    ab = _lib.PinnedRecords(B, dtype=np.uint8)
+    fbuf, tbuf, ubuf, acts = fb.array, tb.array, ub.array, ab.array
+    written = np.zeros(1, dtype=np.uint64)
+    res = {"nodes": n, "edges": E, "keys": len(keys), "bloom_num_bits": num_bits, "host_batch": B, "repetitions": reps, "densities": {}}
+    regs = rng.integers(0, 30, (B, 64), dtype=np.uint8)
+    more = rng.integers(0, 32, (B, 64), dtype=np.uint8)
+    with ampc.WorkerGraph(nodes, from_ids, to_ids) as graph, ampc.ChangedFilter.bloom(num_bits) as changed, ampc.ChangedFilter.bloom(num_bits) as new, \
+            ampc.CounterTable(capacity_hint=len(keys)) as prev_c, ampc.ValueTable(ampc.KIND_U64, capacity_hint=len(keys)) as prev_d, \
+            ampc.ValueTable(ampc.KIND_KAHAN, capacity_hint=len(keys)) as prev_v:
+        for b in range(0, len(keys), B):
+            m = min(B, len(keys) - b)
+            prev_c.batch_set(keys[b:b + m], regs[:m])
+            prev_d.batch_set(keys[b:b + m], rng.integers(0, 1 << 20, m, dtype=np.uint64))
+        with prev_c.clone() as grown:  # the counters a centrality step compares with: about half of them grew
+            for b in range(0, len(keys), B):
+                m = min(B, len(keys) - b)
+                grown.batch_upsert(keys[b:b + m], more[:m])
+            lib = prev_c.lib
+            for label, share in (("all_changed", None), ("about_10_percent", 0.1), ("about_0.1_percent", 0.001)):
+                changed.clear()
+                if share is None:
+                    changed.fill()
+                else:
+                    changed.insert(nodes[rng.random(n) < share])
+                bits = np.unpackbits(changed.export_bits().view(np.uint8), bitorder="little")
+                t0 = time.perf_counter()
+                edge_mask = bits[slots(from_ids)].astype(bool)
+                t_filter_edges = time.perf_counter() - t0
+                t0 = time.perf_counter()
+                node_mask = bits[slots(nodes)].astype(bool)
+                t_filter_nodes = time.perf_counter() - t0
+                sel_from, sel_to, sel_nodes = from_ids[edge_mask], to_ids[edge_mask], nodes[node_mask]
+                S = len(sel_from)
+                t = {k: [] for k in ("counters_device", "counters_host", "distances_device", "distances_host", "centralities_device", "centralities_host")}
+                t_update = 0.0
+                for r in range(reps + 1):  # the first repetition warms both sides up
+                    with prev_c.clone() as next_d, prev_c.clone() as next_h:
+                        new.clear()
+                        t_dev = timed(lambda: res.__setitem__("_c", ampc.round_counters(prev_c, next_d, graph, changed, new)))
+                        t_host, merged_to = 0.0, []
+                        for b in range(0, S, B):
+                            m = min(B, S - b)
+                            fbuf[:m], tbuf[:m] = sel_from[b:b + m], sel_to[b:b + m]
+                            t_host += timed(lambda: next_h._check(lib.hbu_update_counters(prev_c.h, next_h.h, _lib._ptr(fbuf), _lib._ptr(tbuf), m, _lib._ptr(acts))))
+                            merged_to.append(tbuf[:m][acts[:m] == ampc.MERGED])
+                        t0 = time.perf_counter()
+                        host_new = np.zeros(num_bits, dtype=np.uint8)
+                        if merged_to:
+                            host_new[slots(np.concatenate(merged_to))] = 1
+                        t_update = time.perf_counter() - t0
+                        assert res["_c"][0] == S and new.count() == int(host_new.sum())
+                    with prev_d.clone() as next_d, prev_d.clone() as next_h:
+                        new.clear()
+                        t_dev2 = timed(lambda: res.__setitem__("_d", ampc.round_distances(prev_d, next_d, graph, changed, new)))
+                        t_host2, dests = 0.0, 0
+                        for b in range(0, S, B):
+                            m = min(B, S - b)
+                            fbuf[:m], tbuf[:m] = sel_from[b:b + m], sel_to[b:b + m]
+                            t_host2 += timed(lambda: next_h._check(lib.hbu_update_distances(prev_d.h, next_h.h, _lib._ptr(fbuf), _lib._ptr(tbuf), m, _lib._ptr(ubuf), _lib._ptr(acts),
+                                                                                            written.ctypes.data_as(lib.hbu_update_distances.argtypes[7]))))
+                            dests += int(written[0])
+                        assert res["_d"][0] == S
+                    with prev_v.clone() as next_d, prev_v.clone() as next_h:
+                        t_dev3 = timed(lambda: res.__setitem__("_v", ampc.round_centralities(prev_c, grown, prev_v, next_d, graph, changed, 1)))
+                        t_host3 = 0.0
+                        for b in range(0, len(sel_nodes), B):
+                            m = min(B, len(sel_nodes) - b)
+                            fbuf[:m] = sel_nodes[b:b + m]
+                            t_host3 += timed(lambda: next_h._check(lib.hbu_update_centralities(prev_c.h, grown.h, prev_v.h, next_h.h, _lib._ptr(fbuf), m, 1,
+                                                                                               written.ctypes.data_as(lib.hbu_update_centralities.argtypes[7]))))
+                        assert res["_v"][0] == len(sel_nodes) and len(next_d) == len(next_h)
+                    if r:
+                        for k, v in (("counters_device", t_dev), ("counters_host", t_host), ("distances_device", t_dev2), ("distances_host", t_host2),
+                                     ("centralities_device", t_dev3), ("centralities_host", t_host3)):
+                            t[k].append(v)
+                d = {"selected_edges": S, "selected_edge_share": round(S / max(E, 1), 5), "selected_nodes": len(sel_nodes),
+                     "host_filtering_s": {"edges": round(t_filter_edges, 4), "nodes": round(t_filter_nodes, 4), "filter_update": round(t_update, 4)},
+                     "counts": {"round_counters": list(res.pop("_c")), "round_distances": list(res.pop("_d")), "round_centralities": list(res.pop("_v"))}}
+                for job in ("counters", "distances", "centralities"):
+                    dev, host = spread(t[job + "_device"]), spread(t[job + "_host"])
+                    d["round_" + job] = {"device_call": dev, "host_fed_library_time": host, "median_gain_s": round(host["median_s"] - dev["median_s"], 6),
+                                         "larger_spread_s": round(max(dev["max_s"] - dev["min_s"], host["max_s"] - host["min_s"]), 6),
+                                         "device_walks_Medges_per_s": round((E if job != "centralities" else n) / dev["median_s"] / 1e6, 1)}
+                # device: one 4-byte count per chunk of the default 2^22 edges and 32 bytes of counts per call; host: ids up, actions (and keys) back
+                d["link_bytes_per_selected_edge"] = {"device": round((4 * -(-E // (1 << 22)) + 32) / max(S, 1), 6), "host_route_counters": 33,
+                                                     "host_route_distances": round(32 + 17 * dests / max(S, 1), 1)}
+                res["densities"][label] = d
+                print(label, d, file=sys.stderr, flush=True)
+    for x in (fb, tb, ub, ab):
+        x.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("keys", nargs="?", type=int, default=10_000_000)
@@ -253,7 +380,11 @@ def main():
     ap.add_argument("--op", choices=sorted(OP_NAMES))
     ap.add_argument("--centralities", action="store_true", help="also hbu_update_centralities against the host route")
     ap.add_argument("--edges", action="store_true", help="also hbu_update_counters / hbu_update_distances against the host route")
-    ap.add_argument("--reps", type=int, default=5, help="timed batches per shape and side of --edges (at least 5)")
+    ap.add_argument("--rounds", action="store_true", help="also the resident worker's round calls against the host-fed route")
+    ap.add_argument("--round-edges", type=int, default=100_000_000, help="R-MAT edges of the worker graph of --rounds")
+    ap.add_argument("--round-scale", type=int, default=0, help="R-MAT scale of that graph (0: the largest with 2^scale <= keys)")
+    ap.add_argument("--only-rounds", action="store_true", help="skip the counter-table section (with --rounds)")
+    ap.add_argument("--reps", type=int, default=5, help="timed batches per shape and side of --edges / repetitions of --rounds (at least 5)")
     ap.add_argument("--out")
     args = ap.parse_args()
     K, B = args.keys, args.batch
@@ -262,7 +393,7 @@ def main():
     keys["lo"] = rng.permutation(K).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)
     keys["hi"] = rng.integers(0, 1 << 63, K, dtype=np.uint64)
     out = {"keys": K, "pairs_per_batch": B, "bytes_per_pair": 80}
-    for label, pinned in (("pageable", False), ("pinned", True)):
+    for label, pinned in (() if args.only_rounds and args.rounds else (("pageable", False), ("pinned", True))):
         kb = _lib.PinnedRecords(B, dtype=_lib.U128) if pinned else None
         vb = _lib.PinnedRecords(B * 64, dtype=np.uint8) if pinned else None
         kbuf = kb.array if pinned else np.zeros(B, dtype=_lib.U128)
@@ -321,6 +452,9 @@ def main():
     if args.edges:
         out["edges"] = edges_mode(rng, keys, K, B, max(args.reps, 5))
         print("edges", out["edges"], file=sys.stderr, flush=True)
+    if args.rounds:
+        scale = args.round_scale or max(int(K).bit_length() - 1, 1)
+        out["rounds"] = rounds_mode(rng, K, B, max(args.reps, 5), args.round_edges, scale)
     line = json.dumps(out)
     print(line)
     if args.out:
