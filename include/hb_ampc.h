@@ -26,12 +26,16 @@
  * In: HyperLogLog<64> with HyperLogLog64Upsert; u64 with U64Add / U64Min; f32 with F32Add; f64 with F64Add; KahanSum with KahanSumAdd
  * (upsert.rs:92-152); the copy of a table; update_centralities; update_counters; update_distances; a worker's graph and its changed-node
  * filter (U64BloomFilter, the Exact arm of UpdatedNodes) resident next to the tables, with one call per mapper step (setup_counters,
- * map_cardinalities, RelaxEdges, map_centralities).  Still out: HyperLogLog<8/16/32/128> (no job uses them), the String, meta and
+ * map_cardinalities, RelaxEdges, map_centralities); what the approximated-harmonic coordinator (approximated_harmonic_centrality/
+ * coordinator.rs:82-180) adds to the shortest-path job: the fold of a finished job's distances into the KahanSum table as one device call
+ * (hbu_fold_harmonic), the worker's node sketch (hbu_graph_node_sketch, HyperLogLog<4096> registers) and DhtTable::iter() for a table of any
+ * kind (hbu_export).  Still out: HyperLogLog<8/16/32/128> as table values (no job uses them), HyperLogLog<4096>::size() (its bias rows are
+ * not carried here: the caller merges the registers and estimates), the sampling of sources, the String, meta and
  * bloom-valued tables (a handful of values per shard), the Exact -> Sketch policy of UpdatedNodes and the serde envelopes of the filters
  * (the caller's), a compressed edge layout, raft replication, the network protocol, shards that span ranks.
  * Defined differences: U64Add wraps at 2^64 (the reference panics in a debug build and wraps in a release build), and so does the
  * `+ 1` of hbu_update_distances; an operator that does not belong to the table's kind is refused with HB_ERR_INVALID and changes
- * nothing (the reference panics).
+ * nothing (the reference panics); HBU_FOLD_SKIP_ZERO (off by default) keeps a sampled source's own distance 0 out of the fold.
  *
  * extern "C", never unwinds, 0 = ok, negative = HB_ERR_* of hyperball.h; needs a gfx950 device (no CPU fallback).
  */
@@ -95,6 +99,11 @@ uint32_t hbu_wave_group_length(void);
  * Device-to-device copies only. */
 int hbu_clone(hbu_table *from, hbu_table **out);
 
+/* DhtTable::iter(): every (key, value) of the table, any kind (hbu_create's counter tables included; values_out: len x value_bytes); the
+ * entry with entry number p goes to position p, so keys_out[i] belongs to values_out[i]; the order is otherwise unspecified.  *written =
+ * len.  capacity < len: HB_ERR_INVALID, nothing written.  An empty table: HB_OK, *written = 0, the two arrays may be NULL. */
+int hbu_export(hbu_table *t, hb_u128 *keys_out, void *values_out, uint64_t capacity, uint64_t *written);
+
 /* CentralityMapper::update_centralities (mapper.rs:157-209) for `count` nodes, all four tables on one device: a node found in BOTH
  * counter tables with d = next.size() saturating-minus prev.size() != 0 gets
  *     next_centrality[node] = (prev_centrality[node] or KahanSum::default()) + d as f64 / (round + 1) as f64
@@ -127,6 +136,24 @@ int hbu_update_counters(hbu_table *prev_counters, hbu_table *next_counters, cons
 int hbu_update_distances(hbu_table *prev_distances, hbu_table *next_distances, const hb_u128 *from, const hb_u128 *to, uint64_t count,
                          hb_u128 *keys_out, uint8_t *actions_out, uint64_t *written);
 
+#define HBU_FOLD_SKIP_ZERO 1u /* defined difference, off by default: entries with distance 0 (the source) are not folded */
+/* approximated_harmonic_centrality/coordinator.rs:139-145 for one finished shortest-path job: for every (node, d) of `distances`
+ * (HBU_KIND_U64), in one kernel of its own (the keys of a table are distinct: nothing is sorted or grouped),
+ *     v = (1.0 / (double)d) * norm;   centralities[node] = absent ? KahanSum{v, 0.0} : centralities[node] += KahanSum{v, 0.0}
+ * with AddAssign<KahanSum> as written (kahan_sum.rs:65-72: y = (v + 0.0) - err; t = sum + y; err = (t - sum) - y; sum = t), every
+ * operation rounded on its own (no fused multiply-add).  `centralities` is HBU_KIND_KAHAN on the same device and may grow; `distances`
+ * is only read.  *folded = the entries folded, *inserted = the new keys among them (either may be NULL).  The call runs on
+ * centralities' stream after a synchronise of distances'; everything is visible on return.  Equal, bit for bit, to hbu_batch_get_values
+ * of every key of `distances`, v on the host and hbu_batch_upsert_values(HBU_OP_KAHAN_ADD) for norm > 0.
+ * `norm` is taken as given, inf included (the reference's num_samples == 1 gives 1.0 / 0).  A distance of 0 (the source itself) is
+ * folded as the reference folds it: v = inf, so the first fold into a node stores {inf, 0 or NaN}, the next gives err = NaN, the one
+ * after that sum = NaN: a sampled source ends up inf or NaN unless HBU_FOLD_SKIP_ZERO is set.  The sign and payload of a NaN are not
+ * pinned (x86 and gfx950 produce different default NaNs for inf - inf).  2^64 - 1 and 2^53 + 1 convert as Rust's `as f64` does (round to
+ * nearest even).  An empty `distances`: HB_OK, zero counts, nothing touched.  Refused with HB_ERR_INVALID, nothing changed, hbu_last_error
+ * set on centralities: NULL, a wrong kind on either table, tables on different devices, a broken table, unknown flag bits.
+ * Transactional like every batch call: after a HIP error `centralities` holds the keys it held before. */
+int hbu_fold_harmonic(hbu_table *distances, hbu_table *centralities, double norm, uint32_t flags, uint64_t *folded, uint64_t *inserted);
+
 /* ---- the resident worker: its graph and its changed-node filter next to the tables ------------------------------------------------
  * In the reference a worker walks ALL of its edges every round and keeps those whose source passes its changed-nodes filter
  * (CentralityMapper::map_cardinalities, harmonic_centrality/mapper.rs:253-296, with a U64BloomFilter; ShortestPathMapper::relax_all_edges /
@@ -152,6 +179,13 @@ int hbu_graph_create(int32_t device, const hb_u128 *nodes, uint64_t n_nodes, con
                      hbu_graph **out);
 int hbu_graph_len(const hbu_graph *g, uint64_t *n_nodes, uint64_t *n_edges);
 void hbu_graph_destroy(hbu_graph *g);
+
+#define HBU_NODE_SKETCH_REGISTERS 4096
+/* ShortestPathWorker::new (shortest_path/worker.rs:44-49): HyperLogLog<4096>::default() + add_u128(node) for every node of g;
+ * registers_out: 4096 bytes.  add() is hyperloglog.rs:4385-4396 with b = 12: h = low 64 bits of the id * 11400714819323198549 mod 2^64
+ * (the high half is ignored, hyperloglog.rs:4398-4400), register h >> 52 = max(itself, leading_zeros(h << 12) + 1), which is 65 where
+ * h << 12 is zero.  An empty node list: 4096 zeros.  Registers only: merge() is a byte-wise max and size() stays with the caller. */
+int hbu_graph_node_sketch(const hbu_graph *g, uint8_t *registers_out);
 
 /* num_bits() of the bloom crate (lib.rs:40-42): ceil(items * ln(fp) / (-8 * ln(2)^2)) in that operation order, `as u64`.  Host only. */
 uint64_t hbu_bloom_num_bits(uint64_t estimated_items, double fp);

@@ -446,6 +446,9 @@ _SIGNATURES += [
     ("hbu_round_counters", ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     ("hbu_round_distances", ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     ("hbu_round_centralities", ctypes.c_int, [_P, _P, _P, _P, _P, _P, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("hbu_export", ctypes.c_int, [_P, _P, _P, _U64, ctypes.POINTER(_U64)]),
+    ("hbu_fold_harmonic", ctypes.c_int, [_P, _P, ctypes.c_double, ctypes.c_uint32, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("hbu_graph_node_sketch", ctypes.c_int, [_P, _P]),
 ]
 # include/hb_store.h
 _SIGNATURES += [

@@ -7,8 +7,11 @@ dht/store.rs:192-195); update_centralities is mapper.rs:157-209 as one device ca
 update_distances (shortest_path/mapper.rs:64-86) are the two jobs' edge steps between two resident tables: edge ids go up, actions come back.
 WorkerGraph and ChangedFilter keep a worker's edges and its changed-node filter (U64BloomFilter, or the Exact arm of UpdatedNodes) on the
 device as well; setup_counters, round_counters, round_distances and round_centralities are the mapper steps between them and the tables
-(only counts cross the link), run_harmonic_job and run_shortest_path_job the coordinator's loop over one resident shard."""
+(only counts cross the link), run_harmonic_job and run_shortest_path_job the coordinator's loop over one resident shard.  items() is
+DhtTable::iter(); fold_harmonic, WorkerGraph.node_sketch, num_samples and run_approx_harmonic_job are the approximated harmonic centrality
+coordinator (approximated_harmonic_centrality/coordinator.rs:82-148) on top of the shortest-path job."""
 import ctypes
+import math
 
 import numpy as np
 
@@ -59,6 +62,17 @@ class _Table:
         n = ctypes.c_uint64(0)
         self._check(self.lib.hbu_len(self.h, ctypes.byref(n)))
         return n.value
+
+    def items(self):
+        """DhtTable::iter(): (keys, values) of the whole table, keys[i] with values[i], in no particular order.  values: the kind's dtype,
+        uint8[n, 64] for a counter table."""
+        n = len(self)
+        keys = np.zeros(n, dtype=_lib.U128)
+        values = np.zeros((n, 64), dtype=np.uint8) if self.kind == KIND_HLL64 else np.zeros(n, dtype=self.dtype)
+        written = ctypes.c_uint64(0)
+        self._check(self.lib.hbu_export(self.h, _lib._ptr(keys), _lib._ptr(values), n, ctypes.byref(written)))
+        assert written.value == n
+        return keys, values
 
 
 class CounterTable(_Table):
@@ -185,6 +199,30 @@ def update_distances(prev, next, from_ids, to_ids):
     return keys[:written.value].copy(), actions[:written.value].copy()
 
 
+FOLD_SKIP_ZERO = 1  # HBU_FOLD_SKIP_ZERO
+
+
+def fold_harmonic(distances, centralities, norm, skip_zero=False):
+    """coordinator.rs:139-145 of the approximated harmonic centrality for one finished shortest-path job, as one device call: every
+    (node, d) of `distances` (KIND_U64) adds KahanSum::from((1.0 / d as f64) * norm) to centralities[node] (KIND_KAHAN), inserting an absent
+    node.  A distance of 0 (the source) gives inf, as in the reference, unless skip_zero.  Returns (folded, inserted)."""
+    folded, inserted = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    centralities._check(centralities.lib.hbu_fold_harmonic(distances.h, centralities.h, float(norm), FOLD_SKIP_ZERO if skip_zero else 0, ctypes.byref(folded),
+                                                           ctypes.byref(inserted)))
+    return folded.value, inserted.value
+
+
+def num_samples(num_nodes, sample_rate):
+    """coordinator.rs:82-84: ((num_nodes as f64).log2() / sample_rate.powi(2)).ceil() as u64 (`as u64` saturates: NaN and negatives are 0)"""
+    n = float(int(num_nodes))
+    log2 = math.log2(n) if n > 0.0 else -math.inf  # (libm's log2, as Rust's f64::log2)
+    with np.errstate(all="ignore"):
+        v = float(np.ceil(np.float64(log2) / (np.float64(sample_rate) * np.float64(sample_rate))))
+    if not v > 0.0:
+        return 0
+    return min(int(v), (1 << 64) - 1) if v != math.inf else (1 << 64) - 1
+
+
 # ---- a worker's graph and changed-node filter on the device, the mapper steps, the two jobs' loops ----------------------------------
 FILTER_BLOOM, FILTER_EXACT = 0, 1  # HBU_FILTER_*
 SKETCH_THRESHOLD = 16_384  # shortest_path/updated_nodes.rs:22
@@ -234,6 +272,13 @@ class WorkerGraph(_Handle):
         _raise_thread_error(self.lib, self.lib.hbu_graph_len(self.h, ctypes.byref(n), ctypes.byref(m)))
         assert (n.value, m.value) == (self.n_nodes, self.n_edges)
         return m.value
+
+    def node_sketch(self):
+        """ShortestPathWorker::nodes_sketch (shortest_path/worker.rs:44-49): the registers of HyperLogLog<4096> after add_u128 of every node,
+        uint8[4096].  Workers' sketches merge with np.maximum; the estimate stays with the caller."""
+        out = np.zeros(4096, dtype=np.uint8)
+        _raise_thread_error(self.lib, self.lib.hbu_graph_node_sketch(self.h, _lib._ptr(out)))
+        return out
 
 
 class ChangedFilter(_Handle):
@@ -516,3 +561,29 @@ def run_shortest_path_job(graphs, source, max_distance=None, device=-1, on_round
     finally:
         for c in changed + saved:
             c.close()
+
+
+def run_approx_harmonic_job(graphs, sampled_nodes, num_samples, max_distance, device=-1, skip_zero=False, on_source=None):
+    """The approximated harmonic centrality coordinator's loop (approximated_harmonic_centrality/coordinator.rs:107-148) over one resident
+    shard and the workers `graphs`: norm = 1.0 / (num_samples - 1) - from num_samples, not from len(sampled_nodes), which the per-worker
+    div_ceil can make larger -, then for every source of `sampled_nodes` IN THE ORDER GIVEN (it is a node's summation order and therefore its
+    bits) the shortest-path job with `max_distance`, its distances folded into one KahanSum table (fold_harmonic), its tables dropped.
+    Sampling the sources and sizing the sample (node_sketch, num_samples) stay with the caller.  A source's own distance is 0 and folds as
+    inf, as in the reference, unless skip_zero.  Returns {node id as int: f64::from(sum)}.  on_source(state): called after every source
+    with the live centrality table and the fold's counts (tests)."""
+    graphs = list(graphs)
+    if int(num_samples) < 1:
+        raise ValueError("num_samples - 1 underflows (the reference panics)")
+    with np.errstate(all="ignore"):
+        norm = float(np.float64(1.0) / np.float64(int(num_samples) - 1))  # num_samples == 1: 1.0 / 0 = inf
+    with ValueTable(KIND_KAHAN, device) as centralities:
+        for i, source in enumerate(sampled_nodes):
+            distances = run_shortest_path_job(graphs, source, int(max_distance), device)
+            try:
+                folded, inserted = fold_harmonic(distances, centralities, norm, skip_zero)
+            finally:
+                distances.close()  # drop_tables
+            if on_source:
+                on_source(dict(index=i, source=int(source), centralities=centralities, folded=folded, inserted=inserted))
+        keys, values = centralities.items()
+        return {(int(k["hi"]) << 64) | int(k["lo"]): float(v) for k, v in zip(keys, values["sum"])}

@@ -2,7 +2,8 @@
 // scalar value tables with the five scalar upsert operators, a device copy of a table, the update_centralities step and the two edge
 // steps update_counters / update_distances (include/hb_ampc.h cites the reference operations this serves; the scalar kernels live in
 // hb_ampc_values.hip.h, those of the edge steps in hb_ampc_edges.hip.h), and a worker's resident graph and changed-node filter with the
-// mapper steps that work between them and the tables (kernels in hb_ampc_round.hip.h).
+// mapper steps that work between them and the tables (kernels in hb_ampc_round.hip.h), and what the approximated-harmonic job adds: the
+// fold of a distance table into the centrality table, the worker's node sketch (kernels in hb_ampc_fold.hip.h) and the export of a table.
 #include "hb_guard_alloc.h" // FIRST: no-op unless built with -DHB_GUARD_ALLOC=<mode> (debug allocators: guard pages / poison / red zones)
 #include "hb_pool.h"        // then: every hipMalloc / hipFree below goes through the caching device allocator (shipped build)
 #include <hip/hip_runtime.h>
@@ -22,6 +23,7 @@
 #include "hb_ampc_values.hip.h"
 #include "hb_ampc_edges.hip.h"
 #include "hb_ampc_round.hip.h"
+#include "hb_ampc_fold.hip.h"
 #include "hb_internal.h"
 #include "hb_regs.hip.h"
 #include "hb_table.hip.h"
@@ -682,6 +684,85 @@ int hbu_clone(hbu_table *from, hbu_table **out)
     });
 }
 
+int hbu_export(hbu_table *t, hb_u128 *keys_out, void *values_out, uint64_t capacity, uint64_t *written)
+{
+    return guarded(t, [&]() -> int {
+        if (written) *written = 0;
+        if (!t || !written) return t ? fail(t, HB_ERR_INVALID, "NULL argument") : HB_ERR_INVALID;
+        if (t->broken) return fail(t, HB_ERR_INVALID, kBrokenMsg);
+        const uint64_t n = t->committed;
+        if (capacity < n) return fail(t, HB_ERR_INVALID, "capacity below the number of keys");
+        if (n && (!keys_out || !values_out)) return fail(t, HB_ERR_INVALID, "NULL argument");
+        if (!n) return HB_OK;
+        HBU_HIP(hipSetDevice(t->device));
+        Carve probe{nullptr};
+        (void)probe.take<hb_u128>(n);
+        int rc = work_memory(t, probe.used);
+        if (rc) return rc;
+        hb_u128 *d_out = (hb_u128 *)t->d_work;
+        // the keys go where their entry numbers point, which is where the values already are: rows 0 .. committed of the value table
+        hipLaunchKernelGGL(hbr::set_export_kernel, dim3(grid_for(t->slots)), dim3(256), 0, t->stream, (const u128 *)t->d_keys, (const uint32_t *)t->d_pids, t->slots,
+                           (uint32_t)n, d_out);
+        HBU_HIP(hipGetLastError());
+        HBU_HIP(hipMemcpyAsync(keys_out, d_out, n * sizeof(hb_u128), hipMemcpyDeviceToHost, t->stream));
+        HBU_HIP(hipMemcpyAsync(values_out, t->d_table, n * t->vbytes, hipMemcpyDeviceToHost, t->stream));
+        HBU_HIP(hipStreamSynchronize(t->stream));
+        *written = n;
+        return HB_OK;
+    });
+}
+
+int hbu_fold_harmonic(hbu_table *distances, hbu_table *centralities, double norm, uint32_t flags, uint64_t *folded, uint64_t *inserted)
+{
+    hbu_table *t = centralities; // the table that changes: its stream runs the fold, its error text reports it
+    return guarded(t, [&]() -> int {
+        for (uint64_t *p : {folded, inserted})
+            if (p) *p = 0;
+        if (!distances || !t) return t ? fail(t, HB_ERR_INVALID, "NULL argument") : HB_ERR_INVALID;
+        if (distances->kind != HBU_KIND_U64 || t->kind != HBU_KIND_KAHAN) return fail(t, HB_ERR_INVALID, "fold_harmonic needs a u64 table and a KahanSum table");
+        if (distances->device != t->device) return fail(t, HB_ERR_INVALID, "the two tables are not on one device");
+        if (distances->broken || t->broken) return fail(t, HB_ERR_INVALID, kBrokenMsg);
+        if (flags & ~HBU_FOLD_SKIP_ZERO) return fail(t, HB_ERR_INVALID, "unknown flag bits");
+        const uint64_t count = distances->committed;
+        if (!count) return HB_OK;
+        HBU_HIP(hipSetDevice(t->device));
+        if (t->committed + count >= 0xFFFFFFFEull) return fail(t, HB_ERR_LIMIT, "too many keys in one table (< 2^32)");
+        // room for every key of `distances` (each might be new) before the launch: the index never grows inside one
+        int rc;
+        if (2 * (t->committed + count) > t->slots && (rc = rebuild_index(t, t->committed + count, t->committed))) return rc;
+        if ((rc = reserve(t, t->committed + count))) return rc;
+        Carve probe{nullptr};
+        (void)probe.take<unsigned long long>(2);
+        if ((rc = work_memory(t, probe.used))) return rc;
+        unsigned long long *d_counts = (unsigned long long *)t->d_work;
+        HBU_HIP(hipStreamSynchronize(distances->stream)); // distances is only read: idle before this table's stream touches it
+        unsigned long long h_counts[2] = {0, 0};
+        // from here on a failure is a HIP error: the keys the kernel may have put into the index are taken out again, as apply() does
+        auto run = [&]() -> hipError_t {
+            hipError_t e = hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), t->stream);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(hbf::fold_distances_kernel, dim3(grid_for(distances->slots)), dim3(256), 0, t->stream, (const u128 *)distances->d_keys,
+                               (const uint32_t *)distances->d_pids, distances->slots, (uint32_t)count, (const uint64_t *)distances->d_table, table_of(t),
+                               (uint32_t)t->committed, (hbv::Kahan *)t->d_table, norm, flags, d_counts);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            if ((e = hipMemcpyAsync(t->h_word, t->d_next, sizeof(unsigned long long), hipMemcpyDeviceToHost, t->stream)) != hipSuccess) return e;
+            if ((e = hipMemcpyAsync(h_counts, d_counts, sizeof(h_counts), hipMemcpyDeviceToHost, t->stream)) != hipSuccess) return e;
+            return hipStreamSynchronize(t->stream);
+        };
+        const hipError_t e = run();
+        if (e != hipSuccess) {
+            const std::string why = hipGetErrorString(e);
+            (void)hipGetLastError();
+            if (rebuild_index(t, std::max<uint64_t>(t->slots / 2, 512), t->committed)) t->broken = true;
+            return fail(t, e == hipErrorOutOfMemory ? HB_ERR_NOMEM : HB_ERR_HIP, why);
+        }
+        t->committed = *t->h_word;
+        if (folded) *folded = h_counts[0];
+        if (inserted) *inserted = h_counts[1];
+        return HB_OK;
+    });
+}
+
 // hbu_update_centralities; nodes_on_device: the ids are in device memory already, complete with respect to next_centrality's stream
 // (hbu_round_centralities hands its selected nodes over this way)
 static int centralities_step(hbu_table *prev_counters, hbu_table *next_counters, hbu_table *prev_centrality, hbu_table *next_centrality, const hb_u128 *nodes,
@@ -1133,6 +1214,34 @@ void hbu_graph_destroy(hbu_graph *g)
     for (void *p : {(void *)g->d_nodes, (void *)g->d_from, (void *)g->d_to, g->d_work})
         if (p) (void)hipFree(p);
     delete g;
+}
+
+int hbu_graph_node_sketch(const hbu_graph *g, uint8_t *registers_out)
+{
+    return guarded(nullptr, [&]() -> int {
+        hbu_table *t = nullptr; // (HBU_HIP reports through the thread's error text)
+        if (!g || !registers_out) return refuse(HB_ERR_INVALID, "NULL argument");
+        HBU_HIP(hipSetDevice(g->device));
+        // 4096 words for the maxima, then the bytes; a graph has no stream of its own: the device's default one, and the copy waits for it
+        Carve probe{nullptr};
+        (void)probe.take<uint32_t>(HBU_NODE_SKETCH_REGISTERS);
+        (void)probe.take<uint8_t>(HBU_NODE_SKETCH_REGISTERS);
+        int rc = graph_work(g, nullptr, probe.used);
+        if (rc) return rc;
+        Carve carve{(char *)g->d_work};
+        uint32_t *d_words = carve.take<uint32_t>(HBU_NODE_SKETCH_REGISTERS);
+        uint8_t *d_bytes = carve.take<uint8_t>(HBU_NODE_SKETCH_REGISTERS);
+        HBU_HIP(hipMemsetAsync(d_words, 0, HBU_NODE_SKETCH_REGISTERS * sizeof(uint32_t), nullptr));
+        if (g->n_nodes) {
+            hipLaunchKernelGGL(hbf::node_sketch_kernel, dim3(grid_capped(g->n_nodes)), dim3(256), 0, nullptr, (const hb_u128 *)g->d_nodes, g->n_nodes, d_words);
+            HBU_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(hbf::sketch_narrow_kernel, dim3(HBU_NODE_SKETCH_REGISTERS / 256), dim3(256), 0, nullptr, (const uint32_t *)d_words, d_bytes);
+        HBU_HIP(hipGetLastError());
+        HBU_HIP(hipMemcpyAsync(registers_out, d_bytes, HBU_NODE_SKETCH_REGISTERS, hipMemcpyDeviceToHost, nullptr));
+        HBU_HIP(hipStreamSynchronize(nullptr));
+        return HB_OK;
+    });
 }
 
 int hbu_filter_create(int32_t device, uint32_t kind, uint64_t num_bits, hbu_filter **out)

@@ -19,10 +19,15 @@ hbu_round_counters, hbu_round_distances and hbu_round_centralities per repetitio
 about 0.1 % of the nodes inserted) against the route of the calls that were there before - hbu_update_counters / hbu_update_distances /
 hbu_update_centralities fed from page-locked host ids in batches of `pairs per batch`; only the time inside those calls counts for the
 comparator, the host's own filtering and filter update are timed once per density and reported beside it.  --only-rounds skips the
-counter-table section.  --out FILE also writes the JSON line there.
+counter-table section.  --approx adds the approximated-harmonic job: hbu_fold_harmonic against the route of the calls that were there before
+it, in the same process (batch_get_values of every key of the distance table, the terms in numpy - not timed -, batch_upsert_values(KAHAN_ADD),
+page-locked buffers, only the time inside the calls) into a centrality table of that many keys from distance tables of 100 %, 10 % and 0.1 %
+of them, every key present and half of them absent; hbu_export of a table of every kind; and whole sources of run_approx_harmonic_job's loop
+on the --rounds R-MAT worker graph with max_distance = 5, with the fold's share of a source.  --only-approx skips the counter-table section.
+--out FILE also writes the JSON line there.
 usage: tools/ampc_bench.py [keys, default 10000000] [pairs per batch, default 1000000] [--values] [--kind K] [--op OP] [--centralities]
-                           [--edges] [--rounds] [--round-edges N, default 100000000] [--round-scale S] [--only-rounds] [--reps N, default 5]
-                           [--out FILE]"""
+                           [--edges] [--rounds] [--round-edges N, default 100000000] [--round-scale S] [--only-rounds] [--approx] [--only-approx]
+                           [--sources N, default 5] [--reps N, default 5] [--out FILE]"""
 import argparse
 import json
 import os
@@ -371,6 +376,123 @@ def rounds_mode(rng, K, B, reps, total_edges, scale):
     return res
 
 
+def rmat_worker(scale, total_edges):
+    """the R-MAT worker graph of --rounds: (nodes, from_ids, to_ids), edges in stream order"""
+    from stract_amd import synth
+    g = synth.RmatGraph(scale, total_edges)
+    E = g.stream_len(0)
+    from_ids, to_ids = np.zeros(E, dtype=_lib.U128), np.zeros(E, dtype=_lib.U128)
+    at = 0
+    for slab in g.stream():
+        from_ids[at:at + len(slab)], to_ids[at:at + len(slab)] = slab["from"], slab["to"]
+        at += len(slab)
+    nodes = np.array(g.ids)
+    g.close()
+    return nodes, from_ids, to_ids
+
+
+def approx_mode(rng, keys, K, reps, total_edges, scale, n_sources):
+    """hbu_fold_harmonic against the composed route, hbu_export, and whole sources of the approximated-harmonic loop (see the module's docstring)"""
+    res = {"repetitions": reps, "fold": {}, "export": {}}
+    norm = 1.0 / 2657.0
+    kb, db, pb, ab, fb = (_lib.PinnedRecords(K, dtype=_lib.U128), _lib.PinnedRecords(K, dtype=np.uint64), _lib.PinnedRecords(K, dtype=ampc.KAHAN),
+                          _lib.PinnedRecords(K, dtype=np.uint8), _lib.PinnedRecords(K, dtype=np.uint8))
+    kbuf, dbuf, pbuf, acts, found = kb.array, db.array, pb.array, ab.array, fb.array
+    fresh = np.zeros(K, dtype=_lib.U128)  # keys the centrality table does not hold
+    fresh["lo"], fresh["hi"] = np.arange(K, dtype=np.uint64) * np.uint64(0xD6E8FEB86659FD93) + np.uint64(7), np.uint64((1 << 63) + 5)
+    folded, inserted = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
+    with ampc.ValueTable(ampc.KIND_KAHAN, capacity_hint=K) as base:
+        lib = base.lib
+        u64p = lib.hbu_fold_harmonic.argtypes[4]
+        for b in range(0, K, 1_000_000):
+            base.batch_set(keys[b:b + 1_000_000], random_values(rng, ampc.KIND_KAHAN, len(keys[b:b + 1_000_000])))
+        for share in (1.0, 0.1, 0.001):
+            n = max(int(K * share), 1)
+            for label, absent in (("all_present", 0), ("half_absent", n // 2)):
+                ids = np.concatenate([keys[rng.permutation(K)[:n - absent]], fresh[:absent]])
+                rng.shuffle(ids)
+                kbuf[:n] = ids
+                with ampc.ValueTable(ampc.KIND_U64, capacity_hint=n) as dist:
+                    dist.batch_set(ids, rng.integers(1, 8, n, dtype=np.uint64))
+                    t_dev, t_host, t_get, t_up = [], [], [], []
+                    for r in range(reps + 1):  # the first repetition warms both sides up; both start from a fresh copy every time
+                        with base.clone() as cent_d, base.clone() as cent_h:
+                            td = timed(lambda: cent_d._check(lib.hbu_fold_harmonic(dist.h, cent_d.h, norm, 0, folded.ctypes.data_as(u64p), inserted.ctypes.data_as(u64p))))
+                            assert (int(folded[0]), int(inserted[0])) == (n, absent)
+                            tg = timed(lambda: dist._check(lib.hbu_batch_get_values(dist.h, _lib._ptr(kbuf), n, _lib._ptr(dbuf), _lib._ptr(found))))
+                            pbuf["sum"][:n] = (1.0 / dbuf[:n].astype(np.float64)) * norm  # host work, not timed
+                            pbuf["err"][:n] = 0.0
+                            tu = timed(lambda: cent_h._check(lib.hbu_batch_upsert_values(cent_h.h, ampc.OP_KAHAN_ADD, _lib._ptr(kbuf), _lib._ptr(pbuf), n, _lib._ptr(acts))))
+                            if r == reps:  # both routes leave the same table
+                                check = ids[rng.integers(0, n, min(n, 100000))]
+                                a, b2 = cent_d.batch_get(check)[0], cent_h.batch_get(check)[0]
+                                assert np.array_equal(a.view(np.uint64), b2.view(np.uint64)) and len(cent_d) == len(cent_h) == K + absent
+                        if r:
+                            t_dev.append(td)
+                            t_host.append(tg + tu)
+                            t_get.append(tg)
+                            t_up.append(tu)
+                dev, host = spread(t_dev), spread(t_host)
+                gap = max(dev["max_s"] - dev["min_s"], host["max_s"] - host["min_s"])
+                cell = {"entries": n, "absent": absent, "fold_harmonic": dev, "composed_route": host, "composed_batch_get": spread(t_get),
+                        "composed_batch_upsert": spread(t_up), "median_gain_s": round(host["median_s"] - dev["median_s"], 6), "larger_spread_s": round(gap, 6),
+                        "beats_by_more_than_the_spread": bool(host["median_s"] - dev["median_s"] > gap),
+                        "fold_Mentries_per_s": round(n / dev["median_s"] / 1e6, 1), "composed_Mentries_per_s": round(n / host["median_s"] / 1e6, 1),
+                        "link_bytes_per_entry": {"fold_harmonic": 0, "composed_route": 16 + 9 + 32 + 1}}
+                res["fold"]["%g_percent_%s" % (share * 100, label)] = cell
+                print("fold", share, label, cell, file=sys.stderr, flush=True)
+    for x in (db, pb, ab, fb):
+        x.close()
+    # ---- hbu_export of K keys, every kind, into page-locked memory
+    written = np.zeros(1, dtype=np.uint64)
+    for name, kind in [("hll64", ampc.KIND_HLL64)] + sorted(KINDS.items()):
+        vbytes = 64 if kind == ampc.KIND_HLL64 else ampc.DTYPES[kind].itemsize
+        vb = _lib.PinnedRecords(K * vbytes, dtype=np.uint8)
+        with (ampc.CounterTable(capacity_hint=K) if kind == ampc.KIND_HLL64 else ampc.ValueTable(kind, capacity_hint=K)) as tab:
+            for b in range(0, K, 1_000_000):
+                m = len(keys[b:b + 1_000_000])
+                tab.batch_set(keys[b:b + m], rng.integers(0, 40, (m, 64), dtype=np.uint8) if kind == ampc.KIND_HLL64 else random_values(rng, kind, m))
+            times = [timed(lambda: tab._check(tab.lib.hbu_export(tab.h, _lib._ptr(kbuf), _lib._ptr(vb.array), K, written.ctypes.data_as(tab.lib.hbu_export.argtypes[4]))))
+                     for _ in range(reps + 1)][1:]
+            assert int(written[0]) == K
+        sp = spread(times)
+        res["export"][name] = dict(sp, value_bytes=vbytes, Mkeys_per_s=round(K / sp["median_s"] / 1e6, 1), GBs=round(K * (16 + vbytes) / sp["median_s"] / 1e9, 2))
+        print("export", name, res["export"][name], file=sys.stderr, flush=True)
+        vb.close()
+    kb.close()
+    # ---- whole sources: the shortest-path job with max_distance = 5, then the fold
+    t0 = time.perf_counter()
+    nodes, from_ids, to_ids = rmat_worker(scale, total_edges)
+    print("graph: %d nodes, %d edges, %.1f s" % (len(nodes), len(from_ids), time.perf_counter() - t0), file=sys.stderr, flush=True)
+    out_deg_sources = np.unique(from_ids[rng.integers(0, len(from_ids), 4 * n_sources + 4)])  # sources with out-links, as random_page_nodes_with_outgoing picks
+    sources = [(int(k["hi"]) << 64) | int(k["lo"]) for k in out_deg_sources[:n_sources + 1]]
+    per = []
+    with ampc.WorkerGraph(nodes, from_ids, to_ids) as graph, ampc.ValueTable(ampc.KIND_KAHAN) as cent:
+        t0 = time.perf_counter()
+        sketch = graph.node_sketch()
+        t_sketch = time.perf_counter() - t0
+        t_sketch = min(t_sketch, timed(graph.node_sketch))
+        for i, source in enumerate(sources):  # the first source warms up
+            t0 = time.perf_counter()
+            dist = ampc.run_shortest_path_job([graph], source, 5)
+            t1 = time.perf_counter()
+            f, ins = ampc.fold_harmonic(dist, cent, norm)
+            t2 = time.perf_counter()
+            dist.close()
+            if i:
+                per.append({"walk_s": round(t1 - t0, 6), "fold_s": round(t2 - t1, 6), "reached": f, "inserted": ins})
+        t_items = timed(cent.items)
+        total_keys = len(cent)
+    whole = [p["walk_s"] + p["fold_s"] for p in per]
+    share = [p["fold_s"] / (p["walk_s"] + p["fold_s"]) for p in per]
+    res["whole_source"] = {"nodes": len(nodes), "edges": len(from_ids), "max_distance": 5, "sources": per, "source": spread(whole),
+                           "fold": spread([p["fold_s"] for p in per]), "fold_share_median": round(sorted(share)[len(share) // 2], 5),
+                           "fold_share_max": round(max(share), 5), "node_sketch_s": round(t_sketch, 6), "node_sketch_registers_set": int(np.count_nonzero(sketch)),
+                           "items_s": round(t_items, 6), "centrality_keys": total_keys}
+    print("whole_source", res["whole_source"], file=sys.stderr, flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("keys", nargs="?", type=int, default=10_000_000)
@@ -384,6 +506,9 @@ def main():
     ap.add_argument("--round-edges", type=int, default=100_000_000, help="R-MAT edges of the worker graph of --rounds")
     ap.add_argument("--round-scale", type=int, default=0, help="R-MAT scale of that graph (0: the largest with 2^scale <= keys)")
     ap.add_argument("--only-rounds", action="store_true", help="skip the counter-table section (with --rounds)")
+    ap.add_argument("--approx", action="store_true", help="also the approximated-harmonic job: the fold against the composed route, export, whole sources")
+    ap.add_argument("--only-approx", action="store_true", help="skip the counter-table section (with --approx)")
+    ap.add_argument("--sources", type=int, default=5, help="timed sources of --approx (one more warms up)")
     ap.add_argument("--reps", type=int, default=5, help="timed batches per shape and side of --edges / repetitions of --rounds (at least 5)")
     ap.add_argument("--out")
     args = ap.parse_args()
@@ -393,7 +518,7 @@ def main():
     keys["lo"] = rng.permutation(K).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)
     keys["hi"] = rng.integers(0, 1 << 63, K, dtype=np.uint64)
     out = {"keys": K, "pairs_per_batch": B, "bytes_per_pair": 80}
-    for label, pinned in (() if args.only_rounds and args.rounds else (("pageable", False), ("pinned", True))):
+    for label, pinned in (() if (args.only_rounds and args.rounds) or (args.only_approx and args.approx) else (("pageable", False), ("pinned", True))):
         kb = _lib.PinnedRecords(B, dtype=_lib.U128) if pinned else None
         vb = _lib.PinnedRecords(B * 64, dtype=np.uint8) if pinned else None
         kbuf = kb.array if pinned else np.zeros(B, dtype=_lib.U128)
@@ -455,6 +580,9 @@ def main():
     if args.rounds:
         scale = args.round_scale or max(int(K).bit_length() - 1, 1)
         out["rounds"] = rounds_mode(rng, K, B, max(args.reps, 5), args.round_edges, scale)
+    if args.approx:
+        scale = args.round_scale or max(int(K).bit_length() - 1, 1)
+        out["approx"] = approx_mode(rng, keys, K, max(args.reps, 5), args.round_edges, scale, max(args.sources, 1))
     line = json.dumps(out)
     print(line)
     if args.out:
