@@ -14,7 +14,7 @@
  * merged = op(old, new) and the action is `Merged` iff merged != old (Rust's derived PartialEq: an IEEE comparison for the float kinds,
  * so a NaN result is always `Merged` and -0.0 turning into +0.0 is `NoChange` although the merged bits are stored), else `NoChange`.
  * This header is the C ABI a GPU worker would put behind those calls.  A table lives in HBM: the key -> slot index is a device hash
- * table (hb_table.hip.h), the values one array of 64 / 8 / 4 / 8 / 16 bytes each.  A batch is grouped by key with its order kept and
+ * table (hb_table.hip.h), the values one array of 64 / 8 / 4 / 8 / 16 / 64 bytes each.  A batch is grouped by key with its order kept and
  * every group is folded by one writer in that order (HyperLogLog: one quad per key; the scalar kinds: one thread per key, one wave for
  * a key with many pairs).  hbu_update_centralities is CentralityMapper::update_centralities (mapper.rs:157-209) as one device call:
  * no counter and no size crosses the link.  The two steps that walk the EDGES are device calls between two resident tables as well:
@@ -29,8 +29,13 @@
  * map_cardinalities, RelaxEdges, map_centralities); what the approximated-harmonic coordinator (approximated_harmonic_centrality/
  * coordinator.rs:82-180) adds to the shortest-path job: the fold of a finished job's distances into the KahanSum table as one device call
  * (hbu_fold_harmonic), the worker's node sketch (hbu_graph_node_sketch, HyperLogLog<4096> registers) and DhtTable::iter() for a table of any
- * kind (hbu_export).  Still out: HyperLogLog<8/16/32/128> as table values (no job uses them), HyperLogLog<4096>::size() (its bias rows are
- * not carried here: the caller merges the registers and estimates), the sampling of sources, the String, meta and
+ * kind (hbu_export); and the step that job needs to run at a useful speed, several sampled sources per walk over the edges: a sixth table
+ * kind whose 64-byte row holds one u8 distance for each of up to 64 sources (HBU_KIND_DIST64, HBU_OP_DIST64_MIN), RelaxEdges for all of
+ * them in one pass (hbu_round_lane_distances) and their fold in source order (hbu_fold_harmonic_lanes).  The reference's max_distance is
+ * a u8 (config/mod.rs:718), so a distance fits a lane; max_distance = 255 stays with the per-source route.
+ * Still out: HyperLogLog<8/16/32/128> as table values (no job uses them), HyperLogLog<4096>::size() (its bias rows are
+ * not carried here: the caller merges the registers and estimates), the sampling of sources, more than 64 lanes or 16-bit lanes, a lane
+ * form of the host-fed edge step, the String, meta and
  * bloom-valued tables (a handful of values per shard), the Exact -> Sketch policy of UpdatedNodes and the serde envelopes of the filters
  * (the caller's), a compressed edge layout, raft replication, the network protocol, shards that span ranks.
  * Defined differences: U64Add wraps at 2^64 (the reference panics in a debug build and wraps in a release build), and so does the
@@ -61,6 +66,7 @@ typedef struct hbu_table hbu_table;
 #define HBU_KIND_F32   2 /*  4 B                                                    */
 #define HBU_KIND_F64   3 /*  8 B                                                    */
 #define HBU_KIND_KAHAN 4 /* 16 B: {double sum, err}  (kahan_sum.rs:30-33)           */
+#define HBU_KIND_DIST64 5 /* 64 B: 64 lanes of u8, one per source of a batch; HBU_DIST_NONE = no distance */
 
 #define HBU_OP_HLL64     0 /* register-wise max                                      upsert.rs:67-89   */
 #define HBU_OP_U64_ADD   1 /* old + new, wrapping                                    upsert.rs:92-103  */
@@ -68,6 +74,10 @@ typedef struct hbu_table hbu_table;
 #define HBU_OP_F32_ADD   3 /* old + new: one f32 addition per pair, in batch order   upsert.rs:118-129 */
 #define HBU_OP_F64_ADD   4 /* old + new: one f64 addition per pair, in batch order   upsert.rs:131-142 */
 #define HBU_OP_KAHAN_ADD 5 /* old += new.sum (kahan_sum.rs:47-54); new.err ignored   upsert.rs:143-152 */
+#define HBU_OP_DIST64_MIN 6 /* byte-wise min: U64Min (upsert.rs:105-116) on each of a row's 64 lanes    */
+
+#define HBU_DIST_LANES 64   /* lanes of an HBU_KIND_DIST64 row                                          */
+#define HBU_DIST_NONE  0xFF /* a lane without a distance; lanes hold 0 .. 254                           */
 
 /* device < 0: current device.  capacity_hint: expected number of keys (the table grows as needed). */
 int hbu_create(int32_t device, uint64_t capacity_hint, hbu_table **out);
@@ -89,7 +99,10 @@ int hbu_batch_upsert(hbu_table *t, const hb_u128 *keys, const uint8_t *counters,
  * HBU_OP_HLL64); the three calls above are refused (HB_ERR_INVALID, table untouched) on a table of another kind, and so is an
  * operator that does not belong to the table's kind. */
 int hbu_batch_set_values(hbu_table *t, const hb_u128 *keys, const void *values, uint64_t count);
-/* an absent key: found[i] = 0 and zero bytes (0 / 0.0 / KahanSum::default()) */
+/* an absent key: found[i] = 0 and zero bytes (0 / 0.0 / KahanSum::default()); on an HBU_KIND_DIST64 table 64 bytes of HBU_DIST_NONE: "no
+ * distance", not zero, is that kind's default.  HBU_OP_DIST64_MIN follows the rule above: an absent key is Inserted with the pair's row
+ * verbatim (a row of 64 x HBU_DIST_NONE included), otherwise merged = byte-wise min(old, new), Merged iff merged != old.  The three counter
+ * calls are refused on an HBU_KIND_DIST64 table although its rows are as wide. */
 int hbu_batch_get_values(hbu_table *t, const hb_u128 *keys, uint64_t count, void *values_out, uint8_t *found);
 int hbu_batch_upsert_values(hbu_table *t, uint32_t op, const hb_u128 *keys, const void *values, uint64_t count, uint8_t *actions);
 /* pairs of one key up to this many are folded by one thread, more by one wave (tests place groups at this length) */
@@ -153,6 +166,17 @@ int hbu_update_distances(hbu_table *prev_distances, hbu_table *next_distances, c
  * set on centralities: NULL, a wrong kind on either table, tables on different devices, a broken table, unknown flag bits.
  * Transactional like every batch call: after a HIP error `centralities` holds the keys it held before. */
 int hbu_fold_harmonic(hbu_table *distances, hbu_table *centralities, double norm, uint32_t flags, uint64_t *folded, uint64_t *inserted);
+
+/* hbu_fold_harmonic for a finished batch of up to 64 shortest-path jobs held as lane rows: for every key of `lanes` (HBU_KIND_DIST64) and
+ * l = 0 .. n_lanes - 1 IN ASCENDING ORDER where byte l is not HBU_DIST_NONE, exactly what hbu_fold_harmonic does for (key, d = byte l) - the
+ * first addend of a key absent from `centralities` written as {v, 0.0}, every other one added -, so that the result equals, bit for bit
+ * except for a NaN's sign and payload, n_lanes calls of hbu_fold_harmonic, one per lane in lane order, on HBU_KIND_U64 tables holding that
+ * lane's entries.  Lanes at or above n_lanes are ignored.  HBU_FOLD_SKIP_ZERO skips lanes that hold 0.  A key with no lane to fold is not
+ * inserted and claims no entry.  *folded = the lanes folded, *inserted = the new keys (either may be NULL).  Room is made first for
+ * committed + len(lanes) keys.  An empty `lanes`: HB_OK, zero counts, nothing touched.  Refused with HB_ERR_INVALID, nothing changed,
+ * hbu_last_error set on centralities: n_lanes of 0 or above 64, NULL, a wrong kind on either table, tables on different devices, a broken
+ * table, unknown flag bits.  Stream rule and transactionality: those of hbu_fold_harmonic. */
+int hbu_fold_harmonic_lanes(hbu_table *lanes, hbu_table *centralities, double norm, uint32_t n_lanes, uint32_t flags, uint64_t *folded, uint64_t *inserted);
 
 /* ---- the resident worker: its graph and its changed-node filter next to the tables ------------------------------------------------
  * In the reference a worker walks ALL of its edges every round and keeps those whose source passes its changed-nodes filter
@@ -233,6 +257,22 @@ int hbu_round_counters(hbu_table *prev_counters, hbu_table *next_counters, const
  * ForwardlinksQuery ... skip_self_links(false).deduplicate(false). */
 int hbu_round_distances(hbu_table *prev_distances, hbu_table *next_distances, const hbu_graph *g, hbu_filter *changed, hbu_filter *new_changed, uint64_t *selected,
                         uint64_t *changed_nodes);
+/* RelaxEdges (shortest_path/mapper.rs:105-190) for 64 sources in one pass over the edges of g; both tables HBU_KIND_DIST64.  Edge e is
+ * selected iff `changed` contains from[e] AND from[e] has a row in prev (an edge whose source has none is skipped and inserts nothing, as in
+ * hbu_update_distances).  Its pair is (to[e], cand) with cand[l] = prev[from[e]][l] + 1 on every lane that is not HBU_DIST_NONE and
+ * HBU_DIST_NONE elsewhere; 254 + 1 is HBU_DIST_NONE, no candidate.  The row is gathered when the pair is folded; per edge only the source's
+ * slot is staged.  The pairs are upserted into `next` with HBU_OP_DIST64_MIN in edge order (a candidate row of 64 x HBU_DIST_NONE like any
+ * other: NoChange on a present key, Inserted on an absent one); to[e] of every pair whose action is_changed() (Merged OR Inserted) goes into
+ * new_changed if that is not NULL.  *selected: the selected edges = the pairs; *merged / *inserted: the pairs with those actions; the round
+ * had changes iff merged + inserted > 0.  Tables, counts and new_changed equal, bit for bit, those of hbu_batch_get_values(prev, from) of
+ * the selected edges, the `+ 1` on the host and hbu_batch_upsert_values(next, HBU_OP_DIST64_MIN, to, ...).
+ * Refusals: those of hbu_round_distances (NULL, a wrong kind on either table, different devices, prev == next, changed == new_changed, a
+ * broken table: HB_ERR_INVALID, nothing changed, hbu_last_error on next).  Transactionality: that of hbu_round_distances (a HIP error in a
+ * multi-chunk call leaves earlier chunks applied and next with the keys it held before the failing chunk).  Stream: the call runs on next's
+ * stream after a synchronise of prev's and of both filters'; everything is visible on return.  Chunking is invisible: the pairs apply in
+ * order and a minimum is associative. */
+int hbu_round_lane_distances(hbu_table *prev, hbu_table *next, const hbu_graph *g, hbu_filter *changed, hbu_filter *new_changed, uint64_t *selected,
+                             uint64_t *merged, uint64_t *inserted);
 /* map_centralities (mapper.rs:298-333): the nodes of g that `changed` contains go through hbu_update_centralities, a chunk at a time;
  * *written sums the chunks' distinct nodes (the reference's batches are as separate). */
 int hbu_round_centralities(hbu_table *prev_counters, hbu_table *next_counters, hbu_table *prev_centrality, hbu_table *next_centrality, const hbu_graph *g,

@@ -449,6 +449,8 @@ _SIGNATURES += [
     ("hbu_export", ctypes.c_int, [_P, _P, _P, _U64, ctypes.POINTER(_U64)]),
     ("hbu_fold_harmonic", ctypes.c_int, [_P, _P, ctypes.c_double, ctypes.c_uint32, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     ("hbu_graph_node_sketch", ctypes.c_int, [_P, _P]),
+    ("hbu_fold_harmonic_lanes", ctypes.c_int, [_P, _P, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("hbu_round_lane_distances", ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
 ]
 # include/hb_store.h
 _SIGNATURES += [

@@ -9,7 +9,9 @@ WorkerGraph and ChangedFilter keep a worker's edges and its changed-node filter 
 device as well; setup_counters, round_counters, round_distances and round_centralities are the mapper steps between them and the tables
 (only counts cross the link), run_harmonic_job and run_shortest_path_job the coordinator's loop over one resident shard.  items() is
 DhtTable::iter(); fold_harmonic, WorkerGraph.node_sketch, num_samples and run_approx_harmonic_job are the approximated harmonic centrality
-coordinator (approximated_harmonic_centrality/coordinator.rs:82-148) on top of the shortest-path job."""
+coordinator (approximated_harmonic_centrality/coordinator.rs:82-148) on top of the shortest-path job.  LaneTable holds one u8 distance
+for each of up to 64 sources per row (HBU_KIND_DIST64); round_lane_distances, fold_harmonic_lanes and run_shortest_paths_job walk a whole
+batch of sampled sources in one pass over the edges, and run_approx_harmonic_job(sources_per_walk=2..64) is the coordinator on top of them."""
 import ctypes
 import math
 
@@ -22,6 +24,8 @@ KIND_HLL64, KIND_U64, KIND_F32, KIND_F64, KIND_KAHAN = range(5)  # HBU_KIND_*
 OP_HLL64, OP_U64_ADD, OP_U64_MIN, OP_F32_ADD, OP_F64_ADD, OP_KAHAN_ADD = range(6)  # HBU_OP_*
 KAHAN = np.dtype([("sum", "<f8"), ("err", "<f8")])  # KahanSum, kahan_sum.rs:30-33
 DTYPES = {KIND_U64: np.dtype(np.uint64), KIND_F32: np.dtype(np.float32), KIND_F64: np.dtype(np.float64), KIND_KAHAN: KAHAN}
+KIND_DIST64, OP_DIST64_MIN = 5, 6  # HBU_KIND_DIST64, HBU_OP_DIST64_MIN: LaneTable's (not in DTYPES / OPS: those list the scalar kinds)
+DIST_LANES, DIST_NONE = 64, 0xFF  # HBU_DIST_LANES, HBU_DIST_NONE
 OPS = {KIND_HLL64: (OP_HLL64,), KIND_U64: (OP_U64_ADD, OP_U64_MIN), KIND_F32: (OP_F32_ADD,), KIND_F64: (OP_F64_ADD,), KIND_KAHAN: (OP_KAHAN_ADD,)}
 
 
@@ -65,10 +69,10 @@ class _Table:
 
     def items(self):
         """DhtTable::iter(): (keys, values) of the whole table, keys[i] with values[i], in no particular order.  values: the kind's dtype,
-        uint8[n, 64] for a counter table."""
+        uint8[n, 64] for a counter table or a lane table."""
         n = len(self)
         keys = np.zeros(n, dtype=_lib.U128)
-        values = np.zeros((n, 64), dtype=np.uint8) if self.kind == KIND_HLL64 else np.zeros(n, dtype=self.dtype)
+        values = np.zeros((n, 64), dtype=np.uint8) if self.kind in (KIND_HLL64, KIND_DIST64) else np.zeros(n, dtype=self.dtype)
         written = ctypes.c_uint64(0)
         self._check(self.lib.hbu_export(self.h, _lib._ptr(keys), _lib._ptr(values), n, ctypes.byref(written)))
         assert written.value == n
@@ -151,6 +155,53 @@ class ValueTable(_Table):
         return actions
 
 
+class LaneTable(_Table):
+    """A table of 64-lane distance rows (HBU_KIND_DIST64): values are uint8[n, 64], lane l = the distance from source l of a batch, DIST_NONE
+    (0xFF) = none.  batch_upsert is the byte-wise minimum (OP_DIST64_MIN)."""
+    kind = KIND_DIST64
+
+    def __init__(self, device=-1, capacity_hint=0):
+        self.lib = _lib.load()
+        h = ctypes.c_void_p()
+        rc = self.lib.hbu_create_kind(device, capacity_hint, KIND_DIST64, ctypes.byref(h))
+        if rc != _lib.HB_OK:
+            raise _lib.HyperballError(rc, (self.lib.hbu_last_error(None) or b"").decode())
+        self.h = h
+
+    @staticmethod
+    def _args(keys, rows):
+        keys = np.ascontiguousarray(keys, dtype=_lib.U128)
+        rows = np.ascontiguousarray(rows, dtype=np.uint8).reshape(len(keys), DIST_LANES)
+        return keys, rows
+
+    def batch_set(self, keys, rows):
+        keys, rows = self._args(keys, rows)
+        self._check(self.lib.hbu_batch_set_values(self.h, _lib._ptr(keys), _lib._ptr(rows), len(keys)))
+
+    def batch_get(self, keys):
+        """(rows, found): an absent key reads as 64 x DIST_NONE"""
+        keys = np.ascontiguousarray(keys, dtype=_lib.U128)
+        out = np.zeros((len(keys), DIST_LANES), dtype=np.uint8)
+        found = np.zeros(len(keys), dtype=np.uint8)
+        self._check(self.lib.hbu_batch_get_values(self.h, _lib._ptr(keys), len(keys), _lib._ptr(out), _lib._ptr(found)))
+        return out, found.astype(bool)
+
+    def batch_upsert(self, keys, rows, op=OP_DIST64_MIN):
+        """The pairs in order under the byte-wise minimum; returns the action of every pair."""
+        keys, rows = self._args(keys, rows)
+        actions = np.zeros(len(keys), dtype=np.uint8)
+        self._check(self.lib.hbu_batch_upsert_values(self.h, op, _lib._ptr(keys), _lib._ptr(rows), len(keys), _lib._ptr(actions)))
+        return actions
+
+    def round_lane_distances(self, next, graph, changed, new_changed=None):
+        """round_lane_distances(self, next, ...)"""
+        return round_lane_distances(self, next, graph, changed, new_changed)
+
+    def fold_harmonic_lanes(self, centralities, norm, n_lanes, skip_zero=False):
+        """fold_harmonic_lanes(self, centralities, ...)"""
+        return fold_harmonic_lanes(self, centralities, norm, n_lanes, skip_zero)
+
+
 def wave_group_length():
     """Pairs of one key in a batch up to this many are folded by one thread of the upsert kernel, more by a whole wave."""
     return int(_lib.load().hbu_wave_group_length())
@@ -209,6 +260,16 @@ def fold_harmonic(distances, centralities, norm, skip_zero=False):
     folded, inserted = ctypes.c_uint64(0), ctypes.c_uint64(0)
     centralities._check(centralities.lib.hbu_fold_harmonic(distances.h, centralities.h, float(norm), FOLD_SKIP_ZERO if skip_zero else 0, ctypes.byref(folded),
                                                            ctypes.byref(inserted)))
+    return folded.value, inserted.value
+
+
+def fold_harmonic_lanes(lanes, centralities, norm, n_lanes, skip_zero=False):
+    """fold_harmonic for a finished batch held as lane rows (LaneTable): per node the lanes 0 .. n_lanes - 1 that hold a distance are folded
+    in ascending order, which equals n_lanes calls of fold_harmonic, one per source in source order, bit for bit.  A node with no lane to
+    fold is not inserted.  Returns (lanes folded, nodes inserted)."""
+    folded, inserted = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    centralities._check(centralities.lib.hbu_fold_harmonic_lanes(lanes.h, centralities.h, float(norm), int(n_lanes), FOLD_SKIP_ZERO if skip_zero else 0,
+                                                                 ctypes.byref(folded), ctypes.byref(inserted)))
     return folded.value, inserted.value
 
 
@@ -387,6 +448,16 @@ def round_distances(prev, next, graph, changed, new_changed=None):
     return s.value, c.value
 
 
+def round_lane_distances(prev, next, graph, changed, new_changed=None):
+    """RelaxEdges for 64 sources in one pass over the graph's edges, between two LaneTables: an edge whose source `changed` contains and
+    that has a row in `prev` gives its destination that row + 1 on every lane with a distance (254 + 1: none), upserted into `next` with the
+    byte-wise minimum in edge order; every Merged or Inserted destination is inserted into new_changed.  Returns (selected, merged,
+    inserted)."""
+    s, m, i = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    next._check(next.lib.hbu_round_lane_distances(prev.h, next.h, graph.h, _h(changed), _h(new_changed), ctypes.byref(s), ctypes.byref(m), ctypes.byref(i)))
+    return s.value, m.value, i.value
+
+
 def round_centralities(prev_counters, next_counters, prev_centrality, next_centrality, graph, changed, round):
     """map_centralities (mapper.rs:298-333): the graph's nodes that `changed` contains go through update_centralities.  Returns (selected,
     written)."""
@@ -563,21 +634,108 @@ def run_shortest_path_job(graphs, source, max_distance=None, device=-1, on_round
             c.close()
 
 
-def run_approx_harmonic_job(graphs, sampled_nodes, num_samples, max_distance, device=-1, skip_zero=False, on_source=None):
+def _ids(values):
+    ids = np.zeros(len(values), dtype=_lib.U128)
+    ids["lo"] = [int(v) & ((1 << 64) - 1) for v in values]
+    ids["hi"] = [int(v) >> 64 for v in values]
+    return ids
+
+
+def run_shortest_paths_job(graphs, sources, max_distance, device=-1, on_round=None):
+    """run_shortest_path_job's loop for 1 .. 64 sources at once, lane l of every row = the distance from sources[l] (max_distance <= 254: a
+    lane is a u8 and 0xFF means none).  The first table holds one row per DISTINCT source with 0 in every lane that names it (a source
+    listed twice has two lanes); every worker's changed set gets ALL the batch's sources added each round; the loop ends when a round
+    changed nothing or `max_distance` rounds ran.  The table does not depend on which edges the changed sets select (a candidate is never
+    below the BFS distance, and the union over the lanes misses no edge a lane needs), so lane l equals run_shortest_path_job(sources[l]).
+    Returns the LaneTable; the caller closes it."""
+    graphs, sources = list(graphs), [int(s) for s in sources]
+    if not 1 <= len(sources) <= DIST_LANES:
+        raise ValueError("1 .. 64 sources per walk")
+    if not 0 <= int(max_distance) <= DIST_NONE - 1:
+        raise ValueError("max_distance <= 254 in a lane table (255 stays with run_shortest_path_job, the per-source route)")
+    total_nodes = max(sum(g.n_nodes for g in graphs), 1)
+    first = {}
+    for lane, s in enumerate(sources):
+        first.setdefault(s, np.full(DIST_LANES, DIST_NONE, dtype=np.uint8))[lane] = 0
+    src = _ids(list(first))
+    prev = LaneTable(device)
+    changed = [_UpdatedNodes(total_nodes, device) for _ in graphs]
+    saved, nxt = [], None  # nxt: the clone of the round under way, closed if the round does not end
+    try:
+        prev.batch_set(src, np.stack(list(first.values())))
+        rounds, had_changes = 0, True
+        while had_changes and rounds < int(max_distance):  # ShortestPathFinish::is_finished
+            nxt = prev.clone()
+            now, counts, saved = False, [], []
+            for w, g in enumerate(graphs):  # RelaxEdges
+                changed[w].add(src)
+                new = _UpdatedNodes(total_nodes, device)
+                saved.append(new)
+                selected, merged, inserted = round_lane_distances(prev, nxt, g, changed[w].f, new.f)
+                new.settle()
+                now |= merged + inserted > 0
+                counts.append((selected, merged, inserted))
+            for w in range(len(graphs)):  # UpdateChangedNodes
+                acc = _UpdatedNodes(total_nodes, device)
+                for other in saved:
+                    merged_set = acc.union(other)
+                    acc.close()
+                    acc = merged_set
+                changed[w].close()
+                changed[w] = acc
+            rounds += 1
+            if on_round:
+                on_round(dict(round=rounds - 1, prev=prev, next=nxt, filters=[c.f for c in changed], saved=[s.f for s in saved], counts=counts, had_changes=now))
+            for s_ in saved:
+                s_.close()
+            saved = []
+            prev.close()
+            prev, had_changes, nxt = nxt, now, None
+        return prev
+    except BaseException:
+        prev.close()
+        if nxt is not None:
+            nxt.close()
+        raise
+    finally:
+        for c in changed + saved:
+            c.close()
+
+
+def run_approx_harmonic_job(graphs, sampled_nodes, num_samples, max_distance, device=-1, skip_zero=False, on_source=None, sources_per_walk=1):
     """The approximated harmonic centrality coordinator's loop (approximated_harmonic_centrality/coordinator.rs:107-148) over one resident
     shard and the workers `graphs`: norm = 1.0 / (num_samples - 1) - from num_samples, not from len(sampled_nodes), which the per-worker
     div_ceil can make larger -, then for every source of `sampled_nodes` IN THE ORDER GIVEN (it is a node's summation order and therefore its
     bits) the shortest-path job with `max_distance`, its distances folded into one KahanSum table (fold_harmonic), its tables dropped.
     Sampling the sources and sizing the sample (node_sketch, num_samples) stay with the caller.  A source's own distance is 0 and folds as
     inf, as in the reference, unless skip_zero.  Returns {node id as int: f64::from(sum)}.  on_source(state): called after every source
-    with the live centrality table and the fold's counts (tests)."""
+    with the live centrality table and the fold's counts (tests).
+    sources_per_walk = 2 .. 64: the sources are taken in the order given in consecutive batches of that many, each batch is one
+    run_shortest_paths_job (one walk over the edges per round for all of its sources) and one fold_harmonic_lanes; the result is the same
+    dictionary bit for bit.  on_source is then called once per batch: index = the batch's first index, sources = its list, lanes = the
+    batch's LaneTable (closed after the call).  max_distance above 254 does not fit a lane."""
     graphs = list(graphs)
+    sources_per_walk = int(sources_per_walk)
+    if not 1 <= sources_per_walk <= DIST_LANES:
+        raise ValueError("sources_per_walk: 1 .. 64")
+    if sources_per_walk > 1 and int(max_distance) > DIST_NONE - 1:
+        raise ValueError("max_distance above 254 does not fit a lane: use the per-source route (sources_per_walk=1)")
     if int(num_samples) < 1:
         raise ValueError("num_samples - 1 underflows (the reference panics)")
     with np.errstate(all="ignore"):
         norm = float(np.float64(1.0) / np.float64(int(num_samples) - 1))  # num_samples == 1: 1.0 / 0 = inf
     with ValueTable(KIND_KAHAN, device) as centralities:
-        for i, source in enumerate(sampled_nodes):
+        batched = [int(s) for s in sampled_nodes] if sources_per_walk > 1 else []
+        for i in range(0, len(batched), sources_per_walk):  # several sources per walk: one lane table per batch
+            batch = batched[i:i + sources_per_walk]
+            lanes = run_shortest_paths_job(graphs, batch, int(max_distance), device)
+            try:
+                folded, inserted = fold_harmonic_lanes(lanes, centralities, norm, len(batch), skip_zero)
+                if on_source:
+                    on_source(dict(index=i, sources=batch, lanes=lanes, centralities=centralities, folded=folded, inserted=inserted))
+            finally:
+                lanes.close()  # drop_tables
+        for i, source in enumerate(sampled_nodes if sources_per_walk == 1 else ()):
             distances = run_shortest_path_job(graphs, source, int(max_distance), device)
             try:
                 folded, inserted = fold_harmonic(distances, centralities, norm, skip_zero)

@@ -3,7 +3,8 @@
 // steps update_counters / update_distances (include/hb_ampc.h cites the reference operations this serves; the scalar kernels live in
 // hb_ampc_values.hip.h, those of the edge steps in hb_ampc_edges.hip.h), and a worker's resident graph and changed-node filter with the
 // mapper steps that work between them and the tables (kernels in hb_ampc_round.hip.h), and what the approximated-harmonic job adds: the
-// fold of a distance table into the centrality table, the worker's node sketch (kernels in hb_ampc_fold.hip.h) and the export of a table.
+// fold of a distance table into the centrality table, the worker's node sketch (kernels in hb_ampc_fold.hip.h) and the export of a table,
+// and the 64-lane distance rows that walk a batch of sampled sources at once (kernels in hb_ampc_lanes.hip.h).
 #include "hb_guard_alloc.h" // FIRST: no-op unless built with -DHB_GUARD_ALLOC=<mode> (debug allocators: guard pages / poison / red zones)
 #include "hb_pool.h"        // then: every hipMalloc / hipFree below goes through the caching device allocator (shipped build)
 #include <hip/hip_runtime.h>
@@ -24,6 +25,7 @@
 #include "hb_ampc_edges.hip.h"
 #include "hb_ampc_round.hip.h"
 #include "hb_ampc_fold.hip.h"
+#include "hb_ampc_lanes.hip.h"
 #include "hb_internal.h"
 #include "hb_regs.hip.h"
 #include "hb_table.hip.h"
@@ -267,6 +269,7 @@ uint32_t bytes_of_kind(uint32_t kind)
     case HBU_KIND_F32: return 4;
     case HBU_KIND_F64: return 8;
     case HBU_KIND_KAHAN: return 16;
+    case HBU_KIND_DIST64: return 64;
     default: return 0;
     }
 }
@@ -279,6 +282,7 @@ uint32_t kind_of_op(uint32_t op)
     case HBU_OP_F32_ADD: return HBU_KIND_F32;
     case HBU_OP_F64_ADD: return HBU_KIND_F64;
     case HBU_OP_KAHAN_ADD: return HBU_KIND_KAHAN;
+    case HBU_OP_DIST64_MIN: return HBU_KIND_DIST64;
     default: return 0xFFFFFFFFu;
     }
 }
@@ -292,6 +296,8 @@ struct Pairs {
     bool on_device;
     // update_counters: `values` is NULL and the counter of pair i is gathered from another table while the pair is folded
     const hbe::CounterSource *gather = nullptr;
+    // round_lane_distances: `values` is NULL and the row of pair i is gathered from another lane table, with the `+ 1`, likewise
+    const hbl::LaneSource *lanes = nullptr;
 };
 // update_distances: what comes back is one (key, action) per key GROUP of the batch instead of one action per pair (host memory,
 // room for `count` entries each; the number of groups is *distinct)
@@ -311,7 +317,7 @@ int apply(hbu_table *t, uint32_t op, Pairs in, uint64_t count, uint8_t *actions,
           const DeviceSink *sink = nullptr)
 {
     const bool upsert = op != kOpSet;
-    if (!t || (count && (!in.keys || (!in.values && !in.gather))) || (upsert && count && !actions && !per_group && !sink))
+    if (!t || (count && (!in.keys || (!in.values && !in.gather && !in.lanes))) || (upsert && count && !actions && !per_group && !sink))
         return t ? fail(t, HB_ERR_INVALID, "NULL argument") : HB_ERR_INVALID;
     if (t->broken) return fail(t, HB_ERR_INVALID, kBrokenMsg);
     if (upsert && kind_of_op(op) != t->kind) return fail(t, HB_ERR_INVALID, "the upsert operator does not belong to the table's kind");
@@ -409,8 +415,14 @@ int apply(hbu_table *t, uint32_t op, Pairs in, uint64_t count, uint8_t *actions,
         b = tmp_bytes;
         if ((e = rocprim::select(d_tmp, b, iota, flags, d_heads, d_groups, (size_t)count, t->stream)) != hipSuccess) return e;
         const unsigned blocks = (unsigned)std::min<uint64_t>((count + 63) / 64, 1u << 16);
-        if (t->kind != HBU_KIND_HLL64)
+        if (t->vbytes != 64)
             launch_values();
+        else if (t->kind == HBU_KIND_DIST64 && in.lanes)
+            hipLaunchKernelGGL(hbl::upsert_lanes_kernel<true>, dim3(blocks), dim3(256), 0, t->stream, (uint4 *)t->d_table, (const uint32_t *)d_slot_s, (const uint32_t *)d_heads,
+                               (const uint32_t *)d_groups, n32, first_new, (const uint32_t *)d_perm, (const uint4 *)nullptr, *in.lanes, d_act);
+        else if (t->kind == HBU_KIND_DIST64 && upsert)
+            hipLaunchKernelGGL(hbl::upsert_lanes_kernel<false>, dim3(blocks), dim3(256), 0, t->stream, (uint4 *)t->d_table, (const uint32_t *)d_slot_s, (const uint32_t *)d_heads,
+                               (const uint32_t *)d_groups, n32, first_new, (const uint32_t *)d_perm, (const uint4 *)vals_d, hbl::LaneSource{nullptr, nullptr}, d_act);
         else if (in.gather)
             hipLaunchKernelGGL(hbe::upsert_edges_kernel, dim3(blocks), dim3(256), 0, t->stream, (uint4 *)t->d_table, (const uint32_t *)d_slot_s, (const uint32_t *)d_heads,
                                (const uint32_t *)d_groups, n32, first_new, (const uint32_t *)d_perm, *in.gather, d_act);
@@ -476,7 +488,10 @@ int get(hbu_table *t, const hb_u128 *keys, uint64_t count, void *values_out, uin
                        (uint32_t)t->committed, d_slots, d_found);
 #define HBU_GET(RAW) \
     hipLaunchKernelGGL(hbv::get_values_kernel<RAW>, dim3(grid_for(count)), dim3(256), 0, t->stream, (const RAW *)t->d_table, (const uint32_t *)d_slots, (uint32_t)count, (RAW *)d_out)
-    if (t->vbytes == 64)
+    if (t->kind == HBU_KIND_DIST64)
+        hipLaunchKernelGGL(hbl::get_lanes_kernel, dim3((unsigned)((count * 4 + 255) / 256)), dim3(256), 0, t->stream, (const uint4 *)t->d_table, (const uint32_t *)d_slots,
+                           (uint32_t)count, (uint4 *)d_out);
+    else if (t->vbytes == 64)
         hipLaunchKernelGGL(get_kernel, dim3((unsigned)((count * 4 + 255) / 256)), dim3(256), 0, t->stream, (const uint4 *)t->d_table, (const uint32_t *)d_slots,
                            (uint32_t)count, (uint4 *)d_out);
     else if (t->vbytes == 4) HBU_GET(uint32_t);
@@ -712,14 +727,17 @@ int hbu_export(hbu_table *t, hb_u128 *keys_out, void *values_out, uint64_t capac
     });
 }
 
-int hbu_fold_harmonic(hbu_table *distances, hbu_table *centralities, double norm, uint32_t flags, uint64_t *folded, uint64_t *inserted)
+// shared body of hbu_fold_harmonic (n_lanes == 0: `distances` is HBU_KIND_U64) and hbu_fold_harmonic_lanes (HBU_KIND_DIST64, 1 .. 64 lanes)
+static int fold_step(hbu_table *distances, hbu_table *centralities, double norm, uint32_t n_lanes, uint32_t flags, uint64_t *folded, uint64_t *inserted)
 {
     hbu_table *t = centralities; // the table that changes: its stream runs the fold, its error text reports it
-    return guarded(t, [&]() -> int {
+    const bool lanes = n_lanes != 0;
+    {
         for (uint64_t *p : {folded, inserted})
             if (p) *p = 0;
         if (!distances || !t) return t ? fail(t, HB_ERR_INVALID, "NULL argument") : HB_ERR_INVALID;
-        if (distances->kind != HBU_KIND_U64 || t->kind != HBU_KIND_KAHAN) return fail(t, HB_ERR_INVALID, "fold_harmonic needs a u64 table and a KahanSum table");
+        if (distances->kind != (lanes ? HBU_KIND_DIST64 : HBU_KIND_U64) || t->kind != HBU_KIND_KAHAN)
+            return fail(t, HB_ERR_INVALID, lanes ? "fold_harmonic_lanes needs a 64-lane distance table and a KahanSum table" : "fold_harmonic needs a u64 table and a KahanSum table");
         if (distances->device != t->device) return fail(t, HB_ERR_INVALID, "the two tables are not on one device");
         if (distances->broken || t->broken) return fail(t, HB_ERR_INVALID, kBrokenMsg);
         if (flags & ~HBU_FOLD_SKIP_ZERO) return fail(t, HB_ERR_INVALID, "unknown flag bits");
@@ -741,9 +759,14 @@ int hbu_fold_harmonic(hbu_table *distances, hbu_table *centralities, double norm
         auto run = [&]() -> hipError_t {
             hipError_t e = hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), t->stream);
             if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(hbf::fold_distances_kernel, dim3(grid_for(distances->slots)), dim3(256), 0, t->stream, (const u128 *)distances->d_keys,
-                               (const uint32_t *)distances->d_pids, distances->slots, (uint32_t)count, (const uint64_t *)distances->d_table, table_of(t),
-                               (uint32_t)t->committed, (hbv::Kahan *)t->d_table, norm, flags, d_counts);
+            if (lanes)
+                hipLaunchKernelGGL(hbl::fold_lanes_kernel, dim3(grid_for(distances->slots)), dim3(256), 0, t->stream, (const u128 *)distances->d_keys,
+                                   (const uint32_t *)distances->d_pids, distances->slots, (uint32_t)count, (const uint4 *)distances->d_table, n_lanes, table_of(t),
+                                   (uint32_t)t->committed, (hbv::Kahan *)t->d_table, norm, flags, d_counts);
+            else
+                hipLaunchKernelGGL(hbf::fold_distances_kernel, dim3(grid_for(distances->slots)), dim3(256), 0, t->stream, (const u128 *)distances->d_keys,
+                                   (const uint32_t *)distances->d_pids, distances->slots, (uint32_t)count, (const uint64_t *)distances->d_table, table_of(t),
+                                   (uint32_t)t->committed, (hbv::Kahan *)t->d_table, norm, flags, d_counts);
             if ((e = hipGetLastError()) != hipSuccess) return e;
             if ((e = hipMemcpyAsync(t->h_word, t->d_next, sizeof(unsigned long long), hipMemcpyDeviceToHost, t->stream)) != hipSuccess) return e;
             if ((e = hipMemcpyAsync(h_counts, d_counts, sizeof(h_counts), hipMemcpyDeviceToHost, t->stream)) != hipSuccess) return e;
@@ -760,6 +783,23 @@ int hbu_fold_harmonic(hbu_table *distances, hbu_table *centralities, double norm
         if (folded) *folded = h_counts[0];
         if (inserted) *inserted = h_counts[1];
         return HB_OK;
+    }
+}
+
+int hbu_fold_harmonic(hbu_table *distances, hbu_table *centralities, double norm, uint32_t flags, uint64_t *folded, uint64_t *inserted)
+{
+    return guarded(centralities, [&]() -> int { return fold_step(distances, centralities, norm, 0, flags, folded, inserted); });
+}
+
+int hbu_fold_harmonic_lanes(hbu_table *lanes, hbu_table *centralities, double norm, uint32_t n_lanes, uint32_t flags, uint64_t *folded, uint64_t *inserted)
+{
+    return guarded(centralities, [&]() -> int {
+        if (n_lanes == 0 || n_lanes > HBU_DIST_LANES) {
+            for (uint64_t *p : {folded, inserted})
+                if (p) *p = 0;
+            return centralities ? fail(centralities, HB_ERR_INVALID, "n_lanes must be 1 .. 64") : HB_ERR_INVALID;
+        }
+        return fold_step(lanes, centralities, norm, n_lanes, flags, folded, inserted);
     });
 }
 
@@ -1036,10 +1076,13 @@ int round_refusal(std::initializer_list<hbu_table *> read_only, hbu_table *t, co
     return HB_OK;
 }
 
-// the two edge steps share everything but the kernels: DISTANCES = RelaxEdges, else map_cardinalities
-template <bool DISTANCES>
+// the edge steps share everything but the kernels: kRoundCounters = map_cardinalities, kRoundDistances = RelaxEdges, kRoundLanes = RelaxEdges
+// for the 64 sources of a lane row (staged per edge: the source's slot, as for the counters, and no register)
+enum RoundMode { kRoundCounters = 0, kRoundDistances = 1, kRoundLanes = 2 };
+template <RoundMode MODE>
 int round_edges(hbu_table *prev, hbu_table *t, const hbu_graph *g, hbu_filter *changed, hbu_filter *new_changed, uint64_t counts_out[4])
 {
+    constexpr bool DISTANCES = MODE == kRoundDistances, LANES = MODE == kRoundLanes;
     const uint64_t chunk = std::min<uint64_t>(g->chunk, std::max<uint64_t>(g->n_edges, 1));
     size_t tmp_bytes = 0;
     {
@@ -1066,8 +1109,8 @@ int round_edges(hbu_table *prev, hbu_table *t, const hbu_graph *g, hbu_filter *c
         d_flag = c.take<uint8_t>(chunk);
         d_slot = c.take<uint32_t>(DISTANCES ? 0 : chunk);
         d_slot_c = c.take<uint32_t>(DISTANCES ? 0 : chunk);
-        d_jp = c.take<uint16_t>(DISTANCES ? 0 : chunk);
-        d_jp_c = c.take<uint16_t>(DISTANCES ? 0 : chunk);
+        d_jp = c.take<uint16_t>(DISTANCES || LANES ? 0 : chunk);
+        d_jp_c = c.take<uint16_t>(DISTANCES || LANES ? 0 : chunk);
         d_cand = c.take<uint64_t>(DISTANCES ? chunk : 0);
         d_cand_c = c.take<uint64_t>(DISTANCES ? chunk : 0);
         d_keys = c.take<hb_u128>(chunk);
@@ -1096,6 +1139,10 @@ int round_edges(hbu_table *prev, hbu_table *t, const hbu_graph *g, hbu_filter *c
                                d_cand, d_counts + 3);
             HBU_HIP(hipGetLastError());
             HBU_HIP(rocprim::select(d_tmp, tb, to, (const uint8_t *)d_flag, d_keys, d_n, (size_t)n, t->stream));
+        } else if (LANES) {
+            hipLaunchKernelGGL(hbl::select_lane_edges_kernel, dim3(grid_for(n)), dim3(256), 0, t->stream, from, (uint32_t)n, in, side_of<uint4>(prev), d_flag, d_slot);
+            HBU_HIP(hipGetLastError());
+            HBU_HIP(rocprim::select(d_tmp, tb, to, (const uint8_t *)d_flag, d_keys, d_n, (size_t)n, t->stream));
         } else {
             hipLaunchKernelGGL(hbr::select_counter_edges_kernel, dim3(grid_for(n)), dim3(256), 0, t->stream, from, (uint32_t)n, in, side_of<uint4>(prev), d_flag, d_slot,
                                d_jp);
@@ -1115,20 +1162,27 @@ int round_edges(hbu_table *prev, hbu_table *t, const hbu_graph *g, hbu_filter *c
         } else {
             tb = tmp_bytes;
             HBU_HIP(rocprim::select(d_tmp, tb, (const uint32_t *)d_slot, (const uint8_t *)d_flag, d_slot_c, d_n + 1, (size_t)n, t->stream));
-            tb = tmp_bytes;
-            HBU_HIP(rocprim::select(d_tmp, tb, (const uint16_t *)d_jp, (const uint8_t *)d_flag, d_jp_c, d_n + 2, (size_t)n, t->stream));
+            if (!LANES) {
+                tb = tmp_bytes;
+                HBU_HIP(rocprim::select(d_tmp, tb, (const uint16_t *)d_jp, (const uint8_t *)d_flag, d_jp_c, d_n + 2, (size_t)n, t->stream));
+            }
         }
         if (new_changed && (rc = set_reserve(new_changed, pairs))) return fail(t, rc, new_changed->t->err);
         const hbr::Filter out = filter_view(new_changed);
         DeviceSink sink;
         sink.per_group = DISTANCES;
         sink.note = [&](const hb_u128 *keys, const uint8_t *actions, const uint32_t *d_count) -> hipError_t {
-            const uint32_t mask = DISTANCES ? ((1u << HBU_MERGED) | (1u << HBU_INSERTED)) : (1u << HBU_MERGED);
+            const uint32_t mask = DISTANCES || LANES ? ((1u << HBU_MERGED) | (1u << HBU_INSERTED)) : (1u << HBU_MERGED);
             hipLaunchKernelGGL(hbr::note_actions_kernel, dim3(grid_capped(pairs)), dim3(256), 0, t->stream, keys, actions, d_count, (uint32_t)pairs, mask, out, d_counts);
             return hipGetLastError();
         };
         if (DISTANCES) {
             rc = apply(t, HBU_OP_U64_MIN, Pairs{d_keys, d_cand_c, true}, pairs, nullptr, nullptr, nullptr, &sink);
+        } else if (LANES) {
+            const hbl::LaneSource src{(const uint4 *)prev->d_table, d_slot_c};
+            Pairs p{d_keys, nullptr, true};
+            p.lanes = &src;
+            rc = apply(t, HBU_OP_DIST64_MIN, p, pairs, nullptr, nullptr, nullptr, &sink);
         } else {
             const hbe::CounterSource src{(const uint4 *)prev->d_table, d_slot_c, d_jp_c};
             Pairs p{d_keys, nullptr, true};
@@ -1508,7 +1562,7 @@ int hbu_round_counters(hbu_table *prev_counters, hbu_table *next_counters, const
         if (!g->n_edges) return HB_OK;
         HBU_HIP(hipSetDevice(t->device));
         uint64_t c[4] = {0, 0, 0, 0};
-        rc = round_edges<false>(prev_counters, t, g, changed, new_changed, c);
+        rc = round_edges<kRoundCounters>(prev_counters, t, g, changed, new_changed, c);
         if (selected) *selected = c[0];
         if (merged) *merged = c[1];
         if (inserted) *inserted = c[2];
@@ -1529,9 +1583,30 @@ int hbu_round_distances(hbu_table *prev_distances, hbu_table *next_distances, co
         if (!g->n_edges) return HB_OK;
         HBU_HIP(hipSetDevice(t->device));
         uint64_t c[4] = {0, 0, 0, 0};
-        rc = round_edges<true>(prev_distances, t, g, changed, new_changed, c);
+        rc = round_edges<kRoundDistances>(prev_distances, t, g, changed, new_changed, c);
         if (selected) *selected = c[0];
         if (changed_nodes) *changed_nodes = c[1] + c[2];
+        return rc;
+    });
+}
+
+int hbu_round_lane_distances(hbu_table *prev, hbu_table *next, const hbu_graph *g, hbu_filter *changed, hbu_filter *new_changed, uint64_t *selected, uint64_t *merged,
+                             uint64_t *inserted)
+{
+    hbu_table *t = next;
+    return guarded(t, [&]() -> int {
+        for (uint64_t *p : {selected, merged, inserted})
+            if (p) *p = 0;
+        int rc = round_refusal({prev}, t, g, changed, new_changed, true);
+        if (rc) return rc;
+        if (prev->kind != HBU_KIND_DIST64 || t->kind != HBU_KIND_DIST64) return fail(t, HB_ERR_INVALID, "round_lane_distances needs two 64-lane distance tables");
+        if (!g->n_edges) return HB_OK;
+        HBU_HIP(hipSetDevice(t->device));
+        uint64_t c[4] = {0, 0, 0, 0};
+        rc = round_edges<kRoundLanes>(prev, t, g, changed, new_changed, c);
+        if (selected) *selected = c[0];
+        if (merged) *merged = c[1];
+        if (inserted) *inserted = c[2];
         return rc;
     });
 }

@@ -24,10 +24,15 @@ it, in the same process (batch_get_values of every key of the distance table, th
 page-locked buffers, only the time inside the calls) into a centrality table of that many keys from distance tables of 100 %, 10 % and 0.1 %
 of them, every key present and half of them absent; hbu_export of a table of every kind; and whole sources of run_approx_harmonic_job's loop
 on the --rounds R-MAT worker graph with max_distance = 5, with the fold's share of a source.  --only-approx skips the counter-table section.
+--lanes adds, on the same worker graph with max_distance = 5, 64 sampled sources through the per-source route (run_shortest_path_job +
+fold_harmonic each) and through one 64-lane walk (run_shortest_paths_job + fold_harmonic_lanes), alternating in this process, a warm-up and
+--reps timed repetitions with the folds included and the two results compared bit for bit; and the round call alone,
+hbu_round_lane_distances against hbu_round_distances, on the state each job holds after each of its rounds.  --only-lanes skips the
+counter-table section.
 --out FILE also writes the JSON line there.
 usage: tools/ampc_bench.py [keys, default 10000000] [pairs per batch, default 1000000] [--values] [--kind K] [--op OP] [--centralities]
                            [--edges] [--rounds] [--round-edges N, default 100000000] [--round-scale S] [--only-rounds] [--approx] [--only-approx]
-                           [--sources N, default 5] [--reps N, default 5] [--out FILE]"""
+                           [--sources N, default 5] [--lanes] [--only-lanes] [--reps N, default 5] [--out FILE]"""
 import argparse
 import json
 import os
@@ -493,6 +498,92 @@ def approx_mode(rng, keys, K, reps, total_edges, scale, n_sources):
     return res
 
 
+def lanes_mode(rng, reps, total_edges, scale, n_sources=64):
+    """64 sampled sources of the approximated-harmonic loop (max_distance = 5, the fold included) through the per-source route
+    (run_shortest_path_job + fold_harmonic per source) and through one 64-lane walk (run_shortest_paths_job + fold_harmonic_lanes), in this
+    process, alternating, one warm-up and `reps` timed repetitions each; and the round call alone, hbu_round_lane_distances against
+    hbu_round_distances, on the tables and filters the two jobs hold after each of their rounds."""
+    norm, max_distance = 1.0 / 2657.0, 5
+    t0 = time.perf_counter()
+    nodes, from_ids, to_ids = rmat_worker(scale, total_edges)
+    print("graph: %d nodes, %d edges, %.1f s" % (len(nodes), len(from_ids), time.perf_counter() - t0), file=sys.stderr, flush=True)
+    picked = np.unique(from_ids[rng.integers(0, len(from_ids), 4 * n_sources + 4)])  # sources with out-links, as random_page_nodes_with_outgoing picks
+    rng.shuffle(picked)
+    sources = [(int(k["hi"]) << 64) | int(k["lo"]) for k in picked[:n_sources]]
+    res = {"nodes": len(nodes), "edges": len(from_ids), "max_distance": max_distance, "sources": len(sources), "repetitions": reps}
+
+    def result_of(cent):
+        keys, values = cent.items()
+        order = np.lexsort((keys["lo"], keys["hi"]))
+        return keys[order], values[order]
+
+    with ampc.WorkerGraph(nodes, from_ids, to_ids) as graph:
+        def per_source(keep):
+            with ampc.ValueTable(ampc.KIND_KAHAN) as cent:
+                t0 = time.perf_counter()
+                for s_ in sources:
+                    dist = ampc.run_shortest_path_job([graph], s_, max_distance)
+                    ampc.fold_harmonic(dist, cent, norm)
+                    dist.close()
+                t = time.perf_counter() - t0
+                return t, (result_of(cent) if keep else None)
+
+        def one_walk(keep):
+            with ampc.ValueTable(ampc.KIND_KAHAN) as cent:
+                t0 = time.perf_counter()
+                lanes = ampc.run_shortest_paths_job([graph], sources, max_distance)
+                t1 = time.perf_counter()
+                folded, inserted = ampc.fold_harmonic_lanes(lanes, cent, norm, len(sources))
+                t2 = time.perf_counter()
+                lanes.close()
+                return t2 - t0, t2 - t1, (folded, inserted), (result_of(cent) if keep else None)
+
+        t_old, t_new, t_fold = [], [], []
+        for r in range(reps + 1):  # the first repetition warms both routes up and compares their results
+            to, old = per_source(r == 0)
+            tn, tf, counts, new = one_walk(r == 0)
+            if r == 0:
+                same = (np.array_equal(old[0], new[0]) and np.array_equal(old[1]["sum"].view(np.uint64), new[1]["sum"].view(np.uint64))
+                        and np.array_equal(old[1]["err"].view(np.uint64), new[1]["err"].view(np.uint64)))
+                res.update(results_equal_bit_for_bit=bool(same), centrality_keys=len(old[0]), lanes_folded=counts[0], keys_inserted=counts[1])
+                assert same, "the two routes differ"
+            else:
+                t_old.append(to)
+                t_new.append(tn)
+                t_fold.append(tf)
+            print("repetition", r, round(to, 4), round(tn, 4), file=sys.stderr, flush=True)
+        old, new = spread(t_old), spread(t_new)
+        gap = max(old["max_s"] - old["min_s"], new["max_s"] - new["min_s"])
+        res["job_of_64_sources"] = {"per_source_route": old, "one_64_lane_walk": new, "fold_harmonic_lanes": spread(t_fold),
+                                    "median_gain_s": round(old["median_s"] - new["median_s"], 6), "larger_spread_s": round(gap, 6),
+                                    "beats_by_more_than_the_spread": bool(old["median_s"] - new["median_s"] > gap),
+                                    "ratio_of_medians": round(old["median_s"] / new["median_s"], 2)}
+        print("job", res["job_of_64_sources"], file=sys.stderr, flush=True)
+
+        # ---- the round call alone: the call the next round makes, repeated on a fresh clone of its `next`
+        def time_round(call, state):
+            times, counts = [], None
+            for r in range(reps + 1):
+                with state["next"].clone() as scratch:
+                    t0 = time.perf_counter()
+                    counts = call(state["next"], scratch, graph, state["filters"][0], None)
+                    t = time.perf_counter() - t0
+                if r:
+                    times.append(t)
+            return dict(spread(times), selected=counts[0], filter="exact" if state["filters"][0].kind == ampc.FILTER_EXACT else "bloom")
+
+        single, batch = {}, {}
+        ampc.run_shortest_path_job([graph], sources[0], max_distance, on_round=lambda st: single.__setitem__(st["round"] + 1, time_round(ampc.round_distances, st))).close()
+        ampc.run_shortest_paths_job([graph], sources, max_distance, on_round=lambda st: batch.__setitem__(st["round"] + 1, time_round(ampc.round_lane_distances, st))).close()
+        res["round_call"] = {}
+        for rnd in sorted(set(single) & set(batch)):
+            a, b = single[rnd], batch[rnd]
+            res["round_call"]["round_%d" % rnd] = {"hbu_round_distances_one_source": a, "hbu_round_lane_distances_64_sources": b,
+                                                   "lane_call_in_single_calls": round(b["median_s"] / a["median_s"], 2)}
+        print("round_call", res["round_call"], file=sys.stderr, flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("keys", nargs="?", type=int, default=10_000_000)
@@ -508,6 +599,8 @@ def main():
     ap.add_argument("--only-rounds", action="store_true", help="skip the counter-table section (with --rounds)")
     ap.add_argument("--approx", action="store_true", help="also the approximated-harmonic job: the fold against the composed route, export, whole sources")
     ap.add_argument("--only-approx", action="store_true", help="skip the counter-table section (with --approx)")
+    ap.add_argument("--lanes", action="store_true", help="also 64 sources through the per-source route and through one 64-lane walk, and the round call alone")
+    ap.add_argument("--only-lanes", action="store_true", help="skip the counter-table section (with --lanes)")
     ap.add_argument("--sources", type=int, default=5, help="timed sources of --approx (one more warms up)")
     ap.add_argument("--reps", type=int, default=5, help="timed batches per shape and side of --edges / repetitions of --rounds (at least 5)")
     ap.add_argument("--out")
@@ -518,7 +611,7 @@ def main():
     keys["lo"] = rng.permutation(K).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)
     keys["hi"] = rng.integers(0, 1 << 63, K, dtype=np.uint64)
     out = {"keys": K, "pairs_per_batch": B, "bytes_per_pair": 80}
-    for label, pinned in (() if (args.only_rounds and args.rounds) or (args.only_approx and args.approx) else (("pageable", False), ("pinned", True))):
+    for label, pinned in (() if (args.only_rounds and args.rounds) or (args.only_approx and args.approx) or (args.only_lanes and args.lanes) else (("pageable", False), ("pinned", True))):
         kb = _lib.PinnedRecords(B, dtype=_lib.U128) if pinned else None
         vb = _lib.PinnedRecords(B * 64, dtype=np.uint8) if pinned else None
         kbuf = kb.array if pinned else np.zeros(B, dtype=_lib.U128)
@@ -583,6 +676,9 @@ def main():
     if args.approx:
         scale = args.round_scale or max(int(K).bit_length() - 1, 1)
         out["approx"] = approx_mode(rng, keys, K, max(args.reps, 5), args.round_edges, scale, max(args.sources, 1))
+    if args.lanes:
+        scale = args.round_scale or max(int(K).bit_length() - 1, 1)
+        out["lanes"] = lanes_mode(rng, max(args.reps, 5), args.round_edges, scale)
     line = json.dumps(out)
     print(line)
     if args.out:
