@@ -32,8 +32,11 @@
  * kind (hbu_export); and the step that job needs to run at a useful speed, several sampled sources per walk over the edges: a sixth table
  * kind whose 64-byte row holds one u8 distance for each of up to 64 sources (HBU_KIND_DIST64, HBU_OP_DIST64_MIN), RelaxEdges for all of
  * them in one pass (hbu_round_lane_distances) and their fold in source order (hbu_fold_harmonic_lanes).  The reference's max_distance is
- * a u8 (config/mod.rs:718), so a distance fits a lane; max_distance = 255 stays with the per-source route.
- * Still out: HyperLogLog<8/16/32/128> as table values (no job uses them), HyperLogLog<4096>::size() (its bias rows are
+ * a u8 (config/mod.rs:718), so a distance fits a lane; max_distance = 255 stays with the per-source route; and the finish of both jobs:
+ * the stored value of every key of the centrality table (f64::from(c) / (num_nodes - 1) as f64, harmonic_centrality/coordinator.rs:204-211;
+ * f64::from(*c), approximated_harmonic_centrality/coordinator.rs:152-157), store_harmonic and top_nodes (webgraph/centrality/mod.rs:33-114)
+ * as three device calls (hbu_finish_centralities, hbu_top_centralities, hbu_store_centralities): only the results cross the link.
+ * Still out: harmonic.csv (it needs node names), HyperLogLog<8/16/32/128> as table values (no job uses them), HyperLogLog<4096>::size() (its bias rows are
  * not carried here: the caller merges the registers and estimates), the sampling of sources, more than 64 lanes or 16-bit lanes, a lane
  * form of the host-fed edge step, the String, meta and
  * bloom-valued tables (a handful of values per shard), the Exact -> Sketch policy of UpdatedNodes and the serde envelopes of the filters
@@ -277,6 +280,37 @@ int hbu_round_lane_distances(hbu_table *prev, hbu_table *next, const hbu_graph *
  * *written sums the chunks' distinct nodes (the reference's batches are as separate). */
 int hbu_round_centralities(hbu_table *prev_counters, hbu_table *next_counters, hbu_table *prev_centrality, hbu_table *next_centrality, const hbu_graph *g,
                            hbu_filter *changed, uint64_t round, uint64_t *selected, uint64_t *written);
+
+/* ---- the finish of a job: what the two coordinators do with the finished centrality table (harmonic_centrality/coordinator.rs:204-233,
+ * approximated_harmonic_centrality/coordinator.rs:152-177): the stored value, store_harmonic (webgraph/centrality/mod.rs:72-114) and
+ * top_nodes (mod.rs:33-52).  `centrality` is HBU_KIND_KAHAN - the value is .sum = f64::from(KahanSum) (kahan_sum.rs:35-39), err is ignored -
+ * or HBU_KIND_F64.  EVERY key of the table is a result whatever its value: negatives, -0.0, +inf (a sampled source's own distance folds as
+ * inf) and NaNs are results like any other; hb_result_copy's "< 0 = absent" does not apply.  The result value is the IEEE quotient
+ * value / divisor; no divisor is refused: the harmonic job passes (double)(num_nodes - 1), which is 0 for a one-key job, the approximated
+ * job 1.0 (x / 1.0 is x).  The rank order is store_harmonic's (Reverse(SortableFloat(c)), NodeID): the quotient descending under
+ * f64::total_cmp (+NaN > +inf > ... > +0.0 > -0.0 > ... > -inf > -NaN), ties by NodeID ascending (128-bit, unsigned) - hb_result_ranks'
+ * definition.  The sign and payload of a NaN that the division creates are the device's (x86 and gfx950 produce different default NaNs),
+ * and the ranks follow the values the call returns.
+ * The table is only read and holds the same keys and values afterwards; everything is visible on return.  Refused with HB_ERR_INVALID and
+ * hbu_last_error set (hbu_last_error(NULL) for a NULL table): a NULL table, a table of any other kind, a broken table, an empty `output`.
+ * There is no result handle: each call derives what it needs by itself on the device (the keys by entry number, one 128-bit sort of the ids
+ * carrying the entry number, the quotients and their sort keys in that order, one stable 64-bit sort), so three calls mean three times
+ * those sorts. */
+
+/* Entry j of the ascending-NodeID order (hb_result_copy's order, so the three arrays line up): ids_out[j], vals_out[j] = the quotient,
+ * ranks_out[j] = its position in the rank order.  Any of the three may be NULL (all three: only *written is set).  *written = len (may be
+ * NULL).  capacity < len with an output that is not NULL: HB_ERR_INVALID, nothing written.  An empty table: HB_OK, *written = 0. */
+int hbu_finish_centralities(hbu_table *centrality, double divisor, hb_u128 *ids_out, double *vals_out, uint64_t *ranks_out, uint64_t capacity,
+                            uint64_t *written);
+/* top_nodes as hb_result_top defines it: the first min(k, len) entries of the rank order, gathered on the device - only they cross the link.
+ * ids_out / vals_out: room for min(k, len) entries, either may be NULL.  *written = min(k, len).  k = 0: HB_OK, *written = 0. */
+int hbu_top_centralities(hbu_table *centrality, double divisor, uint64_t k, hb_u128 *ids_out, double *vals_out, uint64_t *written);
+/* store_harmonic: the databases `harmonic` (NodeID -> f64) and `harmonic_rank` (NodeID -> u64) under `output`, byte for byte what
+ * hb_store_harmonic(output, ids, vals, ranks, len, ...) writes from the arrays of hbu_finish_centralities; the key order of the databases
+ * (ascending bincode key bytes) comes from the device as in hb_store_harmonic_results, from the ids the device already holds: values, ranks
+ * and the sorted key records come down, no id does.  Failures are the writer's own (HB_ERR_IO ...): nothing is left behind, no meta.json
+ * appears before both databases are complete, and the call can be repeated.  err (may be NULL): the message, as hbu_last_error has it. */
+int hbu_store_centralities(hbu_table *centrality, double divisor, const char *output, char *err, uint64_t err_len);
 
 #ifdef __cplusplus
 }

@@ -451,6 +451,9 @@ _SIGNATURES += [
     ("hbu_graph_node_sketch", ctypes.c_int, [_P, _P]),
     ("hbu_fold_harmonic_lanes", ctypes.c_int, [_P, _P, ctypes.c_double, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     ("hbu_round_lane_distances", ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.POINTER(_U64), ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("hbu_finish_centralities", ctypes.c_int, [_P, ctypes.c_double, _P, _P, _P, _U64, ctypes.POINTER(_U64)]),
+    ("hbu_top_centralities", ctypes.c_int, [_P, ctypes.c_double, _U64, _P, _P, ctypes.POINTER(_U64)]),
+    ("hbu_store_centralities", ctypes.c_int, [_P, ctypes.c_double, ctypes.c_char_p, ctypes.c_char_p, _U64]),
 ]
 # include/hb_store.h
 _SIGNATURES += [

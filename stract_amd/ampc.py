@@ -14,6 +14,7 @@ for each of up to 64 sources per row (HBU_KIND_DIST64); round_lane_distances, fo
 batch of sampled sources in one pass over the edges, and run_approx_harmonic_job(sources_per_walk=2..64) is the coordinator on top of them."""
 import ctypes
 import math
+import os
 
 import numpy as np
 
@@ -154,6 +155,18 @@ class ValueTable(_Table):
         self._check(self.lib.hbu_batch_upsert_values(self.h, op, _lib._ptr(keys), _lib._ptr(values), len(keys), _lib._ptr(actions)))
         return actions
 
+    def finish_centralities(self, divisor=1.0):
+        """finish_centralities(self, divisor)"""
+        return finish_centralities(self, divisor)
+
+    def top_centralities(self, k, divisor=1.0):
+        """top_centralities(self, k, divisor)"""
+        return top_centralities(self, k, divisor)
+
+    def store_centralities(self, output, divisor=1.0):
+        """store_centralities(self, output, divisor)"""
+        return store_centralities(self, output, divisor)
+
 
 class LaneTable(_Table):
     """A table of 64-lane distance rows (HBU_KIND_DIST64): values are uint8[n, 64], lane l = the distance from source l of a batch, DIST_NONE
@@ -271,6 +284,39 @@ def fold_harmonic_lanes(lanes, centralities, norm, n_lanes, skip_zero=False):
     centralities._check(centralities.lib.hbu_fold_harmonic_lanes(lanes.h, centralities.h, float(norm), int(n_lanes), FOLD_SKIP_ZERO if skip_zero else 0,
                                                                  ctypes.byref(folded), ctypes.byref(inserted)))
     return folded.value, inserted.value
+
+
+def finish_centralities(table, divisor=1.0):
+    """The finished job's results from its centrality table (KIND_KAHAN: f64::from(KahanSum) = .sum; or KIND_F64), every key a result:
+    (ids, vals, ranks) in ascending NodeID order - vals = value / divisor (harmonic_centrality/coordinator.rs:204-211 passes num_nodes - 1,
+    the approximated job 1.0), ranks = the position in store_harmonic's order (value descending under f64::total_cmp, ties by NodeID
+    ascending; webgraph/centrality/mod.rs:92-103).  Sorted on the device; the table is only read."""
+    n = len(table)
+    ids, vals, ranks = np.zeros(n, dtype=_lib.U128), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.uint64)
+    written = ctypes.c_uint64(0)
+    table._check(table.lib.hbu_finish_centralities(table.h, float(divisor), _lib._ptr(ids), _lib._ptr(vals), _lib._ptr(ranks), n, ctypes.byref(written)))
+    assert written.value == n
+    return ids, vals, ranks
+
+
+def top_centralities(table, k, divisor=1.0):
+    """top_nodes (webgraph/centrality/mod.rs:33-52): (ids, vals) of the first min(k, len) entries of the rank order of finish_centralities,
+    gathered on the device."""
+    top = min(int(k), len(table))
+    ids, vals = np.zeros(top, dtype=_lib.U128), np.zeros(top, dtype=np.float64)
+    written = ctypes.c_uint64(0)
+    table._check(table.lib.hbu_top_centralities(table.h, float(divisor), int(k), _lib._ptr(ids), _lib._ptr(vals), ctypes.byref(written)))
+    assert written.value == top
+    return ids, vals
+
+
+def store_centralities(table, output, divisor=1.0):
+    """store_harmonic (webgraph/centrality/mod.rs:72-114): the databases `harmonic` and `harmonic_rank` under `output`, the same files as
+    _lib.store_harmonic(output, *finish_centralities(table, divisor)); values, ranks and key order come off the device."""
+    err = ctypes.create_string_buffer(512)
+    rc = table.lib.hbu_store_centralities(table.h, float(divisor), os.fsencode(output), err, len(err))
+    if rc != _lib.HB_OK:
+        raise _lib.HyperballError(rc, err.value.decode(errors="replace"))
 
 
 def num_samples(num_nodes, sample_rate):
@@ -467,13 +513,14 @@ def round_centralities(prev_counters, next_counters, prev_centrality, next_centr
     return s.value, w.value
 
 
-def run_harmonic_job(graphs, device=-1, on_round=None):
+def run_harmonic_job(graphs, device=-1, on_round=None, output=None):
     """The harmonic-centrality coordinator's loop (harmonic_centrality/coordinator.rs:122-135, ampc/coordinator.rs:151-213) over one resident
     shard and the workers `graphs` (WorkerGraph each): per round clone, then SetupCounters (round 0), SetupBloom (round 0: every filter
     filled, num_bits = bloom_num_bits(sum of the workers' node counts, 0.05), worker.rs:49-71), Cardinalities, SaveBloom / UpdateBloom
     (every worker's filter becomes the union of all of them), Centralities, swap - until a round neither merged nor inserted.  Returns
     {node id as int: f64::from(centrality) / (num_keys - 1)} (coordinator.rs:204-211).  on_round(state): called at the end of every round
-    with the live tables, filters and counts (tests)."""
+    with the live tables, filters and counts (tests).  output: a directory that gets store_harmonic's two databases (coordinator.rs:213-214)
+    from the resident table, store_centralities(centrality, output, num_keys - 1), before the tables close."""
     graphs = list(graphs)
     total_nodes = sum(g.n_nodes for g in graphs)
     if not total_nodes:
@@ -517,6 +564,8 @@ def run_harmonic_job(graphs, device=-1, on_round=None):
             prev_v.close()
             prev_c, prev_v, had_changes = next_c, next_v, now
             open_tables.clear()
+        if output is not None:
+            store_centralities(prev_v, output, float(len(prev_c) - 1))
         nodes = np.unique(np.concatenate([g.nodes for g in graphs]))
         vals, found = prev_v.batch_get(nodes)
         with np.errstate(all="ignore"):
@@ -702,7 +751,7 @@ def run_shortest_paths_job(graphs, sources, max_distance, device=-1, on_round=No
             c.close()
 
 
-def run_approx_harmonic_job(graphs, sampled_nodes, num_samples, max_distance, device=-1, skip_zero=False, on_source=None, sources_per_walk=1):
+def run_approx_harmonic_job(graphs, sampled_nodes, num_samples, max_distance, device=-1, skip_zero=False, on_source=None, sources_per_walk=1, output=None):
     """The approximated harmonic centrality coordinator's loop (approximated_harmonic_centrality/coordinator.rs:107-148) over one resident
     shard and the workers `graphs`: norm = 1.0 / (num_samples - 1) - from num_samples, not from len(sampled_nodes), which the per-worker
     div_ceil can make larger -, then for every source of `sampled_nodes` IN THE ORDER GIVEN (it is a node's summation order and therefore its
@@ -713,7 +762,9 @@ def run_approx_harmonic_job(graphs, sampled_nodes, num_samples, max_distance, de
     sources_per_walk = 2 .. 64: the sources are taken in the order given in consecutive batches of that many, each batch is one
     run_shortest_paths_job (one walk over the edges per round for all of its sources) and one fold_harmonic_lanes; the result is the same
     dictionary bit for bit.  on_source is then called once per batch: index = the batch's first index, sources = its list, lanes = the
-    batch's LaneTable (closed after the call).  max_distance above 254 does not fit a lane."""
+    batch's LaneTable (closed after the call).  max_distance above 254 does not fit a lane.
+    output: a directory that gets store_harmonic's two databases (coordinator.rs:159-160) from the resident table,
+    store_centralities(centralities, output, 1.0), before the table closes."""
     graphs = list(graphs)
     sources_per_walk = int(sources_per_walk)
     if not 1 <= sources_per_walk <= DIST_LANES:
@@ -743,5 +794,7 @@ def run_approx_harmonic_job(graphs, sampled_nodes, num_samples, max_distance, de
                 distances.close()  # drop_tables
             if on_source:
                 on_source(dict(index=i, source=int(source), centralities=centralities, folded=folded, inserted=inserted))
+        if output is not None:
+            store_centralities(centralities, output, 1.0)
         keys, values = centralities.items()
         return {(int(k["hi"]) << 64) | int(k["lo"]): float(v) for k, v in zip(keys, values["sum"])}

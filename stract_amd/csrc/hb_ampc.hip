@@ -4,7 +4,8 @@
 // hb_ampc_values.hip.h, those of the edge steps in hb_ampc_edges.hip.h), and a worker's resident graph and changed-node filter with the
 // mapper steps that work between them and the tables (kernels in hb_ampc_round.hip.h), and what the approximated-harmonic job adds: the
 // fold of a distance table into the centrality table, the worker's node sketch (kernels in hb_ampc_fold.hip.h) and the export of a table,
-// and the 64-lane distance rows that walk a batch of sampled sources at once (kernels in hb_ampc_lanes.hip.h).
+// and the 64-lane distance rows that walk a batch of sampled sources at once (kernels in hb_ampc_lanes.hip.h), and the finish of both jobs:
+// a centrality table's values, ranks, top nodes and store (kernels in hb_ampc_finish.hip.h, the sorts are hb_ingest.hip's).
 #include "hb_guard_alloc.h" // FIRST: no-op unless built with -DHB_GUARD_ALLOC=<mode> (debug allocators: guard pages / poison / red zones)
 #include "hb_pool.h"        // then: every hipMalloc / hipFree below goes through the caching device allocator (shipped build)
 #include <hip/hip_runtime.h>
@@ -26,6 +27,7 @@
 #include "hb_ampc_round.hip.h"
 #include "hb_ampc_fold.hip.h"
 #include "hb_ampc_lanes.hip.h"
+#include "hb_ampc_finish.hip.h"
 #include "hb_internal.h"
 #include "hb_regs.hip.h"
 #include "hb_table.hip.h"
@@ -1665,6 +1667,189 @@ int hbu_round_centralities(hbu_table *prev_counters, hbu_table *next_counters, h
         }
         return HB_OK;
     });
+}
+
+} // extern "C"
+
+// ---- the finish of a job: values, ranks, top nodes, store ---------------------------------------------------------------------------
+namespace {
+// temporaries of one finish call (the caching allocator's: they go back to it when the call returns)
+struct Temps {
+    std::vector<void *> ptrs;
+    ~Temps()
+    {
+        for (void *p : ptrs)
+            if (p) (void)hipFree(p);
+    }
+    template <class T>
+    hipError_t alloc(T **out, uint64_t count)
+    {
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, std::max<size_t>((size_t)count * sizeof(T), 256));
+        if (e == hipSuccess) ptrs.push_back(p);
+        *out = (T *)p;
+        return e;
+    }
+    void release(void *p)
+    {
+        for (void *&q : ptrs)
+            if (q == p && p) {
+                (void)hipFree(p);
+                q = nullptr;
+            }
+    }
+};
+// the entries of a centrality table in ascending-NodeID order, on the device: ids, quotients, the rank order and (if asked for) the ranks
+struct Finished {
+    hb_u128 *d_ids = nullptr;
+    double *d_vals = nullptr;
+    uint64_t *d_order = nullptr; // d_order[i] = the entry at position i of (value descending under total_cmp, NodeID ascending)
+    uint64_t *d_rank = nullptr;
+};
+
+int finish_refusal(hbu_table *t)
+{
+    if (!t) return fail(t, HB_ERR_INVALID, "NULL table");
+    if (t->kind != HBU_KIND_KAHAN && t->kind != HBU_KIND_F64) return fail(t, HB_ERR_INVALID, "a centrality table is a KahanSum or an f64 table");
+    if (t->broken) return fail(t, HB_ERR_INVALID, kBrokenMsg);
+    return HB_OK;
+}
+int sort_error(hbu_table *t, const std::string &e)
+{
+    (void)hipGetLastError();
+    return fail(t, e.find("memory") != std::string::npos ? HB_ERR_NOMEM : HB_ERR_HIP, e);
+}
+
+// keys by entry number -> one 128-bit sort carrying the entry number -> quotient and sort key of every entry in that order -> a stable
+// 64-bit sort of the sort keys -> the scatter of the ranks.  The table is only read.  n = t->committed > 0.
+int finish_on_device(hbu_table *t, double divisor, bool want_ranks, Temps &m, Finished *f)
+{
+    const uint64_t n = t->committed;
+    hb_u128 *d_raw = nullptr;
+    uint32_t *d_entry = nullptr;
+    uint64_t *d_key = nullptr;
+    HBU_HIP(m.alloc(&d_raw, n));
+    HBU_HIP(m.alloc(&f->d_ids, n));
+    HBU_HIP(m.alloc(&d_entry, n));
+    hipLaunchKernelGGL(hbr::set_export_kernel, dim3(grid_for(t->slots)), dim3(256), 0, t->stream, (const u128 *)t->d_keys, (const uint32_t *)t->d_pids, t->slots, (uint32_t)n,
+                       d_raw);
+    HBU_HIP(hipGetLastError());
+    std::string e = hb::gpu_sort_ids_device((void *)t->stream, d_raw, n, f->d_ids, d_entry);
+    if (!e.empty()) return sort_error(t, e);
+    m.release(d_raw);
+    HBU_HIP(m.alloc(&f->d_vals, n));
+    HBU_HIP(m.alloc(&d_key, n));
+    if (t->kind == HBU_KIND_KAHAN)
+        hipLaunchKernelGGL(hbn::finish_values_kernel<2>, dim3(grid_for(n)), dim3(256), 0, t->stream, (const double *)t->d_table, (const uint32_t *)d_entry, n, divisor, f->d_vals,
+                           d_key);
+    else
+        hipLaunchKernelGGL(hbn::finish_values_kernel<1>, dim3(grid_for(n)), dim3(256), 0, t->stream, (const double *)t->d_table, (const uint32_t *)d_entry, n, divisor, f->d_vals,
+                           d_key);
+    HBU_HIP(hipGetLastError());
+    HBU_HIP(m.alloc(&f->d_order, n));
+    if (want_ranks) HBU_HIP(m.alloc(&f->d_rank, n));
+    e = hb::gpu_rank_keys_device((void *)t->stream, d_key, n, f->d_order, f->d_rank);
+    if (!e.empty()) return sort_error(t, e);
+    m.release(d_key);
+    m.release(d_entry);
+    return HB_OK;
+}
+} // namespace
+
+extern "C" {
+
+int hbu_finish_centralities(hbu_table *centrality, double divisor, hb_u128 *ids_out, double *vals_out, uint64_t *ranks_out, uint64_t capacity, uint64_t *written)
+{
+    hbu_table *t = centrality;
+    return guarded(t, [&]() -> int {
+        if (written) *written = 0;
+        int rc = finish_refusal(t);
+        if (rc) return rc;
+        const uint64_t n = t->committed;
+        const bool any = ids_out || vals_out || ranks_out;
+        if (any && capacity < n) return fail(t, HB_ERR_INVALID, "capacity below the number of keys");
+        if (written) *written = n;
+        if (!n || !any) return HB_OK;
+        HBU_HIP(hipSetDevice(t->device));
+        Temps m;
+        Finished f;
+        if ((rc = finish_on_device(t, divisor, ranks_out != nullptr, m, &f))) {
+            if (written) *written = 0;
+            return rc;
+        }
+        if (ids_out) HBU_HIP(hipMemcpyAsync(ids_out, f.d_ids, n * sizeof(hb_u128), hipMemcpyDeviceToHost, t->stream));
+        if (vals_out) HBU_HIP(hipMemcpyAsync(vals_out, f.d_vals, n * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+        if (ranks_out) HBU_HIP(hipMemcpyAsync(ranks_out, f.d_rank, n * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
+        HBU_HIP(hipStreamSynchronize(t->stream));
+        return HB_OK;
+    });
+}
+
+int hbu_top_centralities(hbu_table *centrality, double divisor, uint64_t k, hb_u128 *ids_out, double *vals_out, uint64_t *written)
+{
+    hbu_table *t = centrality;
+    return guarded(t, [&]() -> int {
+        if (written) *written = 0;
+        int rc = finish_refusal(t);
+        if (rc) return rc;
+        const uint64_t top = std::min<uint64_t>(k, t->committed);
+        if (written) *written = top;
+        if (!top || (!ids_out && !vals_out)) return HB_OK;
+        HBU_HIP(hipSetDevice(t->device));
+        Temps m;
+        Finished f;
+        if ((rc = finish_on_device(t, divisor, false, m, &f))) {
+            if (written) *written = 0;
+            return rc;
+        }
+        hb_u128 *d_top_ids = nullptr;
+        double *d_top_vals = nullptr;
+        if (ids_out) HBU_HIP(m.alloc(&d_top_ids, top));
+        if (vals_out) HBU_HIP(m.alloc(&d_top_vals, top));
+        hipLaunchKernelGGL(hbn::top_gather_kernel, dim3(grid_for(top)), dim3(256), 0, t->stream, (const uint64_t *)f.d_order, top, (const hb_u128 *)f.d_ids,
+                           (const double *)f.d_vals, d_top_ids, d_top_vals);
+        HBU_HIP(hipGetLastError());
+        if (ids_out) HBU_HIP(hipMemcpyAsync(ids_out, d_top_ids, top * sizeof(hb_u128), hipMemcpyDeviceToHost, t->stream));
+        if (vals_out) HBU_HIP(hipMemcpyAsync(vals_out, d_top_vals, top * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+        HBU_HIP(hipStreamSynchronize(t->stream));
+        return HB_OK;
+    });
+}
+
+int hbu_store_centralities(hbu_table *centrality, double divisor, const char *output, char *err, uint64_t err_len)
+{
+    hbu_table *t = centrality;
+    if (err && err_len) err[0] = 0;
+    const int rc = guarded(t, [&]() -> int {
+        int rc2 = finish_refusal(t);
+        if (rc2) return rc2;
+        if (!output || !*output) return fail(t, HB_ERR_INVALID, "hbu_store_centralities: output is empty");
+        const uint64_t n = t->committed;
+        // what crosses the link: the values, the ranks and the key order of the two databases - the ids stay where they are
+        hb::RawVec<double> vals(n);
+        hb::RawVec<uint64_t> ranks(n);
+        hb::StoreKeyVec sorted(n);
+        if (n) {
+            HBU_HIP(hipSetDevice(t->device));
+            Temps m;
+            Finished f;
+            if ((rc2 = finish_on_device(t, divisor, true, m, &f))) return rc2;
+            HBU_HIP(hipMemcpyAsync(vals.data(), f.d_vals, n * sizeof(double), hipMemcpyDeviceToHost, t->stream));
+            HBU_HIP(hipMemcpyAsync(ranks.data(), f.d_rank, n * sizeof(uint64_t), hipMemcpyDeviceToHost, t->stream));
+            HBU_HIP(hipStreamSynchronize(t->stream));
+            m.release(f.d_vals);
+            m.release(f.d_rank);
+            m.release(f.d_order);
+            const std::string e = hb::gpu_store_keys_device((void *)t->stream, f.d_ids, n, sorted.data());
+            if (!e.empty()) return sort_error(t, "hbu_store_centralities: " + e);
+        }
+        char msg[512] = {0};
+        const int rc3 = hb::store_harmonic_presorted(output, &sorted, vals.data(), ranks.data(), msg, sizeof(msg));
+        if (rc3) return fail(t, rc3, msg);
+        return HB_OK;
+    });
+    if (rc && err && err_len) std::snprintf(err, (size_t)err_len, "%s", hbu_last_error(t));
+    return rc;
 }
 
 } // extern "C"

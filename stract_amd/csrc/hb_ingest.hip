@@ -925,6 +925,50 @@ std::string gpu_ingest_reduce(void *stream_v, const hb_u128 *node_ids, uint64_t 
     return "";
 }
 
+// `count` distinct ids, given by entry number, in ascending numeric u128 order: d_sorted[j] = the j-th smallest id, d_entry[j] = the entry
+// number it came from.  One 128-bit radix sort carrying the entry number (the sort finalize runs on the endpoint table's keys).  Device
+// pointers; synchronised on return.
+std::string gpu_sort_ids_device(void *stream_v, const hb_u128 *d_ids, uint64_t count, hb_u128 *d_sorted, uint32_t *d_entry)
+{
+    hipStream_t stream = (hipStream_t)stream_v;
+    if (!count) return "";
+    if (count >= (1ull << 32)) return "too many entries";
+    DevMem mem;
+    auto iota = rocprim::make_counting_iterator<uint32_t>(0);
+    size_t bytes = 0;
+    IG_HIP(rocprim::radix_sort_pairs(nullptr, bytes, (const u128 *)d_ids, (u128 *)d_sorted, iota, d_entry, (size_t)count, 0, 128, stream));
+    char *tmp = nullptr;
+    IG_HIP(mem.alloc(&tmp, bytes));
+    IG_HIP(rocprim::radix_sort_pairs(tmp, bytes, (const u128 *)d_ids, (u128 *)d_sorted, iota, d_entry, (size_t)count, 0, 128, stream));
+    IG_HIP(hipStreamSynchronize(stream)); // (the temporary storage goes back to the allocator on return)
+    return "";
+}
+
+// d_key: k sort keys (Reverse(total_cmp) as unsigned order, what rank_keys_kernel writes) in ascending-NodeID order.  d_order[i] = the index
+// of the entry at position i of the order (key ascending, ties by index: the sort is stable); d_rank[j] = the position of entry j (may be
+// NULL).  Device pointers; synchronised on return.
+std::string gpu_rank_keys_device(void *stream_v, const uint64_t *d_key, uint64_t k, uint64_t *d_order, uint64_t *d_rank)
+{
+    hipStream_t stream = (hipStream_t)stream_v;
+    if (!k) return "";
+    DevMem mem;
+    uint64_t *d_key_s = nullptr;
+    IG_HIP(mem.alloc(&d_key_s, k));
+    auto iota = rocprim::make_counting_iterator<uint64_t>(0);
+    size_t bytes = 0;
+    // stable: equal centralities keep ascending NodeID order
+    IG_HIP(rocprim::radix_sort_pairs(nullptr, bytes, d_key, d_key_s, iota, d_order, (size_t)k, 0, 64, stream));
+    char *tmp = nullptr;
+    IG_HIP(mem.alloc(&tmp, bytes));
+    IG_HIP(rocprim::radix_sort_pairs(tmp, bytes, d_key, d_key_s, iota, d_order, (size_t)k, 0, 64, stream));
+    if (d_rank) {
+        hipLaunchKernelGGL(rank_scatter_kernel, dim3(grid_for(k)), dim3(256), 0, stream, (const uint64_t *)d_order, k, d_rank);
+        IG_HIP(hipGetLastError());
+    }
+    IG_HIP(hipStreamSynchronize(stream));
+    return "";
+}
+
 // ranks[j] for the j-th kept result (ascending NodeID): its position in the store_harmonic order.
 // order_out (optional): the result indices of the first `top` positions of that order (top_nodes, centrality/mod.rs:33-52).
 std::string gpu_rank_results(void *stream_v, const double *d_vals, uint64_t n, uint64_t expect, uint64_t *ranks_out, uint64_t *order_out,
@@ -933,12 +977,11 @@ std::string gpu_rank_results(void *stream_v, const double *d_vals, uint64_t n, u
     hipStream_t stream = (hipStream_t)stream_v;
     if (n == 0 || expect == 0) return "";
     DevMem mem;
-    uint64_t *d_key = nullptr, *d_kkey = nullptr, *d_kkey_s = nullptr, *d_idx_s = nullptr, *d_rank = nullptr, *d_cnt = nullptr;
+    uint64_t *d_key = nullptr, *d_kkey = nullptr, *d_idx_s = nullptr, *d_rank = nullptr, *d_cnt = nullptr;
     uint8_t *d_keep = nullptr;
     IG_HIP(mem.alloc(&d_key, n));
     IG_HIP(mem.alloc(&d_keep, n));
     IG_HIP(mem.alloc(&d_kkey, expect));
-    IG_HIP(mem.alloc(&d_kkey_s, expect));
     IG_HIP(mem.alloc(&d_idx_s, expect));
     IG_HIP(mem.alloc(&d_rank, expect));
     IG_HIP(mem.alloc(&d_cnt, 1));
@@ -962,17 +1005,10 @@ std::string gpu_rank_results(void *stream_v, const double *d_vals, uint64_t n, u
     IG_HIP(hipMemcpyAsync(&k, d_cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     IG_HIP(hipStreamSynchronize(stream));
     if (k != expect) return "gpu rank: kept-result count mismatch";
-    auto iota = rocprim::make_counting_iterator<uint64_t>(0);
-    bytes = 0;
-    // stable: equal centralities keep ascending NodeID order
-    IG_HIP(rocprim::radix_sort_pairs(nullptr, bytes, d_kkey, d_kkey_s, iota, d_idx_s, (size_t)k, 0, 64, stream));
-    IG_HIP(need(bytes));
-    IG_HIP(rocprim::radix_sort_pairs(tmp, bytes, d_kkey, d_kkey_s, iota, d_idx_s, (size_t)k, 0, 64, stream));
-    if (ranks_out) {
-        hipLaunchKernelGGL(rank_scatter_kernel, dim3(grid_for(k)), dim3(256), 0, stream, (const uint64_t *)d_idx_s, k, d_rank);
-        IG_HIP(hipGetLastError());
-        IG_HIP(hipMemcpyAsync(ranks_out, d_rank, k * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    }
+    mem.release(tmp);
+    const std::string e = gpu_rank_keys_device(stream_v, d_kkey, k, d_idx_s, ranks_out ? d_rank : nullptr);
+    if (!e.empty()) return e;
+    if (ranks_out) IG_HIP(hipMemcpyAsync(ranks_out, d_rank, k * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     if (order_out && top) IG_HIP(hipMemcpyAsync(order_out, d_idx_s, std::min(top, k) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
     IG_HIP(hipStreamSynchronize(stream));
     return "";
@@ -1024,21 +1060,17 @@ __global__ __launch_bounds__(256) void store_keys_pack_kernel(const u128 *key, c
 }
 } // namespace
 
-std::string gpu_store_keys(void *stream_v, const hb_u128 *ids, uint64_t count, StoreKey *sorted_out)
+namespace {
+// the sort of gpu_store_keys from ids that are in device memory; `uploaded`: a copy of the ids that `mem` owns (it is given back before the
+// packed records are allocated) or NULL where the ids are the caller's
+std::string store_keys_sorted(hipStream_t stream, DevMem &mem, const hb_u128 *d_ids, hb_u128 *uploaded, uint64_t count, StoreKey *sorted_out)
 {
-    hipStream_t stream = (hipStream_t)stream_v;
-    if (!count) return "";
-    if (count >= (1ull << 56)) return "too many entries";
-    DevMem mem;
-    hb_u128 *d_ids = nullptr;
     u128 *d_key = nullptr, *d_key2 = nullptr;
     uint64_t *d_w = nullptr, *d_w2 = nullptr, *d_out = nullptr;
-    IG_HIP(mem.alloc(&d_ids, count));
     IG_HIP(mem.alloc(&d_key, count));
     IG_HIP(mem.alloc(&d_key2, count));
     IG_HIP(mem.alloc(&d_w, count));
     IG_HIP(mem.alloc(&d_w2, count));
-    IG_HIP(hipMemcpyAsync(d_ids, ids, count * sizeof(hb_u128), hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(store_keys_kernel, dim3(grid_for(count)), dim3(256), 0, stream, (const hb_u128 *)d_ids, count, d_key, d_w);
     IG_HIP(hipGetLastError());
     // LSD: first the 17th key byte (the top byte of the index word; ties keep the ascending index), then the first 16 bytes
@@ -1049,13 +1081,34 @@ std::string gpu_store_keys(void *stream_v, const hb_u128 *ids, uint64_t count, S
     IG_HIP(mem.alloc(&tmp, std::max(b1, b2)));
     IG_HIP(rocprim::radix_sort_pairs(tmp, b1, (const uint64_t *)d_w, d_w2, (const u128 *)d_key, d_key2, (size_t)count, 56, 64, stream));
     IG_HIP(rocprim::radix_sort_pairs(tmp, b2, (const u128 *)d_key2, d_key, (const uint64_t *)d_w2, d_w, (size_t)count, 0, 128, stream));
-    mem.release(d_ids);
+    if (uploaded) mem.release(uploaded);
     IG_HIP(mem.alloc(&d_out, 3 * count));
     hipLaunchKernelGGL(store_keys_pack_kernel, dim3(grid_for(count)), dim3(256), 0, stream, (const u128 *)d_key, (const uint64_t *)d_w, count, d_out);
     IG_HIP(hipGetLastError());
     IG_HIP(hipMemcpyAsync(sorted_out, d_out, count * sizeof(StoreKey), hipMemcpyDeviceToHost, stream));
     IG_HIP(hipStreamSynchronize(stream));
     return "";
+}
+} // namespace
+
+std::string gpu_store_keys(void *stream_v, const hb_u128 *ids, uint64_t count, StoreKey *sorted_out)
+{
+    hipStream_t stream = (hipStream_t)stream_v;
+    if (!count) return "";
+    if (count >= (1ull << 56)) return "too many entries";
+    DevMem mem;
+    hb_u128 *d_ids = nullptr;
+    IG_HIP(mem.alloc(&d_ids, count));
+    IG_HIP(hipMemcpyAsync(d_ids, ids, count * sizeof(hb_u128), hipMemcpyHostToDevice, stream));
+    return store_keys_sorted(stream, mem, d_ids, d_ids, count, sorted_out);
+}
+
+std::string gpu_store_keys_device(void *stream_v, const hb_u128 *d_ids, uint64_t count, StoreKey *sorted_out)
+{
+    if (!count) return "";
+    if (count >= (1ull << 56)) return "too many entries";
+    DevMem mem;
+    return store_keys_sorted((hipStream_t)stream_v, mem, d_ids, nullptr, count, sorted_out);
 }
 
 } // namespace hb

@@ -343,5 +343,14 @@ using StoreKeyVec = RawVec<StoreKey>;
 std::string gpu_store_keys(void *stream, const hb_u128 *ids, uint64_t count, StoreKey *sorted_out);
 // store_harmonic (centrality/mod.rs:72-114) from keys that are already in order; *sorted is consumed
 int store_harmonic_presorted(const char *output, StoreKeyVec *sorted, const double *centralities, const uint64_t *ranks, char *err, size_t err_len);
+// ---- the same sorts on arrays that are in device memory already (hb_ampc.hip: the finish of an AMPC job, whose table is a hash table with
+// neither dense nor ordered results); "" or an error text, synchronised with `stream` on return
+//   gpu_store_keys for ids the device holds: nothing goes up, the sorted records come back
+std::string gpu_store_keys_device(void *stream, const hb_u128 *d_ids, uint64_t count, StoreKey *sorted_out);
+//   `count` (< 2^32) distinct ids by entry number -> d_sorted: ascending numeric u128 order, d_entry[j]: the entry number of d_sorted[j]
+std::string gpu_sort_ids_device(void *stream, const hb_u128 *d_ids, uint64_t count, hb_u128 *d_sorted, uint32_t *d_entry);
+//   d_key: Reverse(total_cmp) sort keys of k entries in ascending-NodeID order -> d_order[i]: the entry at position i of the store_harmonic
+//   order (stable: ties by NodeID), d_rank[j] (may be NULL): the position of entry j - the sort and scatter gpu_rank_results ends with
+std::string gpu_rank_keys_device(void *stream, const uint64_t *d_key, uint64_t k, uint64_t *d_order, uint64_t *d_rank);
 } // namespace hb
 #endif

@@ -28,11 +28,14 @@ on the --rounds R-MAT worker graph with max_distance = 5, with the fold's share 
 fold_harmonic each) and through one 64-lane walk (run_shortest_paths_job + fold_harmonic_lanes), alternating in this process, a warm-up and
 --reps timed repetitions with the folds included and the two results compared bit for bit; and the round call alone,
 hbu_round_lane_distances against hbu_round_distances, on the state each job holds after each of its rounds.  --only-lanes skips the
-counter-table section.
+counter-table section.  --finish adds the finish of a job: finish_centralities, top_centralities(1 000 000) and store_centralities (into a
+memory file system) against today's route in the same process - items(), the division and np.lexsort in numpy, hb_store_harmonic on the host
+arrays -, alternating, a warm-up in which the two routes' outputs are compared and --reps timed repetitions, on the centrality table one
+64-lane walk of --lanes leaves and on a synthetic KahanSum table of `keys` keys.  --only-finish skips the counter-table section.
 --out FILE also writes the JSON line there.
 usage: tools/ampc_bench.py [keys, default 10000000] [pairs per batch, default 1000000] [--values] [--kind K] [--op OP] [--centralities]
                            [--edges] [--rounds] [--round-edges N, default 100000000] [--round-scale S] [--only-rounds] [--approx] [--only-approx]
-                           [--sources N, default 5] [--lanes] [--only-lanes] [--reps N, default 5] [--out FILE]"""
+                           [--sources N, default 5] [--lanes] [--only-lanes] [--finish] [--only-finish] [--reps N, default 5] [--out FILE]"""
 import argparse
 import json
 import os
@@ -584,6 +587,132 @@ def lanes_mode(rng, reps, total_edges, scale, n_sources=64):
     return res
 
 
+def finish_mode(rng, keys, K, reps, total_edges, scale, n_sources=64):
+    """The finish of a job (finish_centralities, top_centralities(1 000 000), store_centralities into a memory file system) against today's
+    route in this process - items(), the division in numpy, np.lexsort for the id order, the ranks and the top list, hb_store_harmonic on
+    the host arrays -, alternating, one warm-up (in which the outputs of the two routes are compared) and `reps` timed repetitions each; on
+    the centrality table one 64-lane walk of --lanes leaves (divisor 1.0, the approximated job's) and on a synthetic KahanSum table of K
+    keys (divisor K - 1, the harmonic job's)."""
+    import hashlib
+    import shutil
+    import tempfile
+    top_k = 1_000_000
+    res = {"repetitions": reps, "top_k": top_k, "tables": {}}
+    base = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
+    scratch = tempfile.mkdtemp(prefix="ampc_finish_", dir=base)
+    res["store_directory_is_memory_backed"] = base is not None
+
+    def total_key(vals):
+        b = vals.view(np.uint64)
+        return np.where(b >> np.uint64(63) != 0, ~b, b | np.uint64(1 << 63))
+
+    def host_values(tab, divisor):
+        k, v = tab.items()
+        with np.errstate(all="ignore"):
+            return k, v["sum"] / np.float64(divisor)
+
+    def host_finish(tab, divisor):
+        k, q = host_values(tab, divisor)
+        order = np.lexsort((k["lo"], k["hi"]))
+        ids, vals = k[order], q[order]
+        by_rank = np.argsort(~total_key(vals), kind="stable")  # (ids ascend: a stable sort leaves ties in id order)
+        ranks = np.empty(len(ids), dtype=np.uint64)
+        ranks[by_rank] = np.arange(len(ids), dtype=np.uint64)
+        return ids, vals, ranks
+
+    def host_top(tab, divisor, k_top):
+        k, q = host_values(tab, divisor)
+        first = np.lexsort((k["lo"], k["hi"], ~total_key(q)))[:k_top]
+        return k[first], q[first]
+
+    def files_of(out):
+        found = {}
+        for db in sorted(os.listdir(out)):
+            for f in sorted(os.listdir(os.path.join(out, db))):
+                h = hashlib.sha256()
+                with open(os.path.join(out, db, f), "rb") as fh:
+                    for block in iter(lambda: fh.read(1 << 24), b""):
+                        h.update(block)
+                if f != "meta.json":  # (meta.json names the segment: a fresh uuid per store)
+                    found[(db, os.path.splitext(f)[1])] = h.hexdigest()
+        return found
+
+    def canon(vals):
+        b = vals.view(np.uint64).copy()
+        b[np.isnan(vals)] = 0x7FF8000000000000
+        return b
+
+    def measure(name, tab, divisor):
+        n = len(tab)
+        t = {x: [] for x in ("finish_dev", "finish_host", "top_dev", "top_host", "store_dev", "store_host", "store_host_writer")}
+        same = {}
+        for r in range(reps + 1):  # the first repetition warms both routes up and compares their outputs
+            t0 = time.perf_counter()
+            d = ampc.finish_centralities(tab, divisor)
+            t1 = time.perf_counter()
+            h = host_finish(tab, divisor)
+            t2 = time.perf_counter()
+            dt = ampc.top_centralities(tab, top_k, divisor)
+            t3 = time.perf_counter()
+            ht = host_top(tab, divisor, top_k)
+            t4 = time.perf_counter()
+            a, b = os.path.join(scratch, "dev"), os.path.join(scratch, "host")
+            ampc.store_centralities(tab, a, divisor)
+            t5 = time.perf_counter()
+            hs = host_finish(tab, divisor)
+            t6 = time.perf_counter()
+            _lib.store_harmonic(b, *hs)
+            t7 = time.perf_counter()
+            if r == 0:
+                same = {"ids": bool(np.array_equal(d[0], h[0])), "values": bool(np.array_equal(canon(d[1]), canon(h[1]))), "ranks": bool(np.array_equal(d[2], h[2])),
+                        "top_ids": bool(np.array_equal(dt[0], ht[0])), "top_values": bool(np.array_equal(canon(dt[1]), canon(ht[1]))),
+                        "store_files": files_of(a) == files_of(b), "nan_values": int(np.isnan(d[1]).sum()), "infinite_values": int(np.isinf(d[1]).sum())}
+                stored_bytes = sum(os.path.getsize(os.path.join(a, db, f)) for db in os.listdir(a) for f in os.listdir(os.path.join(a, db)))
+            else:
+                for key, dt_ in zip(t, (t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4, t7 - t5, t7 - t6)):
+                    t[key].append(dt_)
+            shutil.rmtree(a)
+            shutil.rmtree(b)
+            print(name, "repetition", r, [round(x, 4) for x in (t1 - t0, t2 - t1, t3 - t2, t4 - t3, t5 - t4, t7 - t5)], file=sys.stderr, flush=True)
+        cell = {"keys": n, "divisor": divisor, "outputs_equal_in_the_warm_up": same, "store_bytes": stored_bytes}
+        for what in ("finish", "top", "store"):
+            dev, host = spread(t[what + "_dev"]), spread(t[what + "_host"])
+            gap = max(dev["max_s"] - dev["min_s"], host["max_s"] - host["min_s"])
+            cell[what] = {"device_route": dev, "host_route": host, "median_gain_s": round(host["median_s"] - dev["median_s"], 6), "larger_spread_s": round(gap, 6),
+                          "beats_by_more_than_the_spread": bool(host["median_s"] - dev["median_s"] > gap), "ratio_of_medians": round(host["median_s"] / dev["median_s"], 2)}
+        cell["store"]["host_route_hb_store_harmonic_alone"] = spread(t["store_host_writer"])
+        cell["link_bytes_per_key"] = {"finish": {"device_route": 32, "host_route": 32}, "top": {"device_route": round(24 * min(top_k, n) / max(n, 1), 2), "host_route": 32},
+                                      "store": {"device_route": 40, "host_route": 32}}
+        res["tables"][name] = cell
+        print(name, cell, file=sys.stderr, flush=True)
+
+    try:
+        t0 = time.perf_counter()
+        nodes, from_ids, to_ids = rmat_worker(scale, total_edges)
+        print("graph: %d nodes, %d edges, %.1f s" % (len(nodes), len(from_ids), time.perf_counter() - t0), file=sys.stderr, flush=True)
+        picked = np.unique(from_ids[rng.integers(0, len(from_ids), 4 * n_sources + 4)])
+        rng.shuffle(picked)
+        sources = [(int(k["hi"]) << 64) | int(k["lo"]) for k in picked[:n_sources]]
+        with ampc.ValueTable(ampc.KIND_KAHAN) as cent:
+            with ampc.WorkerGraph(nodes, from_ids, to_ids) as graph:
+                lanes = ampc.run_shortest_paths_job([graph], sources, 5)
+                ampc.fold_harmonic_lanes(lanes, cent, 1.0 / 2657.0, len(sources))
+                lanes.close()
+            del nodes, from_ids, to_ids
+            measure("lanes_job_centralities", cent, 1.0)
+        with ampc.ValueTable(ampc.KIND_KAHAN, capacity_hint=K) as tab:
+            for b in range(0, K, 1_000_000):
+                v = np.zeros(len(keys[b:b + 1_000_000]), dtype=ampc.KAHAN)
+                v["sum"] = np.floor(rng.random(len(v)) * 1e6)  # a million levels: ties of about K / 1e6 keys each
+                v["err"] = rng.random(len(v)) * 1e-9
+                tab.batch_set(keys[b:b + 1_000_000], v)
+            measure("synthetic_kahan", tab, float(K - 1))
+    finally:
+        shutil.rmtree(scratch, ignore_errors=True)
+    res["all_outputs_equal"] = all(v for c in res["tables"].values() for k, v in c["outputs_equal_in_the_warm_up"].items() if isinstance(v, bool))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("keys", nargs="?", type=int, default=10_000_000)
@@ -601,6 +730,8 @@ def main():
     ap.add_argument("--only-approx", action="store_true", help="skip the counter-table section (with --approx)")
     ap.add_argument("--lanes", action="store_true", help="also 64 sources through the per-source route and through one 64-lane walk, and the round call alone")
     ap.add_argument("--only-lanes", action="store_true", help="skip the counter-table section (with --lanes)")
+    ap.add_argument("--finish", action="store_true", help="also the finish of a job (values, ranks, top nodes, store) against items() + numpy + hb_store_harmonic")
+    ap.add_argument("--only-finish", action="store_true", help="skip the counter-table section (with --finish)")
     ap.add_argument("--sources", type=int, default=5, help="timed sources of --approx (one more warms up)")
     ap.add_argument("--reps", type=int, default=5, help="timed batches per shape and side of --edges / repetitions of --rounds (at least 5)")
     ap.add_argument("--out")
@@ -611,7 +742,7 @@ def main():
     keys["lo"] = rng.permutation(K).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)
     keys["hi"] = rng.integers(0, 1 << 63, K, dtype=np.uint64)
     out = {"keys": K, "pairs_per_batch": B, "bytes_per_pair": 80}
-    for label, pinned in (() if (args.only_rounds and args.rounds) or (args.only_approx and args.approx) or (args.only_lanes and args.lanes) else (("pageable", False), ("pinned", True))):
+    for label, pinned in (() if (args.only_rounds and args.rounds) or (args.only_approx and args.approx) or (args.only_lanes and args.lanes) or (args.only_finish and args.finish) else (("pageable", False), ("pinned", True))):
         kb = _lib.PinnedRecords(B, dtype=_lib.U128) if pinned else None
         vb = _lib.PinnedRecords(B * 64, dtype=np.uint8) if pinned else None
         kbuf = kb.array if pinned else np.zeros(B, dtype=_lib.U128)
@@ -679,11 +810,16 @@ def main():
     if args.lanes:
         scale = args.round_scale or max(int(K).bit_length() - 1, 1)
         out["lanes"] = lanes_mode(rng, max(args.reps, 5), args.round_edges, scale)
+    if args.finish:
+        scale = args.round_scale or max(int(K).bit_length() - 1, 1)
+        out["finish"] = finish_mode(rng, keys, K, max(args.reps, 5), args.round_edges, scale)
     line = json.dumps(out)
     print(line)
     if args.out:
         with open(args.out, "w") as f:
             f.write(line + "\n")
+    if args.finish and not out["finish"]["all_outputs_equal"]:
+        sys.exit("--finish: the two routes differ (see outputs_equal_in_the_warm_up)")
 
 
 if __name__ == "__main__":
