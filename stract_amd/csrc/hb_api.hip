@@ -17,6 +17,7 @@
 #include <thread>
 #include <vector>
 
+#include "hb_owned.h" // (after hb_pool.h: DevPtr frees through the allocator this file sees)
 #include "hb_internal.h"
 #include "hb_experiments.h" // HB_XBITS: the switches of the experiments build (none in the product library)
 #include "hb_kernels.hip.h"
@@ -41,44 +42,8 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
-// The one owner of a hipMalloc'ed buffer that is not on a context's `allocs` list (dev_alloc below): scratch of a single call, the input
-// CSR of a load, the sampled operator's state.  Move-only; freed when the holder goes out of scope or is assigned over.  (hipMalloc /
-// hipFree are the ones this file sees: the caching allocator, or the debug allocators of hb_guard_alloc.h.)
-template <class T>
-struct DevPtr {
-    DevPtr() = default;
-    explicit DevPtr(T *q) : p(q) {}
-    DevPtr(DevPtr &&o) noexcept : p(o.release()) {}
-    DevPtr &operator=(DevPtr &&o) noexcept
-    {
-        reset(o.release());
-        return *this;
-    }
-    DevPtr(const DevPtr &) = delete;
-    DevPtr &operator=(const DevPtr &) = delete;
-    ~DevPtr() { reset(); }
-    T *get() const { return p; }
-    explicit operator bool() const { return p != nullptr; }
-    T *release()
-    {
-        T *q = p;
-        p = nullptr;
-        return q;
-    }
-    void reset(T *q = nullptr)
-    {
-        if (p) (void)hipFree(p);
-        p = q;
-    }
-    hipError_t alloc(size_t count) // `count` elements; whatever the holder had is freed first
-    {
-        reset();
-        return hipMalloc((void **)&p, count * sizeof(T));
-    }
-
-private:
-    T *p = nullptr;
-};
+// DevPtr<T> (hb_owned.h) is the one owner of a hipMalloc'ed buffer that is not on a context's `allocs` list (dev_alloc below): scratch of
+// a single call, the input CSR of a load, the sampled operator's state.
 
 // DeviceCsr (hb_internal.h: a plain struct, the host-only sources include it too) with an owner: the device ingest or hb_load_dense fills
 // `d`, plan_and_upload takes the whole thing by move and frees it when the plan exists

@@ -469,3 +469,42 @@ def test_ampc_shortest_path_rounds_on_device_tables():
         assert_table(d_prev, kind, dist, space, "bfs")
     finally:
         d_prev.close()
+
+
+def test_batch_sizes_across_the_work_memory_pieces():
+    """One u64 table and one exact ChangedFilter through batches of 1, 16, 17, 64, 65, 257, 17 and 1: 16 and 17 sixteen-byte keys straddle
+    one 256-byte piece of the work memory, 64 and 65 groups one block of the group kernels, and the last two batches are smaller than the
+    work memory they find.  Every call that lays the work memory out runs at every size - batch_upsert (U64_MIN, keys repeated inside the
+    batch), batch_get of present and absent keys, items(), and the filter's insert, contains and export_ids - and every answer equals a
+    dict / set model exactly."""
+    rng = np.random.default_rng(41)
+    kind, op = ampc.KIND_U64, ampc.OP_U64_MIN
+
+    def name(i):
+        return i | ((i % 3) << 100)
+
+    model, members = {}, set()
+    with ampc.ValueTable(kind, capacity_hint=4) as tab, ampc.ChangedFilter.exact() as filt:
+        for step, n in enumerate([1, 16, 17, 64, 65, 257, 17, 1]):
+            what = (step, n)
+            fresh = [name(1000 * (step + 1) + i) for i in range(max(1, 2 * n // 3))]
+            pool = fresh + list(model)[:5]
+            keys = [pool[i] for i in rng.integers(0, len(pool), n)]
+            if n > 1:
+                keys[-1] = keys[0]  # (whatever the draw: one key twice)
+            upsert_both(tab, kind, model, op, keys, value_pool(kind, rng, n), what)
+            known = list(model)
+            ask = [known[i % len(known)] if i % 2 == 0 else name(500_000 + 1000 * step + i) for i in range(n)]
+            assert sum(k in model for k in ask) == (n + 1) // 2, what
+            assert_table(tab, kind, model, ask, what)
+            got_keys, got_vals = tab.items()
+            assert len(got_keys) == len(model), what
+            assert {key_int(k): int(v) for k, v in zip(got_keys, got_vals)} == model, what
+            ids = [keys[i] if i % 3 else name(900_000 + 1000 * step + i) for i in range(n)]
+            filt.insert(u128(ids))
+            members |= set(ids)
+            assert filt.count() == len(members), what
+            assert filt.contains(u128(ask)).tolist() == [k in members for k in ask], what
+            assert filt.contains(u128(ids)).all(), what
+            out = filt.export_ids()
+            assert len(out) == len(members) and {key_int(k) for k in out} == members, what
