@@ -468,8 +468,9 @@ int hb_debug_copy_betweenness_batch(hb_ctx *ctx, uint8_t *dist, uint64_t *sigma,
  * no node of the graph has an empty BitVec: its sim is 0, it counts in L or D (and in hb_similarity_stats.unknown).
  * Defined differences: in(v) is the WHOLE in-list of the loaded graph - unique edges, self links as loaded, the relation filter of the
  * load (HB_SKIPPED_REL_MASK drops NOFOLLOW among others; HB_FLAG_ALL_RELS keeps everything).  The reference takes
- * EdgeLimit::Limit(512) backlinks in search order before it filters, which nothing can reproduce: the two agree wherever every host
- * involved has at most 512 inbound records.
+ * EdgeLimit::Limit(512) backlinks in search order before it filters: the two agree wherever every host involved has at most 512
+ * inbound records.  (With the order hb_nearest_seed defined, that cut is a defined object - hb_backlinks below builds it; using it here
+ * is a follow-up.)
  * Entry 16 b + j (liked entries first, then the disliked ones, in caller order) is slot j of batch b; a batch is one level of the walk
  * the other operators share (hb_sampled_harmonic, hb_betweenness) with sixteen u32 counts per 64-byte row and a plain add as the join.
  * Single rank only.  The call borrows the HyperBall state as those walks do: hb_step needs a new hb_begin afterwards, a later hb_run
@@ -590,6 +591,89 @@ int hb_nearest_seed_copy(hb_ctx *ctx, hb_u128 *ids, double *vals, uint64_t cap);
 int hb_nearest_seed_all(hb_ctx *ctx, double *vals, uint64_t cap);
 int hb_nearest_seed_top(hb_ctx *ctx, uint64_t k, hb_u128 *ids, double *vals, uint64_t *written);
 int hb_nearest_seed_seeds(hb_ctx *ctx, hb_u128 *seed, uint8_t *has_seed, uint64_t cap);
+
+/* ---- limited, rank-ordered host backlinks: HostBacklinksQuery::new(v).with_limit(EdgeLimit::Limit(L)) (query/backlink.rs:230-360) ---- */
+/* The link query the reference's callers reach the graph with (inbound_similarity::Scorer: L = 512 per liked / disliked host;
+ * SimilarHostsFinder::potential_nodes, similar_hosts.rs:118-165: L = 128; harmonic_nearest_seed: L = 1; RemoteWebgraph::batch_search
+ * sends them by the thousand), for a LIST of hosts per call.
+ * in(v) = the in-neighbours u != v of v in the loaded graph: edges are unique, the load applied its relation filter, a self link is
+ * skipped as LinksQuery.skip_self_links does (HB_LINKS_KEEP_SELF keeps it).  key[u] = a u64 per node, u64::MAX for a node that is not
+ * listed, as in the reference.  Order: (key[u], NodeID u) ascending - sids ascend with the NodeIDs, so (key, sid); the order
+ * hb_nearest_seed defined.  backlinks(v, L) = the first min(L, |in(v)|) elements of in(v) in that order, LISTED in that order;
+ * degree(v) = |in(v)|, what HostGroupQuery::backlinks(v, ToHostId, FromHostId) counts.  hb_nearest_seed's seed(v) is backlinks(v, 1).
+ * Defined differences: the reference stops collecting after L + 128 documents in document order and de-duplicates hosts afterwards -
+ * here the list is the L best of the WHOLE in-list; sort_score saturates in the reference, keys are compared unsaturated (as
+ * hb_nearest_seed); the query's text and rel filters are not supported, the load's relation mask is the filter (load with
+ * HB_FLAG_ALL_RELS for the reference's unfiltered list); EdgeLimit::Unlimited and LimitAndOffset are not offered.
+ * hb_links_set_keys: the key set, either as a list (key_ids, keys, key_count: a duplicate id - the last one wins; an id that is no node
+ * is counted in unknown_keys) or HB_LINKS_KEYS_FROM_RANKS: key = the rank hb_result_ranks reports for the live result (hb_run /
+ * hb_sampled_harmonic), u64::MAX for a node without a result; refused without a live result and together with a list.  The call builds,
+ * on the device and once per key set, the dense order ord[sid] = the position of the node in the sort by (key, sid), its inverse and ord
+ * by device row.  Keys and order stay on the device until the next hb_links_set_keys or the next load.  Without any call every key is
+ * u64::MAX: the order is NodeID order.
+ * hb_backlinks: the lists of `nodes` with 1 <= limit <= 1024.  An id that is no node of the graph gets an empty list and degree 0 (and
+ * is counted in unknown); the same id may be given several times, each occurrence gets the full answer.  slots_per_batch = how many
+ * distinct hosts one batch of the device loop holds (0 = 1024; at most 65536).  Device memory is O(n_pad + nv + slots x (256 + limit))
+ * besides the result (queries x limit): it does not grow with the in-degrees of the queried hosts, and the work is proportional to the
+ * lists of the queried hosts.  The result is deterministic.
+ * Single rank only.  The operator borrows nothing: hb_run / hb_step, hb_result_*, hb_distances, hb_betweenness, hb_inbound_similarity
+ * and hb_nearest_seed results are untouched; its buffers are its own, allocated at first use after a load, freed by the next load and
+ * counted in device_bytes.  The result lives until the next successful hb_backlinks or the next load - a refused call leaves it as it
+ * was.  Both calls are refused (HB_ERR_INVALID) between hb_begin and hb_finish, without a loaded graph and with world_size > 1;
+ * hb_links_set_keys also with a key pointer NULL and a non-zero count; hb_backlinks also with opt == NULL, limit 0 or above 1024,
+ * slots_per_batch above 65536 and nodes == NULL with a non-zero node_count.  DESIGN.md section 27. */
+#define HB_LINKS_KEYS_FROM_RANKS 0x1u /* hb_links_set_keys: key = harmonic rank of the live result; key_* must be NULL / 0 */
+#define HB_LINKS_KEEP_SELF    0x1u  /* hb_backlinks: a self link is an entry like any other */
+#define HB_LINKS_SPREAD_ORDS  0x2u  /* debug: the select runs on ord * floor(2^32 / n) (strictly monotone: same result; all four digits) */
+#define HB_LINKS_NO_SHORTCUT  0x4u  /* debug: lists with degree <= limit go through the select too (same result) */
+
+typedef struct hb_links_key_options {
+    uint32_t struct_size, flags;                    /* struct_size = sizeof(hb_links_key_options); 0 = this version; flags = HB_LINKS_KEYS_* */
+    const hb_u128 *key_ids; const uint64_t *keys; uint64_t key_count;
+} hb_links_key_options;
+
+typedef struct hb_links_key_stats {
+    uint32_t struct_size;         /* = sizeof(hb_links_key_stats); 0 = this version */
+    uint32_t reserved;
+    uint64_t listed;              /* nodes with a key of their own */
+    uint64_t unknown_keys;        /* entries of the key list that are no node of the graph */
+    uint64_t device_bytes;        /* the operator's own buffers */
+    double   ms_total;            /* wall time of the call */
+    double   ms_order;            /* GPU time of the sort and of ord / inverse / ord by row */
+} hb_links_key_stats;
+
+typedef struct hb_links_options {
+    uint32_t struct_size, flags;                    /* struct_size = sizeof(hb_links_options); 0 = this version; flags = HB_LINKS_* */
+    const hb_u128 *nodes; uint64_t node_count;      /* the queried hosts, in the order hb_links_copy answers in */
+    uint32_t limit;                                 /* L: 1 .. 1024 */
+    uint32_t slots_per_batch;                       /* 0 = 1024 */
+} hb_links_options;
+
+typedef struct hb_links_stats {
+    uint32_t struct_size;         /* = sizeof(hb_links_stats); 0 = this version */
+    uint32_t reserved;
+    uint64_t queries;             /* node_count */
+    uint64_t unknown;             /* queries that are no node of the graph */
+    uint64_t distinct;            /* distinct nodes among the others (each is looked up once) */
+    uint64_t batches;
+    uint64_t entries;             /* entries of all lists, as hb_links_copy returns them */
+    uint64_t rows_walked;         /* node and chunk rows scanned by the expansion */
+    uint64_t edges_gathered;      /* source entries counted by the expansion: the sum of degree(v) over the distinct nodes */
+    uint64_t selected;            /* distinct nodes whose list went through the radix select */
+    uint64_t device_bytes;        /* the operator's own buffers */
+    double   ms_total;            /* wall time of the call */
+    double   ms_expand;           /* GPU time of expansion and count */
+    double   ms_select;           /* GPU time of the select rounds */
+    double   ms_emit;             /* GPU time of emit, sort and translation */
+} hb_links_stats;
+
+int hb_links_set_keys(hb_ctx *ctx, const hb_links_key_options *opt, hb_links_key_stats *stats);
+int hb_backlinks(hb_ctx *ctx, const hb_links_options *opt, hb_links_stats *stats);
+/* The result of the last hb_backlinks.  count: its queries and the entries of all lists.  copy: offsets[i] .. offsets[i + 1] is the list
+ * of query i (caller order; queries + 1 offsets), ids / keys the entries in list order (at most cap of them: cap >= entries),
+ * degrees[i] = degree(v_i); any of the four may be NULL, only what is asked for is downloaded. */
+int hb_links_count(hb_ctx *ctx, uint64_t *queries, uint64_t *entries);
+int hb_links_copy(hb_ctx *ctx, uint64_t *offsets, uint64_t *degrees, hb_u128 *ids, uint64_t *keys, uint64_t cap);
 
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) -------------------------------------- */
 /* Rank 0 calls this and distributes the 128 bytes (e.g. torch.distributed broadcast);

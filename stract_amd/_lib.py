@@ -342,6 +342,71 @@ class HbNearestSeedStats(ctypes.Structure):
         return d
 
 
+HB_LINKS_KEYS_FROM_RANKS = 0x1
+HB_LINKS_KEEP_SELF = 0x1
+HB_LINKS_SPREAD_ORDS = 0x2
+HB_LINKS_NO_SHORTCUT = 0x4
+
+
+class HbLinksKeyOptions(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("key_ids", ctypes.c_void_p),
+        ("keys", ctypes.c_void_p),
+        ("key_count", ctypes.c_uint64),
+    ]
+
+
+class HbLinksKeyStats(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("listed", ctypes.c_uint64),
+        ("unknown_keys", ctypes.c_uint64),
+        ("device_bytes", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+        ("ms_order", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class HbLinksOptions(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("nodes", ctypes.c_void_p),
+        ("node_count", ctypes.c_uint64),
+        ("limit", ctypes.c_uint32),
+        ("slots_per_batch", ctypes.c_uint32),
+    ]
+
+
+class HbLinksStats(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("queries", ctypes.c_uint64),
+        ("unknown", ctypes.c_uint64),
+        ("distinct", ctypes.c_uint64),
+        ("batches", ctypes.c_uint64),
+        ("entries", ctypes.c_uint64),
+        ("rows_walked", ctypes.c_uint64),
+        ("edges_gathered", ctypes.c_uint64),
+        ("selected", ctypes.c_uint64),
+        ("device_bytes", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+        ("ms_expand", ctypes.c_double),
+        ("ms_select", ctypes.c_double),
+        ("ms_emit", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/hyperball.h declares: (name, restype, argtypes)
 _P = ctypes.c_void_p
 _U64 = ctypes.c_uint64
@@ -498,6 +563,11 @@ _SIGNATURES += [
     ("hb_nearest_seed_all", ctypes.c_int, [_P, _P, _U64]),
     ("hb_nearest_seed_top", ctypes.c_int, [_P, _U64, _P, _P, ctypes.POINTER(_U64)]),
     ("hb_nearest_seed_seeds", ctypes.c_int, [_P, _P, _P, _U64]),
+    # include/hyperball.h: limited, rank-ordered host backlinks (HostBacklinksQuery .. Limit(L))
+    ("hb_links_set_keys", ctypes.c_int, [_P, ctypes.POINTER(HbLinksKeyOptions), ctypes.POINTER(HbLinksKeyStats)]),
+    ("hb_backlinks", ctypes.c_int, [_P, ctypes.POINTER(HbLinksOptions), ctypes.POINTER(HbLinksStats)]),
+    ("hb_links_count", ctypes.c_int, [_P, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("hb_links_copy", ctypes.c_int, [_P, _P, _P, _P, _P, _U64]),
 ]
 SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -1035,6 +1105,57 @@ class Context:
         has = np.zeros(n, dtype=np.uint8)
         self._check(self.lib.hb_nearest_seed_seeds(self.h, _ptr(seed), _ptr(has), n))
         return seed, has.astype(bool)
+
+    # -- limited, rank-ordered host backlinks (HostBacklinksQuery .. Limit(L), webgraph/query/backlink.rs:230-360)
+    def links_set_keys(self, key_ids=None, keys=None, from_ranks=False, flags=0):
+        """hb_links_set_keys: the order keys of the backlink lists (U128 / uint64 arrays; unlisted nodes have 2^64 - 1), or
+        from_ranks=True for the harmonic ranks of the context's live result; builds the dense order on the device.  Returns the stats."""
+        o = HbLinksKeyOptions()
+        o.struct_size = ctypes.sizeof(HbLinksKeyOptions)
+        o.flags = int(flags) | (HB_LINKS_KEYS_FROM_RANKS if from_ranks else 0)
+        if key_ids is not None and len(key_ids):
+            key_ids = np.ascontiguousarray(key_ids, dtype=U128)
+            keys = np.ascontiguousarray(keys, dtype=np.uint64)
+            if len(key_ids) != len(keys):
+                raise ValueError("key_ids and keys differ in length")
+            o.key_ids, o.keys, o.key_count = key_ids.ctypes.data, keys.ctypes.data, len(key_ids)
+        st = HbLinksKeyStats()
+        st.struct_size = ctypes.sizeof(HbLinksKeyStats)
+        self._check(self.lib.hb_links_set_keys(self.h, ctypes.byref(o), ctypes.byref(st)))
+        return st.as_dict()
+
+    def backlinks(self, nodes, limit, flags=0, slots_per_batch=0):
+        """hb_backlinks: the first `limit` in-neighbours of every node of `nodes` (U128 array) in the order (key, NodeID); returns the
+        stats, links_copy() the lists."""
+        o = HbLinksOptions()
+        o.struct_size = ctypes.sizeof(HbLinksOptions)
+        o.flags = int(flags)
+        nodes = np.ascontiguousarray(nodes, dtype=U128)
+        if len(nodes):
+            o.nodes, o.node_count = nodes.ctypes.data, len(nodes)
+        o.limit = int(limit)
+        o.slots_per_batch = int(slots_per_batch)
+        st = HbLinksStats()
+        st.struct_size = ctypes.sizeof(HbLinksStats)
+        self._check(self.lib.hb_backlinks(self.h, ctypes.byref(o), ctypes.byref(st)))
+        return st.as_dict()
+
+    def links_count(self):
+        """(queries, entries) of the last backlinks() call"""
+        q, e = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self.lib.hb_links_count(self.h, ctypes.byref(q), ctypes.byref(e)))
+        return q.value, e.value
+
+    def links_copy(self, ids=True, keys=True):
+        """The lists of the last backlinks() call: (offsets uint64 [queries + 1], ids U128, keys uint64, degrees uint64); query i's list
+        is ids[offsets[i]:offsets[i + 1]], in (key, NodeID) order.  ids=False / keys=False leaves that array on the device (None)."""
+        q, e = self.links_count()
+        offsets = np.zeros(q + 1, dtype=np.uint64)
+        degrees = np.zeros(q, dtype=np.uint64)
+        out_ids = np.zeros(e, dtype=U128) if ids else None
+        out_keys = np.zeros(e, dtype=np.uint64) if keys else None
+        self._check(self.lib.hb_links_copy(self.h, _ptr(offsets), _ptr(degrees), _ptr(out_ids) if ids else None, _ptr(out_keys) if keys else None, e))
+        return offsets, out_ids, out_keys, degrees
 
     # -- results
     def results(self):

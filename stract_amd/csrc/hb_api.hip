@@ -27,6 +27,7 @@
 #include "hb_betweenness.hip.h"
 #include "hb_similarity.hip.h"
 #include "hb_nearest_seed.hip.h"
+#include "hb_links.hip.h"
 #ifdef HB_EXPERIMENTS
 #include "hb_experiments.hip.h"
 #endif
@@ -253,6 +254,32 @@ struct GraphDeviceState {
         uint64_t results = 0;
         uint64_t bytes = 0;                      // device bytes of the above
     } nst;
+    // hb_links_set_keys / hb_backlinks (hb_api_links.inc): the key set and its dense order, the buffers of a batch and the last result.
+    // The holders own them (they grow with the limit, the slots of a batch and the queries of a call): freed by the next load, counted in
+    // `bytes` and in hb_stats.device_bytes.  The operator borrows nothing of the HyperBall state
+    struct LinksState {
+        bool ready = false; // key / ord / inv / ord_row exist and describe the current key set (none: NodeID order)
+        bool valid = false; // the result below is that of a finished hb_backlinks
+        DevPtr<unsigned long long> d_key; // n: key by sid, ~0 = not listed
+        DevPtr<uint32_t> d_ord;           // n: position of the sid in the sort by (key, sid)
+        DevPtr<uint32_t> d_inv;           // n: the sid at a position
+        DevPtr<uint32_t> d_ord_row;       // n_pad: ord by device row, kNone for padding rows
+        DevPtr<uint2> d_items;            // slots + nv + 16: (slot, row) of a batch, level by level
+        DevPtr<uint32_t> d_ctl;           // 5 x slots (deg, sel_k, sel_prefix, thr, cursor) + 64 level counts + 8 flag words
+        DevPtr<uint32_t> d_hist;          // slots x 256
+        DevPtr<uint32_t> d_out;           // slots x limit: the kept ords of a batch
+        DevPtr<uint32_t> d_slot_row;      // distinct: device row of every distinct queried node (ascending sid)
+        DevPtr<uint32_t> d_slot_self;     // distinct: the row its list must not hold (kNone: HB_LINKS_KEEP_SELF)
+        DevPtr<uint32_t> d_res_sid;       // distinct x limit: the lists as sids
+        DevPtr<unsigned long long> d_res_key; // distinct x limit: ... and their keys
+        uint64_t cap_key = 0, cap_ord = 0, cap_inv = 0, cap_ord_row = 0, cap_items = 0, cap_ctl = 0, cap_hist = 0, cap_out = 0, cap_slot_row = 0,
+                 cap_slot_self = 0, cap_res_sid = 0, cap_res_key = 0; // entries the holders have
+        uint32_t limit = 0;               // of the result
+        std::vector<uint32_t> query_slot; // per query of the last call: its distinct node, kNone = no node of the graph
+        std::vector<uint32_t> degree;     // per distinct node: degree(v)
+        uint64_t entries = 0;             // entries of all lists of the result
+        uint64_t bytes = 0;               // device bytes of the above
+    } lnk;
 };
 
 // The timing events of a pass (one set: hb_ctx::ev, or an EvSet), in the order a pass records them; kEvLevel1 lies between kEvStart and
@@ -1553,3 +1580,5 @@ int hb_store_harmonic_results(hb_ctx *c, const char *output, char *err, uint64_t
 #include "hb_api_similarity.inc"
 
 #include "hb_api_nearest_seed.inc"
+
+#include "hb_api_links.inc"
