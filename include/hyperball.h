@@ -618,8 +618,8 @@ int hb_nearest_seed_seeds(hb_ctx *ctx, hb_u128 *seed, uint8_t *has_seed, uint64_
  * lists of the queried hosts.  The result is deterministic.
  * Single rank only.  The operator borrows nothing: hb_run / hb_step, hb_result_*, hb_distances, hb_betweenness, hb_inbound_similarity
  * and hb_nearest_seed results are untouched; its buffers are its own, allocated at first use after a load, freed by the next load and
- * counted in device_bytes.  The result lives until the next successful hb_backlinks or the next load - a refused call leaves it as it
- * was.  Both calls are refused (HB_ERR_INVALID) between hb_begin and hb_finish, without a loaded graph and with world_size > 1;
+ * counted in device_bytes.  The result lives until the next successful hb_backlinks / hb_forwardlinks or the next load - a refused call
+ * leaves it as it was.  Both calls are refused (HB_ERR_INVALID) between hb_begin and hb_finish, without a loaded graph and with world_size > 1;
  * hb_links_set_keys also with a key pointer NULL and a non-zero count; hb_backlinks also with opt == NULL, limit 0 or above 1024,
  * slots_per_batch above 65536 and nodes == NULL with a non-zero node_count.  DESIGN.md section 27. */
 #define HB_LINKS_KEYS_FROM_RANKS 0x1u /* hb_links_set_keys: key = harmonic rank of the live result; key_* must be NULL / 0 */
@@ -669,11 +669,86 @@ typedef struct hb_links_stats {
 
 int hb_links_set_keys(hb_ctx *ctx, const hb_links_key_options *opt, hb_links_key_stats *stats);
 int hb_backlinks(hb_ctx *ctx, const hb_links_options *opt, hb_links_stats *stats);
-/* The result of the last hb_backlinks.  count: its queries and the entries of all lists.  copy: offsets[i] .. offsets[i + 1] is the list
+/* ---- limited, rank-ordered host forward links: HostForwardlinksQuery::new(u).with_limit(EdgeLimit::Limit(L)) (query/forwardlink.rs:183-330) ----
+ * The mirror of hb_backlinks, what SimilarHostsFinder::potential_nodes (similar_hosts.rs:118-165) sends with L = 512 from the sources of
+ * the liked hosts' backlinks.  out(u) = the out-neighbours v != u of u in the loaded graph (HB_LINKS_KEEP_SELF keeps a self link);
+ * order: (key[v], NodeID v) ascending - for a fixed source the reference's sort_score = source_rank + destination_rank orders by the
+ * destination's rank, so this is the order hb_links_set_keys built; forwardlinks(u, L) = the first min(L, |out(u)|) elements of out(u)
+ * in that order, listed in that order; degree(u) = |out(u)|.  The same options struct, limit range, batch knob, debug flags, refusals and
+ * defined differences as hb_backlinks (the L best of the WHOLE out-list, no L + 128 document short-circuit; keys unsaturated; no text
+ * or rel filters, no Unlimited, no offset).  In the stats rows_walked counts the pieces of 2048 reader-list entries the batches scanned,
+ * edges_gathered the sum of degree(u) over the distinct nodes.
+ * The first call after a load builds, besides the holders hb_backlinks has, a table of 4 x virtual_rows bytes (the node row on top of
+ * every hub-chunk row: an out-edge into a hub enters its chunk tree at some chunk row) and, in a context without sweep support
+ * (HB_FLAG_NO_SPARSE, unfused passes), the row -> readers transpose that hb_distances builds; it refuses with "unexpected plan layout"
+ * when a chunk row does not have exactly one reader.  Device memory is O(n_pad + nv + slots x (256 + limit)) besides the result: it does
+ * not grow with the out-degrees.  The result is deterministic and replaces that of the last hb_backlinks / hb_forwardlinks:
+ * hb_links_count / hb_links_copy read the last successful call of either direction.  DESIGN.md section 28. */
+int hb_forwardlinks(hb_ctx *ctx, const hb_links_options *opt, hb_links_stats *stats);
+/* The result of the last hb_backlinks / hb_forwardlinks.  count: its queries and the entries of all lists.  copy: offsets[i] .. offsets[i + 1] is the list
  * of query i (caller order; queries + 1 offsets), ids / keys the entries in list order (at most cap of them: cap >= entries),
  * degrees[i] = degree(v_i); any of the four may be NULL, only what is asked for is downloaded. */
 int hb_links_count(hb_ctx *ctx, uint64_t *queries, uint64_t *entries);
 int hb_links_copy(hb_ctx *ctx, uint64_t *offsets, uint64_t *degrees, hb_u128 *ids, uint64_t *keys, uint64_t cap);
+
+/* ---- similar hosts: scored_nodes of SimilarHostsFinder::find_similar_hosts (similar_hosts.rs:54-272) for a list of liked hosts ---- */
+/* Input: nodes[0 .. N) and limit k.  N counts the entries as given: a duplicate counts twice in the score and in N, an id that is no node
+ * contributes nothing but counts in N.  With backlinks / forwardlinks as defined above, under the current key set:
+ *  1. In512(a) = backlinks(a, 512) of every distinct liked host; its first 128 entries are backlinks(a, 128) (similar_hosts.rs:118-131).
+ *  2. B = the distinct sources in those 128-prefixes, nb = |B|.
+ *  3. forwardlinks(b, 512) of every b in B (:133-143).
+ *  4. count[v] = the number of those lists that contain v.  apply = nb > 32; with apply only count[v] <= ceil(0.25 nb) stay - the bound
+ *     is computed in integers as (nb + 3) / 4 (:145-151); the rest ordered by (count descending, NodeID ascending) - the reference's tie
+ *     order is hash-map iteration order, this one is the defined difference -; the first (apply ? 256 : 1024) are taken; only THEN are
+ *     the liked hosts dropped (:152-164, in that order: a liked host inside the prefix leaves the list one short).
+ *  5. BitVec of a candidate c = backlinks(c, 512): len = min(degree, 512), the entries sorted, the 64-bit bloom mask of
+ *     hb_inbound_similarity (bit (low64(id) x 11400714819323198549) & 63) over THOSE entries only (searcher/api/mod.rs:199-216,
+ *     ranking/bitvec_similarity.rs:131-180).
+ *  6. score[c] = max(0, (sum over the entries a in caller order, from 0.0, of sim(a, c)) / max(N, 1)) - Scorer::new(liked, [],
+ *     normalized = true).  sim = 0 when 4 popcount(mask_a & mask_c) < max(popcount mask_a, popcount mask_c) (integers) or a list is
+ *     empty, else |In512(a) & In512(c)| / (sqrt((double)len_a) x sqrt((double)len_c)): IEEE sqrt, one multiply, one divide, no FMA
+ *     contraction, no floating-point atomics.
+ *  7. the first min(k, candidates) by (score descending, NodeID descending): sorted_k over Reverse((SortableFloat, NodeID)), the tie
+ *     rule of hb_similarity_top.
+ * The reference's dead-link pass (:228-237) is not built: on one consistent graph it is vacuous - a candidate was reached over an edge
+ * from some b != c, so its in-degree is at least 1.  Names, root_domain and the `limit + len + 30` arithmetic stay with the caller
+ * (stract_amd/similar_hosts.py does them in Python).  The steps run on the device; sizes and the two final lists (at most 1024 entries
+ * each) come to the host.  hb_similar_candidates returns the pre-selection of step 4 after the liked hosts are dropped, in its order,
+ * with the counts.  flags: HB_LINKS_SPREAD_ORDS / HB_LINKS_NO_SHORTCUT reach the list selects (debug: same result).
+ * The operator borrows nothing, leaves the result of the last hb_backlinks / hb_forwardlinks readable (its lists go to buffers of its
+ * own, counted in device_bytes), and its result lives until the next successful call or the next load; a refused call changes nothing.
+ * Refused (HB_ERR_INVALID): opt == NULL, node_count == 0, nodes == NULL, more than 256 distinct known nodes, limit outside 1 .. 1024,
+ * between hb_begin and hb_finish, without a loaded graph, world_size > 1.  DESIGN.md section 28. */
+typedef struct hb_similar_options {
+    uint32_t struct_size, flags;                    /* struct_size = sizeof(hb_similar_options); 0 = this version */
+    const hb_u128 *nodes; uint64_t node_count;      /* the liked hosts, in the order the score sums them */
+    uint32_t limit, reserved;                       /* k: 1 .. 1024 */
+} hb_similar_options;
+
+typedef struct hb_similar_stats {
+    uint32_t struct_size;         /* = sizeof(hb_similar_stats); 0 = this version */
+    uint32_t apply;               /* 1 = the popularity filter was on (nb > 32) */
+    uint64_t liked_distinct;      /* distinct known liked hosts */
+    uint64_t unknown;             /* entries that are no node of the graph */
+    uint64_t nb;                  /* |B| */
+    uint64_t forward_entries;     /* entries of the forward lists of B */
+    uint64_t distinct_targets;    /* nodes with count > 0 */
+    uint64_t count_bound;         /* (nb + 3) / 4 */
+    uint64_t taken;               /* entries taken in step 4 before the liked hosts are dropped */
+    uint64_t candidates;          /* ... after */
+    uint64_t pairs_gated;         /* (candidate, entry) pairs the bloom gate set to 0 */
+    uint64_t pairs_intersected;   /* ... whose lists were intersected */
+    uint64_t written;             /* min(k, candidates) */
+    uint64_t device_bytes;        /* the operator's own buffers */
+    double   ms_total;            /* wall time of the call */
+    double   ms_in, ms_forward, ms_count, ms_bitvec, ms_score;   /* wall time per stage: steps 1-2, 3, 4, 5, 6-7 */
+    double   ms_gpu_lists, ms_gpu_score;                         /* GPU time of the list selects; of score + top */
+} hb_similar_stats;
+
+int hb_similar_hosts(hb_ctx *ctx, const hb_similar_options *opt, hb_similar_stats *stats);
+int hb_similar_count(hb_ctx *ctx, uint64_t *count);
+int hb_similar_copy(hb_ctx *ctx, hb_u128 *ids, double *scores, uint64_t cap);   /* the top list, at most cap >= count entries */
+int hb_similar_candidates(hb_ctx *ctx, hb_u128 *ids, uint64_t *counts, uint64_t cap, uint64_t *written); /* ids / counts may be NULL */
 
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) -------------------------------------- */
 /* Rank 0 calls this and distributes the 128 bytes (e.g. torch.distributed broadcast);

@@ -348,6 +348,29 @@ HB_LINKS_SPREAD_ORDS = 0x2
 HB_LINKS_NO_SHORTCUT = 0x4
 
 
+class HbSimilarOptions(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("nodes", ctypes.c_void_p),
+        ("node_count", ctypes.c_uint64),
+        ("limit", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class HbSimilarStats(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("apply", ctypes.c_uint32),
+    ] + [(k, ctypes.c_uint64) for k in ("liked_distinct", "unknown", "nb", "forward_entries", "distinct_targets", "count_bound", "taken", "candidates",
+                                        "pairs_gated", "pairs_intersected", "written", "device_bytes")] + [
+        (k, ctypes.c_double) for k in ("ms_total", "ms_in", "ms_forward", "ms_count", "ms_bitvec", "ms_score", "ms_gpu_lists", "ms_gpu_score")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class HbLinksKeyOptions(ctypes.Structure):
     _fields_ = [
         ("struct_size", ctypes.c_uint32),
@@ -566,8 +589,14 @@ _SIGNATURES += [
     # include/hyperball.h: limited, rank-ordered host backlinks (HostBacklinksQuery .. Limit(L))
     ("hb_links_set_keys", ctypes.c_int, [_P, ctypes.POINTER(HbLinksKeyOptions), ctypes.POINTER(HbLinksKeyStats)]),
     ("hb_backlinks", ctypes.c_int, [_P, ctypes.POINTER(HbLinksOptions), ctypes.POINTER(HbLinksStats)]),
+    ("hb_forwardlinks", ctypes.c_int, [_P, ctypes.POINTER(HbLinksOptions), ctypes.POINTER(HbLinksStats)]),
     ("hb_links_count", ctypes.c_int, [_P, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
     ("hb_links_copy", ctypes.c_int, [_P, _P, _P, _P, _P, _U64]),
+    # include/hyperball.h: similar hosts (scored_nodes of SimilarHostsFinder)
+    ("hb_similar_hosts", ctypes.c_int, [_P, ctypes.POINTER(HbSimilarOptions), ctypes.POINTER(HbSimilarStats)]),
+    ("hb_similar_count", ctypes.c_int, [_P, ctypes.POINTER(_U64)]),
+    ("hb_similar_copy", ctypes.c_int, [_P, _P, _P, _U64]),
+    ("hb_similar_candidates", ctypes.c_int, [_P, _P, _P, _U64, ctypes.POINTER(_U64)]),
 ]
 SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -1127,6 +1156,14 @@ class Context:
     def backlinks(self, nodes, limit, flags=0, slots_per_batch=0):
         """hb_backlinks: the first `limit` in-neighbours of every node of `nodes` (U128 array) in the order (key, NodeID); returns the
         stats, links_copy() the lists."""
+        return self._links_query(self.lib.hb_backlinks, nodes, limit, flags, slots_per_batch)
+
+    def forwardlinks(self, nodes, limit, flags=0, slots_per_batch=0):
+        """hb_forwardlinks (HostForwardlinksQuery .. Limit(L), webgraph/query/forwardlink.rs:183-330): the first `limit` out-neighbours
+        of every node of `nodes` (U128 array) in the order (key, NodeID); returns the stats, links_copy() the lists."""
+        return self._links_query(self.lib.hb_forwardlinks, nodes, limit, flags, slots_per_batch)
+
+    def _links_query(self, call, nodes, limit, flags, slots_per_batch):
         o = HbLinksOptions()
         o.struct_size = ctypes.sizeof(HbLinksOptions)
         o.flags = int(flags)
@@ -1137,17 +1174,17 @@ class Context:
         o.slots_per_batch = int(slots_per_batch)
         st = HbLinksStats()
         st.struct_size = ctypes.sizeof(HbLinksStats)
-        self._check(self.lib.hb_backlinks(self.h, ctypes.byref(o), ctypes.byref(st)))
+        self._check(call(self.h, ctypes.byref(o), ctypes.byref(st)))
         return st.as_dict()
 
     def links_count(self):
-        """(queries, entries) of the last backlinks() call"""
+        """(queries, entries) of the last backlinks() / forwardlinks() call"""
         q, e = ctypes.c_uint64(0), ctypes.c_uint64(0)
         self._check(self.lib.hb_links_count(self.h, ctypes.byref(q), ctypes.byref(e)))
         return q.value, e.value
 
     def links_copy(self, ids=True, keys=True):
-        """The lists of the last backlinks() call: (offsets uint64 [queries + 1], ids U128, keys uint64, degrees uint64); query i's list
+        """The lists of the last backlinks() / forwardlinks() call: (offsets uint64 [queries + 1], ids U128, keys uint64, degrees uint64); query i's list
         is ids[offsets[i]:offsets[i + 1]], in (key, NodeID) order.  ids=False / keys=False leaves that array on the device (None)."""
         q, e = self.links_count()
         offsets = np.zeros(q + 1, dtype=np.uint64)
@@ -1156,6 +1193,40 @@ class Context:
         out_keys = np.zeros(e, dtype=np.uint64) if keys else None
         self._check(self.lib.hb_links_copy(self.h, _ptr(offsets), _ptr(degrees), _ptr(out_ids) if ids else None, _ptr(out_keys) if keys else None, e))
         return offsets, out_ids, out_keys, degrees
+
+    # -- similar hosts (scored_nodes of SimilarHostsFinder::find_similar_hosts, similar_hosts.rs:54-272)
+    def similar_hosts(self, nodes, limit, flags=0):
+        """hb_similar_hosts: the `limit` hosts most similar to the liked hosts `nodes` (U128 array, caller order; duplicates and unknown
+        ids count); returns the stats, similar_copy() the list, similar_candidates() the co-citation pre-selection."""
+        o = HbSimilarOptions()
+        o.struct_size = ctypes.sizeof(HbSimilarOptions)
+        o.flags = int(flags)
+        nodes = np.ascontiguousarray(nodes, dtype=U128)
+        if len(nodes):
+            o.nodes, o.node_count = nodes.ctypes.data, len(nodes)
+        o.limit = int(limit)
+        st = HbSimilarStats()
+        st.struct_size = ctypes.sizeof(HbSimilarStats)
+        self._check(self.lib.hb_similar_hosts(self.h, ctypes.byref(o), ctypes.byref(st)))
+        return st.as_dict()
+
+    def similar_copy(self):
+        """(ids U128, scores float64) of the last similar_hosts() call, best first"""
+        k = ctypes.c_uint64(0)
+        self._check(self.lib.hb_similar_count(self.h, ctypes.byref(k)))
+        ids = np.zeros(k.value, dtype=U128)
+        scores = np.zeros(k.value, dtype=np.float64)
+        self._check(self.lib.hb_similar_copy(self.h, _ptr(ids), _ptr(scores), k.value))
+        return ids, scores
+
+    def similar_candidates(self):
+        """(ids U128, counts uint64): the pre-selection of the last similar_hosts() call after the liked hosts were dropped, in its order"""
+        w = ctypes.c_uint64(0)
+        self._check(self.lib.hb_similar_candidates(self.h, None, None, 0, ctypes.byref(w)))
+        ids = np.zeros(w.value, dtype=U128)
+        counts = np.zeros(w.value, dtype=np.uint64)
+        self._check(self.lib.hb_similar_candidates(self.h, _ptr(ids), _ptr(counts), w.value, ctypes.byref(w)))
+        return ids, counts
 
     # -- results
     def results(self):

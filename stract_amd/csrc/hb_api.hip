@@ -28,6 +28,7 @@
 #include "hb_similarity.hip.h"
 #include "hb_nearest_seed.hip.h"
 #include "hb_links.hip.h"
+#include "hb_similar.hip.h"
 #ifdef HB_EXPERIMENTS
 #include "hb_experiments.hip.h"
 #endif
@@ -254,32 +255,61 @@ struct GraphDeviceState {
         uint64_t results = 0;
         uint64_t bytes = 0;                      // device bytes of the above
     } nst;
-    // hb_links_set_keys / hb_backlinks (hb_api_links.inc): the key set and its dense order, the buffers of a batch and the last result.
+    // hb_links_set_keys / hb_backlinks / hb_forwardlinks (hb_api_links.inc): the key set and its dense order, the buffers of a batch and the last result.
     // The holders own them (they grow with the limit, the slots of a batch and the queries of a call): freed by the next load, counted in
     // `bytes` and in hb_stats.device_bytes.  The operator borrows nothing of the HyperBall state
     struct LinksState {
         bool ready = false; // key / ord / inv / ord_row exist and describe the current key set (none: NodeID order)
-        bool valid = false; // the result below is that of a finished hb_backlinks
+        bool valid = false; // the result below is that of a finished hb_backlinks / hb_forwardlinks
         DevPtr<unsigned long long> d_key; // n: key by sid, ~0 = not listed
         DevPtr<uint32_t> d_ord;           // n: position of the sid in the sort by (key, sid)
         DevPtr<uint32_t> d_inv;           // n: the sid at a position
         DevPtr<uint32_t> d_ord_row;       // n_pad: ord by device row, kNone for padding rows
         DevPtr<uint2> d_items;            // slots + nv + 16: (slot, row) of a batch, level by level
-        DevPtr<uint32_t> d_ctl;           // 5 x slots (deg, sel_k, sel_prefix, thr, cursor) + 64 level counts + 8 flag words
+        DevPtr<uint32_t> d_ctl;           // 5 x slots (deg, sel_k, sel_prefix, thr, cursor) + 64 level counts + 8 flag words (+ forward: slots lengths, slots + 1 segment offsets)
         DevPtr<uint32_t> d_hist;          // slots x 256
         DevPtr<uint32_t> d_out;           // slots x limit: the kept ords of a batch
         DevPtr<uint32_t> d_slot_row;      // distinct: device row of every distinct queried node (ascending sid)
         DevPtr<uint32_t> d_slot_self;     // distinct: the row its list must not hold (kNone: HB_LINKS_KEEP_SELF)
         DevPtr<uint32_t> d_res_sid;       // distinct x limit: the lists as sids
         DevPtr<unsigned long long> d_res_key; // distinct x limit: ... and their keys
+        DevPtr<uint32_t> d_top_row;       // nv: hb_forwardlinks: the node row at the top of every chunk row's tree (kNone: a padding row)
+        bool top_ready = false;           // d_top_row describes the loaded graph (built by the first hb_forwardlinks after a load)
         uint64_t cap_key = 0, cap_ord = 0, cap_inv = 0, cap_ord_row = 0, cap_items = 0, cap_ctl = 0, cap_hist = 0, cap_out = 0, cap_slot_row = 0,
-                 cap_slot_self = 0, cap_res_sid = 0, cap_res_key = 0; // entries the holders have
+                 cap_slot_self = 0, cap_res_sid = 0, cap_res_key = 0, cap_top_row = 0; // entries the holders have
         uint32_t limit = 0;               // of the result
         std::vector<uint32_t> query_slot; // per query of the last call: its distinct node, kNone = no node of the graph
         std::vector<uint32_t> degree;     // per distinct node: degree(v)
         uint64_t entries = 0;             // entries of all lists of the result
         uint64_t bytes = 0;               // device bytes of the above
     } lnk;
+    // hb_similar_hosts (hb_api_similar.inc): its four sets of lists, the counters and the last result.  The holders own them (they grow
+    // with the liked hosts and the co-citation sources of a call): freed by the next load, counted in `bytes` and in
+    // hb_stats.device_bytes.  The operator borrows nothing and leaves the links result as it is; the buffers of a batch of the list
+    // builder are the links state's
+    struct SimilarHostsState {
+        bool valid = false; // the result below is that of a finished hb_similar_hosts
+        DevPtr<uint32_t> d_in, d_in_len;          // liked x 512: In512 of the distinct liked hosts (sorted by sid once scored), their degrees
+        DevPtr<unsigned long long> d_in_mask;     // liked: their bloom masks
+        DevPtr<uint32_t> d_src;                   // liked x 128: B, the distinct sources of the 128-prefixes
+        DevPtr<uint32_t> d_fw, d_fw_len;          // nb x 512: their forward lists, the degrees
+        DevPtr<uint32_t> d_count;                 // n: the flag words of B, then count[v]
+        DevPtr<uint32_t> d_touched;               // min(n, nb x 512): the distinct targets
+        DevPtr<uint32_t> d_cand, d_cand_count;    // 1024: the pre-selection and its counts
+        DevPtr<uint32_t> d_cin, d_cin_len;        // 1024 x 512: In512 of the candidates
+        DevPtr<unsigned long long> d_cin_mask;    // 1024
+        DevPtr<unsigned long long> d_keys;        // the lists' keys (the list builder writes them; nobody reads them here)
+        DevPtr<uint32_t> d_liked, d_anchor;       // liked: the distinct liked sids ascending; N: the entries in caller order as slots
+        DevPtr<double> d_score, d_top_score;      // 1024
+        DevPtr<uint32_t> d_top_sid;               // 1024
+        DevPtr<unsigned long long> d_cnt;         // 8 words: cursors (as u32) and the pair counters
+        uint64_t cap_in = 0, cap_in_len = 0, cap_in_mask = 0, cap_src = 0, cap_fw = 0, cap_fw_len = 0, cap_count = 0, cap_touched = 0, cap_cand = 0,
+                 cap_cand_count = 0, cap_cin = 0, cap_cin_len = 0, cap_cin_mask = 0, cap_keys = 0, cap_liked = 0, cap_anchor = 0, cap_score = 0,
+                 cap_top_score = 0, cap_top_sid = 0, cap_cnt = 0;
+        std::vector<uint32_t> cand_sid, cand_count, top_sid; // the result on the host: at most 1024 entries each
+        std::vector<double> top_score;
+        uint64_t bytes = 0;
+    } shs;
 };
 
 // The timing events of a pass (one set: hb_ctx::ev, or an EvSet), in the order a pass records them; kEvLevel1 lies between kEvStart and
@@ -1582,3 +1612,4 @@ int hb_store_harmonic_results(hb_ctx *c, const char *output, char *err, uint64_t
 #include "hb_api_nearest_seed.inc"
 
 #include "hb_api_links.inc"
+#include "hb_api_similar.inc"

@@ -1,7 +1,8 @@
 // hb_api_links.inc - part of the hb_api.hip translation unit (included at its end; uses its hb_ctx and helpers).
 // hb_links_set_keys / hb_backlinks: HostBacklinksQuery::new(node).with_limit(EdgeLimit::Limit(L)) (webgraph/query/backlink.rs:230-360)
 // for a list of hosts per call - the L best in-neighbours of every queried host in the order (key, NodeID), by a radix select on a dense
-// order that stays on the device between calls (kernels: hb_links.hip.h).  Definitions: include/hyperball.h.  Like hb_distances and
+// order that stays on the device between calls (kernels: hb_links.hip.h) - and hb_forwardlinks, HostForwardlinksQuery .. Limit(L)
+// (webgraph/query/forwardlink.rs:183-330), the same for the out-neighbours.  Definitions: include/hyperball.h.  Like hb_distances and
 // hb_nearest_seed the operator borrows nothing: no claim_rows, no take_image; every buffer is its own (GraphDeviceState::lnk).
 
 namespace {
@@ -133,22 +134,57 @@ int links_set_keys(hb_ctx *c, const hb_links_key_options *opt_in, hb_links_key_s
     return HB_OK;
 }
 
-int backlinks(hb_ctx *c, const hb_links_options *opt_in, hb_links_stats *st_out)
+// hb_forwardlinks: the transpose (built here for a context without sweep support) and top_row, once per load.  A reader list names the
+// chunk row an edge enters a hub's tree at; top_row[chunk row - n_pad] = the hub's node row.  One launch per virtual level from the
+// highest down: a chunk row's single reader is its hub or a chunk row of a higher level.  A chunk row with a list and a reader count
+// other than one (or a reader that is no higher level) is refused, not resolved.
+int links_top_rows(hb_ctx *c, const std::string &who, double *ms)
+{
+    auto &s = c->lnk;
+    const Plan &p = c->plan;
+    int rc;
+    if ((rc = ensure_transpose(c, who.c_str()))) return rc;
+    if (s.top_ready) return HB_OK;
+    if ((rc = links_hold(c, s.d_top_row, s.cap_top_row, p.nv + 1))) return rc; // (+ 1: the flag word behind the table)
+    uint32_t *top = s.d_top_row.get(), *flag = top + p.nv;
+    HB_HIP(hipMemsetAsync(top, 0xFF, p.nv * sizeof(uint32_t), c->stream));
+    HB_HIP(hipMemsetAsync(flag, 0, sizeof(uint32_t), c->stream));
+    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    for_each_virtual_level(p, false, [&](uint64_t lo, uint64_t hi) { // the highest level first: a level reads the tops of the levels above it
+        hipLaunchKernelGGL(hbk::fw_top_row_kernel, dim3(grid_blocks(c, (hi - lo + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr,
+                           (const uint64_t *)c->d_out_ptr, (const uint32_t *)c->d_out_rows, p.n_pad, p.n_pad + p.nv, lo, hi, top, flag);
+    });
+    HB_HIP(hipGetLastError());
+    uint32_t *h32 = (uint32_t *)c->h_counters;
+    HB_HIP(hipMemcpyAsync(h32, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = nearest_seed_lap(c, ms))) return rc;
+    if (h32[0]) return fail(c, HB_ERR_INVALID, who + ": unexpected plan layout (a chunk row with a list does not have exactly one reader above it)");
+    s.top_ready = true;
+    return HB_OK;
+}
+
+int links_lists(hb_ctx *c, const std::string &who, bool forward, const uint32_t *h_sids, const uint32_t *d_sids, uint64_t U, const hb_links_options &o,
+                uint32_t *res_sid, unsigned long long *res_key, uint32_t *d_len, std::vector<uint32_t> &degree, hb_links_stats &st);
+
+// hb_backlinks (forward = false) and hb_forwardlinks: the refusals, the distinct queried nodes, the holders and the result are the same;
+// a batch is the in-lists' item walk or the out-lists' segment walk
+int links_query(hb_ctx *c, const hb_links_options *opt_in, hb_links_stats *st_out, bool forward)
 {
     const double t0 = now_ms();
+    const std::string who = forward ? "hb_forwardlinks" : "hb_backlinks";
     hb_links_options o{};
     copy_in(opt_in, &o);
     // ---- refusals: all of them before anything of the previous result is touched
-    if (!opt_in) return fail(c, HB_ERR_INVALID, "hb_backlinks: opt == NULL (limit has no default)");
-    if (o.limit < 1 || o.limit > hbk::kLkMaxLimit) return fail(c, HB_ERR_INVALID, "hb_backlinks: limit must be 1 .. 1024");
-    if (o.slots_per_batch > kLinksMaxSlots) return fail(c, HB_ERR_INVALID, "hb_backlinks: slots_per_batch > 65536");
-    if (o.node_count && !o.nodes) return fail(c, HB_ERR_INVALID, "hb_backlinks: node_count without nodes");
-    if (o.node_count >= (1ull << 32)) return fail(c, HB_ERR_INVALID, "hb_backlinks: too many queries");
+    if (!opt_in) return fail(c, HB_ERR_INVALID, who + ": opt == NULL (limit has no default)");
+    if (o.limit < 1 || o.limit > hbk::kLkMaxLimit) return fail(c, HB_ERR_INVALID, who + ": limit must be 1 .. 1024");
+    if (o.slots_per_batch > kLinksMaxSlots) return fail(c, HB_ERR_INVALID, who + ": slots_per_batch > 65536");
+    if (o.node_count && !o.nodes) return fail(c, HB_ERR_INVALID, who + ": node_count without nodes");
+    if (o.node_count >= (1ull << 32)) return fail(c, HB_ERR_INVALID, who + ": too many queries");
     const Plan &p = c->plan;
     const uint64_t n = p.n, limit = o.limit;
     size_t nlev = 0;
     for_each_virtual_level(p, true, [&](uint64_t, uint64_t) { nlev++; });
-    if (nlev + 2 > 64) return fail(c, HB_ERR_INVALID, "hb_backlinks: unexpected plan layout (more than 62 virtual levels)");
+    if (nlev + 2 > 64) return fail(c, HB_ERR_INVALID, who + ": unexpected plan layout (more than 62 virtual levels)");
     auto &s = c->lnk;
     hb_links_stats st{};
     int rc;
@@ -168,6 +204,7 @@ int backlinks(hb_ctx *c, const hb_links_options *opt_in, hb_links_stats *st_out)
         if (qsid[i] == kNone) st.unknown++;
         else query_slot[i] = (uint32_t)(std::lower_bound(distinct.begin(), distinct.end(), qsid[i]) - distinct.begin());
     }
+    if (forward && U && (rc = links_top_rows(c, who, &st.ms_expand))) return rc; // (it may refuse: before the previous result is touched)
     s.valid = false;
     auto finish = [&]() {
         s.query_slot.swap(query_slot);
@@ -184,20 +221,38 @@ int backlinks(hb_ctx *c, const hb_links_options *opt_in, hb_links_stats *st_out)
         return HB_OK;
     };
     if (!U) return finish();
+    if ((rc = links_hold(c, s.d_res_sid, s.cap_res_sid, U * limit))) return rc;
+    if ((rc = links_hold(c, s.d_res_key, s.cap_res_key, U * limit))) return rc;
+    if ((rc = links_lists(c, who, forward, distinct.data(), nullptr, U, o, s.d_res_sid.get(), s.d_res_key.get(), nullptr, degree, st))) return rc;
+    return finish();
+}
+
+// The lists of U distinct nodes - their sids on the host (h_sids) or on the device (d_sids) - into res_sid / res_key (U x limit each,
+// list order; the caller's buffers) and their degrees; d_len, if given, gets the degrees on the device as well.  The batch loop of
+// hb_backlinks / hb_forwardlinks, and what hb_similar_hosts builds its four sets of lists with.  The buffers of a batch are the links
+// state's: they hold nothing between two calls.
+int links_lists(hb_ctx *c, const std::string &who, bool forward, const uint32_t *h_sids, const uint32_t *d_sids, uint64_t U, const hb_links_options &o,
+                uint32_t *res_sid, unsigned long long *res_key, uint32_t *d_len, std::vector<uint32_t> &degree, hb_links_stats &st)
+{
+    const Plan &p = c->plan;
+    const uint64_t n = p.n, limit = o.limit;
+    size_t nlev = 0;
+    for_each_virtual_level(p, true, [&](uint64_t, uint64_t) { nlev++; });
+    auto &s = c->lnk;
+    int rc;
     if ((rc = links_alloc(c, true))) return rc;
     const uint64_t slots_max = std::min<uint64_t>(o.slots_per_batch ? o.slots_per_batch : kLinksDefaultSlots, U);
-    const uint64_t item_cap = slots_max + p.nv + 16, ctl_words = 5 * slots_max + 64 + 8;
-    if ((rc = links_hold(c, s.d_items, s.cap_items, item_cap))) return rc;
+    // (forward: no items; behind the backlinks' control words the lengths of the reader lists and the segment offsets, slots + 1)
+    const uint64_t item_cap = slots_max + p.nv + 16, ctl_words = 5 * slots_max + 64 + 8 + (forward ? 2 * slots_max + 1 : 0);
+    if (!forward && (rc = links_hold(c, s.d_items, s.cap_items, item_cap))) return rc;
     if ((rc = links_hold(c, s.d_hist, s.cap_hist, slots_max * 256))) return rc;
     if ((rc = links_hold(c, s.d_ctl, s.cap_ctl, ctl_words))) return rc;
     if ((rc = links_hold(c, s.d_out, s.cap_out, slots_max * limit))) return rc;
     if ((rc = links_hold(c, s.d_slot_row, s.cap_slot_row, U))) return rc;
     if ((rc = links_hold(c, s.d_slot_self, s.cap_slot_self, U))) return rc;
-    if ((rc = links_hold(c, s.d_res_sid, s.cap_res_sid, U * limit))) return rc;
-    if ((rc = links_hold(c, s.d_res_key, s.cap_res_key, U * limit))) return rc;
     // the rows of the distinct nodes (the plan's sid -> row table is on the device: gathered there, from the sids in d_slot_self)
     {
-        HB_HIP(hipMemcpyAsync(s.d_slot_self.get(), distinct.data(), U * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HB_HIP(hipMemcpyAsync(s.d_slot_self.get(), h_sids ? h_sids : d_sids, U * sizeof(uint32_t), h_sids ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
         hipLaunchKernelGGL(hbk::lk_rows_kernel, dim3(grid_blocks(c, (U + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint32_t *)c->d_dev_of, U,
                            (o.flags & HB_LINKS_KEEP_SELF) ? 1u : 0u, s.d_slot_row.get(), s.d_slot_self.get());
         HB_HIP(hipGetLastError());
@@ -206,7 +261,7 @@ int backlinks(hb_ctx *c, const hb_links_options *opt_in, hb_links_stats *st_out)
     const uint64_t mult = spread ? (1ull << 32) / n : 1ull, max_value = (n - 1) * mult;
     const int top_digit = max_value >= (1ull << 24) ? 3 : max_value >= (1ull << 16) ? 2 : max_value >= (1ull << 8) ? 1 : 0; // the rounds n's bits need
     uint32_t *h32 = (uint32_t *)c->h_counters; // (pinned words of the context; hb_run rewrites them before it reads them)
-    std::vector<uint32_t> deg(slots_max);
+    std::vector<uint32_t> deg(slots_max), seg_base(forward ? slots_max + 1 : 0);
 
     for (uint64_t base = 0; base < U; base += slots_max) {
         const uint64_t S = std::min<uint64_t>(slots_max, U - base);
@@ -236,23 +291,50 @@ int backlinks(hb_ctx *c, const hb_links_options *opt_in, hb_links_stats *st_out)
         const unsigned slot_blocks = (unsigned)((S + 255) / 256);
         st.batches++;
 
-        // ---- expand and count: level by level down the queried hosts' trees
+        // ---- expand and count: level by level down the queried hosts' trees; forward: the reader lists, cut into segments
         HB_HIP(hipMemsetAsync(ctl, 0, ctl_words * sizeof(uint32_t), c->stream));
         HB_HIP(hipMemsetAsync(b.hist, 0, S * 256 * sizeof(uint32_t), c->stream));
         HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
-        hipLaunchKernelGGL(hbk::lk_seed_kernel, dim3(slot_blocks), dim3(256), 0, c->stream, b);
         uint64_t lo = 0, hi = S;
-        for (size_t lev = 0; lo < hi; lev++) {
-            if (lev > nlev) return fail(c, HB_ERR_INVALID, "hb_backlinks: unexpected plan layout (a chunk tree is deeper than the virtual levels)");
-            hipLaunchKernelGGL(hbk::lk_expand_kernel, dim3(grid_blocks(c, (hi - lo + hbk::kLkItems - 1) / hbk::kLkItems, 8, 1)), dim3(256), 0, c->stream, b, lo, hi, hi,
-                               lvl_cnt + lev);
+        hbk::FwBatch f{};
+        unsigned seg_blocks = 1;
+        if (forward) {
+            uint32_t *raw = b.flag + 8, *d_seg_base = raw + slots_max;
+            f.out_ptr = c->d_out_ptr;
+            f.out_rows = c->d_out_rows;
+            f.top_row = s.d_top_row.get();
+            f.seg_base = d_seg_base;
+            hipLaunchKernelGGL(hbk::fw_len_kernel, dim3(slot_blocks), dim3(256), 0, c->stream, b, f, raw);
             HB_HIP(hipGetLastError());
-            HB_HIP(hipMemcpyAsync(h32, lvl_cnt + lev, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-            HB_HIP(hipMemcpyAsync(h32 + 1, b.flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            HB_HIP(hipMemcpyAsync(deg.data(), raw, S * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             HB_HIP(hipStreamSynchronize(c->stream));
-            if (h32[1] || hi + h32[0] > item_cap) return fail(c, HB_ERR_INVALID, "hb_backlinks: unexpected plan layout (the chunk rows of a batch outnumber the plan's)");
-            lo = hi;
-            hi += h32[0];
+            uint64_t segs = 0;
+            for (uint64_t i = 0; i < S; i++) {
+                seg_base[i] = (uint32_t)segs;
+                segs += (deg[i] + hbk::kFwSegment - 1) / hbk::kFwSegment;
+            }
+            seg_base[S] = (uint32_t)segs;
+            if (segs >= (1ull << 32)) return fail(c, HB_ERR_INVALID, who + ": unexpected plan layout (the reader lists of a batch exceed the plan's entries)");
+            f.segs = (uint32_t)segs;
+            hi = segs; // (what rows_walked counts: the segments scanned)
+            HB_HIP(hipMemcpyAsync(d_seg_base, seg_base.data(), (S + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+            seg_blocks = grid_blocks(c, std::max<uint64_t>(segs, 1), 8, 1);
+            if (segs) hipLaunchKernelGGL(hbk::fw_count_kernel, dim3(seg_blocks), dim3(256), 0, c->stream, b, f);
+            HB_HIP(hipGetLastError());
+        } else {
+            hipLaunchKernelGGL(hbk::lk_seed_kernel, dim3(slot_blocks), dim3(256), 0, c->stream, b);
+            for (size_t lev = 0; lo < hi; lev++) {
+                if (lev > nlev) return fail(c, HB_ERR_INVALID, who + ": unexpected plan layout (a chunk tree is deeper than the virtual levels)");
+                hipLaunchKernelGGL(hbk::lk_expand_kernel, dim3(grid_blocks(c, (hi - lo + hbk::kLkItems - 1) / hbk::kLkItems, 8, 1)), dim3(256), 0, c->stream, b, lo, hi, hi,
+                                   lvl_cnt + lev);
+                HB_HIP(hipGetLastError());
+                HB_HIP(hipMemcpyAsync(h32, lvl_cnt + lev, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                HB_HIP(hipMemcpyAsync(h32 + 1, b.flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                HB_HIP(hipStreamSynchronize(c->stream));
+                if (h32[1] || hi + h32[0] > item_cap) return fail(c, HB_ERR_INVALID, who + ": unexpected plan layout (the chunk rows of a batch outnumber the plan's)");
+                lo = hi;
+                hi += h32[0];
+            }
         }
         const uint64_t total = hi;
         st.rows_walked += total;
@@ -267,14 +349,18 @@ int backlinks(hb_ctx *c, const hb_links_options *opt_in, hb_links_stats *st_out)
         st.selected += selecting;
 
         // ---- select: the threshold of every slot that has more than it may keep
-        uint64_t blocks = grid_blocks(c, (total + hbk::kLkItems - 1) / hbk::kLkItems, 4, 1);
-        const uint64_t per_block = ((total + blocks - 1) / blocks + hbk::kLkItems - 1) / hbk::kLkItems * hbk::kLkItems;
-        blocks = (total + per_block - 1) / per_block;
+        uint64_t blocks = 1, per_block = 0; // (backlinks: contiguous item ranges per workgroup)
+        if (!forward) {
+            blocks = grid_blocks(c, (total + hbk::kLkItems - 1) / hbk::kLkItems, 4, 1);
+            per_block = ((total + blocks - 1) / blocks + hbk::kLkItems - 1) / hbk::kLkItems * hbk::kLkItems;
+            blocks = (total + per_block - 1) / per_block;
+        }
         HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
         hipLaunchKernelGGL(hbk::lk_plan_kernel, dim3(slot_blocks), dim3(256), 0, c->stream, b, no_shortcut ? 1u : 0u);
         if (selecting) {
             for (int d = top_digit; d >= 0; d--) {
-                hipLaunchKernelGGL(hbk::lk_hist_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, b, total, per_block, d);
+                if (forward) hipLaunchKernelGGL(hbk::fw_hist_kernel, dim3(seg_blocks), dim3(256), 0, c->stream, b, f, d);
+                else hipLaunchKernelGGL(hbk::lk_hist_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, b, total, per_block, d);
                 hipLaunchKernelGGL(hbk::lk_pick_kernel, dim3(slot_blocks), dim3(256), 0, c->stream, b, d);
             }
         }
@@ -283,13 +369,15 @@ int backlinks(hb_ctx *c, const hb_links_options *opt_in, hb_links_stats *st_out)
 
         // ---- emit, sort, translate
         HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
-        hipLaunchKernelGGL(hbk::lk_emit_kernel, dim3(grid_blocks(c, (total + hbk::kLkItems - 1) / hbk::kLkItems, 8, 1)), dim3(256), 0, c->stream, b, total);
+        if (!forward) hipLaunchKernelGGL(hbk::lk_emit_kernel, dim3(grid_blocks(c, (total + hbk::kLkItems - 1) / hbk::kLkItems, 8, 1)), dim3(256), 0, c->stream, b, total);
+        else if (f.segs) hipLaunchKernelGGL(hbk::fw_emit_kernel, dim3(seg_blocks), dim3(256), 0, c->stream, b, f);
         hipLaunchKernelGGL(hbk::lk_sort_kernel, dim3((unsigned)S), dim3(256), 0, c->stream, b, (const uint32_t *)s.d_inv.get(),
-                           (const unsigned long long *)s.d_key.get(), n, s.d_res_sid.get() + base * limit, s.d_res_key.get() + base * limit);
+                           (const unsigned long long *)s.d_key.get(), n, res_sid + base * limit, res_key + base * limit);
         HB_HIP(hipGetLastError());
+        if (d_len) HB_HIP(hipMemcpyAsync(d_len + base, b.deg, S * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
         if ((rc = nearest_seed_lap(c, &st.ms_emit))) return rc;
     }
-    return finish();
+    return HB_OK;
 }
 
 const char *const kNoBacklinks = "no backlinks result (call hb_backlinks)";
@@ -305,7 +393,12 @@ int hb_links_set_keys(hb_ctx *c, const hb_links_key_options *opt, hb_links_key_s
 
 int hb_backlinks(hb_ctx *c, const hb_links_options *opt, hb_links_stats *stats)
 {
-    return operator_entry(c, "hb_backlinks", [&]() { return backlinks(c, opt, stats); });
+    return operator_entry(c, "hb_backlinks", [&]() { return links_query(c, opt, stats, false); });
+}
+
+int hb_forwardlinks(hb_ctx *c, const hb_links_options *opt, hb_links_stats *stats)
+{
+    return operator_entry(c, "hb_forwardlinks", [&]() { return links_query(c, opt, stats, true); });
 }
 
 int hb_links_count(hb_ctx *c, uint64_t *queries, uint64_t *entries)

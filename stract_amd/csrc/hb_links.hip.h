@@ -1,7 +1,9 @@
 // hb_links.hip.h - device code of hb_links_set_keys / hb_backlinks (HostBacklinksQuery::new(node).with_limit(EdgeLimit::Limit(L)),
 // webgraph/query/backlink.rs:230-360): the first L in-neighbours of each QUERIED host in the order (key, NodeID), listed in that order.
 // Part of the hb_api.hip translation unit (included after hb_nearest_seed.hip.h).  Driver: hb_api_links.inc.  Definitions:
-// include/hyperball.h.  DESIGN.md section 27.
+// include/hyperball.h.  DESIGN.md section 27.  The mirror, hb_forwardlinks (the first L OUT-neighbours: DESIGN.md section 28), shares
+// the order, the select arithmetic (lk_value, lk_plan_kernel, lk_pick_kernel) and lk_sort_kernel; its own kernels are at the end of
+// this file.
 //
 // The order is dense: ord[sid] = the position of the node in the sort by (key, sid), a u32 permutation built once per key set
 // (lk_ord_kernel, from the device sort hb_ingest.hip exposes), inv = its inverse, ord_row = ord by device row.  ord values are unique,
@@ -276,6 +278,159 @@ __global__ __launch_bounds__(256) void lk_sort_kernel(const LkBatch b, const uin
         const uint32_t sid = o < n ? inv[o] : kNone;
         res_sid[(size_t)slot * b.limit + i] = sid;
         res_key[(size_t)slot * b.limit + i] = sid < n ? key[sid] : ~0ull;
+    }
+}
+
+// ---- forward links (hb_forwardlinks) --------------------------------------------------------------------------------------------------
+// HostForwardlinksQuery::new(u).with_limit(EdgeLimit::Limit(L)) (webgraph/query/forwardlink.rs:183-330): the first L out-neighbours of
+// each queried host in the same order.  The out-list of node row r is the reader list out_rows[out_ptr[r] .. out_ptr[r + 1]) of the
+// plan's transpose.  A reader >= n_pad is a chunk row of some hub's tree: the edge's target is the node row at the top of that tree,
+// top_row[chunk row - n_pad], a per-graph table built once per load from the highest virtual level down (fw_top_row_kernel).  The table
+// exists because the alternative - climbing out_rows of the chunk row, level by level, per entry and per select round - costs up to
+// `depth` dependent loads for every entry of a hub-bound edge, five times per call.
+// An out-list has no length bound, so a slot's work is cut into SEGMENTS of kFwSegment entries and a workgroup takes one segment at a
+// time: seg_base[slot] = the number of segments before the slot (an exclusive scan of ceil(length / kFwSegment) over the batch, slots + 1
+// words), a workgroup finds the slot of segment g by bisection.  No list of pieces is stored: memory does not grow with the out-degrees.
+//   count:  deg[slot] += the entries of the segment whose resolved target is not the slot's own row (summed in LDS, one atomic add).
+//   select: the radix select of the backlinks (lk_plan_kernel, lk_pick_kernel) with fw_hist_kernel as its histogram: a segment belongs
+//           to ONE slot, so the 256 bins live in LDS and are flushed once per segment.
+//   emit:   as lk_emit_kernel, per segment; lk_sort_kernel orders and translates.  The cursor hands out positions in workgroup order, the
+//           sort makes the list independent of it (ord is unique).
+struct FwBatch {
+    const uint64_t *out_ptr;   // rows_total + 1
+    const uint32_t *out_rows;
+    const uint32_t *top_row;   // nv
+    const uint32_t *seg_base;  // slots + 1
+    uint32_t segs;             // seg_base[slots]
+};
+
+constexpr uint32_t kFwSegment = 2048; // out-list entries of one segment (8 per lane)
+
+// one virtual level [lo, hi), the highest first.  A chunk row with a list has exactly ONE reader - its hub's node row, or a chunk row
+// of a higher level whose top is known already; a chunk row without a list (the padding that fills a level to whole tiles) has none
+// and no top.  Anything else raises flag[0]: the caller refuses, it does not pick a reader.
+__global__ __launch_bounds__(256) void fw_top_row_kernel(const uint64_t *row_ptr, const uint64_t *out_ptr, const uint32_t *out_rows, uint64_t n_pad, uint64_t rows_total,
+                                                         uint64_t lo, uint64_t hi, uint32_t *top_row, uint32_t *flag)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t r = lo + (uint64_t)blockIdx.x * 256 + threadIdx.x; r < hi; r += stride) {
+        const uint64_t readers = out_ptr[r + 1] - out_ptr[r], len = row_ptr[r + 1] - row_ptr[r];
+        uint32_t top = kNone;
+        if (readers == 1) {
+            const uint32_t up = out_rows[out_ptr[r]];
+            if (up < n_pad) top = up;
+            else if (up >= hi && up < rows_total) top = top_row[up - n_pad]; // (a higher level: written by an earlier launch)
+            if (top >= n_pad) flag[0] = 1;
+        } else if (readers != 0 || len != 0) {
+            flag[0] = 1;
+        }
+        top_row[r - n_pad] = top < n_pad ? top : kNone;
+    }
+}
+
+// raw[slot] = the length of the slot's reader list (self link and chunk rows included: what the segments are cut from)
+__global__ __launch_bounds__(256) void fw_len_kernel(const LkBatch b, const FwBatch f, uint32_t *raw)
+{
+    const uint32_t slot = blockIdx.x * 256 + threadIdx.x;
+    if (slot >= b.slots) return;
+    const uint32_t r = b.slot_row[slot];
+    HB_DBG_ASSERT(r < b.n_pad);
+    raw[slot] = (uint32_t)(f.out_ptr[r + 1] - f.out_ptr[r]);
+}
+
+struct FwPiece {
+    uint32_t slot, self;
+    uint64_t beg, end; // its entries of out_rows
+};
+
+// the slot that segment `seg` belongs to - the last one whose base is <= seg (empty slots in front of it share its base) - and its entries
+__device__ __forceinline__ FwPiece fw_piece(const LkBatch &b, const FwBatch &f, uint32_t seg)
+{
+    uint32_t lo = 0, hi = b.slots; // seg_base[lo] <= seg < seg_base[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (f.seg_base[mid] <= seg) lo = mid;
+        else hi = mid;
+    }
+    FwPiece p;
+    p.slot = lo;
+    p.self = b.slot_self[lo];
+    const uint32_t r = b.slot_row[lo];
+    const uint64_t all_end = f.out_ptr[r + 1];
+    p.beg = f.out_ptr[r] + (uint64_t)(seg - f.seg_base[lo]) * kFwSegment;
+    p.end = p.beg + kFwSegment < all_end ? p.beg + kFwSegment : all_end;
+    HB_DBG_ASSERT(p.beg < all_end);
+    return p;
+}
+
+// the node row an entry of a reader list stands for; kNone = none (cannot happen on a table that fw_top_row_kernel accepted)
+__device__ __forceinline__ uint32_t fw_target(const LkBatch &b, const FwBatch &f, uint64_t e)
+{
+    const uint32_t t = f.out_rows[e];
+    if (t < b.n_pad) return t;
+    HB_DBG_ASSERT(t < b.rows_total);
+    return t < b.rows_total ? f.top_row[t - b.n_pad] : kNone;
+}
+
+__global__ __launch_bounds__(256) void fw_count_kernel(const LkBatch b, const FwBatch f)
+{
+    __shared__ uint32_t s_cnt;
+    for (uint32_t seg = blockIdx.x; seg < f.segs; seg += gridDim.x) { // workgroup-uniform
+        if (threadIdx.x == 0) s_cnt = 0;
+        __syncthreads();
+        const FwPiece p = fw_piece(b, f, seg);
+        uint32_t mine = 0;
+        for (uint64_t e = p.beg + threadIdx.x; e < p.end; e += 256) {
+            const uint32_t t = fw_target(b, f, e);
+            mine += (t < b.n_pad && t != p.self) ? 1u : 0u;
+        }
+        if (mine) atomicAdd(&s_cnt, mine);
+        __syncthreads();
+        if (threadIdx.x == 0 && s_cnt) atomicAdd(&b.deg[p.slot], s_cnt);
+        __syncthreads();
+    }
+}
+
+// one round of the select on digit `d`, a segment at a time
+__global__ __launch_bounds__(256) void fw_hist_kernel(const LkBatch b, const FwBatch f, int d)
+{
+    __shared__ uint32_t s_hist[256];
+    s_hist[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint32_t seg = blockIdx.x; seg < f.segs; seg += gridDim.x) { // workgroup-uniform
+        const FwPiece p = fw_piece(b, f, seg);
+        if (!b.sel_k[p.slot]) continue; // (uniform: one slot per segment)
+        const uint32_t prefix = b.sel_prefix[p.slot];
+        for (uint64_t e = p.beg + threadIdx.x; e < p.end; e += 256) {
+            const uint32_t t = fw_target(b, f, e);
+            if (t >= b.n_pad || t == p.self) continue;
+            const uint32_t v = lk_value(b.ord_row[t], b.mult);
+            if (d < 3 && (v >> (8 * (d + 1))) != prefix) continue;
+            atomicAdd(&s_hist[(v >> (8 * d)) & 255u], 1u);
+        }
+        __syncthreads();
+        const uint32_t v = s_hist[threadIdx.x];
+        if (v) atomicAdd(&b.hist[(size_t)p.slot * 256 + threadIdx.x], v);
+        s_hist[threadIdx.x] = 0;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void fw_emit_kernel(const LkBatch b, const FwBatch f)
+{
+    for (uint32_t seg = blockIdx.x; seg < f.segs; seg += gridDim.x) {
+        const FwPiece p = fw_piece(b, f, seg);
+        const uint32_t thr = b.thr[p.slot];
+        for (uint64_t e = p.beg + threadIdx.x; e < p.end; e += 256) {
+            const uint32_t t = fw_target(b, f, e);
+            if (t >= b.n_pad || t == p.self) continue;
+            const uint32_t o = b.ord_row[t];
+            if (lk_value(o, b.mult) <= thr) {
+                const uint32_t pos = atomicAdd(&b.cursor[p.slot], 1u);
+                HB_DBG_ASSERT(pos < b.limit);
+                if (pos < b.limit) b.out[(size_t)p.slot * b.limit + pos] = o;
+            }
+        }
     }
 }
 
