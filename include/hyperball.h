@@ -466,11 +466,21 @@ int hb_debug_copy_betweenness_batch(hb_ctx *ctx, uint8_t *dist, uint64_t *sigma,
  * max(L, 1) with HB_SIM_NORMALIZED; L / D = the number of liked / disliked entries; both sums run in entry order from +0.0; an entry
  * whose id is v contributes self_score (1.0 unless HB_SIM_SELF_SCORE) instead of sim.  Duplicate entries each count.  An entry that is
  * no node of the graph has an empty BitVec: its sim is 0, it counts in L or D (and in hb_similarity_stats.unknown).
- * Defined differences: in(v) is the WHOLE in-list of the loaded graph - unique edges, self links as loaded, the relation filter of the
- * load (HB_SKIPPED_REL_MASK drops NOFOLLOW among others; HB_FLAG_ALL_RELS keeps everything).  The reference takes
- * EdgeLimit::Limit(512) backlinks in search order before it filters: the two agree wherever every host involved has at most 512
- * inbound records.  (With the order hb_nearest_seed defined, that cut is a defined object - hb_backlinks below builds it; using it here
- * is a follow-up.)
+ * Defined differences: the relation filter of the load applies (HB_SKIPPED_REL_MASK drops NOFOLLOW among others; HB_FLAG_ALL_RELS keeps
+ * everything), edges are unique, and in(v) depends on hb_similarity_options.limit:
+ *   limit == 0: in(v) is the WHOLE in-list of the loaded graph, self links as loaded.  The reference takes EdgeLimit::Limit(512) backlinks
+ *     in search order before it filters: the two agree wherever every host involved has at most 512 inbound records and no self link.
+ *   1 <= limit <= 1024 (the reference's Scorer: 512, searcher/api/mod.rs:199-216 batch_raw_ingoing_hosts(nodes, EdgeLimit::Limit(512))):
+ *     in(v) = backlinks(v, limit) as hb_backlinks below defines it under the CURRENT key set (hb_links_set_keys; none: NodeID order) - the
+ *     in-neighbours u != v (LinksQuery.skip_self_links), ordered by (key[u], NodeID u) ascending, the first min(limit, degree(v)) of them.
+ *     This holds for EVERY node, anchors included: len = min(degree(v), limit), the bloom covers THOSE entries only, the intersection is
+ *     |inL(a) & inL(v)|.  What differs from the reference is then what differs for hb_backlinks: the limit best of the whole list instead
+ *     of the first limit + 128 documents, unsaturated keys, the load's relation filter.  hb_inbound_similarity(limit = 512) +
+ *     hb_similarity_top give that score for ALL hosts, without the <= 1024-candidate pre-selection of hb_similar_hosts.
+ *     A node row is LISTED when its cut differs from its list as loaded (degree > limit, or a self link); only listed rows get an explicit
+ *     cut list (limit x 4 bytes each, plus one u32 per node row), built at the first limited call and kept while graph, key set and limit
+ *     stay the same: hb_links_set_keys, a call with another limit > 0 and the next load drop it.  limit > 1024 is refused
+ *     (HB_ERR_INVALID) before the previous result is touched.
  * Entry 16 b + j (liked entries first, then the disliked ones, in caller order) is slot j of batch b; a batch is one level of the walk
  * the other operators share (hb_sampled_harmonic, hb_betweenness) with sixteen u32 counts per 64-byte row and a plain add as the join.
  * Single rank only.  The call borrows the HyperBall state as those walks do: hb_step needs a new hb_begin afterwards, a later hb_run
@@ -489,6 +499,8 @@ typedef struct hb_similarity_options {
     const hb_u128 *liked;    uint64_t liked_count;
     const hb_u128 *disliked; uint64_t disliked_count;
     double self_score;                              /* used only with HB_SIM_SELF_SCORE */
+    uint32_t limit, reserved;                       /* 0 = whole in-lists (also what a caller with the shorter struct_size gets); 1 .. 1024 =
+                                                     * every BitVec from backlinks(v, limit); the reference's Scorer uses 512 */
 } hb_similarity_options;
 
 typedef struct hb_similarity_stats {
@@ -503,9 +515,13 @@ typedef struct hb_similarity_stats {
     uint64_t device_bytes;      /* the operator's own buffers */
     double   ms_total;          /* wall time of the call */
     double   ms_bloom;          /* GPU time of the per-graph state (0 when it existed) */
-    double   ms_count;          /* GPU time of the count levels */
+    double   ms_count;          /* GPU time of the count levels; with a limit also of the list-count kernel: sum(ms_mode) + ms_list_count */
     double   ms_score;          /* GPU time of seed + accumulate + score */
-    double   ms_mode[3];        /* GPU time of the count levels per mode */
+    double   ms_mode[3];        /* GPU time of the count levels per mode (the walk alone: ms_list_count is in none of them) */
+    uint64_t listed_rows;       /* limited mode: node rows that hold an explicit cut list (0 with limit == 0) */
+    uint64_t list_entries;      /* ... the entries of those lists */
+    double   ms_lists;          /* ... GPU time of building them (0 when they existed) */
+    double   ms_list_count;     /* ... GPU time of the list-count kernel over the batches: part of ms_count, of no ms_mode entry */
 } hb_similarity_stats;
 
 int hb_inbound_similarity(hb_ctx *ctx, const hb_similarity_options *opt, hb_similarity_stats *stats);
@@ -519,7 +535,9 @@ int hb_similarity_lookup(hb_ctx *ctx, const hb_u128 *ids, uint64_t count, double
 int hb_similarity_top(hb_ctx *ctx, uint64_t k, uint32_t flags, hb_u128 *ids, double *vals, uint64_t *written);
 /* Debug: the counts of the LAST batch of the last hb_inbound_similarity (n x 16, entry sid * 16 + slot: |in(v) & in(anchor)|; slots
  * without a known anchor are 0), and the per-graph bloom masks and in-degrees (n each), ascending-NodeID order; any of the three may be
- * NULL.  The counts lie in the borrowed HyperBall state: refused once another call has used that state. */
+ * NULL.  The counts lie in the borrowed HyperBall state: refused once another call has used that state.  After a limited call the three
+ * are the limited ones (|inL(v) & inL(anchor)|, the bloom over the cut entries, min(degree, limit)): refused once hb_links_set_keys has
+ * dropped the cut lists. */
 int hb_debug_copy_similarity_batch(hb_ctx *ctx, uint32_t *counts, uint64_t *bloom, uint32_t *len);
 
 /* ---- nearest-seed centrality: HarmonicNearestSeed (entrypoint/centrality.rs:126-201, `stract centrality harmonic-nearest-seed`) ------ */

@@ -64,6 +64,7 @@ HB_X_SCATTER_TRANSPOSE = 0x2000000
 HB_X_SWEEP_ROUNDS = 0x4000000
 HB_X_GENERIC_LEVEL1 = 0x8000000
 HB_X_PROBE_NO_SIZE = 0x10000000
+HB_X_SIM_SMALL_PIECES = 0x20000000
 
 # numpy views of the plain-data structs
 U128 = np.dtype([("lo", "<u8"), ("hi", "<u8")])
@@ -271,6 +272,8 @@ class HbSimilarityOptions(ctypes.Structure):
         ("disliked", ctypes.c_void_p),
         ("disliked_count", ctypes.c_uint64),
         ("self_score", ctypes.c_double),
+        ("limit", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
     ]
 
 
@@ -291,6 +294,10 @@ class HbSimilarityStats(ctypes.Structure):
         ("ms_count", ctypes.c_double),
         ("ms_score", ctypes.c_double),
         ("ms_mode", ctypes.c_double * 3),
+        ("listed_rows", ctypes.c_uint64),
+        ("list_entries", ctypes.c_uint64),
+        ("ms_lists", ctypes.c_double),
+        ("ms_list_count", ctypes.c_double),
     ]
 
     def as_dict(self):
@@ -1018,11 +1025,13 @@ class Context:
     # -- inbound similarity (Scorer, ranking/inbound_similarity.rs:61-138)
     _SIM_MODES = {None: 0, "auto": 0, "dense": HB_SIM_DENSE_ONLY, "sparse": HB_SIM_SPARSE_ONLY}
 
-    def inbound_similarity(self, liked=(), disliked=(), normalized=False, self_score=None, mode=None, flags=0):
+    def inbound_similarity(self, liked=(), disliked=(), normalized=False, self_score=None, mode=None, flags=0, limit=0):
         """hb_inbound_similarity: scores every node against `liked` / `disliked` (U128 arrays of node ids, duplicates and unknown ids
-        allowed); returns the stats.  mode: None / "dense" / "sparse" (forced kind of count level)."""
+        allowed); returns the stats.  mode: None / "dense" / "sparse" (forced kind of count level).  limit: 0 = whole in-lists,
+        1 .. 1024 = every BitVec from the `limit` best backlinks under the current key set (links_set_keys); the reference uses 512."""
         o = HbSimilarityOptions()
         o.struct_size = ctypes.sizeof(HbSimilarityOptions)
+        o.limit = int(limit)
         o.flags = int(flags) | (HB_SIM_NORMALIZED if normalized else 0) | self._SIM_MODES[mode]
         if self_score is not None:
             o.flags |= HB_SIM_SELF_SCORE
@@ -1064,7 +1073,7 @@ class Context:
 
     def debug_similarity_batch(self):
         """counts (n, 16) uint32 of the LAST batch of the last inbound_similarity() call, and the per-graph bloom masks (n) uint64 and
-        in-degrees (n) uint32, ascending NodeID."""
+        in-degrees (n) uint32, ascending NodeID; after a limited call: those of the cut lists."""
         n = self.n()
         counts = np.zeros((n, 16), dtype=np.uint32)
         bloom = np.zeros(n, dtype=np.uint64)

@@ -29,6 +29,7 @@
 #include "hb_nearest_seed.hip.h"
 #include "hb_links.hip.h"
 #include "hb_similar.hip.h"
+#include "hb_similarity_limit.hip.h"
 #ifdef HB_EXPERIMENTS
 #include "hb_experiments.hip.h"
 #endif
@@ -227,6 +228,7 @@ struct GraphDeviceState {
         bool normalized = false;
         double self_score = 1.0;
         uint32_t last_slots = 0;               // slots of the last batch
+        uint32_t limit = 0;                    // hb_similarity_options.limit of the last call (0 = whole in-lists)
         uint64_t bytes = 0;                    // device bytes of the above (and of dst.d_indeg when this operator built it)
     } sim;
     // hb_nearest_seed (hb_api_nearest_seed.inc): the candidates, the seeds, the double-buffered values and the last result, dev_alloc'ed at
@@ -310,6 +312,23 @@ struct GraphDeviceState {
         std::vector<double> top_score;
         uint64_t bytes = 0;
     } shs;
+    // hb_inbound_similarity with a limit (hb_api_similarity.inc, hb_similarity_limit.hip.h): the cut lists of the LISTED rows - degree > limit,
+    // or a self link - for one graph, one key set and one limit.  Built at the first limited call, kept while the three stay the same:
+    // dropped by hb_links_set_keys, by a call with another limit (similarity_limit_drop) and by the next load.  The holders own them,
+    // counted in `bytes` and in hb_stats.device_bytes.  The state borrows nothing
+    struct SimilarityLimitState {
+        bool ready = false;               // the buffers below describe the loaded graph under the current key set and `limit`
+        uint32_t limit = 0;
+        uint64_t listed = 0, entries = 0; // listed rows, the entries of their lists
+        DevPtr<uint32_t> d_idx;           // n_pad: the list index of a node row, kNone = not listed (the plan's list is its cut)
+        DevPtr<uint32_t> d_list_row;      // listed: the device row of list k
+        DevPtr<uint32_t> d_lists;         // listed x limit: list k at k x limit, device rows in the order (key, NodeID)
+        DevPtr<uint32_t> d_len;           // listed: min(degree, limit)
+        DevPtr<uint64_t> d_bloom;         // listed: the bloom mask over the list's entries
+        DevPtr<uint32_t> d_seed_rows;     // 16: the batch's anchors that seed from the plan's lists
+        DevPtr<unsigned long long> d_cnt; // 4 counters of the list-count kernel
+        uint64_t bytes = 0;
+    } lim;
 };
 
 // The timing events of a pass (one set: hb_ctx::ev, or an EvSet), in the order a pass records them; kEvLevel1 lies between kEvStart and
@@ -1607,9 +1626,8 @@ int hb_store_harmonic_results(hb_ctx *c, const char *output, char *err, uint64_t
 
 #include "hb_api_betweenness.inc"
 
-#include "hb_api_similarity.inc"
-
 #include "hb_api_nearest_seed.inc"
 
 #include "hb_api_links.inc"
+#include "hb_api_similarity.inc" // (after the links: the limited mode builds its cut lists with their list builder)
 #include "hb_api_similar.inc"

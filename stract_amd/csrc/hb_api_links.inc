@@ -72,6 +72,8 @@ int links_alloc(hb_ctx *c, bool default_order)
     return HB_OK;
 }
 
+void similarity_limit_drop(hb_ctx *c); // hb_api_similarity.inc: the cut lists of the limited inbound similarity follow the key set
+
 int links_set_keys(hb_ctx *c, const hb_links_key_options *opt_in, hb_links_key_stats *st_out)
 {
     const double t0 = now_ms();
@@ -120,6 +122,7 @@ int links_set_keys(hb_ctx *c, const hb_links_key_options *opt_in, hb_links_key_s
             has[sids[i]] = 1;
         }
     }
+    similarity_limit_drop(c); // (the order is about to change)
     if (n) {
         s.ready = false; // (an error below leaves no half-built order behind: the next call builds the default one)
         if ((rc = links_alloc(c, false))) return rc;

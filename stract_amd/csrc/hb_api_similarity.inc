@@ -3,7 +3,9 @@
 // for every node of the loaded graph - sixteen liked / disliked hosts per batch in the 64-byte rows of the HyperBall plan, one level of
 // the shared walk per batch (kernels: hb_similarity.hip.h).  Definitions: include/hyperball.h.  The walk borrows d_regs / d_part / the
 // changed bitmaps / the sweep scratch as hb_betweenness does (claim_rows); the per-graph state, the sums and the result live
-// in buffers of their own.
+// in buffers of their own.  With hb_similarity_options.limit the BitVecs are those of the limit best backlinks: the rows whose cut
+// differs from their list as loaded get explicit cut lists (GraphDeviceState::lim, built here with the list builder of hb_api_links.inc),
+// a seed and a count kernel of their own (hb_similarity_limit.hip.h); the walk level, the accumulate and the readers are shared.
 
 namespace {
 
@@ -48,6 +50,100 @@ int similarity_alloc(hb_ctx *c, double *ms_out)
     return HB_OK;
 }
 
+// ---- the limited mode (hb_similarity_options.limit > 0; kernels: hb_similarity_limit.hip.h) ------------------------------------------
+template <class T>
+int limit_hold(hb_ctx *c, DevPtr<T> &h, uint64_t count)
+{
+    const uint64_t bytes = std::max<uint64_t>(count * sizeof(T), 256);
+    const hipError_t e = h.alloc((bytes + sizeof(T) - 1) / sizeof(T));
+    if (e != hipSuccess) return fail(c, HB_ERR_NOMEM, "hipMalloc(" + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
+    c->lim.bytes += bytes;
+    c->stats.device_bytes += bytes;
+    return HB_OK;
+}
+
+// the cut lists describe one graph, one key set and one limit: hb_links_set_keys and a call with another limit end here (a load frees
+// the whole graph state)
+void similarity_limit_drop(hb_ctx *c)
+{
+    c->stats.device_bytes -= c->lim.bytes;
+    c->lim = GraphDeviceState::SimilarityLimitState{};
+}
+
+// The listed rows and their cut lists under the current key set, once per (graph, key set, limit); *ms_out += its GPU time.  The list
+// builder's result buffers are this function's (the keys) and the state's (the lists): the user's hb_backlinks / hb_forwardlinks result
+// stays readable.  Needs the per-graph state of similarity_alloc (pos, the in-degrees) and links_top_rows.
+int similarity_limit_build(hb_ctx *c, uint32_t limit, double *ms_out)
+{
+    auto &s = c->lim;
+    if (s.ready && s.limit == limit) return HB_OK;
+    similarity_limit_drop(c);
+    const Plan &p = c->plan;
+    const std::string who = "hb_inbound_similarity";
+    const uint64_t n_pad = p.n_pad, rows_total = n_pad + p.nv;
+    int rc;
+    if ((rc = limit_hold(c, s.d_idx, n_pad))) return rc;
+    if ((rc = limit_hold(c, s.d_seed_rows, hbk::kSimSlots))) return rc;
+    if ((rc = limit_hold(c, s.d_cnt, 4))) return rc;
+    DevPtr<uint32_t> d_flag, d_sids, d_deg; // (work memory of the build: gone at its end)
+    DevPtr<uint64_t> d_off;
+    DevPtr<unsigned long long> d_keys;
+    if (d_flag.alloc(std::max<uint64_t>(n_pad, 64)) != hipSuccess || d_off.alloc(n_pad + 1) != hipSuccess)
+        return fail(c, HB_ERR_NOMEM, who + ": out of device memory for the listed rows");
+    // ---- which rows are listed: a self link, or more in-neighbours than the limit
+    HB_HIP(hipMemsetAsync(d_flag.get(), 0, std::max<uint64_t>(n_pad, 64) * sizeof(uint32_t), c->stream));
+    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    hipLaunchKernelGGL(hbk::siml_self_kernel, dim3(grid_blocks(c, (rows_total + 63) / 64, 8, 1)), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr,
+                       (const uint32_t *)c->d_src, (const uint32_t *)c->lnk.d_top_row.get(), n_pad, rows_total, d_flag.get());
+    hipLaunchKernelGGL(hbk::siml_mark_kernel, dim3(grid_blocks(c, (n_pad + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint32_t *)c->d_sid_of,
+                       (const uint32_t *)c->dst.d_indeg, limit, n_pad, d_flag.get());
+    HB_HIP(hipGetLastError());
+    const std::string e = device_prefix((void *)c->stream, d_flag.get(), n_pad, d_off.get());
+    if (!e.empty()) return fail(c, HB_ERR_HIP, who + ": " + e);
+    uint64_t listed = 0;
+    HB_HIP(hipMemcpyAsync(&listed, d_off.get() + n_pad, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = nearest_seed_lap(c, ms_out))) return rc;
+    if (listed > n_pad) return fail(c, HB_ERR_INVALID, who + ": more listed rows than node rows (internal error)");
+    if ((rc = limit_hold(c, s.d_list_row, listed))) return rc;
+    if ((rc = limit_hold(c, s.d_lists, listed * limit))) return rc;
+    if ((rc = limit_hold(c, s.d_len, listed))) return rc;
+    if ((rc = limit_hold(c, s.d_bloom, listed))) return rc;
+    const uint64_t piece_max = xbit(c, HB_X_SIM_SMALL_PIECES) ? 64 : kLinksMaxSlots;
+    if (d_sids.alloc(std::max<uint64_t>(listed, 64)) != hipSuccess || d_deg.alloc(std::max<uint64_t>(listed, 64)) != hipSuccess ||
+        d_keys.alloc(std::max<uint64_t>(std::min(listed, piece_max) * limit, 64)) != hipSuccess)
+        return fail(c, HB_ERR_NOMEM, who + ": out of device memory for the list builder's keys");
+    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    hipLaunchKernelGGL(hbk::siml_assign_kernel, dim3(grid_blocks(c, (n_pad + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint32_t *)c->d_sid_of,
+                       (const uint32_t *)d_flag.get(), (const uint64_t *)d_off.get(), n_pad, listed, s.d_idx.get(), s.d_list_row.get(), d_sids.get());
+    HB_HIP(hipGetLastError());
+    if ((rc = nearest_seed_lap(c, ms_out))) return rc;
+    // ---- their cut lists: the list builder of hb_backlinks, a piece of hosts at a time; then sid -> device row, len and bloom per list
+    hb_links_options lo{};
+    lo.limit = limit;
+    hb_links_stats ls{};
+    std::vector<uint32_t> degree;
+    uint64_t entries = 0;
+    for (uint64_t base = 0; base < listed; base += piece_max) {
+        const uint64_t P = std::min(piece_max, listed - base);
+        degree.assign(P, 0);
+        if ((rc = links_lists(c, who, false, nullptr, d_sids.get() + base, P, lo, s.d_lists.get() + base * limit, d_keys.get(), d_deg.get() + base, degree, ls)))
+            return rc;
+        for (uint32_t d : degree) entries += std::min<uint64_t>(d, limit);
+        HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+        hipLaunchKernelGGL(hbk::siml_finish_kernel, dim3(grid_blocks(c, (P + 3) / 4, 8, 1)), dim3(256), 0, c->stream, s.d_lists.get() + base * limit,
+                           (const uint32_t *)d_deg.get() + base, (const uint32_t *)c->d_dev_of, (const uint8_t *)c->sim.d_pos, P, limit, p.n, n_pad,
+                           s.d_len.get() + base, s.d_bloom.get() + base);
+        HB_HIP(hipGetLastError());
+        if ((rc = nearest_seed_lap(c, ms_out))) return rc;
+    }
+    *ms_out += ls.ms_expand + ls.ms_select + ls.ms_emit;
+    s.listed = listed;
+    s.entries = entries;
+    s.limit = limit;
+    s.ready = true;
+    return HB_OK;
+}
+
 // Scorer::calculate_score for an id that is no node of the graph: an empty BitVec, so only the entries equal to the id contribute
 double similarity_unknown_score(const hb_ctx *c, const hb_u128 &id)
 {
@@ -74,10 +170,18 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
         return fail(c, HB_ERR_INVALID, "hb_inbound_similarity: a count without its list");
     const uint64_t L = o.liked_count, D = o.disliked_count, E = L + D;
     if (!E) return fail(c, HB_ERR_INVALID, "hb_inbound_similarity: no liked and no disliked host");
+    if (o.limit > hbk::kLkMaxLimit) return fail(c, HB_ERR_INVALID, "hb_inbound_similarity: limit must be 0 (whole in-lists) or 1 .. 1024");
     const Plan &p = c->plan;
     auto &s = c->sim;
-    s.valid = false;
     hb_similarity_stats st{};
+    const bool limited = o.limit != 0 && p.n != 0;
+    if (limited) { // what the list builder may refuse: before the previous result is touched
+        size_t nlev = 0;
+        for_each_virtual_level(p, true, [&](uint64_t, uint64_t) { nlev++; });
+        if (nlev + 2 > 64) return fail(c, HB_ERR_INVALID, "hb_inbound_similarity: unexpected plan layout (more than 62 virtual levels)");
+        if ((rc = links_top_rows(c, "hb_inbound_similarity", &st.ms_lists))) return rc;
+    }
+    s.valid = false;
     st.liked = L;
     st.disliked = D;
     // entry e = liked[e] below L, disliked[e - L] above: its sid, kNone = no node of the graph
@@ -89,8 +193,9 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
     s.normalized = (o.flags & HB_SIM_NORMALIZED) != 0;
     s.self_score = (o.flags & HB_SIM_SELF_SCORE) ? o.self_score : 1.0;
     s.last_slots = 0;
+    s.limit = limited ? o.limit : 0;
     auto finish = [&]() {
-        st.device_bytes = s.bytes;
+        st.device_bytes = s.bytes + c->lim.bytes;
         st.ms_total = now_ms() - t0;
         copy_out(st_out, st);
         return HB_OK;
@@ -100,6 +205,12 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
         return finish();
     }
     if ((rc = similarity_alloc(c, &st.ms_bloom))) return rc;
+    auto &lm = c->lim;
+    if (limited) {
+        if ((rc = similarity_limit_build(c, o.limit, &st.ms_lists))) return rc;
+        st.listed_rows = lm.listed;
+        st.list_entries = lm.entries;
+    }
     const uint64_t n_pad = p.n_pad, rows_total = p.n_pad + p.nv;
     HB_HIP(hipMemsetAsync(s.d_acc, 0, n_pad * 2 * sizeof(double), c->stream));
     HB_HIP(hipMemsetAsync(s.d_anchor, 0, p.n, c->stream));
@@ -123,13 +234,23 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
             HB_HIP(hipMemcpyAsync(s.d_anchor_sids, sids.data() + b0, count * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
             hipLaunchKernelGGL(hbk::sim_anchor_rows_kernel, dim3(1), dim3(64), 0, c->stream, (const uint32_t *)s.d_anchor_sids, count, (const uint32_t *)c->d_dev_of,
                                s.d_anchor_rows, s.d_anchor);
-            hipLaunchKernelGGL(hbk::sim_seed_node_kernel, dim3(count), dim3(256), 0, c->stream, (const uint32_t *)s.d_anchor_rows, count, (const uint64_t *)c->d_row_ptr,
+            const uint32_t *seed_rows = s.d_anchor_rows; // the anchors that seed from the plan's lists: all of them, or the unlisted ones
+            if (limited) {
+                hipLaunchKernelGGL(hbk::sim_seed_rows_kernel, dim3(1), dim3(64), 0, c->stream, (const uint32_t *)s.d_anchor_rows, count, (const uint32_t *)lm.d_idx.get(),
+                                   lm.d_seed_rows.get());
+                seed_rows = lm.d_seed_rows.get();
+            }
+            hipLaunchKernelGGL(hbk::sim_seed_node_kernel, dim3(count), dim3(256), 0, c->stream, seed_rows, count, (const uint64_t *)c->d_row_ptr,
                                (const uint32_t *)c->d_src, (uint32_t *)c->d_regs[0], c->d_bits[0], s.d_vmask, (const uint32_t *)c->d_outdeg, n_pad, rows_total, s.d_cnt);
             for_each_virtual_level(p, false, [&](uint64_t lo, uint64_t hi) { // the chunk rows of the anchors' lists, the highest virtual level first
                 hipLaunchKernelGGL(hbk::sim_seed_virt_kernel, dim3(grid_blocks(c, (hi - lo + 3) / 4, 8, 1)), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr,
                                    (const uint32_t *)c->d_src, (uint32_t *)c->d_regs[0], c->d_bits[0], s.d_vmask, (const uint32_t *)c->d_outdeg, n_pad, rows_total, lo,
                                    hi, s.d_cnt);
             });
+            if (limited && lm.listed) // a listed anchor: its stored cut list
+                hipLaunchKernelGGL(hbk::sim_seed_list_kernel, dim3(count), dim3(256), 0, c->stream, (const uint32_t *)s.d_anchor_rows, count,
+                                   (const uint32_t *)lm.d_idx.get(), (const uint32_t *)lm.d_lists.get(), (const uint32_t *)lm.d_len.get(), lm.limit,
+                                   (uint32_t *)c->d_regs[0], c->d_bits[0], s.d_vmask, (const uint32_t *)c->d_outdeg, n_pad, rows_total, s.d_cnt);
             HB_HIP(hipGetLastError());
             HB_HIP(hipMemcpyAsync(h, s.d_cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         }
@@ -161,6 +282,32 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
             st.ms_count += lv.ms;
             st.rows_nonzero += lv.cnt[0];
             st.edges_gathered += lv.cnt[2];
+            if (limited && lm.listed) { // the walk summed the WHOLE lists of the listed rows: their counts again, from the cut lists
+                hbk::SimListParams lp{};
+                lp.rd = c->d_regs[0];
+                lp.bits_rd = c->d_bits[0];
+                lp.wr = c->d_regs[1];
+                lp.bits_wr = c->d_bits[1];
+                lp.list_row = lm.d_list_row.get();
+                lp.lists = lm.d_lists.get();
+                lp.len_l = lm.d_len.get();
+                lp.cnt = lm.d_cnt.get();
+                lp.listed = lm.listed;
+                lp.n_pad = n_pad;
+                lp.limit = lm.limit;
+                HB_HIP(hipMemsetAsync(lm.d_cnt.get(), 0, 4 * sizeof(unsigned long long), c->stream));
+                HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+                hipLaunchKernelGGL(hbk::sim_list_count_kernel, dim3(grid_blocks(c, (lm.listed + 3) / 4, 8, 1)), dim3(256), 0, c->stream, lp);
+                HB_HIP(hipGetLastError());
+                HB_HIP(hipMemcpyAsync(h, lm.d_cnt.get(), 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+                double lms = 0.0;
+                if ((rc = nearest_seed_lap(c, &lms))) return rc;
+                st.ms_list_count += lms;
+                st.ms_count += lms;
+                st.rows_nonzero += h[0];
+                st.rows_nonzero -= h[1];
+                st.edges_gathered += h[2];
+            }
         }
         // ---- accumulate: the slots in order (an anchor without in-links still scores itself)
         if (any_known) {
@@ -172,6 +319,11 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
             ap.bits = c->d_bits[1];
             ap.len = c->dst.d_indeg;
             ap.bloom = s.d_bloom;
+            if (limited) {
+                ap.lidx = lm.d_idx.get();
+                ap.len_l = lm.d_len.get();
+                ap.bloom_l = lm.d_bloom.get();
+            }
             ap.acc = s.d_acc;
             ap.self_score = s.self_score;
             ap.n_pad = n_pad;
@@ -280,6 +432,9 @@ int hb_debug_copy_similarity_batch(hb_ctx *c, uint32_t *counts, uint64_t *bloom,
         const Plan &p = c->plan;
         auto &s = c->sim;
         if (!p.n) return HB_OK;
+        const auto &lm = c->lim;
+        if (s.limit && !(lm.ready && lm.limit == s.limit))
+            return fail(c, HB_ERR_INVALID, "hb_debug_copy_similarity_batch: the cut lists of the last call are gone (hb_links_set_keys)");
         const bool counts_live = c->rows == RowsOf::Similarity; // (s.valid holds: d_regs[1] / d_bits[1] still hold the last batch's counts)
         if (counts && !counts_live)
             return fail(c, HB_ERR_INVALID, "hb_debug_copy_similarity_batch: the counts of the last batch are gone (another call has used the HyperBall state)");
@@ -290,7 +445,9 @@ int hb_debug_copy_similarity_batch(hb_ctx *c, uint32_t *counts, uint64_t *bloom,
         HB_HIP(d_bloom.alloc(p.n));
         const uint32_t *bits = counts_live ? c->d_bits[1] : nullptr; // (bloom / len alone: no counts are read)
         hipLaunchKernelGGL(hbk::sim_export_kernel, dim3(grid_blocks(c, (p.n + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint32_t *)c->d_regs[1], bits,
-                           (const uint64_t *)s.d_bloom, (const uint32_t *)c->dst.d_indeg, (const uint32_t *)c->d_dev_of, p.n, d_counts.get(), d_bloom.get(), d_len.get());
+                           (const uint64_t *)s.d_bloom, (const uint32_t *)c->dst.d_indeg, s.limit ? (const uint32_t *)lm.d_idx.get() : nullptr,
+                           (const uint32_t *)lm.d_len.get(), (const uint64_t *)lm.d_bloom.get(), (const uint32_t *)c->d_dev_of, p.n, d_counts.get(), d_bloom.get(),
+                           d_len.get());
         HB_HIP(hipGetLastError());
         if (counts) HB_HIP(hipMemcpyAsync(counts, d_counts.get(), p.n * hbk::kSimSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         if (bloom) HB_HIP(hipMemcpyAsync(bloom, d_bloom.get(), p.n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));

@@ -37,4 +37,5 @@ enum hb_xbit : uint32_t {
     HB_X_SWEEP_ROUNDS = 0x4000000u,       // bit 26  sweep passes: a touched row's sources 8 per round (index / bit word / gather each a round trip) instead of all at once
     HB_X_GENERIC_LEVEL1 = 0x8000000u,     // bit 27  pass 0: the first hub-chunk level through the generic INIT kernel instead of init_level1_kernel (A/B)
     HB_X_PROBE_NO_SIZE = 0x10000000u,     // bit 28  TIMING PROBE, WRONG RESULTS: the dense fused node rows neither read nor write size[] (16 B per row less state traffic)
+    HB_X_SIM_SMALL_PIECES = 0x20000000u,  // bit 29  hb_inbound_similarity with a limit: the cut lists are built in pieces of 64 hosts instead of 65536 (tests: several pieces)
 };

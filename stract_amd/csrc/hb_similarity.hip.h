@@ -3,10 +3,11 @@
 // HyperBall device plan.  Part of the hb_api.hip translation unit (included after hb_betweenness.hip.h; the count level is a walk of
 // hb_walk.hip.h).  Driver: hb_api_similarity.inc.  Definitions: include/hyperball.h.
 //
-// Defined differences from the reference: the in-neighbour set of a node is its WHOLE in-list in the loaded graph (unique edges, self
-// links as loaded, the relation filter of the load: HB_SKIPPED_REL_MASK, nothing with HB_FLAG_ALL_RELS); the reference takes
-// EdgeLimit::Limit(512) backlinks in search order before it filters, which nothing can reproduce.  The two agree wherever every host
-// involved has at most 512 inbound records.
+// Defined differences from the reference: with hb_similarity_options.limit == 0 the in-neighbour set of a node is its WHOLE in-list in
+// the loaded graph (unique edges, self links as loaded, the relation filter of the load: HB_SKIPPED_REL_MASK, nothing with
+// HB_FLAG_ALL_RELS); the reference takes EdgeLimit::Limit(512) backlinks in search order before it filters.  limit = L cuts every list as
+// hb_backlinks defines the cut (hb_similarity_limit.hip.h: explicit cut lists for the rows whose cut differs from their list as loaded);
+// the differences that remain are that operator's.
 //
 // Per graph: pos[row] = (low id word x 11400714819323198549) & 63 - both bloom indices of VeryJankyBloomFilter::hash come from that one
 // product and 16 divides 64, so the word is determined by the bit and the 16-word bloom is exactly one u64 mask; bloom[row] = OR of
@@ -180,6 +181,10 @@ struct SimAccParams {
     const uint32_t *bits;        // the level-1 bitmap
     const uint32_t *len;         // in-degree per row
     const uint64_t *bloom;
+    const uint32_t *lidx;        // limited mode (hb_similarity_limit.hip.h): the list index per node row, kNone = the row keeps len / bloom
+                                 // above; NULL = whole in-lists
+    const uint32_t *len_l;       // ... per list: min(degree, limit)
+    const uint64_t *bloom_l;     // ... and the bloom over the cut entries
     double *acc;                 // n_pad x 2: liked, disliked
     double self_score;
     uint64_t n_pad;
@@ -196,14 +201,24 @@ __device__ __forceinline__ double sim_term(uint32_t inter, uint32_t len_v, unsig
     return (double)inter / (sqrt((double)len_a) * sqrt((double)len_v));
 }
 
+// len and bloom of a node row: the cut list's where the row has one
+__device__ __forceinline__ void sim_len_bloom(const uint32_t *len, const uint64_t *bloom, const uint32_t *lidx, const uint32_t *len_l, const uint64_t *bloom_l,
+                                              uint64_t row, uint32_t &len_v, unsigned long long &bloom_v)
+{
+    const uint32_t k = lidx ? lidx[row] : kNone;
+    len_v = k != kNone ? len_l[k] : len[row];
+    bloom_v = k != kNone ? bloom_l[k] : bloom[row];
+}
+
 // a thread per node row; the slots in order, so every sum is the reference's sequential one
 __global__ __launch_bounds__(256) void sim_accumulate_kernel(const SimAccParams p)
 {
     const uint64_t stride = (uint64_t)gridDim.x * 256;
     for (uint64_t row = (uint64_t)blockIdx.x * 256 + threadIdx.x; row < p.n_pad; row += stride) {
         const bool has = (p.bits[row >> 5] >> (row & 31u)) & 1u;
-        const uint32_t len_v = p.len[row];
-        const unsigned long long bloom_v = p.bloom[row];
+        uint32_t len_v, len_a;
+        unsigned long long bloom_v, bloom_a;
+        sim_len_bloom(p.len, p.bloom, p.lidx, p.len_l, p.bloom_l, row, len_v, bloom_v);
         double liked = p.acc[row * 2], disliked = p.acc[row * 2 + 1];
         for (uint32_t j = 0; j < p.count; j++) {
             const uint32_t a = p.anchor_rows[j];
@@ -211,7 +226,10 @@ __global__ __launch_bounds__(256) void sim_accumulate_kernel(const SimAccParams 
             double term;
             if (a == row) term = p.self_score;
             else if (!has) continue;
-            else term = sim_term(p.counts[row * kSimSlots + j], len_v, bloom_v, p.len[a], p.bloom[a]);
+            else {
+                sim_len_bloom(p.len, p.bloom, p.lidx, p.len_l, p.bloom_l, a, len_a, bloom_a);
+                term = sim_term(p.counts[row * kSimSlots + j], len_v, bloom_v, len_a, bloom_a);
+            }
             if (term == 0.0) continue;
             if (j < p.liked) liked += term;
             else disliked += term;
@@ -270,17 +288,22 @@ __global__ __launch_bounds__(256) void sim_top_keys_kernel(const double *score, 
     }
 }
 
-// debug export: counts / bloom / len of device row -> sid order (rows without a set bit have no counts; bits == NULL: no counts at all)
+// debug export: counts / bloom / len of device row -> sid order (rows without a set bit have no counts; bits == NULL: no counts at all;
+// lidx / len_l / bloom_l as in SimAccParams)
 __global__ __launch_bounds__(256) void sim_export_kernel(const uint32_t *counts, const uint32_t *bits, const uint64_t *bloom, const uint32_t *len,
-                                                         const uint32_t *dev_of, uint64_t n, uint32_t *o_counts, uint64_t *o_bloom, uint32_t *o_len)
+                                                         const uint32_t *lidx, const uint32_t *len_l, const uint64_t *bloom_l, const uint32_t *dev_of, uint64_t n,
+                                                         uint32_t *o_counts, uint64_t *o_bloom, uint32_t *o_len)
 {
     const uint64_t stride = (uint64_t)gridDim.x * 256;
     for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < n; s += stride) {
         const uint64_t row = dev_of[s];
         const bool has = bits && ((bits[row >> 5] >> (row & 31u)) & 1u);
         for (uint32_t j = 0; j < kSimSlots; j++) o_counts[s * kSimSlots + j] = has ? counts[row * kSimSlots + j] : 0u;
-        o_bloom[s] = bloom[row];
-        o_len[s] = len[row];
+        uint32_t len_v;
+        unsigned long long bloom_v;
+        sim_len_bloom(len, bloom, lidx, len_l, bloom_l, row, len_v, bloom_v);
+        o_bloom[s] = bloom_v;
+        o_len[s] = len_v;
     }
 }
 

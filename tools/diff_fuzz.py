@@ -358,12 +358,17 @@ def betweenness_case(rng, max_nodes, case):
 
 def similarity_case(rng, max_nodes, case):
     """hb_inbound_similarity: random graph x random entry lists (duplicates, unknown ids, an entry equal to a scored node - every known
-    entry is one) x the three mode settings, against the host restatement (tests/inbound_similarity_ref.py), bit for bit."""
+    entry is one) x a limit (0 = whole in-lists, and small values that cut) x a key set (few distinct keys: ties are common) x the three
+    mode settings, against the host restatement (tests/inbound_similarity_ref.py over the BitVecs of tests/limited_similarity_ref.py),
+    bit for bit."""
     from stract_amd.harmonic import EdgeListGraph, ids_from_ints
     from tests import inbound_similarity_ref as sref
+    from tests import limited_similarity_ref as lref
     kind, tuples = graphs.random_graph(rng)
     if not tuples:
         return None
+    nodes = sorted({x for e in tuples for x in e[:2]})
+    tuples = sorted(set(tuples) | {(v, v) for v in nodes if rng.integers(0, 8) == 0})  # some self links: listed rows at every limit
     chunk = int(rng.choice([0, 0, 4, 8, 64]))
     flags = _lib.HB_FLAG_ALL_RELS | int(rng.choice([0, 0, _lib.HB_FLAG_NO_REORDER, _lib.HB_FLAG_NO_XCD_MAP, _lib.HB_FLAG_NO_SPARSE]))
     with _lib.Context(flags=flags, chunk=chunk) as ctx:
@@ -372,7 +377,6 @@ def similarity_case(rng, max_nodes, case):
         ids = graph[0]
         ints = sref.id_ints(ids)
         n = len(ints)
-        bv = sref.bitvecs(*graph)
         what = dict(case=case, kind="similarity:" + kind, n=n, m=int(len(graph[2])), chunk=chunk, flags=flags, passes=0)
 
         def entries(k):
@@ -388,11 +392,19 @@ def similarity_case(rng, max_nodes, case):
                 continue
             normalized = bool(rng.integers(0, 2))
             self_score = [None, 0.25, 3.0][int(rng.integers(0, 3))]
+            limit = int(rng.choice([0, 0, 1, 2, 3, 8, 1024]))
+            keys = [(v, int(rng.integers(0, 4))) for v in ints if rng.integers(0, 2)] if rng.integers(0, 2) else []
+            if keys:
+                ctx.links_set_keys(ids_from_ints([v for v, _ in keys]), np.array([k for _, k in keys], dtype=np.uint64))
+            else:
+                ctx.links_set_keys()
+            bv = lref.bitvecs(*graph, keys, limit)
             want = sref.literal(*graph, liked, disliked, normalized, 1.0 if self_score is None else self_score, bv=bv)
             last = (liked + disliked)[(len(liked) + len(disliked) - 1) // 16 * 16:]
             for mode in (None, "dense", "sparse"):
-                run = dict(what, liked=liked, disliked=disliked, normalized=normalized, self_score=self_score, mode=mode)
-                st = ctx.inbound_similarity(ids_from_ints(liked), ids_from_ints(disliked), normalized=normalized, self_score=self_score, mode=mode)
+                run = dict(what, liked=liked, disliked=disliked, normalized=normalized, self_score=self_score, mode=mode, limit=limit, keys=keys)
+                st = ctx.inbound_similarity(ids_from_ints(liked), ids_from_ints(disliked), normalized=normalized, self_score=self_score, mode=mode,
+                                            limit=limit)
                 assert ctx.similarity_all().tobytes() == want.tobytes(), ("scores", run)
                 counts, bloom, length = ctx.debug_similarity_batch()
                 assert np.array_equal(counts[:, :len(last)], sref.counts(bv, ids, last)), ("counts of the last batch", run)
