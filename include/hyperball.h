@@ -768,6 +768,73 @@ int hb_similar_count(hb_ctx *ctx, uint64_t *count);
 int hb_similar_copy(hb_ctx *ctx, hb_u128 *ids, double *scores, uint64_t cap);   /* the top list, at most cap >= count entries */
 int hb_similar_candidates(hb_ctx *ctx, hb_u128 *ids, uint64_t *counts, uint64_t cap, uint64_t *written); /* ids / counts may be NULL */
 
+/* ---- scoring result hosts: inbound_similarity::Scorer::score per search, as the InboundScorer stage calls it ------------------------ */
+/* What the searcher does with a query that carries host rankings (searcher/api/mod.rs:467-501: Scorer::new(webgraph, liked, disliked,
+ * false); :411-465 combine_results and :199-216 batch_raw_ingoing_hosts: the BitVec of every unique result host from
+ * EdgeLimit::Limit(512) backlinks; ranking/pipeline/scorers/inbound_similarity.rs:38-54: Scorer::score(host, inbound) for at most 300
+ * pages) - for several searches per call, with work proportional to (result hosts + anchors) x limit instead of the graph.
+ * Everything holds under the current key set of hb_links_set_keys.
+ * BitVec(v) for 1 <= limit <= 1024 is exactly the BitVec of hb_inbound_similarity with that limit: the entries are backlinks(v, limit),
+ * sorted; len = min(degree(v), limit); the 64-bit bloom mask covers those entries only; an id that is no node of the graph has the
+ * empty BitVec.
+ * A request is (liked[], disliked[], nodes[], flags, self_score).  For every entry v of nodes, in caller order:
+ *   score(v) = max(0.0, s) with s = D + (sum_liked - sum_disliked), in exactly that grouping; with HB_SIM_NORMALIZED s is divided by
+ *   max(L, 1).  L and D count the liked and disliked entries as given: duplicates and unknown ids count.  Each sum runs in caller order
+ *   from +0.0.
+ * A pair (anchor a, node v) is classified in this order:
+ *   1. self: the NodeIDs are equal, also for ids that are no node; it contributes self_score (1.0 unless HB_SIM_SELF_SCORE).
+ *   2. empty: either len is 0; it contributes 0.0.
+ *   3. gated: 4 popcount(ma & mv) < max(popcount(ma), popcount(mv)), in integers; it contributes 0.0.
+ *   4. intersected: it contributes |inL(a) & inL(v)| as f64 / (sqrt(len_a) x sqrt(len_v)) - IEEE sqrt, one multiply and one divide, no
+ *      FMA contraction, no floating-point atomics.
+ * This is NodeScorer::sim + BitVec::sim + Scorer::calculate_score (ranking/inbound_similarity.rs:44-50,99-118).
+ * The contract: for every request the result is bit for bit what hb_inbound_similarity(the same liked, disliked, flags, self_score,
+ * limit) followed by hb_similarity_lookup(nodes) returns on the same context and key set.
+ * The operator borrows nothing (no HyperBall rows, no result image), leaves the results of every other operator readable - the links,
+ * similar-hosts and similarity results included -, keeps holders of its own in the graph state (they only grow, are counted in
+ * device_bytes and freed by the next load: O(distinct x limit) plus one piece of the pair space plus the entries of the call), and its
+ * result lives until the next successful call or the next load; a refused call changes nothing.  A request without nodes yields an
+ * empty slice, one without anchors scores of max(0, 0).
+ * Refused (HB_ERR_INVALID): opt == NULL, request_count == 0 or above 4096, a NULL pointer with a non-zero count, limit outside 1 .. 1024,
+ * slots_per_batch > 65536, more than 2^24 anchor plus node entries in total, more than 262144 distinct known hosts, between hb_begin and
+ * hb_finish, without a loaded graph, world_size > 1, an unexpected plan layout.  DESIGN.md section 30. */
+#define HB_SCORE_SMALL_PIECES 0x100u /* debug: the pair space is walked in pieces of 64 pairs instead of 2^20 (same result) */
+
+typedef struct hb_score_request {
+    const hb_u128 *liked;    uint64_t liked_count;
+    const hb_u128 *disliked; uint64_t disliked_count;
+    const hb_u128 *nodes;    uint64_t node_count;   /* the result hosts, scored in this order; duplicates each get the answer */
+    uint32_t flags, reserved;                       /* HB_SIM_NORMALIZED | HB_SIM_SELF_SCORE */
+    double self_score;                              /* used only with HB_SIM_SELF_SCORE */
+} hb_score_request;
+
+typedef struct hb_score_options {
+    uint32_t struct_size, flags;                    /* struct_size = sizeof(hb_score_options); 0 = this version; flags: HB_LINKS_SPREAD_ORDS /
+                                                       HB_LINKS_NO_SHORTCUT reach the list selects, HB_SCORE_SMALL_PIECES (debug: same result) */
+    const hb_score_request *requests; uint64_t request_count;
+    uint32_t limit, slots_per_batch;                /* 1 .. 1024 (the reference: 512); 0 = the list builder's default */
+} hb_score_options;
+
+typedef struct hb_score_stats {
+    uint32_t struct_size, reserved; /* struct_size = sizeof(hb_score_stats); 0 = this version */
+    uint64_t requests;
+    uint64_t anchors, nodes;                   /* liked + disliked entries / node entries of all requests, as given */
+    uint64_t unknown_anchors, unknown_nodes;   /* ... of which no node of the graph */
+    uint64_t distinct;                         /* the known hosts of the call, each looked up once across all requests */
+    uint64_t pairs;                            /* sum over the requests of nodes x anchors = the four classes below */
+    uint64_t pairs_self, pairs_empty, pairs_gated, pairs_intersected;
+    uint64_t pieces;                           /* launches of the pair kernel's piece loop */
+    uint64_t device_bytes;                     /* the operator's own buffers */
+    double   ms_total;                         /* wall time of the call */
+    double   ms_lists, ms_bitvec, ms_pairs, ms_finish; /* GPU time: the list selects, the BitVec kernel, the pair kernel, the finish kernel */
+} hb_score_stats;
+
+int hb_score_hosts(hb_ctx *ctx, const hb_score_options *opt, hb_score_stats *stats);
+/* The result of the last hb_score_hosts: offsets[r] .. offsets[r + 1] is the slice of request r (requests + 1 offsets), scores[] one f64
+ * per node entry in caller order (cap >= the scores of hb_score_count); either may be NULL. */
+int hb_score_count(hb_ctx *ctx, uint64_t *requests, uint64_t *scores);
+int hb_score_copy(hb_ctx *ctx, uint64_t *offsets /* requests + 1 */, double *scores, uint64_t cap);
+
 /* ---- multi-GPU (one process per GPU, RCCL over xGMI) -------------------------------------- */
 /* Rank 0 calls this and distributes the 128 bytes (e.g. torch.distributed broadcast);
  * every rank puts them in hb_options.rccl_id. */

@@ -378,6 +378,46 @@ class HbSimilarStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+HB_SCORE_SMALL_PIECES = 0x100
+
+
+class HbScoreRequest(ctypes.Structure):
+    _fields_ = [
+        ("liked", ctypes.c_void_p),
+        ("liked_count", ctypes.c_uint64),
+        ("disliked", ctypes.c_void_p),
+        ("disliked_count", ctypes.c_uint64),
+        ("nodes", ctypes.c_void_p),
+        ("node_count", ctypes.c_uint64),
+        ("flags", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("self_score", ctypes.c_double),
+    ]
+
+
+class HbScoreOptions(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("flags", ctypes.c_uint32),
+        ("requests", ctypes.POINTER(HbScoreRequest)),
+        ("request_count", ctypes.c_uint64),
+        ("limit", ctypes.c_uint32),
+        ("slots_per_batch", ctypes.c_uint32),
+    ]
+
+
+class HbScoreStats(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ] + [(k, ctypes.c_uint64) for k in ("requests", "anchors", "nodes", "unknown_anchors", "unknown_nodes", "distinct", "pairs", "pairs_self", "pairs_empty",
+                                        "pairs_gated", "pairs_intersected", "pieces", "device_bytes")] + [
+        (k, ctypes.c_double) for k in ("ms_total", "ms_lists", "ms_bitvec", "ms_pairs", "ms_finish")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 class HbLinksKeyOptions(ctypes.Structure):
     _fields_ = [
         ("struct_size", ctypes.c_uint32),
@@ -604,6 +644,10 @@ _SIGNATURES += [
     ("hb_similar_count", ctypes.c_int, [_P, ctypes.POINTER(_U64)]),
     ("hb_similar_copy", ctypes.c_int, [_P, _P, _P, _U64]),
     ("hb_similar_candidates", ctypes.c_int, [_P, _P, _P, _U64, ctypes.POINTER(_U64)]),
+    # include/hyperball.h: scoring result hosts (Scorer::score per search)
+    ("hb_score_hosts", ctypes.c_int, [_P, ctypes.POINTER(HbScoreOptions), ctypes.POINTER(HbScoreStats)]),
+    ("hb_score_count", ctypes.c_int, [_P, ctypes.POINTER(_U64), ctypes.POINTER(_U64)]),
+    ("hb_score_copy", ctypes.c_int, [_P, _P, _P, _U64]),
 ]
 SYMBOLS = [s[0] for s in _SIGNATURES]
 
@@ -1236,6 +1280,48 @@ class Context:
         counts = np.zeros(w.value, dtype=np.uint64)
         self._check(self.lib.hb_similar_candidates(self.h, _ptr(ids), _ptr(counts), w.value, ctypes.byref(w)))
         return ids, counts
+
+    # -- scoring result hosts (Scorer::score per search, ranking/pipeline/scorers/inbound_similarity.rs:38-54)
+    def score_hosts(self, requests, limit=512, flags=0, slots_per_batch=0, small_pieces=False):
+        """hb_score_hosts: every request is a dict with `nodes` (the result hosts, U128 array, scored in this order) and optionally
+        `liked`, `disliked` (U128 arrays; duplicates and unknown ids count), `normalized`, `self_score`.  limit: 1 .. 1024 backlinks
+        per BitVec under the current key set (the reference: 512).  Returns the stats; score_copy() the scores."""
+        keep = []  # (the arrays the request structs point into)
+
+        def arr(a):
+            a = np.ascontiguousarray(a, dtype=U128) if a is not None and len(a) else np.zeros(0, dtype=U128)
+            keep.append(a)
+            return (a.ctypes.data if len(a) else None), len(a)
+
+        reqs = (HbScoreRequest * max(len(requests), 1))()
+        for q, r in zip(reqs, requests):
+            q.liked, q.liked_count = arr(r.get("liked"))
+            q.disliked, q.disliked_count = arr(r.get("disliked"))
+            q.nodes, q.node_count = arr(r.get("nodes"))
+            q.flags = HB_SIM_NORMALIZED if r.get("normalized") else 0
+            if r.get("self_score") is not None:
+                q.flags |= HB_SIM_SELF_SCORE
+                q.self_score = float(r["self_score"])
+        o = HbScoreOptions()
+        o.struct_size = ctypes.sizeof(HbScoreOptions)
+        o.flags = int(flags) | (HB_SCORE_SMALL_PIECES if small_pieces else 0)
+        if len(requests):
+            o.requests, o.request_count = reqs, len(requests)
+        o.limit = int(limit)
+        o.slots_per_batch = int(slots_per_batch)
+        st = HbScoreStats()
+        st.struct_size = ctypes.sizeof(HbScoreStats)
+        self._check(self.lib.hb_score_hosts(self.h, ctypes.byref(o), ctypes.byref(st)))
+        return st.as_dict()
+
+    def score_copy(self):
+        """The scores of the last score_hosts() call: one float64 array per request, in request order, one value per node entry"""
+        r, k = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._check(self.lib.hb_score_count(self.h, ctypes.byref(r), ctypes.byref(k)))
+        offsets = np.zeros(r.value + 1, dtype=np.uint64)
+        scores = np.zeros(k.value, dtype=np.float64)
+        self._check(self.lib.hb_score_copy(self.h, _ptr(offsets), _ptr(scores), k.value))
+        return [scores[int(offsets[i]):int(offsets[i + 1])].copy() for i in range(r.value)]
 
     # -- results
     def results(self):

@@ -30,6 +30,7 @@
 #include "hb_links.hip.h"
 #include "hb_similar.hip.h"
 #include "hb_similarity_limit.hip.h"
+#include "hb_score.hip.h"
 #ifdef HB_EXPERIMENTS
 #include "hb_experiments.hip.h"
 #endif
@@ -329,6 +330,27 @@ struct GraphDeviceState {
         DevPtr<unsigned long long> d_cnt; // 4 counters of the list-count kernel
         uint64_t bytes = 0;
     } lim;
+    // hb_score_hosts (hb_api_score.inc): the BitVecs of the distinct known hosts of a call, the entries of its requests, one piece of
+    // the pair space and the last result.  The holders own them (they grow with the hosts and entries of a call and with the limit):
+    // freed by the next load, counted in `bytes` and in hb_stats.device_bytes.  The operator borrows nothing; the buffers of a batch of
+    // the list builder are the links state's
+    struct ScoreState {
+        bool valid = false; // the result below is that of a finished hb_score_hosts
+        DevPtr<uint32_t> d_lists, d_len;          // distinct x limit: the backlinks of the distinct known hosts (sorted by sid), their degrees
+        DevPtr<unsigned long long> d_mask;        // distinct: their bloom masks
+        DevPtr<unsigned long long> d_keys;        // the lists' keys of one call of the list builder (nobody reads them here)
+        DevPtr<uint32_t> d_node_idx, d_anchor_idx; // the nodes / the anchors of all requests as indices of the call's distinct ids
+        DevPtr<hbk::ScRequest> d_req;
+        DevPtr<hbk::ScRect> d_rect;               // the rectangles of one piece
+        DevPtr<uint32_t> d_pair;                  // the pair words of one piece
+        DevPtr<double> d_acc, d_score;            // nodes x 2: the running sums; nodes: the scores
+        DevPtr<unsigned long long> d_cnt;         // the four pair counters
+        uint64_t cap_lists = 0, cap_len = 0, cap_mask = 0, cap_keys = 0, cap_node_idx = 0, cap_anchor_idx = 0, cap_req = 0, cap_rect = 0, cap_pair = 0,
+                 cap_acc = 0, cap_score = 0, cap_cnt = 0;
+        std::vector<uint64_t> offsets;            // the result on the host: requests + 1 offsets into scores
+        std::vector<double> scores;
+        uint64_t bytes = 0;
+    } sco;
 };
 
 // The timing events of a pass (one set: hb_ctx::ev, or an EvSet), in the order a pass records them; kEvLevel1 lies between kEvStart and
@@ -1631,3 +1653,4 @@ int hb_store_harmonic_results(hb_ctx *c, const char *output, char *err, uint64_t
 #include "hb_api_links.inc"
 #include "hb_api_similarity.inc" // (after the links: the limited mode builds its cut lists with their list builder)
 #include "hb_api_similar.inc"
+#include "hb_api_score.inc"

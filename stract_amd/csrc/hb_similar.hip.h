@@ -112,20 +112,20 @@ __global__ __launch_bounds__(256) void sh_take_kernel(const uint64_t *key, const
     }
 }
 
-// a workgroup per list: sorted by sid in place, its bloom mask
-__global__ __launch_bounds__(256) void sh_bitvec_kernel(uint32_t *lists, const uint32_t *len, const uint32_t *dev_of, const uint64_t *idlow, uint64_t n,
-                                                        unsigned long long *mask)
+// the body of a BitVec kernel, a workgroup per list (sh_bitvec_kernel here, sc_bitvec_kernel in hb_score.hip.h): the first
+// min(len, stride) sids of list `slot` sorted ascending in place - a bitonic sort of `sort_n` LDS words, a power of two >= stride - and
+// the bloom mask of those entries
+__device__ __forceinline__ void sh_bitvec_body(uint32_t *s_v, unsigned long long *s_mask, uint32_t sort_n, uint32_t stride, uint32_t *lists, const uint32_t *len,
+                                               const uint32_t *dev_of, const uint64_t *idlow, uint64_t n, unsigned long long *mask)
 {
-    __shared__ uint32_t s_v[kShList];
-    __shared__ unsigned long long s_mask;
     const uint64_t slot = blockIdx.x;
-    const uint32_t d = len[slot], L = d < kShList ? d : kShList;
-    if (threadIdx.x == 0) s_mask = 0ull;
-    for (uint32_t i = threadIdx.x; i < kShList; i += 256) s_v[i] = i < L ? lists[slot * kShList + i] : kNone;
+    const uint32_t d = len[slot], L = d < stride ? d : stride;
+    if (threadIdx.x == 0) *s_mask = 0ull;
+    for (uint32_t i = threadIdx.x; i < sort_n; i += 256) s_v[i] = i < L ? lists[slot * stride + i] : kNone;
     __syncthreads();
-    for (uint32_t k = 2; k <= kShList; k <<= 1)
+    for (uint32_t k = 2; k <= sort_n; k <<= 1)
         for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < kShList; i += 256) {
+            for (uint32_t i = threadIdx.x; i < sort_n; i += 256) {
                 const uint32_t x = i ^ j;
                 if (x > i) {
                     const uint32_t a = s_v[i], c = s_v[x];
@@ -141,12 +141,21 @@ __global__ __launch_bounds__(256) void sh_bitvec_kernel(uint32_t *lists, const u
     for (uint32_t i = threadIdx.x; i < L; i += 256) {
         const uint32_t v = s_v[i];
         HB_DBG_ASSERT(v < n);
-        lists[slot * kShList + i] = v;
+        lists[slot * stride + i] = v;
         if (v < n) mine |= 1ull << ((idlow[dev_of[v]] * kSimBloomMul) & 63ull);
     }
-    if (mine) atomicOr(&s_mask, mine);
+    if (mine) atomicOr(s_mask, mine);
     __syncthreads();
-    if (threadIdx.x == 0) mask[slot] = s_mask;
+    if (threadIdx.x == 0) mask[slot] = *s_mask;
+}
+
+// a workgroup per list: sorted by sid in place, its bloom mask
+__global__ __launch_bounds__(256) void sh_bitvec_kernel(uint32_t *lists, const uint32_t *len, const uint32_t *dev_of, const uint64_t *idlow, uint64_t n,
+                                                        unsigned long long *mask)
+{
+    __shared__ uint32_t s_v[kShList];
+    __shared__ unsigned long long s_mask;
+    sh_bitvec_body(s_v, &s_mask, kShList, kShList, lists, len, dev_of, idlow, n, mask);
 }
 
 // a workgroup per candidate; anchor_slot: the liked entries in caller order as slots of the anchors' lists, kNone = no node of the graph

@@ -9,7 +9,7 @@ for the `make asan` build).  A failure prints the seed and case that reproduce i
 value, weighted towards 40..58 and 65 (tests/graphs.py crafted_id_low): the estimator's sequential fold, saturated sizes and the six-bit
 wire codes above 47, which ids 1..n never reach; mixed alternates between plain and extreme.
 
-usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|distances|betweenness|similarity|nearest_seed] [--ids plain|extreme|mixed] [--seconds S] [--seed N] [--max-nodes N]"""
+usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|distances|betweenness|similarity|nearest_seed|score_hosts] [--ids plain|extreme|mixed] [--seconds S] [--seed N] [--max-nodes N]"""
 import argparse
 import json
 import os
@@ -421,6 +421,58 @@ def similarity_case(rng, max_nodes, case):
     return what
 
 
+def score_hosts_case(rng, max_nodes, case):
+    """hb_score_hosts: random graph (self links added) x a key set (few distinct keys) x a limit x 1 to 5 requests that share hosts,
+    with unknown ids and duplicates on every side x the piece size and the debug flags of the list selects, against the route it
+    replaces on the same context - hb_inbound_similarity + hb_similarity_lookup per request - and against the literal restatement
+    (tests/score_hosts_ref.py): every score bit for bit, every counter."""
+    from stract_amd.harmonic import EdgeListGraph, ids_from_ints
+    from tests import inbound_similarity_ref as sref
+    from tests import score_hosts_ref as ref
+    kind, tuples = graphs.random_graph(rng)
+    if not tuples:
+        return None
+    nodes = sorted({x for e in tuples for x in e[:2]})
+    tuples = sorted(set(tuples) | {(v, v) for v in nodes if rng.integers(0, 8) == 0})
+    chunk = int(rng.choice([0, 0, 4, 8, 64]))
+    flags = _lib.HB_FLAG_ALL_RELS | int(rng.choice([0, 0, _lib.HB_FLAG_NO_REORDER, _lib.HB_FLAG_NO_XCD_MAP, _lib.HB_FLAG_NO_SPARSE]))
+    with _lib.Context(flags=flags, chunk=chunk) as ctx:
+        ctx.load_edges(EdgeListGraph.from_tuples(tuples).host_edges())
+        graph = ctx.graph()
+        ints = sref.id_ints(graph[0])
+        n = len(ints)
+        what = dict(case=case, kind="score_hosts:" + kind, n=n, m=int(len(graph[2])), chunk=chunk, flags=flags, passes=0)
+        pool = [ints[int(x)] for x in rng.integers(0, n, 12)] + [(1 << 100) + 1, (1 << 100) + 2]  # what the requests share
+
+        def entries(k):
+            return [pool[int(rng.integers(0, len(pool)))] if rng.integers(0, 3) == 0 else ints[int(rng.integers(0, n))] for _ in range(k)]
+
+        for _ in range(2):
+            limit = int(rng.choice([1, 2, 3, 8, 512, 1024]))
+            keys = [(v, int(rng.integers(0, 4))) for v in ints if rng.integers(0, 2)] if rng.integers(0, 2) else []
+            if keys:
+                ctx.links_set_keys(ids_from_ints([v for v, _ in keys]), np.array([k for _, k in keys], dtype=np.uint64))
+            else:
+                ctx.links_set_keys()
+            requests = [dict(liked=entries(int(rng.integers(0, 40))), disliked=entries(int(rng.integers(0, 20))), nodes=entries(int(rng.integers(0, 30))),
+                             normalized=bool(rng.integers(0, 2)), self_score=[None, 0.25, 3.0][int(rng.integers(0, 3))]) for _ in range(int(rng.integers(1, 6)))]
+            want, wst = ref.literal(ref.tables(*graph, keys, limit), requests)
+            sflags = int(rng.choice([0, _lib.HB_LINKS_SPREAD_ORDS, _lib.HB_LINKS_NO_SHORTCUT]))
+            small = bool(rng.integers(0, 2))
+            run = dict(what, limit=limit, keys=keys, requests=requests, sflags=sflags, small_pieces=small)
+            st = ctx.score_hosts([dict(r, liked=ids_from_ints(r["liked"]), disliked=ids_from_ints(r["disliked"]), nodes=ids_from_ints(r["nodes"])) for r in requests],
+                                 limit=limit, flags=sflags, small_pieces=small, slots_per_batch=int(rng.choice([0, 3])))
+            got = ctx.score_copy()
+            assert [g.tobytes() for g in got] == [w.tobytes() for w in want], ("scores against the restatement", run)
+            assert {k: st[k] for k in wst} == wst, ("stats", run, st)
+            for r, g in zip(requests, got):
+                if r["liked"] or r["disliked"]:
+                    ctx.inbound_similarity(ids_from_ints(r["liked"]), ids_from_ints(r["disliked"]), normalized=r["normalized"], self_score=r["self_score"], limit=limit)
+                    assert ctx.similarity_lookup(ids_from_ints(r["nodes"])).tobytes() == g.tobytes(), ("scores against the lookup route", run)
+            what["passes"] += st["pieces"]
+    return what
+
+
 def nearest_seed_case(rng, max_nodes, case):
     """hb_nearest_seed: random graph (self links added) x random original / key lists (duplicates, unknown ids, 0.0, few distinct keys so
     that ties are common, u64::MAX) x rounds x discount, against the host restatement (tests/nearest_seed_ref.py): the seed of every
@@ -472,7 +524,7 @@ def nearest_seed_case(rng, max_nodes, case):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "distances", "betweenness", "similarity", "nearest_seed"], default="passes")
+    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "distances", "betweenness", "similarity", "nearest_seed", "score_hosts"], default="passes")
     ap.add_argument("--ids", choices=["plain", "extreme", "mixed"], default="plain")
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--seed", type=int, default=1)
@@ -493,6 +545,8 @@ def main():
                 w = similarity_case(rng, a.max_nodes, case)
             elif a.mode == "nearest_seed":
                 w = nearest_seed_case(rng, a.max_nodes, case)
+            elif a.mode == "score_hosts":
+                w = score_hosts_case(rng, a.max_nodes, case)
             elif a.mode == "ranks" or (a.mode == "mixed" and case % 6 == 4):
                 w = ranks_case(rng, a.max_nodes, case, extreme)
             elif a.mode == "tail" or (a.mode == "mixed" and case % 6 == 5):
