@@ -9,7 +9,12 @@ for the `make asan` build).  A failure prints the seed and case that reproduce i
 value, weighted towards 40..58 and 65 (tests/graphs.py crafted_id_low): the estimator's sequential fold, saturated sizes and the six-bit
 wire codes above 47, which ids 1..n never reach; mixed alternates between plain and extreme.
 
-usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|distances|betweenness|similarity|nearest_seed|score_hosts] [--ids plain|extreme|mixed] [--seconds S] [--seed N] [--max-nodes N]"""
+The operator modes (distances ... sampled; `operators` alternates over all nine) run the bodies of tests/operator_cases.py, each against the
+CPU restatement of its operator, on contexts of that module's layout recipe: chunk 4 / 8 / 16 / 64, tune[3..5] (band width, minimum
+sources before a band cut, largest row that is not split) and two of NO_REORDER / NO_XCD_MAP / HOST_PLAN / NO_SPARSE.
+
+usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|operators|distances|betweenness|similarity|nearest_seed|score_hosts|backlinks|forwardlinks|similar_hosts|sampled]
+                          [--ids plain|extreme|mixed] [--seconds S] [--seed N] [--max-nodes N]"""
 import argparse
 import json
 import os
@@ -24,6 +29,7 @@ from oracle import hbo  # noqa: E402
 from stract_amd import _lib  # noqa: E402
 from stract_amd.harmonic import EdgeListGraph  # noqa: E402
 from tests import graphs  # noqa: E402
+from tests import operator_cases as oc  # noqa: E402
 
 FLAG_POOL = ["NO_REORDER", "NO_XCD_MAP", "UNFUSED", "NO_SPARSE", "NO_FRONTIER", "PASS_STATS", "HOST_PLAN", "NO_INIT_PASS"]
 
@@ -285,246 +291,28 @@ def ranks_case(rng, max_nodes, case, extreme=False):
     return what
 
 
-def distances_case(rng, max_nodes, case):
-    """hb_distances: random graph x random source set x direction x max_dist x forced step, against the host restatement
-    (tests/distance_ref.py: the literal dijkstra_multi with the u8 rule)."""
-    from stract_amd.harmonic import EdgeListGraph
-    from tests import distance_ref as dref
-    kind, tuples = graphs.random_graph(rng)
-    if not tuples:
-        return None
-    chunk = int(rng.choice([0, 0, 4, 8, 64]))
-    flags = _lib.HB_FLAG_ALL_RELS | int(rng.choice([0, 0, _lib.HB_FLAG_NO_REORDER, _lib.HB_FLAG_NO_XCD_MAP, _lib.HB_FLAG_NO_SPARSE]))
-    with _lib.Context(flags=flags, chunk=chunk) as ctx:
-        ctx.load_edges(EdgeListGraph.from_tuples(tuples).host_edges())
-        ids, row_ptr, src = ctx.graph()
-        n = len(ids)
-        what = dict(case=case, kind="distances:" + kind, n=n, m=int(len(src)), chunk=chunk, flags=flags, passes=0)
-        for _ in range(4):
-            srcs = sorted(set(int(x) for x in rng.integers(0, n, int(rng.integers(1, 5)))))
-            rev = bool(rng.integers(0, 2))
-            md = [None, 0, 1, 7, 15, 200][int(rng.integers(0, 6))]
-            mode = [None, "top_down", "bottom_up"][int(rng.integers(0, 3))]
-            want = dref.dijkstra(n, row_ptr, src, srcs, reversed=rev, max_dist=md)
-            gids, gdist, st = ctx.distances(ids[np.asarray(srcs, dtype=np.int64)], reversed=rev, max_dist=md, mode=mode)
-            keep = want != dref.UNREACHED
-            run = dict(what, sources=srcs, reversed=rev, max_dist=md, mode=mode)
-            assert np.array_equal(gids, ids[keep]) and np.array_equal(gdist, want[keep]), ("distance list", run)
-            assert np.array_equal(ctx.distance_all(), want) and st["reached"] == int(keep.sum()) == sum(st["frontier"]), ("distance array / counters", run)
-            what["passes"] += st["levels"]
-    return what
+OPERATOR_MODES = ["distances", "betweenness", "similarity", "nearest_seed", "score_hosts", "backlinks", "forwardlinks", "similar_hosts", "sampled"]
 
 
-def betweenness_case(rng, max_nodes, case):
-    """hb_betweenness: random graph x random source set x forced mode, against the host restatement (tests/betweenness_ref.py: the
-    literal betweenness.rs:50-122) under the comparison rule of tests/test_betweenness.py."""
-    from stract_amd.harmonic import EdgeListGraph
-    from tests import betweenness_ref as bref
-    kind, tuples = graphs.random_graph(rng)
-    if not tuples:
-        return None
-    chunk = int(rng.choice([0, 0, 4, 8, 64]))
-    flags = _lib.HB_FLAG_ALL_RELS | int(rng.choice([0, 0, _lib.HB_FLAG_NO_REORDER, _lib.HB_FLAG_NO_XCD_MAP, _lib.HB_FLAG_NO_SPARSE]))
-    with _lib.Context(flags=flags, chunk=chunk) as ctx:
-        ctx.load_edges(EdgeListGraph.from_tuples(tuples).host_edges())
-        ids, row_ptr, src = ctx.graph()
-        n = len(ids)
-        what = dict(case=case, kind="betweenness:" + kind, n=n, m=int(len(src)), chunk=chunk, flags=flags, passes=0)
-        for _ in range(3):
-            srcs = sorted(set(int(x) for x in rng.integers(0, n, int(rng.integers(1, 20)))))
-            mode = [None, "dense", "sparse"][int(rng.integers(0, 3))]
-            raw = bool(rng.integers(0, 2))
-            run = dict(what, sources=srcs, mode=mode, raw=raw)
-            res = bref.literal(n, row_ptr, src, srcs)
-            if res.max_dist > 254 or max(max(s) for s in res.sigma) >= 2 ** 64 - 1:
-                continue  # (HB_ERR_LIMIT cases: tests/test_betweenness.py)
-            tol = bref.rtol(n, row_ptr, src, res)
-            gids, gvals, st = ctx.betweenness(ids[np.asarray(srcs, dtype=np.int64)], raw=raw, mode=mode)
-            want = res.values(raw)[res.reached]
-            assert np.array_equal(gids, ids[res.reached]) and st["max_dist"] == res.max_dist and st["results"] == len(gids), ("result set / max_dist", run)
-            assert np.array_equal(np.isnan(gvals), np.isnan(want)) and np.array_equal(np.isinf(gvals), np.isinf(want)), ("NaN / inf pattern", run)
-            fin = np.isfinite(want)
-            assert not gvals[fin & (want == 0.0)].view(np.uint64).any(), ("+0.0 values", run)
-            assert (np.abs(gvals[fin] - want[fin]) <= tol * np.abs(want[fin])).all(), ("values", run, tol)
-            dist, sigma, delta = ctx.debug_betweenness_batch()
-            first = (len(srcs) - 1) // 8 * 8
-            for lane, k in enumerate(range(first, len(srcs))):
-                assert np.array_equal(dist[:, lane], np.where(res.dist[k] < 0, 255, res.dist[k]).astype(np.uint8)), ("dist of source %d" % k, run)
-                assert [int(x) for x in sigma[:, lane]] == res.sigma[k], ("sigma of source %d" % k, run)
-                assert (np.abs(delta[:, lane] - res.delta[k]) <= tol * np.abs(res.delta[k])).all(), ("delta of source %d" % k, run)
-            what["passes"] += st["levels_forward"] + st["levels_backward"]
-    return what
-
-
-def similarity_case(rng, max_nodes, case):
-    """hb_inbound_similarity: random graph x random entry lists (duplicates, unknown ids, an entry equal to a scored node - every known
-    entry is one) x a limit (0 = whole in-lists, and small values that cut) x a key set (few distinct keys: ties are common) x the three
-    mode settings, against the host restatement (tests/inbound_similarity_ref.py over the BitVecs of tests/limited_similarity_ref.py),
-    bit for bit."""
-    from stract_amd.harmonic import EdgeListGraph, ids_from_ints
-    from tests import inbound_similarity_ref as sref
-    from tests import limited_similarity_ref as lref
-    kind, tuples = graphs.random_graph(rng)
-    if not tuples:
-        return None
-    nodes = sorted({x for e in tuples for x in e[:2]})
-    tuples = sorted(set(tuples) | {(v, v) for v in nodes if rng.integers(0, 8) == 0})  # some self links: listed rows at every limit
-    chunk = int(rng.choice([0, 0, 4, 8, 64]))
-    flags = _lib.HB_FLAG_ALL_RELS | int(rng.choice([0, 0, _lib.HB_FLAG_NO_REORDER, _lib.HB_FLAG_NO_XCD_MAP, _lib.HB_FLAG_NO_SPARSE]))
-    with _lib.Context(flags=flags, chunk=chunk) as ctx:
-        ctx.load_edges(EdgeListGraph.from_tuples(tuples).host_edges())
+def operator_case(rng, case, name):
+    """One context of the layout recipe of tests/operator_cases.py - a graph of graphs.random_graph with self links, chunk 4 / 8 / 16 /
+    64, the planner's cut and split knobs tune[3..5], two layout flags - and on it the body of operator `name`, the one the suite runs
+    (tests/test_layouts.py), against the CPU restatement of that operator.  The hubs of the plan's chunk trees and sources inside them
+    are among the body's queries."""
+    kind, tuples = oc.draw_graph(rng)
+    chunk, tune, flags = oc.draw_layout(rng)
+    what = dict(case=case, kind=name + ":" + kind, chunk=chunk, tune=tune, flags=flags)
+    with oc.load(_lib.Context, tuples, chunk, tune, flags) as ctx:
         graph = ctx.graph()
-        ids = graph[0]
-        ints = sref.id_ints(ids)
-        n = len(ints)
-        what = dict(case=case, kind="similarity:" + kind, n=n, m=int(len(graph[2])), chunk=chunk, flags=flags, passes=0)
-
-        def entries(k):
-            e = [ints[int(x)] for x in rng.integers(0, n, k)]
-            if k > 2:
-                e[int(rng.integers(0, k))] = (1 << 100) + int(rng.integers(0, 3))  # no node of the graph
-                e[int(rng.integers(0, k))] = e[0]  # a duplicate
-            return e
-
-        for _ in range(2):
-            liked, disliked = entries(int(rng.integers(0, 40))), entries(int(rng.integers(0, 20)))
-            if not liked and not disliked:
-                continue
-            normalized = bool(rng.integers(0, 2))
-            self_score = [None, 0.25, 3.0][int(rng.integers(0, 3))]
-            limit = int(rng.choice([0, 0, 1, 2, 3, 8, 1024]))
-            keys = [(v, int(rng.integers(0, 4))) for v in ints if rng.integers(0, 2)] if rng.integers(0, 2) else []
-            if keys:
-                ctx.links_set_keys(ids_from_ints([v for v, _ in keys]), np.array([k for _, k in keys], dtype=np.uint64))
-            else:
-                ctx.links_set_keys()
-            bv = lref.bitvecs(*graph, keys, limit)
-            want = sref.literal(*graph, liked, disliked, normalized, 1.0 if self_score is None else self_score, bv=bv)
-            last = (liked + disliked)[(len(liked) + len(disliked) - 1) // 16 * 16:]
-            for mode in (None, "dense", "sparse"):
-                run = dict(what, liked=liked, disliked=disliked, normalized=normalized, self_score=self_score, mode=mode, limit=limit, keys=keys)
-                st = ctx.inbound_similarity(ids_from_ints(liked), ids_from_ints(disliked), normalized=normalized, self_score=self_score, mode=mode,
-                                            limit=limit)
-                assert ctx.similarity_all().tobytes() == want.tobytes(), ("scores", run)
-                counts, bloom, length = ctx.debug_similarity_batch()
-                assert np.array_equal(counts[:, :len(last)], sref.counts(bv, ids, last)), ("counts of the last batch", run)
-                assert [int(x) for x in bloom] == [bv[v].fold() for v in ints], ("bloom", run)
-                assert [int(x) for x in length] == [len(bv[v].ranks) for v in ints], ("len", run)
-                what["passes"] += sum(st["levels_mode"])
-            asked = liked[:3] + [1 << 100, 5]
-            assert ctx.similarity_lookup(ids_from_ints(asked)).tobytes() == \
-                sref.lookup(bv, liked, disliked, normalized, 1.0 if self_score is None else self_score, asked).tobytes(), ("lookup", what)
-            k = int(rng.integers(1, n + 3))
-            tids, tvals = ctx.similarity_top(k)
-            order = sref.top_order(ids, want, k)
-            assert sref.id_ints(tids) == [v for _, v in order] and tvals.tolist() == [x for x, _ in order], ("top", what, k)
-    return what
-
-
-def score_hosts_case(rng, max_nodes, case):
-    """hb_score_hosts: random graph (self links added) x a key set (few distinct keys) x a limit x 1 to 5 requests that share hosts,
-    with unknown ids and duplicates on every side x the piece size and the debug flags of the list selects, against the route it
-    replaces on the same context - hb_inbound_similarity + hb_similarity_lookup per request - and against the literal restatement
-    (tests/score_hosts_ref.py): every score bit for bit, every counter."""
-    from stract_amd.harmonic import EdgeListGraph, ids_from_ints
-    from tests import inbound_similarity_ref as sref
-    from tests import score_hosts_ref as ref
-    kind, tuples = graphs.random_graph(rng)
-    if not tuples:
-        return None
-    nodes = sorted({x for e in tuples for x in e[:2]})
-    tuples = sorted(set(tuples) | {(v, v) for v in nodes if rng.integers(0, 8) == 0})
-    chunk = int(rng.choice([0, 0, 4, 8, 64]))
-    flags = _lib.HB_FLAG_ALL_RELS | int(rng.choice([0, 0, _lib.HB_FLAG_NO_REORDER, _lib.HB_FLAG_NO_XCD_MAP, _lib.HB_FLAG_NO_SPARSE]))
-    with _lib.Context(flags=flags, chunk=chunk) as ctx:
-        ctx.load_edges(EdgeListGraph.from_tuples(tuples).host_edges())
-        graph = ctx.graph()
-        ints = sref.id_ints(graph[0])
-        n = len(ints)
-        what = dict(case=case, kind="score_hosts:" + kind, n=n, m=int(len(graph[2])), chunk=chunk, flags=flags, passes=0)
-        pool = [ints[int(x)] for x in rng.integers(0, n, 12)] + [(1 << 100) + 1, (1 << 100) + 2]  # what the requests share
-
-        def entries(k):
-            return [pool[int(rng.integers(0, len(pool)))] if rng.integers(0, 3) == 0 else ints[int(rng.integers(0, n))] for _ in range(k)]
-
-        for _ in range(2):
-            limit = int(rng.choice([1, 2, 3, 8, 512, 1024]))
-            keys = [(v, int(rng.integers(0, 4))) for v in ints if rng.integers(0, 2)] if rng.integers(0, 2) else []
-            if keys:
-                ctx.links_set_keys(ids_from_ints([v for v, _ in keys]), np.array([k for _, k in keys], dtype=np.uint64))
-            else:
-                ctx.links_set_keys()
-            requests = [dict(liked=entries(int(rng.integers(0, 40))), disliked=entries(int(rng.integers(0, 20))), nodes=entries(int(rng.integers(0, 30))),
-                             normalized=bool(rng.integers(0, 2)), self_score=[None, 0.25, 3.0][int(rng.integers(0, 3))]) for _ in range(int(rng.integers(1, 6)))]
-            want, wst = ref.literal(ref.tables(*graph, keys, limit), requests)
-            sflags = int(rng.choice([0, _lib.HB_LINKS_SPREAD_ORDS, _lib.HB_LINKS_NO_SHORTCUT]))
-            small = bool(rng.integers(0, 2))
-            run = dict(what, limit=limit, keys=keys, requests=requests, sflags=sflags, small_pieces=small)
-            st = ctx.score_hosts([dict(r, liked=ids_from_ints(r["liked"]), disliked=ids_from_ints(r["disliked"]), nodes=ids_from_ints(r["nodes"])) for r in requests],
-                                 limit=limit, flags=sflags, small_pieces=small, slots_per_batch=int(rng.choice([0, 3])))
-            got = ctx.score_copy()
-            assert [g.tobytes() for g in got] == [w.tobytes() for w in want], ("scores against the restatement", run)
-            assert {k: st[k] for k in wst} == wst, ("stats", run, st)
-            for r, g in zip(requests, got):
-                if r["liked"] or r["disliked"]:
-                    ctx.inbound_similarity(ids_from_ints(r["liked"]), ids_from_ints(r["disliked"]), normalized=r["normalized"], self_score=r["self_score"], limit=limit)
-                    assert ctx.similarity_lookup(ids_from_ints(r["nodes"])).tobytes() == g.tobytes(), ("scores against the lookup route", run)
-            what["passes"] += st["pieces"]
-    return what
-
-
-def nearest_seed_case(rng, max_nodes, case):
-    """hb_nearest_seed: random graph (self links added) x random original / key lists (duplicates, unknown ids, 0.0, few distinct keys so
-    that ties are common, u64::MAX) x rounds x discount, against the host restatement (tests/nearest_seed_ref.py): the seed of every
-    node, every value bit for bit, every counter, the top order."""
-    from stract_amd.harmonic import EdgeListGraph, ids_from_ints
-    from tests import inbound_similarity_ref as sref
-    from tests import nearest_seed_ref as nref
-    kind, tuples = graphs.random_graph(rng)
-    if not tuples:
-        return None
-    nodes_in = sorted({x for e in tuples for x in e[:2]})
-    tuples = list(tuples) + [(v, v) for v in nodes_in if rng.random() < 0.1]
-    chunk = int(rng.choice([0, 0, 4, 8, 64]))
-    flags = _lib.HB_FLAG_ALL_RELS | int(rng.choice([0, 0, _lib.HB_FLAG_NO_REORDER, _lib.HB_FLAG_NO_XCD_MAP, _lib.HB_FLAG_NO_SPARSE]))
-    with _lib.Context(flags=flags, chunk=chunk) as ctx:
-        ctx.load_edges(EdgeListGraph.from_tuples(tuples).host_edges())
-        graph = ctx.graph()
-        ints = sref.id_ints(graph[0])
-        n = len(ints)
-        what = dict(case=case, kind="nearest_seed:" + kind, n=n, m=int(len(graph[2])), chunk=chunk, flags=flags, passes=0)
-        for _ in range(3):
-            share = [0.02, 0.1, 0.5][int(rng.integers(0, 3))]
-            orig = [(ints[int(x)], [0.0, float(rng.random()), float(rng.integers(0, 4)) / 4.0][int(rng.integers(0, 3))])
-                    for x in rng.integers(0, n, max(1, int(n * share)))]
-            orig += [((1 << 100) + 1, 0.5), orig[0]]
-            spread = int(rng.choice([1, 3, 1 << 62]))
-            keys = [(v, int(rng.integers(0, spread)) if rng.random() < 0.9 else nref.U64_MAX) for v in ints if rng.random() < 0.8]
-            keys += [((1 << 100) + 2, 0)] + keys[:2]
-            discount = [0.5, 0.3, 0.0, 1.0][int(rng.integers(0, 4))]
-            rounds = int(rng.choice([0, 1, 2, 5, 255]))
-            run = dict(what, discount=discount, rounds=rounds, orig=len(orig), keys=len(keys), spread=spread)
-            seeds, vals, want = nref.literal(*graph, orig, keys, discount, rounds)
-            st = ctx.nearest_seed(ids_from_ints([v for v, _ in orig]), np.array([x for _, x in orig]), ids_from_ints([v for v, _ in keys]),
-                                  np.array([k for _, k in keys], dtype=np.uint64), discount_factor=discount, rounds=rounds)
-            got_seed, got_has = ctx.nearest_seed_seeds()
-            assert {v: s for v, s, h in zip(ints, sref.id_ints(got_seed), got_has.tolist()) if h} == seeds, ("seeds", run)
-            want_all = np.array([vals.get(v, -1.0) for v in ints], dtype=np.float64)
-            assert ctx.nearest_seed_all().tobytes() == want_all.tobytes(), ("values", run)
-            cids, cvals = ctx.nearest_seed_copy()
-            assert sref.id_ints(cids) == [v for v in ints if v in vals] and cvals.tobytes() == want_all[want_all >= 0.0].tobytes(), ("copy", run)
-            assert {k: st[k] for k in nref.STAT_KEYS} == want, ("stats", run, {k: st[k] for k in nref.STAT_KEYS}, want)
-            k = int(rng.integers(1, n + 3))
-            tids, tvals = ctx.nearest_seed_top(k)
-            order = nref.top_order(vals, k)
-            assert sref.id_ints(tids) == [v for v, _ in order] and tvals.tolist() == [x for _, x in order], ("top", run, k)
-            what["passes"] += st["rounds_run"]
+        picks = oc.picks_of(oc.layout_conditions(ctx.plan(), graph[1], chunk))
+        passes = oc.BODIES[name](ctx, graph, rng, what, picks)
+    what.update(n=int(len(graph[0])), m=int(len(graph[2])), passes=int(passes))
     return what
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "distances", "betweenness", "similarity", "nearest_seed", "score_hosts"], default="passes")
+    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "operators"] + OPERATOR_MODES, default="passes")
     ap.add_argument("--ids", choices=["plain", "extreme", "mixed"], default="plain")
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--seed", type=int, default=1)
@@ -537,16 +325,10 @@ def main():
     while time.time() - t0 < a.seconds:
         extreme = a.ids == "extreme" or (a.ids == "mixed" and case % 2 == 1)
         try:
-            if a.mode == "distances":
-                w = distances_case(rng, a.max_nodes, case)
-            elif a.mode == "betweenness":
-                w = betweenness_case(rng, a.max_nodes, case)
-            elif a.mode == "similarity":
-                w = similarity_case(rng, a.max_nodes, case)
-            elif a.mode == "nearest_seed":
-                w = nearest_seed_case(rng, a.max_nodes, case)
-            elif a.mode == "score_hosts":
-                w = score_hosts_case(rng, a.max_nodes, case)
+            if a.mode in OPERATOR_MODES:
+                w = operator_case(rng, case, a.mode)
+            elif a.mode == "operators":
+                w = operator_case(rng, case, OPERATOR_MODES[case % len(OPERATOR_MODES)])
             elif a.mode == "ranks" or (a.mode == "mixed" and case % 6 == 4):
                 w = ranks_case(rng, a.max_nodes, case, extreme)
             elif a.mode == "tail" or (a.mode == "mixed" and case % 6 == 5):
