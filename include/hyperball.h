@@ -104,6 +104,16 @@ typedef struct hb_edge {
 #define HB_FLAG_ALL_RELS      0x8000u /* every edge record is an edge: no SKIPPED_REL filter at ingest (then m_eff == m_unique).  The page
                                           graph of ApproxHarmonic follows every ForwardlinksQuery edge (query/forwardlink.rs:44-53); use
                                           with hb_sampled_harmonic.  Not with HB_FLAG_REFERENCE_TAIL                                     */
+#define HB_FLAG_LIVE_FIRST    0x10000u /* device order "live hosts first": the hosts with >= 1 in-edge by descending out-degree, then the
+                                          hosts WITHOUT an in-edge ("dead": their counter never changes after hb_begin) in the same order
+                                          among themselves.  From pass 1 on the dense passes do not gather dead sources (pass 0 has merged
+                                          their one register into every reader) and the node-row launches of the dense and bitmap passes
+                                          end at the last live row; same results, same per-pass statistics.
+                                          The order is used where the argument holds for the whole graph: one rank, no communicator, no
+                                          destination partition, fused passes, neither HB_FLAG_PASS_STATS nor HB_FLAG_NO_REORDER - every
+                                          other context ignores both flags and plans as before.  Default: on when n >= 2^20.  This flag
+                                          forces it on for smaller graphs, HB_FLAG_NO_LIVE_FIRST off for larger ones (tests, A/B runs)  */
+#define HB_FLAG_NO_LIVE_FIRST 0x20000u /* never use the live-first order (wins over HB_FLAG_LIVE_FIRST)                               */
 #define HB_FLAG_RCCL_SELF     0x80u /* world_size == 1 but still create a 1-rank communicator and run
                                        the collectives (exercises the RCCL call path on one GPU)   */
 
@@ -910,6 +920,10 @@ int hb_debug_copy_graph(hb_ctx *ctx, hb_u128 *ids, uint64_t *row_ptr, uint32_t *
  * level_begin[levels+1]).  The device planner must reproduce the host planner's layout entry for entry. */
 int hb_debug_copy_plan(hb_ctx *ctx, uint64_t sizes[4], uint32_t *order, uint64_t *plan_row_ptr, uint32_t *plan_src,
                        uint64_t *level_begin);
+/* The live-first part of the loaded graph's layout (HB_FLAG_LIVE_FIRST): live = {1 if the order is in use else 0, n_live = hosts with
+ * >= 1 in-edge (device rows [0, n_live) when the order is in use), n_live_pad = the end of the node-row launches of passes t >= 1
+ * (n_live rounded up to 64 with the order, n_pad without)}. */
+int hb_debug_plan_live(hb_ctx *ctx, uint64_t live[3]);
 /* Emulates the collective of one pass between `count` logical ranks that live on ONE device
  * (contexts created with HB_FLAG_NO_RCCL; RCCL refuses two ranks on one device).
  *   phase 0, between hb_step_local and hb_step_finish of every context:
@@ -946,6 +960,11 @@ int hb_host_ingest(const hb_u128 *node_ids, uint64_t n, const hb_edge *edges, ui
 int hb_host_plan(uint64_t n, const uint64_t *row_ptr, const uint32_t *src, uint32_t flags,
                  uint32_t chunk, const uint32_t *tune /* hb_options.tune or NULL */, uint64_t sizes[4],
                  uint32_t *order, uint64_t *plan_row_ptr, uint32_t *plan_src, uint64_t *level_begin);
+/* The live-first order (HB_FLAG_LIVE_FIRST) is planned under the rule of a single-rank context with these `flags` and this n: one
+ * slice, a reordered plan, no flag that makes the passes unfused or counting; on from 2^20 nodes, HB_FLAG_LIVE_FIRST /
+ * HB_FLAG_NO_LIVE_FIRST force it on / off.  hb_host_plan_live: what hb_debug_plan_live reports, for that plan. */
+int hb_host_plan_live(uint64_t n, const uint64_t *row_ptr, const uint32_t *src, uint32_t flags, uint32_t chunk, const uint32_t *tune,
+                      uint64_t live[3]);
 /* Host only (no GPU): the index hb_load_tail_edges / hb_append_tail_edges build from page-level records (taken as ONE
  * segment in doc order) - CSR by SOURCE device row (dev_of[sid]) over the records the per-host LinksScorer yields that
  * pass the rel filter and whose two ids are nodes (harmonic.rs:87,91-92), duplicates dropped.  ptr_out: n_pad + 1 offsets; to_out: target device rows (first to_cap), *to_len = their number. */

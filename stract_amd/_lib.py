@@ -44,6 +44,8 @@ HB_FLAG_CHANGED_ONLY = 0x1000
 HB_FLAG_REFERENCE_TAIL = 0x2000
 HB_FLAG_NO_INIT_PASS = 0x4000
 HB_FLAG_ALL_RELS = 0x8000
+HB_FLAG_LIVE_FIRST = 0x10000
+HB_FLAG_NO_LIVE_FIRST = 0x20000
 HB_SAMPLE_MAX_LEVELS = 16
 
 # switches of the experiments build in hb_options.tune[1] (stract_amd/csrc/hb_experiments.h describes each)
@@ -528,6 +530,8 @@ _SIGNATURES = [
     ("hb_host_ingest", ctypes.c_int, [_P, _U64, _P, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64),
                                       ctypes.POINTER(_U64), _P, _P, _P]),
     ("hb_host_plan", ctypes.c_int, [_U64, _P, _P, ctypes.c_uint32, ctypes.c_uint32, _P, _P, _P, _P, _P, _P]),
+    ("hb_host_plan_live", ctypes.c_int, [_U64, _P, _P, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
+    ("hb_debug_plan_live", ctypes.c_int, [_P, _P]),
 ]
 # include/hb_webgraph.h
 _SIGNATURES += [
@@ -1403,6 +1407,12 @@ class Context:
         self._check(self.lib.hb_debug_copy_plan(self.h, _ptr(sizes), _ptr(order), _ptr(prp), _ptr(psrc), _ptr(lb)))
         return dict(order=order, row_ptr=prp, src=psrc, level_begin=lb, n_pad=n_pad, nv=nv)
 
+    def plan_live(self):
+        """(live-first order in use, n_live, n_live_pad) of the loaded graph's layout (hb_debug_plan_live)."""
+        out = np.zeros(3, dtype=np.uint64)
+        self._check(self.lib.hb_debug_plan_live(self.h, _ptr(out)))
+        return bool(out[0]), int(out[1]), int(out[2])
+
     def graph(self):
         st = self.stats()
         ids = np.zeros(st["n"], dtype=U128)
@@ -1468,4 +1478,9 @@ def host_plan(row_ptr, src, flags=0, chunk=0, tune=()):
     world = int(tn[7]) if tn[7] > 1 else 1
     if world == 1:
         order = order[:n]  # no padding rows inside: a permutation of the sids
-    return dict(order=order, row_ptr=prp, src=psrc, level_begin=lb, n_pad=n_pad, nv=nv, slice=n_pad // world)
+    live = np.zeros(3, dtype=np.uint64)
+    rc = lib.hb_host_plan_live(n, _ptr(row_ptr), _ptr(src), flags, chunk, _ptr(tn), _ptr(live))
+    if rc != HB_OK:
+        raise HyperballError(rc, (lib.hb_last_error(None) or b"").decode())
+    return dict(order=order, row_ptr=prp, src=psrc, level_begin=lb, n_pad=n_pad, nv=nv, slice=n_pad // world,
+                live_first=bool(live[0]), n_live=int(live[1]), n_live_pad=int(live[2]))

@@ -575,6 +575,15 @@ PlanTune plan_tune(uint32_t chunk, const uint32_t *tune)
     return t;
 }
 
+// live-first device order (HB_FLAG_LIVE_FIRST), the part of the rule the option flags and the size decide: fused passes that do not
+// count their gathers, a reordered plan; on from 2^20 nodes (the size from which the result image is staged), the two flags force it
+// on below / off above.  A context adds what it alone knows (plan_and_upload: one rank, no communicator, no destination partition)
+bool live_first_by_flags(uint32_t flags, uint64_t n)
+{
+    if (flags & (HB_FLAG_NO_REORDER | HB_FLAG_PASS_STATS | HB_FLAG_UNFUSED | HB_FLAG_REFERENCE_TAIL | HB_FLAG_NO_LIVE_FIRST)) return false;
+    return n >= (1u << 20) || (flags & HB_FLAG_LIVE_FIRST);
+}
+
 bool multi_rank(const hb_ctx *c) { return c->opt.world_size > 1; }
 // a switch of the experiments build (hb_experiments.h HB_X_*; several or-ed: any of them); always off in the product library
 bool xbit(const hb_ctx *c, uint32_t bits) { return (HB_XBITS(c->opt.tune[1]) & bits) != 0; }

@@ -182,6 +182,48 @@ int hb_host_ingest(const hb_u128 *node_ids, uint64_t n, const hb_edge *edges, ui
     });
 }
 
+// the host planner as hb_host_plan / hb_host_plan_live call it; "" or build_plan's error text
+static std::string host_plan_of(uint64_t n, const uint64_t *row_ptr, const uint32_t *src, uint32_t flags, uint32_t chunk, const uint32_t *tune, Plan *p)
+{
+    std::vector<uint32_t> outdeg;
+    const bool reorder = !(flags & HB_FLAG_NO_REORDER);
+    static const uint64_t zero = 0;
+    if (n == 0) row_ptr = &zero;
+    if (reorder) count_out_degree(row_ptr, src, n, &outdeg);
+    PlanTune pt = plan_tune(chunk, tune);
+    if (tune && tune[7] > 1) pt.world = tune[7]; // destination-partition layout (test hook)
+    pt.xcd_map = !(flags & HB_FLAG_NO_XCD_MAP);
+    pt.live_first = live_first_by_flags(flags, n) && !(flags & HB_FLAG_DEST_PARTITION); // (build_plan ignores it with owner slices)
+    return build_plan(n, row_ptr, src, outdeg, reorder, pt, p);
+}
+
+int hb_host_plan_live(uint64_t n, const uint64_t *row_ptr, const uint32_t *src, uint32_t flags, uint32_t chunk, const uint32_t *tune, uint64_t live[3])
+{
+    return guarded(nullptr, [&]() -> int {
+        hb_ctx *c = nullptr;
+        if (!live || (n && !row_ptr)) return fail(c, HB_ERR_INVALID, "NULL argument");
+        Plan p;
+        const std::string e = host_plan_of(n, row_ptr, src, flags, chunk, tune, &p);
+        if (!e.empty()) return fail(c, HB_ERR_LIMIT, e);
+        live[0] = p.live_first ? 1 : 0;
+        live[1] = p.n_live;
+        live[2] = p.n_live_pad;
+        return HB_OK;
+    });
+}
+
+int hb_debug_plan_live(hb_ctx *c, uint64_t live[3])
+{
+    return guarded(c, [&]() -> int {
+        if (!c || !live) return HB_ERR_INVALID;
+        if (!c->loaded) return fail(c, HB_ERR_INVALID, "hb_debug_plan_live: no graph loaded");
+        live[0] = c->plan.live_first ? 1 : 0;
+        live[1] = c->plan.n_live;
+        live[2] = c->plan.n_live_pad;
+        return HB_OK;
+    });
+}
+
 int hb_host_plan(uint64_t n, const uint64_t *row_ptr, const uint32_t *src, uint32_t flags, uint32_t chunk,
                  const uint32_t *tune, uint64_t sizes[4], uint32_t *order, uint64_t *plan_row_ptr, uint32_t *plan_src,
                  uint64_t *level_begin)
@@ -189,16 +231,8 @@ int hb_host_plan(uint64_t n, const uint64_t *row_ptr, const uint32_t *src, uint3
     return guarded(nullptr, [&]() -> int {
         hb_ctx *c = nullptr;
         if (!sizes || (n && !row_ptr)) return fail(c, HB_ERR_INVALID, "NULL argument");
-        std::vector<uint32_t> outdeg;
-        const bool reorder = !(flags & HB_FLAG_NO_REORDER);
-        static const uint64_t zero = 0;
-        if (n == 0) row_ptr = &zero;
-        if (reorder) count_out_degree(row_ptr, src, n, &outdeg);
         Plan p;
-        PlanTune pt = plan_tune(chunk, tune);
-        if (tune && tune[7] > 1) pt.world = tune[7]; // destination-partition layout (test hook)
-        pt.xcd_map = !(flags & HB_FLAG_NO_XCD_MAP);
-        std::string e = build_plan(n, row_ptr, src, outdeg, reorder, pt, &p);
+        std::string e = host_plan_of(n, row_ptr, src, flags, chunk, tune, &p);
         if (!e.empty()) return fail(c, HB_ERR_LIMIT, e);
         sizes[0] = p.n_pad;
         sizes[1] = p.nv;

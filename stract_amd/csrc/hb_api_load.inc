@@ -172,6 +172,9 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
     PlanTune pt = plan_tune(c->opt.chunk, c->opt.tune);
     pt.xcd_map = !(c->opt.flags & HB_FLAG_NO_XCD_MAP);
     if (dest_mode(c)) pt.world = (uint32_t)std::max(c->opt.world_size, 1);
+    // live-first order (HB_FLAG_LIVE_FIRST): only where "no in-edge here" means "no in-edge at all" and the passes are the fused ones of
+    // one rank (an edge-partitioned rank sees part of a node's in-edges; the counting kernels of HB_FLAG_PASS_STATS count every gather).
+    pt.live_first = reorder && !multi_rank(c) && !linked(c) && !dest_mode(c) && !unfused(c) && live_first_by_flags(c->opt.flags, n);
     // The two counter arrays are what the passes gather from at random: allocate them BEFORE the planner churns
     // through tens of GB of work memory, while the device heap can still back them with large contiguous
     // fragments (allocated after it, the same kernels ran 1-2 % slower: more TLB misses on the gathers).

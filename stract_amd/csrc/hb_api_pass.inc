@@ -128,6 +128,12 @@ int ensure_initial_state(hb_ctx *c)
     return launch_full_init(c);
 }
 
+// live-first order (Plan::live_first, HB_FLAG_LIVE_FIRST): from pass 1 on the device rows at and behind n_live - the nodes without an
+// in-edge - are neither gathered by a dense pass nor visited by the node-row launches.  Pass 0 is unchanged in both of its forms: it
+// gathers every source (so every reader holds the dead sources' one register from then on), visits every row and leaves every row's
+// counter in both buffers, its (0, 0) / lc[63] Kahan and size words in place and its changed / Kahan-dirty bits at zero.
+bool skips_dead_rows(const hb_ctx *c) { return c->plan.live_first && c->t >= 1 && !unfused(c) && !linked(c); } // (a plan is only laid out so for such a context)
+
 hbk::PassParams make_params(hb_ctx *c)
 {
     const Plan &p = c->plan;
@@ -164,6 +170,7 @@ hbk::PassParams make_params(hb_ctx *c)
     pp.self_jp = c->d_self_jp;
     pp.virt_rows = c->d_virt_rows;
     pp.xflags = xbit(c, HB_X_PROBE_NO_SIZE) ? 1u : 0u;
+    pp.live_limit = skips_dead_rows(c) ? (uint32_t)p.n_live : hbk::kNone;
     return pp;
 }
 
@@ -618,7 +625,7 @@ int level_pass(hb_ctx *c, hbk::PassParams pp, hipEvent_t *E, bool frontier, bool
     pp.xcd_map = 0;
     HB_HIP(hipEventRecord(E[kEvLevels], c->stream));
     pp.row_lo = dest_mode(c) ? pp.slice_lo : 0; // destination partition: only the owned rows
-    pp.row_hi = dest_mode(c) ? pp.slice_hi : p.n_pad;
+    pp.row_hi = dest_mode(c) ? pp.slice_hi : (skips_dead_rows(c) ? p.n_live_pad : p.n_pad);
     if (edge_changed_only(c)) {
         int rc = edge_co_alloc(c);
         if (rc) return rc;
@@ -640,6 +647,12 @@ int level_pass(hb_ctx *c, hbk::PassParams pp, hipEvent_t *E, bool frontier, bool
     } else {
         if (lean) pp.rd_init = c->d_regs[c->cur];
         launch_pass(c, pp, true, frontier, fused);
+        if (p.live_first && c->t == 0 && p.n_live_pad < p.n_pad) {
+            // hb_begin put EVERY node into the changed set (harmonic.rs:221-225) and pass 0 has consumed it.  Nobody rewrites the dead
+            // rows' words of that buffer from here on (pass 1 writes its changed bits there, for the live rows only): clear them once,
+            // so that no later bitmap or sweep pass finds a dead row "changed" (n_live_pad is a multiple of 64: whole words)
+            HB_HIP(hipMemsetAsync(c->d_bits[c->cur] + p.n_live_pad / 32, 0, (p.n_pad - p.n_live_pad) / 32 * sizeof(uint32_t), c->stream));
+        }
     }
     HB_HIP(hipEventRecord(E[kEvMerge], c->stream));
     return HB_OK;

@@ -415,7 +415,9 @@ void count_out_degree(const uint64_t *row_ptr, const uint32_t *src, uint64_t n, 
 //
 // Device order: nodes sorted by (global) out-degree, descending - the counters that are
 // gathered most often become one contiguous, cache-resident prefix of the register array
-// (per-XCD L2 4 MiB = 64 Ki counters, Infinity Cache 256 MiB = 4 Mi counters).
+// (per-XCD L2 4 MiB = 64 Ki counters, Infinity Cache 256 MiB = 4 Mi counters).  PlanTune::live_first: the nodes WITHOUT an
+// in-edge follow the others, in the same order among themselves - their counters never change, so from pass 1 on nobody has
+// to gather them or visit their rows; they become the tail of every source list.
 //
 // Hub splitting: a row with more than `chunk` sources is replaced by a tree of "virtual
 // rows" (partial maxima over <= chunk sources each); every level is a separate launch,
@@ -457,15 +459,20 @@ std::string build_plan(uint64_t n, const uint64_t *row_ptr, const uint32_t *src,
     auto from_hot = [&](uint32_t hr) -> uint32_t { return (uint32_t)(((uint64_t)hr % world) * slice + (uint64_t)hr / world); };
     try {
         // ---- device order: inside each owner's slice by descending (global) out-degree
+        // live-first (one slice only): a "dead" bit - the node has no in-edge - between the owner and the out-degree
+        const bool live_first = tune.live_first && reorder && world == 1;
+        p->live_first = live_first;
         if (reorder && n) {
             std::vector<std::pair<uint64_t, uint32_t>> kv(n);
 #pragma omp parallel for schedule(static)
-            for (int64_t s = 0; s < (int64_t)n; s++)
-                kv[s] = {(((uint64_t)s % world) << 32) | (uint64_t)(0xFFFFFFFFu - out_degree[s]), (uint32_t)s};
+            for (int64_t s = 0; s < (int64_t)n; s++) {
+                const uint64_t dead = (live_first && row_ptr[s + 1] == row_ptr[s]) ? 1 : 0;
+                kv[s] = {(((uint64_t)s % world) << 33) | (dead << 32) | (uint64_t)(0xFFFFFFFFu - out_degree[s]), (uint32_t)s};
+            }
             HB_SORT(kv.begin(), kv.end());
             uint64_t pos = 0, cur_owner = 0;
             for (uint64_t i = 0; i < n; i++) {
-                const uint64_t owner = kv[i].first >> 32;
+                const uint64_t owner = kv[i].first >> 33;
                 if (owner != cur_owner) {
                     cur_owner = owner;
                     pos = owner * slice;
@@ -717,6 +724,8 @@ std::string build_plan(uint64_t n, const uint64_t *row_ptr, const uint32_t *src,
         }
         p->direct_edges = direct;
         p->rows_with_in_edges = with_in;
+        p->n_live = with_in;
+        p->n_live_pad = live_first ? (with_in + kRowAlign - 1) / kRowAlign * kRowAlign : n_pad;
         p->row_ptr[n_pad] = total;
         const uint64_t real_total = total;
         for (uint64_t k = 0; k < p->nv; k++) p->row_ptr[p->n_pad + k + 1] = real_total + vrow_ptr[k + 1];

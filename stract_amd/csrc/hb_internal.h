@@ -79,6 +79,11 @@ struct Plan {
     uint64_t level1_rows = 0;        // level-1 chunk rows (without padding rows)
     uint64_t direct_edges = 0;       // real edges gathered directly by node rows
     uint64_t rows_with_in_edges = 0; // nodes with in-degree > 0
+    // live-first order (PlanTune::live_first): device rows [0, n_live) are the nodes with in-degree > 0, the "dead" nodes (no in-edge:
+    // their counter never changes) follow.  Off: n_live = rows_with_in_edges all the same, n_live_pad = n_pad
+    bool live_first = false;
+    uint64_t n_live = 0;     // nodes with in-degree > 0
+    uint64_t n_live_pad = 0; // where the node-row launches of passes t >= 1 end: n_live rounded up to kRowAlign, or n_pad
 };
 
 // XCD-group quotas of the flexible (hot / cold) level-1 chunks; shared by the host planner (hb_host.cpp) and the
@@ -148,6 +153,8 @@ struct PlanTune {
     bool xcd_map = true;            // XCD-affine groups of level-1 chunks (HB_FLAG_NO_XCD_MAP clears it)
     uint32_t world = 1;             // destination partition: rows are laid out as `world` equal slices,
                                     // slice g = the nodes with sid % world == g
+    bool live_first = false;        // device order: nodes with in-degree > 0 first, then the others, each part by descending
+                                    // out-degree (HB_FLAG_LIVE_FIRST); only with reorder and world == 1, ignored otherwise
 };
 
 // --- hb_host.cpp ---------------------------------------------------------------------

@@ -114,6 +114,9 @@ struct PassParams {
     const uint32_t *virt_rows;
     uint32_t xflags;          // experiments build only (0 in the product): bit 0 = the dense fused node rows neither read nor write size[] -
                               // WRONG RESULTS, a timing probe: what a node-row state diet of 16 B per row could buy at most
+    uint32_t live_limit;      // dense passes: a REAL source at or above this device row is not gathered.  kNone = gather every source.  With the
+                              // live-first order (Plan::live_first) and t >= 1: n_live - the rows behind it have no in-edge, their counter is
+                              // still the initial one, and pass 0 has merged that into every reader
     const uint16_t *self_jp;  // per device row: register index | value << 8 of the node's OWN initial counter (0 = padding row), written at
                               // load time with the same arithmetic as src_jp (lean pass 0)
 };
@@ -309,7 +312,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
                 real_src = first < p.n_pad;
             }
             const uint4 *base = real_src ? p.rd : (const uint4 *)(p.part - p.n_pad * 4);
-            for (uint64_t e = beg; e < end; e += 4 * UNROLL) {
+            // a slot is gathered iff its id is below `limit`: kNone (out-of-row slots) never is, and with the live-first order neither is a
+            // dead real source (PassParams::live_limit).  The lists ascend, so a row whose first source is dead has only dead ones: no gather
+            const uint32_t limit = real_src ? p.live_limit : kNone;
+            for (uint64_t e = beg; e < end && first < limit; e += 4 * UNROLL) {
                 uint32_t idx[UNROLL];
                 if (INIT && real_src) {
                     // pass 0: the sources' single registers come with the edge list.  Each lane max-accumulates ITS sources
@@ -344,10 +350,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
                     for (int u = 0; u < UNROLL; u++) {
                         uint32_t s0 = quad_bcast<0>(idx[u]), s1 = quad_bcast<1>(idx[u]);
                         uint32_t s2 = quad_bcast<2>(idx[u]), s3 = quad_bcast<3>(idx[u]);
-                        s0 = (s0 != kNone) ? s0 : first;
-                        s1 = (s1 != kNone) ? s1 : first;
-                        s2 = (s2 != kNone) ? s2 : first;
-                        s3 = (s3 != kNone) ? s3 : first;
+                        s0 = (s0 < limit) ? s0 : first;
+                        s1 = (s1 < limit) ? s1 : first;
+                        s2 = (s2 < limit) ? s2 : first;
+                        s3 = (s3 < limit) ? s3 : first;
                         HB_DBG_ASSERT(s0 < p.rows_total && s1 < p.rows_total && s2 < p.rows_total && s3 < p.rows_total);
                         HB_DBG_ASSERT((s0 < p.n_pad) == real_src && (s1 < p.n_pad) == real_src && (s2 < p.n_pad) == real_src && (s3 < p.n_pad) == real_src);
                         r[u][0] = base[(uint64_t)s0 * 4 + q];

@@ -5,7 +5,7 @@
 // HyperBall passes; a drop-in replacement of HarmonicCentrality::calculate (harmonic.rs:292) is judged on
 // wall time.  What the plan is (device order, hub-row chunk trees, slice cuts, XCD groups) and why is described
 // in hb_host.cpp / DESIGN.md; this file only restates HOW each step is computed in parallel:
-//   device order      stable radix sort of (owner, ~out-degree) carrying the sid
+//   device order      stable radix sort of (owner, dead bit of the live-first order, ~out-degree) carrying the sid
 //   rows + relabel    one 64-bit radix sort of (device row, hotness rank of the source) over all edges
 //   chunk cutting     one wave per hub row walks its sorted list a chunk per step (ballot finds the cut)
 //   XCD groups        stable sort by (slice, longer first), class prefix sums against eight thresholds per
@@ -188,11 +188,14 @@ __device__ __forceinline__ uint32_t band_of(const BandParams bp, uint32_t idx)
 }
 
 // ---- device order --------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void order_keys_kernel(const uint32_t *outdeg, uint64_t n, uint64_t world, uint64_t *key, uint32_t *val)
+// key = owner | dead | ~out-degree.  in_ptr != NULL (live-first order, hb_host.cpp): dead = the node has no in-edge in the input CSR
+__global__ __launch_bounds__(256) void order_keys_kernel(const uint32_t *outdeg, const uint64_t *in_ptr, uint64_t n, uint64_t world, uint64_t *key,
+                                                         uint32_t *val)
 {
     const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (s >= n) return;
-    key[s] = ((s % world) << 32) | (uint64_t)(0xFFFFFFFFu - outdeg[s]);
+    const uint64_t dead = (in_ptr && in_ptr[s + 1] == in_ptr[s]) ? 1 : 0;
+    key[s] = ((s % world) << 33) | (dead << 32) | (uint64_t)(0xFFFFFFFFu - outdeg[s]);
     val[s] = (uint32_t)s;
 }
 // sids of owner o occupy sorted positions [first(o), first(o + 1)); first(o) = number of sids with s % world < o
@@ -207,7 +210,7 @@ __global__ __launch_bounds__(256) void place_sorted_kernel(const uint64_t *key, 
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const uint64_t owner = key[i] >> 32;
+    const uint64_t owner = key[i] >> 33;
     const uint64_t pos = owner * slice + (i - owner_first(n, world, owner));
     order[pos] = val[i];
     dev_of[val[i]] = (uint32_t)pos;
@@ -811,6 +814,7 @@ std::string gpu_build_plan(void *stream_v, uint64_t n, const uint64_t *d_row_ptr
     const uint64_t world = tune.world > 1 ? tune.world : 1;
     const uint64_t slice = ((n + world - 1) / world + kRowAlign - 1) / kRowAlign * kRowAlign;
     const uint64_t n_pad = slice * world;
+    const bool live_first = tune.live_first && reorder && world == 1; // (hb_host.cpp build_plan)
     *out = DevicePlan{};
     p->n = n;
     p->slice = slice;
@@ -866,10 +870,12 @@ std::string gpu_build_plan(void *stream_v, uint64_t n, const uint64_t *d_row_ptr
             PL_HIP(mem.alloc(&k_out, n));
             PL_HIP(mem.alloc(&v_in, n));
             PL_HIP(mem.alloc(&v_out, n));
-            hipLaunchKernelGGL(order_keys_kernel, dim3(grid_for(n)), dim3(256), 0, stream, d_outdeg_sid, n, world, k_in, v_in);
+            hipLaunchKernelGGL(order_keys_kernel, dim3(grid_for(n)), dim3(256), 0, stream, d_outdeg_sid, live_first ? d_row_ptr_in : (const uint64_t *)nullptr, n,
+                               world, k_in, v_in);
             PL_HIP(hipGetLastError());
             size_t bytes = 0;
-            const unsigned end_bit = 32 + (unsigned)bits_for(world);
+            // (one slice: 33 bits as before - the bit that used to be the single owner's is the dead bit now)
+            const unsigned end_bit = 33 + (world > 1 ? (unsigned)bits_for(world) : 0u);
             PL_HIP(rocprim::radix_sort_pairs(nullptr, bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, end_bit, stream));
             PL_HIP(need_tmp(bytes));
             PL_HIP(rocprim::radix_sort_pairs(tmp, bytes, k_in, k_out, v_in, v_out, (size_t)n, 0u, end_bit, stream));
@@ -954,6 +960,9 @@ std::string gpu_build_plan(void *stream_v, uint64_t n, const uint64_t *d_row_ptr
     PL_HIP(hipStreamSynchronize(stream));
     p->direct_edges = h_sums[0];
     p->rows_with_in_edges = h_sums[1];
+    p->live_first = live_first;
+    p->n_live = h_sums[1];
+    p->n_live_pad = live_first ? (p->n_live + kRowAlign - 1) / kRowAlign * kRowAlign : n_pad;
     out->m_global = h_sums[2];
     lap("relabel + sort rows");
 
