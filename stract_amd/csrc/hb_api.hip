@@ -260,27 +260,26 @@ struct GraphDeviceState {
     } nst;
     // hb_links_set_keys / hb_backlinks / hb_forwardlinks (hb_api_links.inc): the key set and its dense order, the buffers of a batch and the last result.
     // The holders own them (they grow with the limit, the slots of a batch and the queries of a call): freed by the next load, counted in
-    // `bytes` and in hb_stats.device_bytes.  The operator borrows nothing of the HyperBall state
+    // `bytes` and in hb_stats.device_bytes.  Here and in the three states below a holder is a GrowPtr, which knows how many entries it
+    // has, and hold() is the one place that allocates and books it.  The operator borrows nothing of the HyperBall state
     struct LinksState {
         bool ready = false; // key / ord / inv / ord_row exist and describe the current key set (none: NodeID order)
         bool valid = false; // the result below is that of a finished hb_backlinks / hb_forwardlinks
-        DevPtr<unsigned long long> d_key; // n: key by sid, ~0 = not listed
-        DevPtr<uint32_t> d_ord;           // n: position of the sid in the sort by (key, sid)
-        DevPtr<uint32_t> d_inv;           // n: the sid at a position
-        DevPtr<uint32_t> d_ord_row;       // n_pad: ord by device row, kNone for padding rows
-        DevPtr<uint2> d_items;            // slots + nv + 16: (slot, row) of a batch, level by level
-        DevPtr<uint32_t> d_ctl;           // 5 x slots (deg, sel_k, sel_prefix, thr, cursor) + 64 level counts + 8 flag words (+ forward: slots lengths, slots + 1 segment offsets)
-        DevPtr<uint32_t> d_hist;          // slots x 256
-        DevPtr<uint32_t> d_out;           // slots x limit: the kept ords of a batch
-        DevPtr<uint32_t> d_slot_row;      // distinct: device row of every distinct queried node (ascending sid)
-        DevPtr<uint32_t> d_slot_self;     // distinct: the row its list must not hold (kNone: HB_LINKS_KEEP_SELF)
-        DevPtr<uint32_t> d_res_sid;       // distinct x limit: the lists as sids
-        DevPtr<unsigned long long> d_res_key; // distinct x limit: ... and their keys
-        DevPtr<uint32_t> d_top_row;       // nv: hb_forwardlinks: the node row at the top of every chunk row's tree (kNone: a padding row)
-        bool top_ready = false;           // d_top_row describes the loaded graph (built by the first hb_forwardlinks after a load)
-        uint64_t cap_key = 0, cap_ord = 0, cap_inv = 0, cap_ord_row = 0, cap_items = 0, cap_ctl = 0, cap_hist = 0, cap_out = 0, cap_slot_row = 0,
-                 cap_slot_self = 0, cap_res_sid = 0, cap_res_key = 0, cap_top_row = 0; // entries the holders have
-        uint32_t limit = 0;               // of the result
+        GrowPtr<unsigned long long> d_key; // n: key by sid, ~0 = not listed
+        GrowPtr<uint32_t> d_ord;           // n: position of the sid in the sort by (key, sid)
+        GrowPtr<uint32_t> d_inv;           // n: the sid at a position
+        GrowPtr<uint32_t> d_ord_row;       // n_pad: ord by device row, kNone for padding rows
+        GrowPtr<uint2> d_items;            // slots + nv + 16: (slot, row) of a batch, level by level
+        GrowPtr<uint32_t> d_ctl;           // 5 x slots (deg, sel_k, sel_prefix, thr, cursor) + 64 level counts + 8 flag words (+ forward: slots lengths, slots + 1 segment offsets)
+        GrowPtr<uint32_t> d_hist;          // slots x 256
+        GrowPtr<uint32_t> d_out;           // slots x limit: the kept ords of a batch
+        GrowPtr<uint32_t> d_slot_row;      // distinct: device row of every distinct queried node (ascending sid)
+        GrowPtr<uint32_t> d_slot_self;     // distinct: the row its list must not hold (kNone: HB_LINKS_KEEP_SELF)
+        GrowPtr<uint32_t> d_res_sid;       // distinct x limit: the lists as sids
+        GrowPtr<unsigned long long> d_res_key; // distinct x limit: ... and their keys
+        GrowPtr<uint32_t> d_top_row;       // nv: hb_forwardlinks: the node row at the top of every chunk row's tree (kNone: a padding row)
+        bool top_ready = false;            // d_top_row describes the loaded graph (built by the first hb_forwardlinks after a load)
+        uint32_t limit = 0;                // of the result
         std::vector<uint32_t> query_slot; // per query of the last call: its distinct node, kNone = no node of the graph
         std::vector<uint32_t> degree;     // per distinct node: degree(v)
         uint64_t entries = 0;             // entries of all lists of the result
@@ -292,23 +291,20 @@ struct GraphDeviceState {
     // builder are the links state's
     struct SimilarHostsState {
         bool valid = false; // the result below is that of a finished hb_similar_hosts
-        DevPtr<uint32_t> d_in, d_in_len;          // liked x 512: In512 of the distinct liked hosts (sorted by sid once scored), their degrees
-        DevPtr<unsigned long long> d_in_mask;     // liked: their bloom masks
-        DevPtr<uint32_t> d_src;                   // liked x 128: B, the distinct sources of the 128-prefixes
-        DevPtr<uint32_t> d_fw, d_fw_len;          // nb x 512: their forward lists, the degrees
-        DevPtr<uint32_t> d_count;                 // n: the flag words of B, then count[v]
-        DevPtr<uint32_t> d_touched;               // min(n, nb x 512): the distinct targets
-        DevPtr<uint32_t> d_cand, d_cand_count;    // 1024: the pre-selection and its counts
-        DevPtr<uint32_t> d_cin, d_cin_len;        // 1024 x 512: In512 of the candidates
-        DevPtr<unsigned long long> d_cin_mask;    // 1024
-        DevPtr<unsigned long long> d_keys;        // the lists' keys (the list builder writes them; nobody reads them here)
-        DevPtr<uint32_t> d_liked, d_anchor;       // liked: the distinct liked sids ascending; N: the entries in caller order as slots
-        DevPtr<double> d_score, d_top_score;      // 1024
-        DevPtr<uint32_t> d_top_sid;               // 1024
-        DevPtr<unsigned long long> d_cnt;         // 8 words: cursors (as u32) and the pair counters
-        uint64_t cap_in = 0, cap_in_len = 0, cap_in_mask = 0, cap_src = 0, cap_fw = 0, cap_fw_len = 0, cap_count = 0, cap_touched = 0, cap_cand = 0,
-                 cap_cand_count = 0, cap_cin = 0, cap_cin_len = 0, cap_cin_mask = 0, cap_keys = 0, cap_liked = 0, cap_anchor = 0, cap_score = 0,
-                 cap_top_score = 0, cap_top_sid = 0, cap_cnt = 0;
+        GrowPtr<uint32_t> d_in, d_in_len;         // liked x 512: In512 of the distinct liked hosts (sorted by sid once scored), their degrees
+        GrowPtr<unsigned long long> d_in_mask;    // liked: their bloom masks
+        GrowPtr<uint32_t> d_src;                  // liked x 128: B, the distinct sources of the 128-prefixes
+        GrowPtr<uint32_t> d_fw, d_fw_len;         // nb x 512: their forward lists, the degrees
+        GrowPtr<uint32_t> d_count;                // n: the flag words of B, then count[v]
+        GrowPtr<uint32_t> d_touched;              // min(n, nb x 512): the distinct targets
+        GrowPtr<uint32_t> d_cand, d_cand_count;   // 1024: the pre-selection and its counts
+        GrowPtr<uint32_t> d_cin, d_cin_len;       // 1024 x 512: In512 of the candidates
+        GrowPtr<unsigned long long> d_cin_mask;   // 1024
+        GrowPtr<unsigned long long> d_keys;       // the lists' keys (the list builder writes them; nobody reads them here)
+        GrowPtr<uint32_t> d_liked, d_anchor;      // liked: the distinct liked sids ascending; N: the entries in caller order as slots
+        GrowPtr<double> d_score, d_top_score;     // 1024
+        GrowPtr<uint32_t> d_top_sid;              // 1024
+        GrowPtr<unsigned long long> d_cnt;        // 8 words: cursors (as u32) and the pair counters
         std::vector<uint32_t> cand_sid, cand_count, top_sid; // the result on the host: at most 1024 entries each
         std::vector<double> top_score;
         uint64_t bytes = 0;
@@ -321,13 +317,13 @@ struct GraphDeviceState {
         bool ready = false;               // the buffers below describe the loaded graph under the current key set and `limit`
         uint32_t limit = 0;
         uint64_t listed = 0, entries = 0; // listed rows, the entries of their lists
-        DevPtr<uint32_t> d_idx;           // n_pad: the list index of a node row, kNone = not listed (the plan's list is its cut)
-        DevPtr<uint32_t> d_list_row;      // listed: the device row of list k
-        DevPtr<uint32_t> d_lists;         // listed x limit: list k at k x limit, device rows in the order (key, NodeID)
-        DevPtr<uint32_t> d_len;           // listed: min(degree, limit)
-        DevPtr<uint64_t> d_bloom;         // listed: the bloom mask over the list's entries
-        DevPtr<uint32_t> d_seed_rows;     // 16: the batch's anchors that seed from the plan's lists
-        DevPtr<unsigned long long> d_cnt; // 4 counters of the list-count kernel
+        GrowPtr<uint32_t> d_idx;           // n_pad: the list index of a node row, kNone = not listed (the plan's list is its cut)
+        GrowPtr<uint32_t> d_list_row;      // listed: the device row of list k
+        GrowPtr<uint32_t> d_lists;         // listed x limit: list k at k x limit, device rows in the order (key, NodeID)
+        GrowPtr<uint32_t> d_len;           // listed: min(degree, limit)
+        GrowPtr<uint64_t> d_bloom;         // listed: the bloom mask over the list's entries
+        GrowPtr<uint32_t> d_seed_rows;     // 16: the batch's anchors that seed from the plan's lists
+        GrowPtr<unsigned long long> d_cnt; // 4 counters of the list-count kernel
         uint64_t bytes = 0;
     } lim;
     // hb_score_hosts (hb_api_score.inc): the BitVecs of the distinct known hosts of a call, the entries of its requests, one piece of
@@ -336,17 +332,15 @@ struct GraphDeviceState {
     // the list builder are the links state's
     struct ScoreState {
         bool valid = false; // the result below is that of a finished hb_score_hosts
-        DevPtr<uint32_t> d_lists, d_len;          // distinct x limit: the backlinks of the distinct known hosts (sorted by sid), their degrees
-        DevPtr<unsigned long long> d_mask;        // distinct: their bloom masks
-        DevPtr<unsigned long long> d_keys;        // the lists' keys of one call of the list builder (nobody reads them here)
-        DevPtr<uint32_t> d_node_idx, d_anchor_idx; // the nodes / the anchors of all requests as indices of the call's distinct ids
-        DevPtr<hbk::ScRequest> d_req;
-        DevPtr<hbk::ScRect> d_rect;               // the rectangles of one piece
-        DevPtr<uint32_t> d_pair;                  // the pair words of one piece
-        DevPtr<double> d_acc, d_score;            // nodes x 2: the running sums; nodes: the scores
-        DevPtr<unsigned long long> d_cnt;         // the four pair counters
-        uint64_t cap_lists = 0, cap_len = 0, cap_mask = 0, cap_keys = 0, cap_node_idx = 0, cap_anchor_idx = 0, cap_req = 0, cap_rect = 0, cap_pair = 0,
-                 cap_acc = 0, cap_score = 0, cap_cnt = 0;
+        GrowPtr<uint32_t> d_lists, d_len;          // distinct x limit: the backlinks of the distinct known hosts (sorted by sid), their degrees
+        GrowPtr<unsigned long long> d_mask;        // distinct: their bloom masks
+        GrowPtr<unsigned long long> d_keys;        // the lists' keys of one call of the list builder (nobody reads them here)
+        GrowPtr<uint32_t> d_node_idx, d_anchor_idx; // the nodes / the anchors of all requests as indices of the call's distinct ids
+        GrowPtr<hbk::ScRequest> d_req;
+        GrowPtr<hbk::ScRect> d_rect;               // the rectangles of one piece
+        GrowPtr<uint32_t> d_pair;                  // the pair words of one piece
+        GrowPtr<double> d_acc, d_score;            // nodes x 2: the running sums; nodes: the scores
+        GrowPtr<unsigned long long> d_cnt;         // the four pair counters
         std::vector<uint64_t> offsets;            // the result on the host: requests + 1 offsets into scores
         std::vector<double> scores;
         uint64_t bytes = 0;
@@ -499,6 +493,44 @@ int dev_alloc(hb_ctx *c, T **out, size_t count)
     return HB_OK;
 }
 
+// A holder of an operator's state (LinksState, SimilarHostsState, SimilarityLimitState, ScoreState) with at least `need` entries: it
+// only grows.  Its bytes are booked in the state's own count (`booked`) and in hb_stats.device_bytes
+template <class T>
+int hold(hb_ctx *c, uint64_t &booked, GrowPtr<T> &h, uint64_t need)
+{
+    if (h && h.have >= need) return HB_OK;
+    const uint64_t old_bytes = h ? std::max<uint64_t>(h.have * sizeof(T), 256) : 0;
+    h.reset();
+    booked -= old_bytes;
+    c->stats.device_bytes -= old_bytes;
+    h.have = 0;
+    const uint64_t bytes = std::max<uint64_t>(need * sizeof(T), 256);
+    const hipError_t e = h.alloc((bytes + sizeof(T) - 1) / sizeof(T));
+    if (e != hipSuccess) return fail(c, HB_ERR_NOMEM, "hipMalloc(" + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
+    h.have = need;
+    booked += bytes;
+    c->stats.device_bytes += bytes;
+    return HB_OK;
+}
+
+// The lap timer of the operators that time a step between kEvMerge and kEvCollective: lap_start marks the beginning on the stream; lap
+// records the end, drains the stream and adds the elapsed GPU time to *ms_out
+int lap_start(hb_ctx *c)
+{
+    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    return HB_OK;
+}
+
+int lap(hb_ctx *c, double *ms_out)
+{
+    HB_HIP(hipEventRecord(c->ev[kEvCollective], c->stream));
+    HB_HIP(hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    HB_HIP(hipEventElapsedTime(&ms, c->ev[kEvMerge], c->ev[kEvCollective]));
+    *ms_out += ms;
+    return HB_OK;
+}
+
 // The same, but the failure is reported as `what` + the error string (messages that name the step rather than the call)
 #define HB_HIP_AS(what, call)                                                                     \
     do {                                                                                          \
@@ -514,7 +546,7 @@ void free_graph_buffers(hb_ctx *c)
     for (void *q : {(void *)c->h_out, (void *)c->rs.h_sid, (void *)c->rs.h_val, (void *)c->rs.h_count})
         if (q) (void)hipHostFree(q);
     tail_index_free(c->tail_index);
-    static_cast<GraphDeviceState &>(*c) = GraphDeviceState{}; // (the sampled operator's holders free their buffers here)
+    static_cast<GraphDeviceState &>(*c) = GraphDeviceState{}; // (the DevPtr / GrowPtr holders of the operators' states free their buffers here)
     c->stats.device_bytes = 0;
 }
 

@@ -9,24 +9,36 @@ namespace {
 
 constexpr uint64_t kLinksDefaultSlots = 1024, kLinksMaxSlots = 65536;
 
-// a holder of the links state with at least `need` entries (it only grows); the bytes are booked with the context's
-template <class T>
-int links_hold(hb_ctx *c, DevPtr<T> &h, uint64_t &have, uint64_t need)
+// the virtual levels of the plan; a plan with more than the list builder's 64 level counters can follow is refused
+int links_levels(hb_ctx *c, const std::string &who, size_t *nlev)
 {
-    if (h && have >= need) return HB_OK;
-    auto &s = c->lnk;
-    const uint64_t old_bytes = h ? std::max<uint64_t>(have * sizeof(T), 256) : 0;
-    h.reset();
-    s.bytes -= old_bytes;
-    c->stats.device_bytes -= old_bytes;
-    have = 0;
-    const uint64_t bytes = std::max<uint64_t>(need * sizeof(T), 256);
-    const hipError_t e = h.alloc((bytes + sizeof(T) - 1) / sizeof(T));
-    if (e != hipSuccess) return fail(c, HB_ERR_NOMEM, "hipMalloc(" + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
-    have = need;
-    s.bytes += bytes;
-    c->stats.device_bytes += bytes;
+    *nlev = 0;
+    for_each_virtual_level(c->plan, true, [&](uint64_t, uint64_t) { (*nlev)++; });
+    if (*nlev + 2 > 64) return fail(c, HB_ERR_INVALID, who + ": unexpected plan layout (more than 62 virtual levels)");
     return HB_OK;
+}
+
+// A list of ids as the operators of this family want it: each distinct known node is looked up once, every entry that names it finds it
+struct ResolvedIds {
+    std::vector<uint32_t> distinct; // the distinct known sids, ascending
+    std::vector<uint32_t> slot;     // per entry: its position in `distinct`, kNone = no node of the graph
+    uint64_t unknown = 0;           // entries that are no node of the graph
+};
+
+ResolvedIds resolve_ids(const hb_ctx *c, const hb_u128 *ids, uint64_t count)
+{
+    ResolvedIds r;
+    r.slot.resize(count);
+    host_find_sids(c->g.ids.data(), c->plan.n, ids, count, r.slot.data()); // (the sids for now)
+    for (uint32_t sid : r.slot)
+        if (sid != kNone) r.distinct.push_back(sid);
+    std::sort(r.distinct.begin(), r.distinct.end());
+    r.distinct.erase(std::unique(r.distinct.begin(), r.distinct.end()), r.distinct.end());
+    for (uint32_t &v : r.slot) {
+        if (v == kNone) r.unknown++;
+        else v = (uint32_t)(std::lower_bound(r.distinct.begin(), r.distinct.end(), v) - r.distinct.begin());
+    }
+    return r;
 }
 
 // ord / inv / ord_row from the keys in d_key (`sorted`: false = no key set, NodeID order)
@@ -39,7 +51,7 @@ int links_build_order(hb_ctx *c, bool sorted, double *ms)
     if (sorted) {
         if (d_order.alloc(n) != hipSuccess || d_rank.alloc(n) != hipSuccess) return fail(c, HB_ERR_NOMEM, "hb_links_set_keys: out of device memory for the sort");
     }
-    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    if (const int rc = lap_start(c)) return rc;
     if (sorted) { // stable: equal keys keep ascending sid order, which is ascending NodeID order
         const std::string e = gpu_rank_keys_device((void *)c->stream, (const uint64_t *)s.d_key.get(), n, d_order.get(), d_rank.get());
         if (!e.empty()) return fail(c, e.find("memory") != std::string::npos ? HB_ERR_NOMEM : HB_ERR_HIP, "hb_links_set_keys: " + e);
@@ -49,7 +61,7 @@ int links_build_order(hb_ctx *c, bool sorted, double *ms)
     hipLaunchKernelGGL(hbk::lk_ord_row_kernel, dim3(grid_blocks(c, (p.n_pad + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint32_t *)s.d_ord.get(),
                        (const uint32_t *)c->d_sid_of, p.n_pad, s.d_ord_row.get());
     HB_HIP(hipGetLastError());
-    return nearest_seed_lap(c, ms); // (drains the stream: the sort's buffers may go)
+    return lap(c, ms); // (drains the stream: the sort's buffers may go)
 }
 
 // the per-graph holders; a context that never saw hb_links_set_keys gets the order of "every key is u64::MAX"
@@ -59,10 +71,10 @@ int links_alloc(hb_ctx *c, bool default_order)
     if (s.ready) return HB_OK;
     const Plan &p = c->plan;
     int rc;
-    if ((rc = links_hold(c, s.d_key, s.cap_key, p.n))) return rc;
-    if ((rc = links_hold(c, s.d_ord, s.cap_ord, p.n))) return rc;
-    if ((rc = links_hold(c, s.d_inv, s.cap_inv, p.n))) return rc;
-    if ((rc = links_hold(c, s.d_ord_row, s.cap_ord_row, p.n_pad))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_key, p.n))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_ord, p.n))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_inv, p.n))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_ord_row, p.n_pad))) return rc;
     if (default_order) {
         HB_HIP(hipMemsetAsync(s.d_key.get(), 0xFF, p.n * sizeof(unsigned long long), c->stream));
         double ms = 0;
@@ -148,11 +160,11 @@ int links_top_rows(hb_ctx *c, const std::string &who, double *ms)
     int rc;
     if ((rc = ensure_transpose(c, who.c_str()))) return rc;
     if (s.top_ready) return HB_OK;
-    if ((rc = links_hold(c, s.d_top_row, s.cap_top_row, p.nv + 1))) return rc; // (+ 1: the flag word behind the table)
+    if ((rc = hold(c, s.bytes, s.d_top_row, p.nv + 1))) return rc; // (+ 1: the flag word behind the table)
     uint32_t *top = s.d_top_row.get(), *flag = top + p.nv;
     HB_HIP(hipMemsetAsync(top, 0xFF, p.nv * sizeof(uint32_t), c->stream));
     HB_HIP(hipMemsetAsync(flag, 0, sizeof(uint32_t), c->stream));
-    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    if ((rc = lap_start(c))) return rc;
     for_each_virtual_level(p, false, [&](uint64_t lo, uint64_t hi) { // the highest level first: a level reads the tops of the levels above it
         hipLaunchKernelGGL(hbk::fw_top_row_kernel, dim3(grid_blocks(c, (hi - lo + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr,
                            (const uint64_t *)c->d_out_ptr, (const uint32_t *)c->d_out_rows, p.n_pad, p.n_pad + p.nv, lo, hi, top, flag);
@@ -160,14 +172,36 @@ int links_top_rows(hb_ctx *c, const std::string &who, double *ms)
     HB_HIP(hipGetLastError());
     uint32_t *h32 = (uint32_t *)c->h_counters;
     HB_HIP(hipMemcpyAsync(h32, flag, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = nearest_seed_lap(c, ms))) return rc;
+    if ((rc = lap(c, ms))) return rc;
     if (h32[0]) return fail(c, HB_ERR_INVALID, who + ": unexpected plan layout (a chunk row with a list does not have exactly one reader above it)");
     s.top_ready = true;
     return HB_OK;
 }
 
-int links_lists(hb_ctx *c, const std::string &who, bool forward, const uint32_t *h_sids, const uint32_t *d_sids, uint64_t U, const hb_links_options &o,
-                uint32_t *res_sid, unsigned long long *res_key, uint32_t *d_len, std::vector<uint32_t> &degree, hb_links_stats &st);
+int links_lists(hb_ctx *c, const std::string &who, size_t nlev, bool forward, const uint32_t *h_sids, const uint32_t *d_sids, uint64_t U,
+                const hb_links_options &o, uint32_t *res_sid, unsigned long long *res_key, uint32_t *d_len, std::vector<uint32_t> &degree, hb_links_stats &st);
+
+// The list builds an operator makes for itself (hb_similar_hosts, hb_score_hosts, the limited hb_inbound_similarity): the options with
+// the operator's two debug flags, statistics of which only the GPU time is reported, and the degrees of the last build's hosts
+struct ListBuild {
+    hb_links_options lo{};
+    hb_links_stats ls{};
+    std::vector<uint32_t> degree;
+    size_t nlev; // of links_levels
+    ListBuild(size_t nlev_, uint32_t limit, uint32_t flags = 0, uint64_t slots_per_batch = 0) : nlev(nlev_)
+    {
+        lo.flags = flags & (HB_LINKS_SPREAD_ORDS | HB_LINKS_NO_SHORTCUT);
+        lo.limit = limit;
+        lo.slots_per_batch = slots_per_batch;
+    }
+    double gpu_ms() const { return ls.ms_expand + ls.ms_select + ls.ms_emit; }
+    int run(hb_ctx *c, const std::string &who, bool forward, const uint32_t *h_sids, const uint32_t *d_sids, uint64_t U, uint32_t *res_sid, unsigned long long *res_key,
+            uint32_t *d_len)
+    {
+        degree.assign(U, 0);
+        return links_lists(c, who, nlev, forward, h_sids, d_sids, U, lo, res_sid, res_key, d_len, degree, ls);
+    }
+};
 
 // hb_backlinks (forward = false) and hb_forwardlinks: the refusals, the distinct queried nodes, the holders and the result are the same;
 // a batch is the in-lists' item walk or the out-lists' segment walk
@@ -183,34 +217,23 @@ int links_query(hb_ctx *c, const hb_links_options *opt_in, hb_links_stats *st_ou
     if (o.slots_per_batch > kLinksMaxSlots) return fail(c, HB_ERR_INVALID, who + ": slots_per_batch > 65536");
     if (o.node_count && !o.nodes) return fail(c, HB_ERR_INVALID, who + ": node_count without nodes");
     if (o.node_count >= (1ull << 32)) return fail(c, HB_ERR_INVALID, who + ": too many queries");
-    const Plan &p = c->plan;
-    const uint64_t n = p.n, limit = o.limit;
-    size_t nlev = 0;
-    for_each_virtual_level(p, true, [&](uint64_t, uint64_t) { nlev++; });
-    if (nlev + 2 > 64) return fail(c, HB_ERR_INVALID, who + ": unexpected plan layout (more than 62 virtual levels)");
+    const uint64_t limit = o.limit;
+    size_t nlev;
+    int rc;
+    if ((rc = links_levels(c, who, &nlev))) return rc;
     auto &s = c->lnk;
     hb_links_stats st{};
-    int rc;
     // ---- the distinct queried nodes, ascending: each is looked up once, every query that names it gets its list
-    std::vector<uint32_t> qsid(o.node_count), distinct;
-    host_find_sids(c->g.ids.data(), n, o.nodes, o.node_count, qsid.data());
-    distinct.reserve(o.node_count);
-    for (uint32_t sid : qsid)
-        if (sid != kNone) distinct.push_back(sid);
-    std::sort(distinct.begin(), distinct.end());
-    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
-    const uint64_t U = distinct.size();
+    ResolvedIds ids = resolve_ids(c, o.nodes, o.node_count);
+    const uint64_t U = ids.distinct.size();
     st.queries = o.node_count;
     st.distinct = U;
-    std::vector<uint32_t> query_slot(o.node_count, kNone), degree(U, 0);
-    for (uint64_t i = 0; i < o.node_count; i++) {
-        if (qsid[i] == kNone) st.unknown++;
-        else query_slot[i] = (uint32_t)(std::lower_bound(distinct.begin(), distinct.end(), qsid[i]) - distinct.begin());
-    }
+    st.unknown = ids.unknown;
+    std::vector<uint32_t> degree(U, 0);
     if (forward && U && (rc = links_top_rows(c, who, &st.ms_expand))) return rc; // (it may refuse: before the previous result is touched)
     s.valid = false;
     auto finish = [&]() {
-        s.query_slot.swap(query_slot);
+        s.query_slot.swap(ids.slot);
         s.degree.swap(degree);
         s.limit = o.limit;
         s.entries = 0;
@@ -224,35 +247,34 @@ int links_query(hb_ctx *c, const hb_links_options *opt_in, hb_links_stats *st_ou
         return HB_OK;
     };
     if (!U) return finish();
-    if ((rc = links_hold(c, s.d_res_sid, s.cap_res_sid, U * limit))) return rc;
-    if ((rc = links_hold(c, s.d_res_key, s.cap_res_key, U * limit))) return rc;
-    if ((rc = links_lists(c, who, forward, distinct.data(), nullptr, U, o, s.d_res_sid.get(), s.d_res_key.get(), nullptr, degree, st))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_res_sid, U * limit))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_res_key, U * limit))) return rc;
+    if ((rc = links_lists(c, who, nlev, forward, ids.distinct.data(), nullptr, U, o, s.d_res_sid.get(), s.d_res_key.get(), nullptr, degree, st))) return rc;
     return finish();
 }
 
 // The lists of U distinct nodes - their sids on the host (h_sids) or on the device (d_sids) - into res_sid / res_key (U x limit each,
-// list order; the caller's buffers) and their degrees; d_len, if given, gets the degrees on the device as well.  The batch loop of
+// list order; the caller's buffers) and their degrees; d_len, if given, gets the degrees on the device as well.  nlev = the virtual levels
+// that links_levels counted (and accepted) before the caller touched its previous result.  The batch loop of
 // hb_backlinks / hb_forwardlinks, and what hb_similar_hosts builds its four sets of lists with.  The buffers of a batch are the links
 // state's: they hold nothing between two calls.
-int links_lists(hb_ctx *c, const std::string &who, bool forward, const uint32_t *h_sids, const uint32_t *d_sids, uint64_t U, const hb_links_options &o,
-                uint32_t *res_sid, unsigned long long *res_key, uint32_t *d_len, std::vector<uint32_t> &degree, hb_links_stats &st)
+int links_lists(hb_ctx *c, const std::string &who, size_t nlev, bool forward, const uint32_t *h_sids, const uint32_t *d_sids, uint64_t U,
+                const hb_links_options &o, uint32_t *res_sid, unsigned long long *res_key, uint32_t *d_len, std::vector<uint32_t> &degree, hb_links_stats &st)
 {
     const Plan &p = c->plan;
     const uint64_t n = p.n, limit = o.limit;
-    size_t nlev = 0;
-    for_each_virtual_level(p, true, [&](uint64_t, uint64_t) { nlev++; });
     auto &s = c->lnk;
     int rc;
     if ((rc = links_alloc(c, true))) return rc;
     const uint64_t slots_max = std::min<uint64_t>(o.slots_per_batch ? o.slots_per_batch : kLinksDefaultSlots, U);
     // (forward: no items; behind the backlinks' control words the lengths of the reader lists and the segment offsets, slots + 1)
     const uint64_t item_cap = slots_max + p.nv + 16, ctl_words = 5 * slots_max + 64 + 8 + (forward ? 2 * slots_max + 1 : 0);
-    if (!forward && (rc = links_hold(c, s.d_items, s.cap_items, item_cap))) return rc;
-    if ((rc = links_hold(c, s.d_hist, s.cap_hist, slots_max * 256))) return rc;
-    if ((rc = links_hold(c, s.d_ctl, s.cap_ctl, ctl_words))) return rc;
-    if ((rc = links_hold(c, s.d_out, s.cap_out, slots_max * limit))) return rc;
-    if ((rc = links_hold(c, s.d_slot_row, s.cap_slot_row, U))) return rc;
-    if ((rc = links_hold(c, s.d_slot_self, s.cap_slot_self, U))) return rc;
+    if (!forward && (rc = hold(c, s.bytes, s.d_items, item_cap))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_hist, slots_max * 256))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_ctl, ctl_words))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_out, slots_max * limit))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_slot_row, U))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_slot_self, U))) return rc;
     // the rows of the distinct nodes (the plan's sid -> row table is on the device: gathered there, from the sids in d_slot_self)
     {
         HB_HIP(hipMemcpyAsync(s.d_slot_self.get(), h_sids ? h_sids : d_sids, U * sizeof(uint32_t), h_sids ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
@@ -297,7 +319,7 @@ int links_lists(hb_ctx *c, const std::string &who, bool forward, const uint32_t 
         // ---- expand and count: level by level down the queried hosts' trees; forward: the reader lists, cut into segments
         HB_HIP(hipMemsetAsync(ctl, 0, ctl_words * sizeof(uint32_t), c->stream));
         HB_HIP(hipMemsetAsync(b.hist, 0, S * 256 * sizeof(uint32_t), c->stream));
-        HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+        if ((rc = lap_start(c))) return rc;
         uint64_t lo = 0, hi = S;
         hbk::FwBatch f{};
         unsigned seg_blocks = 1;
@@ -342,7 +364,7 @@ int links_lists(hb_ctx *c, const std::string &who, bool forward, const uint32_t 
         const uint64_t total = hi;
         st.rows_walked += total;
         HB_HIP(hipMemcpyAsync(deg.data(), b.deg, S * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        if ((rc = nearest_seed_lap(c, &st.ms_expand))) return rc;
+        if ((rc = lap(c, &st.ms_expand))) return rc;
         uint64_t selecting = 0;
         for (uint64_t i = 0; i < S; i++) {
             degree[base + i] = deg[i];
@@ -358,7 +380,7 @@ int links_lists(hb_ctx *c, const std::string &who, bool forward, const uint32_t 
             per_block = ((total + blocks - 1) / blocks + hbk::kLkItems - 1) / hbk::kLkItems * hbk::kLkItems;
             blocks = (total + per_block - 1) / per_block;
         }
-        HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+        if ((rc = lap_start(c))) return rc;
         hipLaunchKernelGGL(hbk::lk_plan_kernel, dim3(slot_blocks), dim3(256), 0, c->stream, b, no_shortcut ? 1u : 0u);
         if (selecting) {
             for (int d = top_digit; d >= 0; d--) {
@@ -368,17 +390,17 @@ int links_lists(hb_ctx *c, const std::string &who, bool forward, const uint32_t 
             }
         }
         HB_HIP(hipGetLastError());
-        if ((rc = nearest_seed_lap(c, &st.ms_select))) return rc;
+        if ((rc = lap(c, &st.ms_select))) return rc;
 
         // ---- emit, sort, translate
-        HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+        if ((rc = lap_start(c))) return rc;
         if (!forward) hipLaunchKernelGGL(hbk::lk_emit_kernel, dim3(grid_blocks(c, (total + hbk::kLkItems - 1) / hbk::kLkItems, 8, 1)), dim3(256), 0, c->stream, b, total);
         else if (f.segs) hipLaunchKernelGGL(hbk::fw_emit_kernel, dim3(seg_blocks), dim3(256), 0, c->stream, b, f);
         hipLaunchKernelGGL(hbk::lk_sort_kernel, dim3((unsigned)S), dim3(256), 0, c->stream, b, (const uint32_t *)s.d_inv.get(),
                            (const unsigned long long *)s.d_key.get(), n, res_sid + base * limit, res_key + base * limit);
         HB_HIP(hipGetLastError());
         if (d_len) HB_HIP(hipMemcpyAsync(d_len + base, b.deg, S * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-        if ((rc = nearest_seed_lap(c, &st.ms_emit))) return rc;
+        if ((rc = lap(c, &st.ms_emit))) return rc;
     }
     return HB_OK;
 }

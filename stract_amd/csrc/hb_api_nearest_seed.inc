@@ -38,17 +38,6 @@ int nearest_seed_alloc(hb_ctx *c)
     return HB_OK;
 }
 
-// elapsed GPU time between the operator's two events (recorded on the stream, which is then drained)
-int nearest_seed_lap(hb_ctx *c, double *ms_out)
-{
-    HB_HIP(hipEventRecord(c->ev[kEvCollective], c->stream));
-    HB_HIP(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HB_HIP(hipEventElapsedTime(&ms, c->ev[kEvMerge], c->ev[kEvCollective]));
-    *ms_out += ms;
-    return HB_OK;
-}
-
 int nearest_seed(hb_ctx *c, const hb_nearest_seed_options *opt_in, hb_nearest_seed_stats *st_out)
 {
     const double t0 = now_ms();
@@ -118,7 +107,7 @@ int nearest_seed(hb_ctx *c, const hb_nearest_seed_options *opt_in, hb_nearest_se
 
     // ---- seed level: candidates, the chunk rows' pairs (virtual levels ascending), the node rows' seeds
     HB_HIP(hipMemcpyAsync(s.d_up_key, up_key.data(), n * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
-    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    if ((rc = lap_start(c))) return rc;
     hipLaunchKernelGGL(hbk::ns_key_kernel, dim3(row_blocks), dim3(256), 0, c->stream, (const unsigned long long *)s.d_up_key, (const uint32_t *)c->d_sid_of, n_pad, s.d_cand);
     for_each_virtual_level(p, true, [&](uint64_t lo, uint64_t hi) { // ascending: a chunk row joins the pairs of the chunk rows below it
         hipLaunchKernelGGL(hbk::ns_seed_kernel<false>, dim3(grid_blocks(c, (hi - lo + 63) / 64, 8, 1)), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr,
@@ -129,7 +118,7 @@ int nearest_seed(hb_ctx *c, const hb_nearest_seed_options *opt_in, hb_nearest_se
                        (const uint32_t *)c->d_src, (const uint4 *)s.d_cand, s.d_part, (const uint32_t *)c->d_sid_of, (const uint32_t *)c->d_dev_of, s.d_seed_row, n_pad,
                        rows_total, (uint64_t)0, n_pad);
     HB_HIP(hipGetLastError());
-    if ((rc = nearest_seed_lap(c, &st.ms_seed))) return rc;
+    if ((rc = lap(c, &st.ms_seed))) return rc;
 
     // ---- round 0: the original values
     if (!from_image) {
@@ -137,7 +126,7 @@ int nearest_seed(hb_ctx *c, const hb_nearest_seed_options *opt_in, hb_nearest_se
         HB_HIP(hipMemcpyAsync(s.d_up_has, up_has.data(), n, hipMemcpyHostToDevice, c->stream));
     }
     HB_HIP(hipMemsetAsync(cnt4, 0, 4 * sizeof(unsigned long long), c->stream));
-    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    if ((rc = lap_start(c))) return rc;
     if (from_image)
         hipLaunchKernelGGL(hbk::ns_init_image_kernel, dim3(row_blocks), dim3(256), 0, c->stream, (const double *)c->d_out, (const uint32_t *)c->d_cid_of, c->out_len, n_pad,
                            s.d_val[0], s.d_has[0], cnt4);
@@ -146,19 +135,19 @@ int nearest_seed(hb_ctx *c, const hb_nearest_seed_options *opt_in, hb_nearest_se
                            (const uint32_t *)c->d_sid_of, n_pad, s.d_val[0], s.d_has[0], cnt4);
     HB_HIP(hipGetLastError());
     HB_HIP(hipMemcpyAsync(h, cnt4, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = nearest_seed_lap(c, &st.ms_fill))) return rc;
+    if ((rc = lap(c, &st.ms_fill))) return rc;
     st.with_original = h[0];
 
     // ---- the rounds: synchronous, state after r - 1 read, state after r written; the first round that fills nothing is the last
     int cur = 0;
     for (uint32_t r = 1; r <= rounds; r++) {
         HB_HIP(hipMemsetAsync(s.d_cnt, 0, hbk::kCounterWords * sizeof(unsigned long long), c->stream));
-        HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+        if ((rc = lap_start(c))) return rc;
         hipLaunchKernelGGL(hbk::ns_fill_kernel, dim3(row_blocks), dim3(256), 0, c->stream, (const double *)s.d_val[cur], (const uint8_t *)s.d_has[cur],
                            (const uint32_t *)s.d_seed_row, n_pad, o.discount_factor, s.d_val[cur ^ 1], s.d_has[cur ^ 1], s.d_cnt);
         HB_HIP(hipGetLastError());
         HB_HIP(hipMemcpyAsync(h, s.d_cnt, hbk::kCounterWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        if ((rc = nearest_seed_lap(c, &st.ms_fill))) return rc;
+        if ((rc = lap(c, &st.ms_fill))) return rc;
         uint64_t filled = 0;
         for (int k = 0; k < hbk::kStripes; k++) filled += h[4 * k];
         st.filled[std::min<uint32_t>(r - 1, 15)] += filled;
@@ -169,12 +158,12 @@ int nearest_seed(hb_ctx *c, const hb_nearest_seed_options *opt_in, hb_nearest_se
 
     // ---- the result by sid, its compacted form (only the results are downloaded by hb_nearest_seed_copy), the final counters
     HB_HIP(hipMemsetAsync(cnt4, 0, 4 * sizeof(unsigned long long), c->stream));
-    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    if ((rc = lap_start(c))) return rc;
     hipLaunchKernelGGL(hbk::ns_by_sid_kernel, dim3(sid_blocks), dim3(256), 0, c->stream, (const double *)s.d_val[cur], (const uint8_t *)s.d_has[cur],
                        (const uint32_t *)s.d_seed_row, (const uint32_t *)c->d_dev_of, (const uint32_t *)c->d_sid_of, n, n_pad, s.d_val_sid, s.d_flag_sid, s.d_seed_sid, cnt4);
     HB_HIP(hipGetLastError());
     HB_HIP(hipMemcpyAsync(h, cnt4, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = nearest_seed_lap(c, &st.ms_fill))) return rc;
+    if ((rc = lap(c, &st.ms_fill))) return rc;
     st.results = h[0];
     st.no_seed = h[1];
     st.seed_without_value = h[2];

@@ -11,25 +11,6 @@ namespace {
 constexpr uint64_t kScoreMaxRequests = 4096, kScoreMaxEntries = 1ull << 24, kScoreMaxDistinct = 262144;
 constexpr uint64_t kScorePiece = 1ull << 20, kScoreSmallPiece = 64; // pairs of a piece (HB_SCORE_SMALL_PIECES: the small one)
 
-template <class T>
-int score_hold(hb_ctx *c, DevPtr<T> &h, uint64_t &have, uint64_t need)
-{
-    if (h && have >= need) return HB_OK;
-    auto &s = c->sco;
-    const uint64_t old_bytes = h ? std::max<uint64_t>(have * sizeof(T), 256) : 0;
-    h.reset();
-    s.bytes -= old_bytes;
-    c->stats.device_bytes -= old_bytes;
-    have = 0;
-    const uint64_t bytes = std::max<uint64_t>(need * sizeof(T), 256);
-    const hipError_t e = h.alloc((bytes + sizeof(T) - 1) / sizeof(T));
-    if (e != hipSuccess) return fail(c, HB_ERR_NOMEM, "hipMalloc(" + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
-    have = need;
-    s.bytes += bytes;
-    c->stats.device_bytes += bytes;
-    return HB_OK;
-}
-
 // The pieces of the pair space: rectangles (request, node range, anchor range) in request order, at most `cap` pairs per piece.  A
 // request that fits goes into one rectangle; one that does not is cut into node ranges of whole anchor lists, and where one anchor list
 // alone is too long, into anchor ranges of one node.  The ranges of a node come in ascending anchor order in DIFFERENT pieces: the
@@ -117,9 +98,9 @@ int score_hosts(hb_ctx *c, const hb_score_options *opt_in, hb_score_stats *st_ou
     if (A + N > kScoreMaxEntries) return fail(c, HB_ERR_INVALID, who + ": more than 2^24 anchor and node entries");
     const Plan &p = c->plan;
     const uint64_t n = p.n;
-    size_t nlev = 0;
-    for_each_virtual_level(p, true, [&](uint64_t, uint64_t) { nlev++; });
-    if (nlev + 2 > 64) return fail(c, HB_ERR_INVALID, who + ": unexpected plan layout (more than 62 virtual levels)");
+    size_t nlev;
+    int rc;
+    if ((rc = links_levels(c, who, &nlev))) return rc;
     // ---- every id once: the anchors of all requests (liked, then disliked), then the nodes of all requests
     std::vector<hb_u128> ids;
     ids.reserve(A + N);
@@ -129,33 +110,26 @@ int score_hosts(hb_ctx *c, const hb_score_options *opt_in, hb_score_stats *st_ou
         ids.insert(ids.end(), q.disliked, q.disliked + q.disliked_count);
     }
     for (uint64_t r = 0; r < R; r++) ids.insert(ids.end(), o.requests[r].nodes, o.requests[r].nodes + o.requests[r].node_count);
-    std::vector<uint32_t> sid(A + N), distinct;
-    host_find_sids(c->g.ids.data(), n, ids.data(), A + N, sid.data());
+    ResolvedIds known = resolve_ids(c, ids.data(), A + N);
+    const std::vector<uint32_t> &distinct = known.distinct;
+    std::vector<uint32_t> &idx = known.slot; // index of entry i: the slot of a known host, U + its position among the strangers otherwise (below)
     std::vector<hb_u128> strangers; // the distinct ids that are no node: self is decided on the index of an id, known or not
-    for (uint64_t i = 0; i < A + N; i++) {
-        if (sid[i] != kNone) distinct.push_back(sid[i]);
-        else strangers.push_back(ids[i]);
-    }
-    std::sort(distinct.begin(), distinct.end());
-    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    for (uint64_t i = 0; i < A + N; i++)
+        if (idx[i] == kNone) strangers.push_back(ids[i]);
     std::sort(strangers.begin(), strangers.end(), u128_less);
     strangers.erase(std::unique(strangers.begin(), strangers.end(), u128_eq), strangers.end());
     const uint64_t U = distinct.size();
     if (U > kScoreMaxDistinct) return fail(c, HB_ERR_INVALID, who + ": more than 262144 distinct known hosts");
     hb_score_stats st{};
-    int rc;
     if (U && (rc = links_top_rows(c, who, &st.ms_lists))) return rc; // (it may refuse: before the previous result is touched)
     st.requests = R;
     st.anchors = A;
     st.nodes = N;
     st.distinct = U;
-    std::vector<uint32_t> idx(A + N); // index of entry i: the slot of a known host, U + its position among the strangers otherwise
     for (uint64_t i = 0; i < A + N; i++) {
-        if (sid[i] != kNone) idx[i] = (uint32_t)(std::lower_bound(distinct.begin(), distinct.end(), sid[i]) - distinct.begin());
-        else {
-            idx[i] = (uint32_t)(U + (std::lower_bound(strangers.begin(), strangers.end(), ids[i], u128_less) - strangers.begin()));
-            (i < A ? st.unknown_anchors : st.unknown_nodes)++;
-        }
+        if (idx[i] != kNone) continue;
+        idx[i] = (uint32_t)(U + (std::lower_bound(strangers.begin(), strangers.end(), ids[i], u128_less) - strangers.begin()));
+        (i < A ? st.unknown_anchors : st.unknown_nodes)++;
     }
     std::vector<hbk::ScRequest> req(R);
     std::vector<uint64_t> node_count(R), offsets(R + 1, 0);
@@ -197,39 +171,32 @@ int score_hosts(hb_ctx *c, const hb_score_options *opt_in, hb_score_stats *st_ou
 
     // ---- the BitVecs of the distinct known hosts: their `limit` backlinks, sorted, the bloom masks
     const uint64_t lists_piece = std::min<uint64_t>(U, kLinksMaxSlots);
-    if ((rc = score_hold(c, s.d_lists, s.cap_lists, U * limit))) return rc;
-    if ((rc = score_hold(c, s.d_len, s.cap_len, U))) return rc;
-    if ((rc = score_hold(c, s.d_mask, s.cap_mask, U))) return rc;
-    if ((rc = score_hold(c, s.d_keys, s.cap_keys, lists_piece * limit))) return rc;
-    if ((rc = score_hold(c, s.d_node_idx, s.cap_node_idx, N))) return rc;
-    if ((rc = score_hold(c, s.d_anchor_idx, s.cap_anchor_idx, A))) return rc;
-    if ((rc = score_hold(c, s.d_req, s.cap_req, R))) return rc;
-    if ((rc = score_hold(c, s.d_rect, s.cap_rect, rects_max))) return rc;
-    if ((rc = score_hold(c, s.d_pair, s.cap_pair, std::min(st.pairs, piece_cap)))) return rc;
-    if ((rc = score_hold(c, s.d_acc, s.cap_acc, N * 2))) return rc;
-    if ((rc = score_hold(c, s.d_score, s.cap_score, N))) return rc;
-    if ((rc = score_hold(c, s.d_cnt, s.cap_cnt, 4))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_lists, U * limit))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_len, U))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_mask, U))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_keys, lists_piece * limit))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_node_idx, N))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_anchor_idx, A))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_req, R))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_rect, rects_max))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_pair, std::min(st.pairs, piece_cap)))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_acc, N * 2))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_score, N))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_cnt, 4))) return rc;
     if (U) {
-        hb_links_options lo{};
-        lo.flags = o.flags & (HB_LINKS_SPREAD_ORDS | HB_LINKS_NO_SHORTCUT);
-        lo.limit = o.limit;
-        lo.slots_per_batch = o.slots_per_batch;
-        hb_links_stats ls{};
-        std::vector<uint32_t> degree;
+        ListBuild lists(nlev, o.limit, o.flags, o.slots_per_batch);
         for (uint64_t base = 0; base < U; base += lists_piece) { // (one call unless the hosts outnumber the list builder's largest batch)
             const uint64_t P = std::min(lists_piece, U - base);
-            degree.assign(P, 0);
-            if ((rc = links_lists(c, who, false, distinct.data() + base, nullptr, P, lo, s.d_lists.get() + base * limit, s.d_keys.get(), s.d_len.get() + base, degree, ls)))
-                return rc;
+            if ((rc = lists.run(c, who, false, distinct.data() + base, nullptr, P, s.d_lists.get() + base * limit, s.d_keys.get(), s.d_len.get() + base))) return rc;
         }
-        st.ms_lists += ls.ms_expand + ls.ms_select + ls.ms_emit;
+        st.ms_lists += lists.gpu_ms();
         uint32_t sort_n = 2;
         while (sort_n < o.limit) sort_n <<= 1;
-        HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+        if ((rc = lap_start(c))) return rc;
         hipLaunchKernelGGL(hbk::sc_bitvec_kernel, dim3((unsigned)U), dim3(256), 0, c->stream, s.d_lists.get(), (const uint32_t *)s.d_len.get(), o.limit, sort_n,
                            (const uint32_t *)c->d_dev_of, (const uint64_t *)c->d_idlow, n, s.d_mask.get());
         HB_HIP(hipGetLastError());
-        if ((rc = nearest_seed_lap(c, &st.ms_bitvec))) return rc;
+        if ((rc = lap(c, &st.ms_bitvec))) return rc;
     }
 
     // ---- the pairs, a piece at a time: classes and counts, then the sums of the piece's nodes
@@ -262,15 +229,15 @@ int score_hosts(hb_ctx *c, const hb_score_options *opt_in, hb_score_stats *st_ou
         st.pieces++;
         HB_HIP(hipMemcpyAsync(s.d_rect.get(), first, rects * sizeof(hbk::ScRect), hipMemcpyHostToDevice, c->stream)); // (pageable: the copy is done when it returns)
         if (groups) {
-            HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+            if ((rc = lap_start(c))) return rc;
             hipLaunchKernelGGL(hbk::sc_pair_kernel, dim3((unsigned)groups), dim3(256), 0, c->stream, sp);
             HB_HIP(hipGetLastError());
-            if ((rc = nearest_seed_lap(c, &st.ms_pairs))) return rc;
+            if ((rc = lap(c, &st.ms_pairs))) return rc;
         }
-        HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+        if ((rc = lap_start(c))) return rc;
         hipLaunchKernelGGL(hbk::sc_finish_kernel, dim3(grid_blocks(c, (sp.lanes + 255) / 256, 8, 1)), dim3(256), 0, c->stream, sp);
         HB_HIP(hipGetLastError());
-        if ((rc = nearest_seed_lap(c, &st.ms_finish))) return rc; // (drains the stream: the next piece may overwrite the rectangles)
+        if ((rc = lap(c, &st.ms_finish))) return rc; // (drains the stream: the next piece may overwrite the rectangles)
     }
     unsigned long long *h64 = c->h_counters; // (pinned words of the context; hb_run rewrites them before it reads them)
     HB_HIP(hipMemcpyAsync(h64, s.d_cnt.get(), 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));

@@ -8,25 +8,6 @@ namespace {
 
 constexpr uint64_t kSimilarMaxLiked = 256;
 
-template <class T>
-int similar_hold(hb_ctx *c, DevPtr<T> &h, uint64_t &have, uint64_t need)
-{
-    if (h && have >= need) return HB_OK;
-    auto &s = c->shs;
-    const uint64_t old_bytes = h ? std::max<uint64_t>(have * sizeof(T), 256) : 0;
-    h.reset();
-    s.bytes -= old_bytes;
-    c->stats.device_bytes -= old_bytes;
-    have = 0;
-    const uint64_t bytes = std::max<uint64_t>(need * sizeof(T), 256);
-    const hipError_t e = h.alloc((bytes + sizeof(T) - 1) / sizeof(T));
-    if (e != hipSuccess) return fail(c, HB_ERR_NOMEM, "hipMalloc(" + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
-    have = need;
-    s.bytes += bytes;
-    c->stats.device_bytes += bytes;
-    return HB_OK;
-}
-
 int similar_hosts(hb_ctx *c, const hb_similar_options *opt_in, hb_similar_stats *st_out)
 {
     const double t0 = now_ms();
@@ -41,26 +22,17 @@ int similar_hosts(hb_ctx *c, const hb_similar_options *opt_in, hb_similar_stats 
     if (o.node_count >= (1ull << 32)) return fail(c, HB_ERR_INVALID, who + ": too many liked hosts");
     const Plan &p = c->plan;
     const uint64_t n = p.n, N = o.node_count, W = hbk::kShList;
-    size_t nlev = 0;
-    for_each_virtual_level(p, true, [&](uint64_t, uint64_t) { nlev++; });
-    if (nlev + 2 > 64) return fail(c, HB_ERR_INVALID, who + ": unexpected plan layout (more than 62 virtual levels)");
-    std::vector<uint32_t> qsid(N), liked;
-    host_find_sids(c->g.ids.data(), n, o.nodes, N, qsid.data());
-    for (uint32_t sid : qsid)
-        if (sid != kNone) liked.push_back(sid);
-    std::sort(liked.begin(), liked.end());
-    liked.erase(std::unique(liked.begin(), liked.end()), liked.end());
+    size_t nlev;
+    int rc;
+    if ((rc = links_levels(c, who, &nlev))) return rc;
+    const ResolvedIds ids = resolve_ids(c, o.nodes, N);
+    const std::vector<uint32_t> &liked = ids.distinct, &anchor = ids.slot; // the distinct liked sids; the entries in caller order as slots
     const uint64_t D = liked.size();
     if (D > kSimilarMaxLiked) return fail(c, HB_ERR_INVALID, who + ": more than 256 distinct liked hosts");
     auto &s = c->shs;
     hb_similar_stats st{};
-    int rc;
     st.liked_distinct = D;
-    std::vector<uint32_t> anchor(N, kNone);
-    for (uint64_t i = 0; i < N; i++) {
-        if (qsid[i] == kNone) st.unknown++;
-        else anchor[i] = (uint32_t)(std::lower_bound(liked.begin(), liked.end(), qsid[i]) - liked.begin());
-    }
+    st.unknown = ids.unknown;
     if (D && (rc = links_top_rows(c, who, &st.ms_gpu_lists))) return rc; // (it may refuse: before the previous result is touched)
     s.valid = false;
     std::vector<uint32_t> cand_sid, cand_count, top_sid;
@@ -79,27 +51,21 @@ int similar_hosts(hb_ctx *c, const hb_similar_options *opt_in, hb_similar_stats 
         return HB_OK;
     };
     if (!D) return finish();
-    hb_links_options lo{};
-    lo.flags = o.flags & (HB_LINKS_SPREAD_ORDS | HB_LINKS_NO_SHORTCUT);
-    lo.limit = (uint32_t)W;
-    hb_links_stats ls{};
-    auto lists_gpu_ms = [&]() { return ls.ms_expand + ls.ms_select + ls.ms_emit; };
+    ListBuild lists(nlev, (uint32_t)W, o.flags);
     uint32_t *h32 = (uint32_t *)c->h_counters; // (pinned words of the context; hb_run rewrites them before it reads them)
-    std::vector<uint32_t> degree;
 
     // ---- steps 1 and 2: In512 of the liked hosts, the distinct sources of their 128-prefixes
     double t = now_ms();
-    if ((rc = similar_hold(c, s.d_in, s.cap_in, D * W))) return rc;
-    if ((rc = similar_hold(c, s.d_in_len, s.cap_in_len, D))) return rc;
-    if ((rc = similar_hold(c, s.d_in_mask, s.cap_in_mask, D))) return rc;
-    if ((rc = similar_hold(c, s.d_keys, s.cap_keys, D * W))) return rc;
-    if ((rc = similar_hold(c, s.d_src, s.cap_src, D * hbk::kShPrefix))) return rc;
-    if ((rc = similar_hold(c, s.d_count, s.cap_count, n))) return rc;
-    if ((rc = similar_hold(c, s.d_cnt, s.cap_cnt, 8))) return rc;
-    if ((rc = similar_hold(c, s.d_liked, s.cap_liked, D))) return rc;
-    if ((rc = similar_hold(c, s.d_anchor, s.cap_anchor, N))) return rc;
-    degree.assign(D, 0);
-    if ((rc = links_lists(c, who, false, liked.data(), nullptr, D, lo, s.d_in.get(), s.d_keys.get(), s.d_in_len.get(), degree, ls))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_in, D * W))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_in_len, D))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_in_mask, D))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_keys, D * W))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_src, D * hbk::kShPrefix))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_count, n))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_cnt, 8))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_liked, D))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_anchor, N))) return rc;
+    if ((rc = lists.run(c, who, false, liked.data(), nullptr, D, s.d_in.get(), s.d_keys.get(), s.d_in_len.get()))) return rc;
     uint32_t *cnt32 = (uint32_t *)s.d_cnt.get(); // [0] |B|, [1] distinct targets, [2] eligible targets, [3] candidates; words 2, 3 as u64: the pair counters
     HB_HIP(hipMemsetAsync(s.d_cnt.get(), 0, 8 * sizeof(unsigned long long), c->stream));
     HB_HIP(hipMemsetAsync(s.d_count.get(), 0, n * sizeof(uint32_t), c->stream));
@@ -114,26 +80,25 @@ int similar_hosts(hb_ctx *c, const hb_similar_options *opt_in, hb_similar_stats 
     st.count_bound = (nb + 3) / 4;
     st.ms_in = now_ms() - t;
     if (!nb) { // no liked host has an in-link: B and the result are empty
-        st.ms_gpu_lists += lists_gpu_ms();
+        st.ms_gpu_lists += lists.gpu_ms();
         return finish();
     }
 
     // ---- step 3: the forward lists of B
     t = now_ms();
-    if ((rc = similar_hold(c, s.d_fw, s.cap_fw, nb * W))) return rc;
-    if ((rc = similar_hold(c, s.d_fw_len, s.cap_fw_len, nb))) return rc;
-    if ((rc = similar_hold(c, s.d_keys, s.cap_keys, nb * W))) return rc;
-    degree.assign(nb, 0);
-    if ((rc = links_lists(c, who, true, nullptr, s.d_src.get(), nb, lo, s.d_fw.get(), s.d_keys.get(), s.d_fw_len.get(), degree, ls))) return rc;
-    for (uint32_t d : degree) st.forward_entries += std::min<uint64_t>(d, W);
+    if ((rc = hold(c, s.bytes, s.d_fw, nb * W))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_fw_len, nb))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_keys, nb * W))) return rc;
+    if ((rc = lists.run(c, who, true, nullptr, s.d_src.get(), nb, s.d_fw.get(), s.d_keys.get(), s.d_fw_len.get()))) return rc;
+    for (uint32_t d : lists.degree) st.forward_entries += std::min<uint64_t>(d, W);
     st.ms_forward = now_ms() - t;
 
     // ---- step 4: count, filter, order, take, drop the liked hosts
     t = now_ms();
     const uint64_t touched_cap = std::max<uint64_t>(std::min<uint64_t>(n, st.forward_entries), 1);
-    if ((rc = similar_hold(c, s.d_touched, s.cap_touched, touched_cap))) return rc;
-    if ((rc = similar_hold(c, s.d_cand, s.cap_cand, hbk::kShMaxCand))) return rc;
-    if ((rc = similar_hold(c, s.d_cand_count, s.cap_cand_count, hbk::kShMaxCand))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_touched, touched_cap))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_cand, hbk::kShMaxCand))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_cand_count, hbk::kShMaxCand))) return rc;
     HB_HIP(hipMemsetAsync(s.d_count.get(), 0, n * sizeof(uint32_t), c->stream));
     hipLaunchKernelGGL(hbk::sh_count_kernel, dim3(grid_blocks(c, (nb * W + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint32_t *)s.d_fw.get(),
                        (const uint32_t *)s.d_fw_len.get(), nb, n, s.d_count.get(), s.d_touched.get(), touched_cap, cnt32 + 1);
@@ -167,7 +132,7 @@ int similar_hosts(hb_ctx *c, const hb_similar_options *opt_in, hb_similar_stats 
     }
     st.ms_count = now_ms() - t;
     if (!C) {
-        st.ms_gpu_lists += lists_gpu_ms();
+        st.ms_gpu_lists += lists.gpu_ms();
         return finish();
     }
     cand_sid.resize(C);
@@ -178,13 +143,12 @@ int similar_hosts(hb_ctx *c, const hb_similar_options *opt_in, hb_similar_stats 
 
     // ---- step 5: the BitVecs - In512 of the candidates; every list sorted by sid, its bloom mask
     t = now_ms();
-    if ((rc = similar_hold(c, s.d_cin, s.cap_cin, hbk::kShMaxCand * W))) return rc;
-    if ((rc = similar_hold(c, s.d_cin_len, s.cap_cin_len, hbk::kShMaxCand))) return rc;
-    if ((rc = similar_hold(c, s.d_cin_mask, s.cap_cin_mask, hbk::kShMaxCand))) return rc;
-    if ((rc = similar_hold(c, s.d_keys, s.cap_keys, hbk::kShMaxCand * W))) return rc;
-    degree.assign(C, 0);
-    if ((rc = links_lists(c, who, false, nullptr, s.d_cand.get(), C, lo, s.d_cin.get(), s.d_keys.get(), s.d_cin_len.get(), degree, ls))) return rc;
-    st.ms_gpu_lists += lists_gpu_ms();
+    if ((rc = hold(c, s.bytes, s.d_cin, hbk::kShMaxCand * W))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_cin_len, hbk::kShMaxCand))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_cin_mask, hbk::kShMaxCand))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_keys, hbk::kShMaxCand * W))) return rc;
+    if ((rc = lists.run(c, who, false, nullptr, s.d_cand.get(), C, s.d_cin.get(), s.d_keys.get(), s.d_cin_len.get()))) return rc;
+    st.ms_gpu_lists += lists.gpu_ms();
     hipLaunchKernelGGL(hbk::sh_bitvec_kernel, dim3((unsigned)D), dim3(256), 0, c->stream, s.d_in.get(), (const uint32_t *)s.d_in_len.get(), (const uint32_t *)c->d_dev_of,
                        (const uint64_t *)c->d_idlow, n, s.d_in_mask.get());
     hipLaunchKernelGGL(hbk::sh_bitvec_kernel, dim3((unsigned)C), dim3(256), 0, c->stream, s.d_cin.get(), (const uint32_t *)s.d_cin_len.get(), (const uint32_t *)c->d_dev_of,
@@ -196,11 +160,11 @@ int similar_hosts(hb_ctx *c, const hb_similar_options *opt_in, hb_similar_stats 
     // ---- steps 6 and 7: the scores, the top k
     t = now_ms();
     const uint64_t k = std::min<uint64_t>(o.limit, C);
-    if ((rc = similar_hold(c, s.d_score, s.cap_score, hbk::kShMaxCand))) return rc;
-    if ((rc = similar_hold(c, s.d_top_score, s.cap_top_score, hbk::kShMaxCand))) return rc;
-    if ((rc = similar_hold(c, s.d_top_sid, s.cap_top_sid, hbk::kShMaxCand))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_score, hbk::kShMaxCand))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_top_score, hbk::kShMaxCand))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_top_sid, hbk::kShMaxCand))) return rc;
     HB_HIP(hipMemcpyAsync(s.d_anchor.get(), anchor.data(), N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    if ((rc = lap_start(c))) return rc;
     hipLaunchKernelGGL(hbk::sh_score_kernel, dim3((unsigned)C), dim3(256), 0, c->stream, (const uint32_t *)s.d_cin.get(), (const uint32_t *)s.d_cin_len.get(),
                        (const unsigned long long *)s.d_cin_mask.get(), (const uint32_t *)s.d_in.get(), (const uint32_t *)s.d_in_len.get(),
                        (const unsigned long long *)s.d_in_mask.get(), (const uint32_t *)s.d_anchor.get(), N, s.d_score.get(), s.d_cnt.get() + 2);
@@ -213,7 +177,7 @@ int similar_hosts(hb_ctx *c, const hb_similar_options *opt_in, hb_similar_stats 
     HB_HIP(hipMemcpyAsync(top_sid.data(), s.d_top_sid.get(), k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HB_HIP(hipMemcpyAsync(top_score.data(), s.d_top_score.get(), k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HB_HIP(hipMemcpyAsync(h64, s.d_cnt.get() + 2, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = nearest_seed_lap(c, &st.ms_gpu_score))) return rc;
+    if ((rc = lap(c, &st.ms_gpu_score))) return rc;
     st.pairs_gated = h64[0];
     st.pairs_intersected = h64[1];
     st.ms_score = now_ms() - t;

@@ -29,7 +29,7 @@ int similarity_alloc(hb_ctx *c, double *ms_out)
     if ((rc = dev_alloc(c, &s.d_anchor, p.n))) return rc;
     if ((rc = dev_alloc(c, &s.d_key, p.n))) return rc;
     if ((rc = dev_alloc(c, &s.d_keep, p.n))) return rc;
-    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    if ((rc = lap_start(c))) return rc;
     if ((rc = distance_indegrees(c))) return rc; // len = the in-degree through the chunk trees (bfs_indegree_kernel), shared with hb_distances
     hipLaunchKernelGGL(hbk::sim_pos_kernel, dim3(grid_blocks(c, (p.n_pad + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint64_t *)c->d_idlow,
                        (const uint32_t *)c->d_sid_of, p.n_pad, s.d_pos);
@@ -40,28 +40,14 @@ int similarity_alloc(hb_ctx *c, double *ms_out)
     for_each_virtual_level(p, true, bloom); // ascending: a chunk row ORs the partials of the chunk rows below it
     if (p.n_pad) bloom(0, p.n_pad);
     HB_HIP(hipGetLastError());
-    HB_HIP(hipEventRecord(c->ev[kEvCollective], c->stream));
-    HB_HIP(hipStreamSynchronize(c->stream));
-    float ms = 0.f;
-    HB_HIP(hipEventElapsedTime(&ms, c->ev[kEvMerge], c->ev[kEvCollective]));
-    *ms_out = ms;
+    *ms_out = 0.0; // (its GPU time alone: set, not added to)
+    if ((rc = lap(c, ms_out))) return rc;
     s.bytes = c->stats.device_bytes - before;
     s.ready = true;
     return HB_OK;
 }
 
 // ---- the limited mode (hb_similarity_options.limit > 0; kernels: hb_similarity_limit.hip.h) ------------------------------------------
-template <class T>
-int limit_hold(hb_ctx *c, DevPtr<T> &h, uint64_t count)
-{
-    const uint64_t bytes = std::max<uint64_t>(count * sizeof(T), 256);
-    const hipError_t e = h.alloc((bytes + sizeof(T) - 1) / sizeof(T));
-    if (e != hipSuccess) return fail(c, HB_ERR_NOMEM, "hipMalloc(" + std::to_string(bytes) + " bytes): " + hipGetErrorString(e));
-    c->lim.bytes += bytes;
-    c->stats.device_bytes += bytes;
-    return HB_OK;
-}
-
 // the cut lists describe one graph, one key set and one limit: hb_links_set_keys and a call with another limit end here (a load frees
 // the whole graph state)
 void similarity_limit_drop(hb_ctx *c)
@@ -72,8 +58,8 @@ void similarity_limit_drop(hb_ctx *c)
 
 // The listed rows and their cut lists under the current key set, once per (graph, key set, limit); *ms_out += its GPU time.  The list
 // builder's result buffers are this function's (the keys) and the state's (the lists): the user's hb_backlinks / hb_forwardlinks result
-// stays readable.  Needs the per-graph state of similarity_alloc (pos, the in-degrees) and links_top_rows.
-int similarity_limit_build(hb_ctx *c, uint32_t limit, double *ms_out)
+// stays readable.  Needs the per-graph state of similarity_alloc (pos, the in-degrees), links_top_rows and the nlev of links_levels.
+int similarity_limit_build(hb_ctx *c, uint32_t limit, size_t nlev, double *ms_out)
 {
     auto &s = c->lim;
     if (s.ready && s.limit == limit) return HB_OK;
@@ -82,9 +68,9 @@ int similarity_limit_build(hb_ctx *c, uint32_t limit, double *ms_out)
     const std::string who = "hb_inbound_similarity";
     const uint64_t n_pad = p.n_pad, rows_total = n_pad + p.nv;
     int rc;
-    if ((rc = limit_hold(c, s.d_idx, n_pad))) return rc;
-    if ((rc = limit_hold(c, s.d_seed_rows, hbk::kSimSlots))) return rc;
-    if ((rc = limit_hold(c, s.d_cnt, 4))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_idx, n_pad))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_seed_rows, hbk::kSimSlots))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_cnt, 4))) return rc;
     DevPtr<uint32_t> d_flag, d_sids, d_deg; // (work memory of the build: gone at its end)
     DevPtr<uint64_t> d_off;
     DevPtr<unsigned long long> d_keys;
@@ -92,7 +78,7 @@ int similarity_limit_build(hb_ctx *c, uint32_t limit, double *ms_out)
         return fail(c, HB_ERR_NOMEM, who + ": out of device memory for the listed rows");
     // ---- which rows are listed: a self link, or more in-neighbours than the limit
     HB_HIP(hipMemsetAsync(d_flag.get(), 0, std::max<uint64_t>(n_pad, 64) * sizeof(uint32_t), c->stream));
-    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    if ((rc = lap_start(c))) return rc;
     hipLaunchKernelGGL(hbk::siml_self_kernel, dim3(grid_blocks(c, (rows_total + 63) / 64, 8, 1)), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr,
                        (const uint32_t *)c->d_src, (const uint32_t *)c->lnk.d_top_row.get(), n_pad, rows_total, d_flag.get());
     hipLaunchKernelGGL(hbk::siml_mark_kernel, dim3(grid_blocks(c, (n_pad + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint32_t *)c->d_sid_of,
@@ -102,41 +88,36 @@ int similarity_limit_build(hb_ctx *c, uint32_t limit, double *ms_out)
     if (!e.empty()) return fail(c, HB_ERR_HIP, who + ": " + e);
     uint64_t listed = 0;
     HB_HIP(hipMemcpyAsync(&listed, d_off.get() + n_pad, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    if ((rc = nearest_seed_lap(c, ms_out))) return rc;
+    if ((rc = lap(c, ms_out))) return rc;
     if (listed > n_pad) return fail(c, HB_ERR_INVALID, who + ": more listed rows than node rows (internal error)");
-    if ((rc = limit_hold(c, s.d_list_row, listed))) return rc;
-    if ((rc = limit_hold(c, s.d_lists, listed * limit))) return rc;
-    if ((rc = limit_hold(c, s.d_len, listed))) return rc;
-    if ((rc = limit_hold(c, s.d_bloom, listed))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_list_row, listed))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_lists, listed * limit))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_len, listed))) return rc;
+    if ((rc = hold(c, s.bytes, s.d_bloom, listed))) return rc;
     const uint64_t piece_max = xbit(c, HB_X_SIM_SMALL_PIECES) ? 64 : kLinksMaxSlots;
     if (d_sids.alloc(std::max<uint64_t>(listed, 64)) != hipSuccess || d_deg.alloc(std::max<uint64_t>(listed, 64)) != hipSuccess ||
         d_keys.alloc(std::max<uint64_t>(std::min(listed, piece_max) * limit, 64)) != hipSuccess)
         return fail(c, HB_ERR_NOMEM, who + ": out of device memory for the list builder's keys");
-    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    if ((rc = lap_start(c))) return rc;
     hipLaunchKernelGGL(hbk::siml_assign_kernel, dim3(grid_blocks(c, (n_pad + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint32_t *)c->d_sid_of,
                        (const uint32_t *)d_flag.get(), (const uint64_t *)d_off.get(), n_pad, listed, s.d_idx.get(), s.d_list_row.get(), d_sids.get());
     HB_HIP(hipGetLastError());
-    if ((rc = nearest_seed_lap(c, ms_out))) return rc;
+    if ((rc = lap(c, ms_out))) return rc;
     // ---- their cut lists: the list builder of hb_backlinks, a piece of hosts at a time; then sid -> device row, len and bloom per list
-    hb_links_options lo{};
-    lo.limit = limit;
-    hb_links_stats ls{};
-    std::vector<uint32_t> degree;
+    ListBuild lists(nlev, limit);
     uint64_t entries = 0;
     for (uint64_t base = 0; base < listed; base += piece_max) {
         const uint64_t P = std::min(piece_max, listed - base);
-        degree.assign(P, 0);
-        if ((rc = links_lists(c, who, false, nullptr, d_sids.get() + base, P, lo, s.d_lists.get() + base * limit, d_keys.get(), d_deg.get() + base, degree, ls)))
-            return rc;
-        for (uint32_t d : degree) entries += std::min<uint64_t>(d, limit);
-        HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+        if ((rc = lists.run(c, who, false, nullptr, d_sids.get() + base, P, s.d_lists.get() + base * limit, d_keys.get(), d_deg.get() + base))) return rc;
+        for (uint32_t d : lists.degree) entries += std::min<uint64_t>(d, limit);
+        if ((rc = lap_start(c))) return rc;
         hipLaunchKernelGGL(hbk::siml_finish_kernel, dim3(grid_blocks(c, (P + 3) / 4, 8, 1)), dim3(256), 0, c->stream, s.d_lists.get() + base * limit,
                            (const uint32_t *)d_deg.get() + base, (const uint32_t *)c->d_dev_of, (const uint8_t *)c->sim.d_pos, P, limit, p.n, n_pad,
                            s.d_len.get() + base, s.d_bloom.get() + base);
         HB_HIP(hipGetLastError());
-        if ((rc = nearest_seed_lap(c, ms_out))) return rc;
+        if ((rc = lap(c, ms_out))) return rc;
     }
-    *ms_out += ls.ms_expand + ls.ms_select + ls.ms_emit;
+    *ms_out += lists.gpu_ms();
     s.listed = listed;
     s.entries = entries;
     s.limit = limit;
@@ -175,10 +156,9 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
     auto &s = c->sim;
     hb_similarity_stats st{};
     const bool limited = o.limit != 0 && p.n != 0;
+    size_t nlev = 0;
     if (limited) { // what the list builder may refuse: before the previous result is touched
-        size_t nlev = 0;
-        for_each_virtual_level(p, true, [&](uint64_t, uint64_t) { nlev++; });
-        if (nlev + 2 > 64) return fail(c, HB_ERR_INVALID, "hb_inbound_similarity: unexpected plan layout (more than 62 virtual levels)");
+        if ((rc = links_levels(c, "hb_inbound_similarity", &nlev))) return rc;
         if ((rc = links_top_rows(c, "hb_inbound_similarity", &st.ms_lists))) return rc;
     }
     s.valid = false;
@@ -207,7 +187,7 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
     if ((rc = similarity_alloc(c, &st.ms_bloom))) return rc;
     auto &lm = c->lim;
     if (limited) {
-        if ((rc = similarity_limit_build(c, o.limit, &st.ms_lists))) return rc;
+        if ((rc = similarity_limit_build(c, o.limit, nlev, &st.ms_lists))) return rc;
         st.listed_rows = lm.listed;
         st.list_entries = lm.entries;
     }
@@ -216,14 +196,13 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
     HB_HIP(hipMemsetAsync(s.d_anchor, 0, p.n, c->stream));
     claim_rows(c, RowsOf::Similarity);
     unsigned long long *h = c->h_counters; // (pinned words of the context; hb_run rewrites them before it reads them)
-    float ms = 0.f;
     for (uint64_t b0 = 0; b0 < E; b0 += hbk::kSimSlots) {
         const uint32_t count = (uint32_t)std::min<uint64_t>(hbk::kSimSlots, E - b0);
         st.batches++;
         s.last_slots = count;
         const bool any_known = std::any_of(sids.begin() + b0, sids.begin() + b0 + count, [](uint32_t v) { return v != kNone; });
         // ---- seed: the indicators (all-zero outside the marked rows), the level-0 bitmap, the anchors' rows
-        HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+        if ((rc = lap_start(c))) return rc;
         HB_HIP(hipMemsetAsync(c->d_bits[1], 0, c->bits_words * 4, c->stream)); // (a batch that runs no level has no count rows)
         uint64_t marked = 0, active = 0;
         if (any_known) {
@@ -254,10 +233,7 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
             HB_HIP(hipGetLastError());
             HB_HIP(hipMemcpyAsync(h, s.d_cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         }
-        HB_HIP(hipEventRecord(c->ev[kEvCollective], c->stream));
-        HB_HIP(hipStreamSynchronize(c->stream));
-        HB_HIP(hipEventElapsedTime(&ms, c->ev[kEvMerge], c->ev[kEvCollective]));
-        st.ms_score += ms;
+        if ((rc = lap(c, &st.ms_score))) return rc;
         if (any_known) {
             marked = h[0];
             active = h[1];
@@ -296,12 +272,12 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
                 lp.n_pad = n_pad;
                 lp.limit = lm.limit;
                 HB_HIP(hipMemsetAsync(lm.d_cnt.get(), 0, 4 * sizeof(unsigned long long), c->stream));
-                HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+                if ((rc = lap_start(c))) return rc;
                 hipLaunchKernelGGL(hbk::sim_list_count_kernel, dim3(grid_blocks(c, (lm.listed + 3) / 4, 8, 1)), dim3(256), 0, c->stream, lp);
                 HB_HIP(hipGetLastError());
                 HB_HIP(hipMemcpyAsync(h, lm.d_cnt.get(), 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
                 double lms = 0.0;
-                if ((rc = nearest_seed_lap(c, &lms))) return rc;
+                if ((rc = lap(c, &lms))) return rc;
                 st.ms_list_count += lms;
                 st.ms_count += lms;
                 st.rows_nonzero += h[0];
@@ -327,23 +303,17 @@ int inbound_similarity(hb_ctx *c, const hb_similarity_options *opt_in, hb_simila
             ap.acc = s.d_acc;
             ap.self_score = s.self_score;
             ap.n_pad = n_pad;
-            HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+            if ((rc = lap_start(c))) return rc;
             hipLaunchKernelGGL(hbk::sim_accumulate_kernel, dim3(grid_blocks(c, (n_pad + 255) / 256, 8, 1)), dim3(256), 0, c->stream, ap);
             HB_HIP(hipGetLastError());
-            HB_HIP(hipEventRecord(c->ev[kEvCollective], c->stream));
-            HB_HIP(hipStreamSynchronize(c->stream));
-            HB_HIP(hipEventElapsedTime(&ms, c->ev[kEvMerge], c->ev[kEvCollective]));
-            st.ms_score += ms;
+            if ((rc = lap(c, &st.ms_score))) return rc;
         }
     }
-    HB_HIP(hipEventRecord(c->ev[kEvMerge], c->stream));
+    if ((rc = lap_start(c))) return rc;
     hipLaunchKernelGGL(hbk::sim_score_kernel, dim3(grid_blocks(c, (p.n + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const double *)s.d_acc, (const uint32_t *)c->d_dev_of,
                        p.n, (double)D, s.normalized ? (double)std::max<uint64_t>(L, 1) : 0.0, s.d_score);
     HB_HIP(hipGetLastError());
-    HB_HIP(hipEventRecord(c->ev[kEvCollective], c->stream));
-    HB_HIP(hipStreamSynchronize(c->stream));
-    HB_HIP(hipEventElapsedTime(&ms, c->ev[kEvMerge], c->ev[kEvCollective]));
-    st.ms_score += ms;
+    if ((rc = lap(c, &st.ms_score))) return rc;
     s.valid = true;
     return finish();
 }

@@ -43,6 +43,14 @@ private:
     T *p = nullptr;
 };
 
+// ... of a buffer that only grows: a DevPtr and the entries it was last asked for (`have` means nothing while the holder is empty).
+// hold() in hb_api.hip is what allocates it and books its bytes.  Move-only like its base; assigning a fresh one over it frees the buffer
+// and forgets the size, which is how a load drops every holder of the graph state.
+template <class T>
+struct GrowPtr : DevPtr<T> {
+    uint64_t have = 0;
+};
+
 // ... of hipHostMalloc'ed (pinned) words
 template <class T>
 struct PinnedPtr {
