@@ -1478,9 +1478,20 @@ def host_plan(row_ptr, src, flags=0, chunk=0, tune=()):
     world = int(tn[7]) if tn[7] > 1 else 1
     if world == 1:
         order = order[:n]  # no padding rows inside: a permutation of the sids
+    live = host_plan_live(row_ptr, src, flags, chunk, tune)
+    return dict(order=order, row_ptr=prp, src=psrc, level_begin=lb, n_pad=n_pad, nv=nv, slice=n_pad // world,
+                live_first=live[0], n_live=live[1], n_live_pad=live[2])
+
+
+def host_plan_live(row_ptr, src, flags=0, chunk=0, tune=()):
+    """Host-only: (live-first order in use, n_live, n_live_pad) of the host planner's layout, as Context.plan_live() gives them."""
+    lib = load()
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.uint64)
+    src = np.ascontiguousarray(src, dtype=np.uint32)
+    tn = np.zeros(8, dtype=np.uint32)
+    tn[:len(tune)] = tune
     live = np.zeros(3, dtype=np.uint64)
-    rc = lib.hb_host_plan_live(n, _ptr(row_ptr), _ptr(src), flags, chunk, _ptr(tn), _ptr(live))
+    rc = lib.hb_host_plan_live(len(row_ptr) - 1, _ptr(row_ptr), _ptr(src), flags, chunk, _ptr(tn), _ptr(live))
     if rc != HB_OK:
         raise HyperballError(rc, (lib.hb_last_error(None) or b"").decode())
-    return dict(order=order, row_ptr=prp, src=psrc, level_begin=lb, n_pad=n_pad, nv=nv, slice=n_pad // world,
-                live_first=bool(live[0]), n_live=int(live[1]), n_live_pad=int(live[2]))
+    return bool(live[0]), int(live[1]), int(live[2])

@@ -111,6 +111,27 @@ def random_graph(rng, kind=None):
     return kind, sorted(edges)
 
 
+def dead_fringe_graph(rng):
+    """("dead_fringe", tuples): a strongly connected live part - hosts 1 .. n_live on a ring, a random chord each - and n_dead hosts behind
+    them that only link into it, so none of them has an in-link.  n_live lies on either side of a multiple of 64 and n_dead around 64
+    (the row tiles of the live-first device order); host 1 is fed by every third live host and every second dead
+    one, so its list is long enough for a chunk tree and ends in dead sources under that order."""
+    n_live = 64 * int(rng.integers(1, 9)) + int(rng.integers(-1, 2))
+    n_dead = int(rng.choice([1, 63, 64, 65, 200]))
+    e = set()
+    for v in range(1, n_live + 1):
+        e.add((v, v % n_live + 1))
+        e.add((v, int(rng.integers(1, n_live + 1))))
+        if v % 3 == 0:
+            e.add((v, 1))
+    for d in range(n_live + 1, n_live + n_dead + 1):
+        for t in rng.integers(1, n_live + 1, int(rng.integers(1, 4))).tolist():
+            e.add((d, int(t)))
+        if d % 2 == 0:
+            e.add((d, 1))
+    return "dead_fringe", sorted((a, b) for a, b in e if a != b)
+
+
 def tailed_graph(core=300, core_edges=1500, chain=120, seed=7, branch=3):
     """A graph that reaches the reference's sqrt(n) tail (harmonic.rs:244-252): an LCG core whose node 1 feeds a
     chain of `chain` hosts with a few side branches.  Ids are salted so that bloom slots are not trivially distinct.

@@ -67,9 +67,10 @@ class Tally:
 
 # ---- the layout recipe ----------------------------------------------------------------------------------------------------------------
 def draw_graph(rng, kind=None):
-    """graphs.random_graph (drawn again while it has no edge) with a self link on an eighth of its nodes"""
+    """graphs.random_graph (drawn again while it has no edge; kind "dead_fringe": graphs.dead_fringe_graph) with a self link on an eighth
+    of its nodes"""
     while True:
-        got, tuples = graphs.random_graph(rng, kind)
+        got, tuples = graphs.dead_fringe_graph(rng) if kind == "dead_fringe" else graphs.random_graph(rng, kind)
         if tuples:
             break
     nodes = sorted({x for e in tuples for x in e[:2]})
@@ -120,9 +121,10 @@ def tree(plan, row):
 
 
 CONDITIONS = ("a", "b", "c", "d", "e", "f")
+LIVE_CONDITIONS = ("g", "h")  # what only a live-first plan shows
 
 
-def layout_conditions(plan, row_ptr, chunk):
+def layout_conditions(plan, row_ptr, chunk, n_live=None):
     """{condition: (hub sid, [member sids])} for the conditions the plan shows, read from the first node row that shows each:
       a  a hub with a non-final lowest-level chunk shorter than `chunk` (a band cut): the first and last entry of that chunk and the
          first entry of the chunk behind it
@@ -130,7 +132,11 @@ def layout_conditions(plan, row_ptr, chunk):
       c  a one-chunk tree, a node row whose list is a single chunk row: the first and the last entry of the chunk
       d  a split row whose in-degree is <= chunk: the first and the last entry of its list
       e  a tree of depth >= 3 (three levels of chunk rows under the node row): the first, a middle and the last entry of its list
-      f  no chunk row at all: (None, [])"""
+      f  no chunk row at all: (None, [])
+    and, where `n_live` says that the plan is a live-first one (device rows from n_live on are the hosts without an in-link, "dead"):
+      g  a lowest-level chunk row whose sources are all dead: its first and its last entry
+      h  a lowest-level chunk row that mixes live and dead sources: its last live and its first dead entry
+    so that the hub, a live member and a dead member of such trees are among the picks."""
     if plan["nv"] == 0:
         return {"f": (None, [])}
     order = plan["order"].astype(np.int64)
@@ -165,6 +171,14 @@ def layout_conditions(plan, row_ptr, chunk):
             note("d", sid, [flat[0], flat[-1]])
         if depth >= 3:
             note("e", sid, [flat[0], flat[len(flat) // 2], flat[-1]])
+        if n_live is not None:
+            for _, ch in chunks:
+                dead = [r for r in ch if r >= n_live]
+                if dead and len(dead) == len(ch):
+                    note("g", sid, [ch[0], ch[-1]])
+                elif dead:
+                    assert ch == sorted(ch) and dead == ch[-len(dead):]  # ascending device rows: the dead sources are the list's tail
+                    note("h", sid, [ch[-len(dead) - 1], dead[0]])
     return found
 
 

@@ -258,14 +258,37 @@ VARIANTS["sparse_always_chunk128"] = dict(chunk=128, tune=(0, 0, 101, 0, 0, 0, 1
 VARIANTS["sparse_always_direct32"] = dict(chunk=32, tune=(0, 0, 101, 5, 8, 8, 1))    # node rows with more than 16 direct sources: several batches
 
 
-@pytest.mark.parametrize("variant", sorted(VARIANTS))
-def test_per_pass_state_matches_oracle(gpu_ctx_factory, variant):
+# The device order.  "plain": the context as the variant writes it - these graphs are far below the size from
+# which the live-first order is taken unasked, so it is the plain out-degree order.  "live": the same context with HB_FLAG_LIVE_FIRST,
+# the order every graph of 2^20 hosts and more gets; a variant the order does not apply to must plan as before and still match.
+ORDERS = {"plain": 0, "live": _lib.HB_FLAG_LIVE_FIRST}
+IGNORES_LIVE_FIRST = _lib.HB_FLAG_NO_REORDER | _lib.HB_FLAG_UNFUSED | _lib.HB_FLAG_PASS_STATS
+
+
+def _under_order(kw, order):
+    """(the context arguments of `kw` under `order`, whether its plan must be a live-first one)"""
+    kw = dict(kw, flags=kw.get("flags", 0) | ORDERS[order])
+    return kw, order == "live" and not kw["flags"] & IGNORES_LIVE_FIRST
+
+
+def _assert_order(ctx, g, on):
+    """the plan in HBM is (not) a live-first one, and the graph has hosts of both kinds, so the two orders differ"""
+    live_first, n_live, n_live_pad = ctx.plan_live()
+    assert live_first is on and 0 < n_live < g.n and n_live == int((np.diff(g.row_ptr.astype(np.int64)) > 0).sum())
+    assert n_live_pad == ((n_live if on else g.n) + 63) // 64 * 64  # (off: n_pad, all the node rows of one rank)
+
+
+# (the plain cases keep the ids they had before the order became a parameter)
+@pytest.mark.parametrize("variant,order", [(v, o) for o in ORDERS for v in sorted(VARIANTS)],
+                         ids=[v if o == "plain" else v + "-order_" + o for o in ORDERS for v in sorted(VARIANTS)])
+def test_per_pass_state_matches_oracle(gpu_ctx_factory, variant, order):
     # long_tail_*: R-MAT core + levelled-DAG tail (tens of passes: dense -> push masks -> worklists)
     g = synth.RmatGraph(13, 60_000, tail=(300, 800, 10)) if variant.startswith("long_tail") else synth.RmatGraph(13, 60_000)
     o = hbo.Dense(g.id_low64(), g.row_ptr, g.src)
-    kw = VARIANTS[variant]
+    kw, live = _under_order(VARIANTS[variant], order)
     with gpu_ctx_factory(**kw) as ctx:
         ctx.load_dense(g.ids, g.row_ptr, g.src)
+        _assert_order(ctx, g, live)
         ctx.begin()
         if not variant.endswith("_lean"):
             assert np.array_equal(ctx.registers(), o.registers())
@@ -326,26 +349,31 @@ def test_run_pipelines_the_convergence_tail_and_books_it_like_single_steps(gpu_c
     vals, keep, k = o.finish()
     keys = ("pass", "changed", "active_edges", "touched", "mode")
     seen = {}
-    for name, kw in (("pipelined", dict()), ("stepwise", dict(tune=(0, _lib.HB_X_NO_TAIL_PIPELINE))), ("pipelined_chunk8", dict(chunk=8)),
-                     ("pipelined_staged_every_pass", dict(tune=(0, _lib.HB_X_SNAPSHOT_EVERY_PASS)))):
-        with gpu_ctx_factory(**kw) as ctx:
+    for order in ORDERS:  # ... and all of it under the live-first order: the queued pass is a shortened launch there
+        for name, kw in (("pipelined", dict()), ("stepwise", dict(tune=(0, _lib.HB_X_NO_TAIL_PIPELINE))), ("pipelined_chunk8", dict(chunk=8)),
+                         ("pipelined_staged_every_pass", dict(tune=(0, _lib.HB_X_SNAPSHOT_EVERY_PASS)))):
+            kw, live = _under_order(kw, order)
+            with gpu_ctx_factory(**kw) as ctx:
+                ctx.load_dense(g.ids, g.row_ptr, g.src)
+                _assert_order(ctx, g, live)
+                for again in range(2):  # (a second run on the same context: the pipeline's buffers and events are reused)
+                    st = ctx.run()
+                    _check_final(ctx, g.ids, T, vals, keep, st)
+                    assert ctx.state_hash() == o.state_hash(), (name, order)   # registers + Kahan words as the LAST REAL pass left them
+                    assert (st["pipelined_passes"] > 10) == (name != "stepwise"), (name, order, st["pipelined_passes"])
+                    seen[name, order] = [tuple(ps[f] for f in keys) for ps in ctx.pass_stats()]
+                    assert len(seen[name, order]) == T and all(ps["ms_gpu"] > 0 for ps in ctx.pass_stats()), (name, order)
+        assert seen["pipelined", order] == seen["stepwise", order] == seen["pipelined_staged_every_pass", order]
+        # ... and the same bookkeeping as stepping through the C ABI one pass at a time
+        with gpu_ctx_factory(flags=ORDERS[order]) as ctx:
             ctx.load_dense(g.ids, g.row_ptr, g.src)
-            for again in range(2):  # (a second run on the same context: the pipeline's buffers and events are reused)
-                st = ctx.run()
-                _check_final(ctx, g.ids, T, vals, keep, st)
-                assert ctx.state_hash() == o.state_hash(), name            # registers + Kahan words as the LAST REAL pass left them
-                assert (st["pipelined_passes"] > 10) == (name != "stepwise"), (name, st["pipelined_passes"])
-                seen[name] = [tuple(ps[f] for f in keys) for ps in ctx.pass_stats()]
-                assert len(seen[name]) == T and all(ps["ms_gpu"] > 0 for ps in ctx.pass_stats()), name
-    assert seen["pipelined"] == seen["stepwise"] == seen["pipelined_staged_every_pass"]
-    # ... and the same bookkeeping as stepping through the C ABI one pass at a time
-    with gpu_ctx_factory() as ctx:
-        ctx.load_dense(g.ids, g.row_ptr, g.src)
-        ctx.begin()
-        while ctx.step():
-            pass
-        ctx.finish()
-        assert [tuple(ps[f] for f in keys) for ps in ctx.pass_stats()] == seen["pipelined"]
+            ctx.begin()
+            while ctx.step():
+                pass
+            ctx.finish()
+            assert [tuple(ps[f] for f in keys) for ps in ctx.pass_stats()] == seen["pipelined", order]
+    # the two orders book the same passes (`touched` of a split row depends on how its list is cut: tests/test_live_first.py)
+    assert [r[:3] + r[4:] for r in seen["pipelined", "plain"]] == [r[:3] + r[4:] for r in seen["pipelined", "live"]]
 
 
 def test_tail_kernel_runs_whole_passes_from_work_lists(gpu_ctx_factory):
@@ -888,14 +916,18 @@ def test_device_plan_equals_host_plan(gpu_ctx_factory):
     cases = [(g.ids, g.row_ptr, g.src) for g in graphs_] + [star]
     empty = (np.zeros(0, _lib.U128), np.zeros(1, np.uint64), np.zeros(0, np.uint32))
     for gi, (ids, row_ptr, src) in enumerate(cases + [empty]):
-        for kw in knobs:
+        for kw, order in [(kw, order) for order in ORDERS for kw in knobs]:
+            kw, live = _under_order(kw, order)
             with gpu_ctx_factory(**kw) as ctx:
                 ctx.load_dense(ids, row_ptr, src)
                 dev = ctx.plan()
+                dev_live = ctx.plan_live()
                 st = ctx.stats()
             host = _lib.host_plan(row_ptr, src, flags=kw.get("flags", 0), chunk=kw.get("chunk", 0), tune=kw.get("tune", ()))
             what = (gi, kw)
             n = len(ids)
+            assert host["live_first"] is live and dev_live == (live, host["n_live"], host["n_live_pad"]), what
+            assert st["rows_with_in_edges"] == host["n_live"] and (n == 0 or 0 < host["n_live"] < n), what  # hosts of both kinds in every graph
             assert dev["n_pad"] == host["n_pad"] and dev["nv"] == host["nv"], what
             assert np.array_equal(dev["level_begin"], host["level_begin"]), what
             assert np.array_equal(dev["order"][:n], host["order"][:n]), what
@@ -922,6 +954,41 @@ def test_device_plan_equals_host_plan(gpu_ctx_factory):
                 assert np.array_equal(dev["level_begin"], host["level_begin"]), what
                 assert np.array_equal(dev["order"], host["order"]), what
                 assert np.array_equal(dev["row_ptr"], host["row_ptr"]) and np.array_equal(dev["src"], host["src"]), what
+
+
+@pytest.mark.parametrize("order", list(ORDERS))
+def test_record_stream_whose_dead_hosts_occur_only_as_from(gpu_ctx_factory, order):
+    """The record boundary in front of a live-first plan: hb_append_edges in batches -> device ingest -> device planner.  200 hosts on a
+    ring with chords, 90 hosts that only ever stand on the `from` side (so the ingest meets them as sources alone and the planner finds
+    them without an in-edge), a hub fed by both kinds (a chunk tree at chunk = 8), duplicates and a record under a skipped flag; the
+    graph and the plan against the host ingest and planner entry for entry, the run against the faithful oracle."""
+    ring, dead = list(range(1, 201)), list(range(1001, 1091))
+    tuples = [(v, v % 200 + 1, 0) for v in ring] + [(v, (v * 7 + 3) % 200 + 1, 0) for v in ring if (v * 7 + 3) % 200 + 1 != v]
+    tuples += [(d, (5 * i + 2) % 200 + 1, 0) for i, d in enumerate(dead)] + [(d, 1, 0) for d in dead[:40]] + [(v, 1, 0) for v in ring[20:50]]
+    tuples += [(dead[0], 7, graphs.NOFOLLOW)] + tuples[::9]
+    recs = EdgeListGraph.from_tuples(tuples).host_edges()
+    recs = recs[np.random.default_rng(5).permutation(len(recs))]
+    fids, fvals, fst = hbo.faithful_run(recs)
+    hi, hrp, hsrc, hmu = _lib.host_ingest(recs)
+    kw, live = _under_order(dict(chunk=8), order)
+    host = _lib.host_plan(hrp, hsrc, flags=kw["flags"], chunk=8)
+    assert host["live_first"] is live and host["n_live"] == 200 and len(hi) == 290
+    with gpu_ctx_factory(**kw) as ctx:
+        for part in np.array_split(recs, 4):
+            ctx.append_edges(part)
+        ctx.finalize()
+        gi, grp, gsrc = ctx.graph()
+        assert np.array_equal(gi, hi) and np.array_equal(grp, hrp) and np.array_equal(gsrc, hsrc)
+        dev = ctx.plan()
+        assert ctx.plan_live() == (live, 200, 256 if live else dev["n_pad"])
+        assert dev["n_pad"] == host["n_pad"] and dev["nv"] == host["nv"] > 0 and np.array_equal(dev["level_begin"], host["level_begin"])
+        assert np.array_equal(dev["order"][:290], host["order"]) and np.array_equal(dev["row_ptr"], host["row_ptr"]) and np.array_equal(dev["src"], host["src"])
+        if live:
+            assert np.all(gi["lo"][dev["order"][200:290].astype(np.int64)] > 1000)  # the `from`-only hosts behind everybody else
+        st = ctx.run()
+        ids, vals = ctx.results()
+    assert (st["n"], st["m_unique"], st["m_eff"], st["passes"]) == (fst["n"], fst["m_unique"], fst["m_eff"], fst["passes"])
+    assert np.array_equal(ids, fids) and np.array_equal(vals.view(np.uint64), fvals.view(np.uint64))
 
 
 def test_c2_device_ingest_and_plan_equal_host(gpu_ctx_factory):
@@ -1127,6 +1194,8 @@ def test_c2_config_bit_exact_and_properties(gpu_ctx_factory):
     for kw in (dict(), dict(flags=_lib.HB_FLAG_NO_REORDER | _lib.HB_FLAG_NO_FRONTIER, chunk=256)):
         with gpu_ctx_factory(**kw) as ctx:
             ctx.load_dense(g.ids, g.row_ptr, g.src)
+            # at this size the live-first order is taken unasked; not where the nodes keep their id order
+            _assert_order(ctx, g, not kw)
             st = ctx.run()
             _check_final(ctx, g.ids, T, vals, keep, st)
             # [r5] at this size (n >= 2^20) the results travel while the passes run under the DEFAULT policy (first snapshot when the

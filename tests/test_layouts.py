@@ -9,7 +9,13 @@ read from the plan: for every layout condition the context shows, the node row o
 The conditions are asserted, not assumed (test_layout_conditions), and so is the share of calls that really compare (test_cap).  Both
 count over the whole list from the host planner and the restatements alone; test_operators_under_layout asserts that the plan in HBM
 is that plan and that its calls were the counted ones.  One crafted case, a small flipped fan under two banded layouts, has closed
-answers.  HB_LAYOUT_CASES = N runs the first N cases only (tests/test_layouts_simt.py)."""
+answers.  HB_LAYOUT_CASES = N runs the first N cases only (tests/test_layouts_simt.py).
+
+A second list (LIVE_CASES, its own seed) draws from the same recipe with HB_FLAG_LIVE_FIRST on every context and graph kinds that have
+hosts without an in-link: the live-first device order of DESIGN.md section 32, in which every graph of 2^20 hosts and more is planned.
+Two more conditions are read from such a plan - a lowest-level chunk row whose sources are all dead, and one that mixes live and dead
+sources - and the hub, a live member and a dead member of such a tree go to the bodies: a dead host is a forward-link query, a walk
+source and a scored host there.  HB_LIVE_LAYOUT_CASES = N runs the first N of them only."""
 import os
 
 import numpy as np
@@ -26,26 +32,29 @@ SEED = 977
 RANDOM_CASES = 40
 STARS_EVERY = 5  # after every five random cases one `stars` graph at chunk = 4 (cases 2, 8, 14, ...): the trees of depth >= 3, scarce in the random draws
 KINDS = ("uniform", "stars", "chains", "dense_core", "bipartite")
+LIVE_SEED = 4
+LIVE_COUNT = 16
+LIVE_KINDS = ("stars", "bipartite", "uniform", "dead_fringe")  # the kinds with hosts that have no in-link
 
 
 class Case:
-    def __init__(self, index, kind, tuples, chunk, tune, flags):
-        self.index, self.kind, self.tuples, self.chunk, self.tune, self.flags = index, kind, tuples, chunk, tune, flags
-        self.name = "%02d-%s-chunk%d-tune%d.%d.%d-flags%x-seed%d" % (index, kind, chunk, tune[3], tune[4], tune[5], flags, SEED)
+    def __init__(self, index, kind, tuples, chunk, tune, flags, seed=SEED):
+        self.index, self.kind, self.tuples, self.chunk, self.tune, self.flags, self.seed = index, kind, tuples, chunk, tune, flags, seed
+        self.name = "%02d-%s-chunk%d-tune%d.%d.%d-flags%x-seed%d" % (index, kind, chunk, tune[3], tune[4], tune[5], flags, seed)
         self._dry = None
 
     def what(self):
-        return dict(case=self.index, kind=self.kind, chunk=self.chunk, tune=self.tune, flags=self.flags, seed=SEED)
+        return dict(case=self.index, kind=self.kind, chunk=self.chunk, tune=self.tune, flags=self.flags, seed=self.seed)
 
     def dry(self):
         """(graph, host plan, conditions, picks, tally): what the case is before any context exists"""
         if self._dry is None:
             graph = graphs.dense_from_tuples(self.tuples)
-            plan = _lib.host_plan(graph[1], graph[2], self.flags & oc.PLAN_FLAGS, self.chunk, self.tune)
-            cond = oc.layout_conditions(plan, graph[1], self.chunk)
+            plan = _lib.host_plan(graph[1], graph[2], self.flags & (oc.PLAN_FLAGS | _lib.HB_FLAG_LIVE_FIRST), self.chunk, self.tune)
+            cond = oc.layout_conditions(plan, graph[1], self.chunk, plan["n_live"] if plan["live_first"] else None)
             picks = oc.picks_of(cond)
             tally = oc.Tally()
-            oc.run_bodies(None, graph, SEED, self.index, self.what(), picks, tally)
+            oc.run_bodies(None, graph, self.seed, self.index, self.what(), picks, tally)
             self._dry = (graph, plan, cond, picks, tally)
         return self._dry
 
@@ -61,9 +70,22 @@ def _cases():
     return out
 
 
+def _live_cases():
+    """the recipe of _cases() with HB_FLAG_LIVE_FIRST on every context, the kinds of LIVE_KINDS in turn; contexts 0, 5, 10 and 15 - one of every kind -
+    at chunk = 4"""
+    rng = np.random.default_rng(LIVE_SEED)
+    out = []
+    while len(out) < LIVE_COUNT:
+        kind, tuples = oc.draw_graph(rng, LIVE_KINDS[len(out) % len(LIVE_KINDS)])
+        chunk, tune, flags = oc.draw_layout(rng, 4 if len(out) % 4 == len(out) // 4 else None)
+        out.append(Case(len(out), kind, tuples, chunk, tune, flags | _lib.HB_FLAG_LIVE_FIRST, LIVE_SEED))
+    return out
+
+
 CASES = _cases()
-RUN = CASES[:int(os.environ.get("HB_LAYOUT_CASES", len(CASES)))]
-LIVE = {}  # case index -> the tally of its run on the context
+LIVE_CASES = _live_cases()
+RUN = CASES[:int(os.environ.get("HB_LAYOUT_CASES", len(CASES)))] + LIVE_CASES[:int(os.environ.get("HB_LIVE_LAYOUT_CASES", len(LIVE_CASES)))]
+LIVE = {}  # (seed, case index) -> the tally of its run on the context
 
 
 @pytest.mark.parametrize("case", RUN, ids=[c.name for c in RUN])
@@ -73,15 +95,21 @@ def test_operators_under_layout(gpu_ctx_factory, case):
         got = ctx.graph()
         assert all(np.array_equal(a, b) for a, b in zip(got, graph)), case.name
         assert oc.plan_equal(ctx.plan(), plan, len(graph[0])), case.name  # the conditions below are those of the plan in HBM
+        assert ctx.plan_live() == (plan["live_first"], plan["n_live"], plan["n_live_pad"]), case.name
         tally = oc.Tally()
-        oc.run_bodies(ctx, got, SEED, case.index, case.what(), picks, tally)
-    LIVE[case.index] = tally
+        oc.run_bodies(ctx, got, case.seed, case.index, case.what(), picks, tally)
+    LIVE[case.seed, case.index] = tally
 
 
 def test_layout_conditions():
     """Every condition of operator_cases.layout_conditions in at least three contexts of the list, and (a) to (e) in at least one whose
     bodies are handed the hub of such a tree and sources inside it.  Counts of the committed seed, out of 48 contexts: (a) 10, (b) 26,
-    (c) 17, (d) 20, (e) 7, (f) 16; every context with one of (a) to (e) hands such picks to its bodies (picks_of)."""
+    (c) 17, (d) 20, (e) 7, (f) 16; every context with one of (a) to (e) hands such picks to its bodies (picks_of).
+
+    The live-first list: the order is in use in every context that does not keep the id order, every graph has hosts with and without an
+    in-link, and (g) and (h) each show in at least three contexts whose bodies are handed the hub, and for (g) two dead members, for (h) a
+    live and a dead member of such a chunk.  Counts of its seed, out of 16 contexts: (a) 7, (b) 11, (c) 7, (d) 8, (e) 3, (f) 3, (g) 10,
+    (h) 8, all of (g) and (h) with their picks inside; 11 contexts hand a dead host to their bodies."""
     count = dict.fromkeys(oc.CONDITIONS, 0)
     targeted = dict.fromkeys(oc.CONDITIONS, 0)
     for case in CASES:
@@ -93,6 +121,23 @@ def test_layout_conditions():
     print("layout conditions over %d contexts: %s; with picks inside: %s" % (len(CASES), count, targeted))
     assert all(count[c] >= 3 for c in oc.CONDITIONS), count
     assert all(targeted[c] >= 1 for c in "abcde"), targeted
+    count = dict.fromkeys(oc.CONDITIONS + oc.LIVE_CONDITIONS, 0)
+    targeted = dict.fromkeys(oc.LIVE_CONDITIONS, 0)
+    dead_picks = 0
+    for case in LIVE_CASES:
+        graph, plan, cond, picks, _ = case.dry()
+        # the order is in use wherever the context does not keep the id order, and every such graph has hosts of both kinds
+        assert plan["live_first"] == (not case.flags & _lib.HB_FLAG_NO_REORDER) and 0 < plan["n_live"] < len(graph[0]), case.name
+        indeg = np.diff(graph[1].astype(np.int64))
+        for c, (hub, members) in cond.items():
+            count[c] += 1
+            if c in targeted and hub in picks.hubs and set(members) <= set(picks.members):
+                assert indeg[hub] > 0 and indeg[members[-1]] == 0 and (c == "g") == (indeg[members[0]] == 0), (case.name, c)
+                targeted[c] += 1
+        dead_picks += any(indeg[s] == 0 for s in picks.all())
+    print("live-first list, layout conditions over %d contexts: %s; (g) / (h) with picks inside: %s; contexts that hand a dead host to the bodies: %d"
+          % (len(LIVE_CASES), count, targeted, dead_picks))
+    assert all(count[c] >= 3 and targeted[c] >= 3 for c in oc.LIVE_CONDITIONS), (count, targeted)
 
 
 def test_cap():
@@ -100,18 +145,21 @@ def test_cap():
     is not compared when the restatement itself hits HB_ERR_LIMIT, a similarity round not when both lists are empty.  Counts of the
     committed seed (compared / calls): sampled 144 / 144, distances 192 / 192, betweenness 144 / 144, similarity 54 / 54,
     similarity_cut 90 / 90, nearest_seed 144 / 144, backlinks 288 / 288, forwardlinks 288 / 288, similar_hosts 144 / 144,
-    score_hosts 96 / 96: no call of the committed list is left out."""
-    total = oc.Tally()
-    for case in CASES:
-        dry = case.dry()[4]
-        total.add(dry)
-        if case.index in LIVE:  # the calls made on the context are the counted ones
-            assert LIVE[case.index].as_dict() == dry.as_dict(), case.name
-    print("compared / calls over %d contexts: %s" % (len(CASES), {op: (total.compared.get(op, 0), total.calls.get(op, 0)) for op in oc.OPERATORS}))
-    for op in oc.OPERATORS:
-        assert total.calls.get(op, 0) > 0 and total.compared[op] * 10 >= total.calls[op] * 9, (op, total.as_dict())
-        for kind in KINDS:
-            assert total.compared.get((op, kind), 0) >= 1, (op, kind, total.as_dict())
+    score_hosts 96 / 96: no call of the committed list is left out.  The live-first list under the same rule and its own four kinds:
+    sampled 48 / 48, distances 64 / 64, betweenness 48 / 48, similarity 21 / 21, similarity_cut 27 / 27, nearest_seed 48 / 48,
+    backlinks 96 / 96, forwardlinks 96 / 96, similar_hosts 48 / 48, score_hosts 32 / 32."""
+    for cases, kinds in ((CASES, KINDS), (LIVE_CASES, LIVE_KINDS)):
+        total = oc.Tally()
+        for case in cases:
+            dry = case.dry()[4]
+            total.add(dry)
+            if (case.seed, case.index) in LIVE:  # the calls made on the context are the counted ones
+                assert LIVE[case.seed, case.index].as_dict() == dry.as_dict(), case.name
+        print("compared / calls over %d contexts: %s" % (len(cases), {op: (total.compared.get(op, 0), total.calls.get(op, 0)) for op in oc.OPERATORS}))
+        for op in oc.OPERATORS:
+            assert total.calls.get(op, 0) > 0 and total.compared[op] * 10 >= total.calls[op] * 9, (op, total.as_dict())
+            for kind in kinds:
+                assert total.compared.get((op, kind), 0) >= 1, (op, kind, total.as_dict())
 
 
 # ---- the crafted case: a small flipped fan under two banded layouts, exact answers ------------------------------------------------------

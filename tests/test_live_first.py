@@ -6,7 +6,12 @@ argument does not cover plan as before, and the plan-reading operators give thei
 
 The crafted graphs (`_fan`) hold what the shortened launches and the gather limit can get wrong: a node row fed only by dead sources, a
 hub row (chunk = 4) with a chunk of dead sources only and one that mixes live and dead ones, n_live of 63, 64, 65 and 128 (the tile
-boundary of the shortened launch), a graph without dead hosts and one whose sources are all dead."""
+boundary of the shortened launch), a graph without dead hosts and one whose sources are all dead.
+
+The tile family (`TILES`) walks n_live and n_dead over both sides of a 64-row tile: dead rows inside the last live tile (n_live_pad =
+n_pad: no row is skipped and no changed word cleared), exactly one tile of dead rows behind it, a live part that ends on a tile
+boundary - read back from the plan in HBM - in the default, the bitmap and the sweep mode.  One context takes its hosts from an
+explicit node list that names hosts with neither an in- nor an out-link."""
 import numpy as np
 import pytest
 
@@ -61,6 +66,45 @@ def _all_sources_dead(sources=200, sinks=90):
     return sorted(e | {(1000 + s, 1, 0) for s in range(0, sources, 3)})
 
 
+def _ring_fringe(n_live, n_dead):
+    """the plainer graph of the tile family: a ring of n_live hosts with one chord each, and n_dead hosts (ids above 1000) that link into it"""
+    e = {(v, v % n_live + 1) for v in range(1, n_live + 1)} | {(v, (v * 7 + 3) % n_live + 1) for v in range(1, n_live + 1)}
+    e |= {(1001 + d, (5 * d + 2) % n_live + 1) for d in range(n_dead)}
+    return sorted((f, t, 0) for f, t in e if f != t)
+
+
+# The tile shapes of the shortened launches (row_hi = n_live_pad) and of the one-time clearing of the dead rows' changed words: n_live and
+# n_live + n_dead on either side of a 64-row tile boundary.  _fan where it has the dead hosts its rows need (32), the ring otherwise.
+TILE_LIVE, TILE_DEAD = (63, 64, 65, 127, 128, 129), (1, 63, 64, 65)
+TILES = {"tile%dx%d" % (nl, nd): (nl, nd) for nl in TILE_LIVE for nd in TILE_DEAD}
+TILE_MODES = ("default", "bitmap_always", "sweep_always")
+
+
+def _tile_shapes(n, n_pad, n_live, n_live_pad):
+    """which of the three shapes a layout has: dead rows inside the last live tile (no row is skipped, no word cleared), exactly one
+    tile of dead rows behind the last live tile, a live part that ends on a tile boundary"""
+    return {"dead_rows_in_the_last_live_tile": n_live < n and n_live_pad == n_pad, "one_dead_tile": n_pad - n_live_pad == 64,
+            "n_live_multiple_of_64": n_live % 64 == 0}
+
+
+def _pad(x):
+    return (x + 63) // 64 * 64
+
+
+# ... as the family was laid out (n_pad = n rounded up to 64 rows on one rank); the test reads the same three from the plan in HBM
+TILE_SHAPES = {name: _tile_shapes(nl + nd, _pad(nl + nd), nl, _pad(nl)) for name, (nl, nd) in TILES.items()}
+assert TILE_SHAPES["tile63x1"] == dict(dead_rows_in_the_last_live_tile=True, one_dead_tile=False, n_live_multiple_of_64=False)
+assert TILE_SHAPES["tile64x64"] == dict(dead_rows_in_the_last_live_tile=False, one_dead_tile=True, n_live_multiple_of_64=True)
+assert TILE_SHAPES["tile129x63"] == dict(dead_rows_in_the_last_live_tile=True, one_dead_tile=False, n_live_multiple_of_64=False)
+assert TILE_SHAPES["tile127x65"] == dict(dead_rows_in_the_last_live_tile=False, one_dead_tile=True, n_live_multiple_of_64=False)
+assert all(sum(s[k] for s in TILE_SHAPES.values()) >= 6 for k in TILE_SHAPES["tile63x1"])
+
+
+def _tile_tuples(name):
+    nl, nd = TILES[name]
+    return _fan(nl, nd) if nd >= 32 else _ring_fringe(nl, nd)
+
+
 GRAPHS = {
     "fan63": lambda: graphs.dense_from_tuples(_fan(63)),
     "fan64": lambda: graphs.dense_from_tuples(_fan(64)),
@@ -70,6 +114,7 @@ GRAPHS = {
     "all_sources_dead": lambda: graphs.dense_from_tuples(_all_sources_dead()),
     "rmat10": lambda: (lambda g: (g.ids.copy(), g.row_ptr.copy(), g.src.copy()))(synth.RmatGraph(10, 6000)),  # (copies: the arrays outlive g)
 }
+GRAPHS.update({name: (lambda name=name: graphs.dense_from_tuples(_tile_tuples(name))) for name in TILES})
 _BUILT = {}
 
 
@@ -112,7 +157,7 @@ def _crafted_conditions(name, plan, n, n_live):
         dead = s >= n_live
         where = "node" if row < n_pad else "chunk"
         kinds.add((where, "dead" if dead.all() else "mixed" if dead.any() else "live"))
-    if name.startswith("fan"):
+    if name.startswith("fan") or (name in TILES and TILES[name][1] >= 32):
         assert {("node", "dead"), ("chunk", "dead"), ("chunk", "mixed"), ("chunk", "live")} <= kinds, (name, kinds)
     if name == "no_dead":
         assert n_live == n and all(k[1] == "live" for k in kinds), (name, kinds)
@@ -120,8 +165,8 @@ def _crafted_conditions(name, plan, n, n_live):
         assert kinds and all(k[1] == "dead" for k in kinds) and ("chunk", "dead") in kinds, (name, kinds)
 
 
-@pytest.mark.parametrize("mode", sorted(MODES))
-@pytest.mark.parametrize("name", sorted(GRAPHS))
+@pytest.mark.parametrize("name,mode", [(name, mode) for mode in sorted(MODES) for name in sorted(set(GRAPHS) - set(TILES))] +
+                         [(name, mode) for mode in TILE_MODES for name in sorted(TILES)])
 def test_per_pass_state_matches_oracle_with_the_order_on(gpu_ctx_factory, name, mode):
     ids, row_ptr, src, id_low = _graph(name)
     n = len(ids)
@@ -134,6 +179,9 @@ def test_per_pass_state_matches_oracle_with_the_order_on(gpu_ctx_factory, name, 
         if name.startswith("fan"):
             assert n_live == int(name[3:])
         plan = ctx.plan()
+        if name in TILES:
+            assert (n_live, n - n_live) == TILES[name]
+            assert _tile_shapes(n, plan["n_pad"], n_live, n_live_pad) == TILE_SHAPES[name], (name, plan["n_pad"], n_live_pad)
         order = plan["order"][:n].astype(np.int64)
         assert np.all(indeg[order[:n_live]] > 0) and np.all(indeg[order[n_live:]] == 0)
         _crafted_conditions(name, plan, n, n_live)
@@ -170,6 +218,32 @@ def test_per_pass_state_matches_oracle_with_the_order_on(gpu_ctx_factory, name, 
         assert st["passes"] == t
         ids2, vals2 = ctx.results()
         assert np.array_equal(ids2, got_ids) and np.array_equal(vals2.view(np.uint64), got_vals.view(np.uint64))
+
+
+def test_isolated_hosts_from_the_node_list(gpu_ctx_factory):
+    """hb_load_edges with an explicit node list that names hosts with neither an in- nor an out-link: they are dead hosts without a
+    place by out-degree either, behind everybody else.  The faithful oracle learns of them from records under a skipped flag (their
+    endpoints count as hosts, harmonic.rs:131); the device is handed the unflagged records alone and the hosts by the node list."""
+    from stract_amd.harmonic import EdgeListGraph, ids_from_ints
+    tuples = _fan(65, 40)
+    lonely = [5001 + i for i in range(7)]
+    fids, fvals, fst = hbo.faithful_run(EdgeListGraph.from_tuples(tuples + [(a, b, graphs.NOFOLLOW) for a, b in zip(lonely, lonely[1:] + lonely[:1])]).host_edges())
+    e = EdgeListGraph.from_tuples(tuples).host_edges()
+    nodes = np.concatenate([np.unique(np.concatenate([e["from"], e["to"]])), ids_from_ints(lonely)])
+    for mode in TILE_MODES:
+        with _ctx(gpu_ctx_factory, mode, ON) as ctx:
+            ctx.load_edges(e, nodes[::-1])
+            ids, row_ptr, src = ctx.graph()
+            n = len(ids)
+            assert n == 65 + 40 + len(lonely) == fst["n"] and ctx.plan_live() == (True, 65, 128)
+            isolated = (np.diff(row_ptr.astype(np.int64)) == 0) & (np.bincount(src, minlength=n) == 0)
+            assert int(isolated.sum()) == len(lonely)
+            order = ctx.plan()["order"][:n].astype(np.int64)
+            assert isolated[order[-len(lonely):]].all(), "hosts without any link lie last"
+            st = ctx.run()
+            got_ids, got_vals = ctx.results()
+            assert (st["n"], st["m_eff"], st["passes"]) == (fst["n"], fst["m_eff"], fst["passes"]), mode
+            assert np.array_equal(got_ids, fids) and np.array_equal(got_vals.view(np.uint64), fvals.view(np.uint64)), mode
 
 
 def test_state_read_between_begin_and_pass0(gpu_ctx_factory):

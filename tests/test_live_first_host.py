@@ -92,6 +92,35 @@ def test_plans_that_ignore_the_option(graph, flags, tune):
     assert _same_plan(got, base) and not got["live_first"] and got["n_live_pad"] == got["n_pad"]
 
 
+THRESHOLD = 1 << 20  # live_first_by_flags (hb_api.hip): on by itself from this many hosts
+
+
+def _ring_with_dead(n_dead, ring=THRESHOLD - 2):
+    """a ring of `ring` hosts and n_dead hosts without an in-edge that link to ring host 0, as (row_ptr, src)"""
+    deg = np.ones(ring + n_dead, dtype=np.uint64)
+    deg[0], deg[ring:] = 1 + n_dead, 0
+    row_ptr = np.concatenate(([0], np.cumsum(deg))).astype(np.uint64)
+    src = np.concatenate(([ring - 1], np.arange(ring, ring + n_dead), np.arange(ring - 1))).astype(np.uint32)
+    return row_ptr, src
+
+
+def test_the_size_gate_and_the_flags_that_close_it():
+    """Without either flag the order is on from 2^20 hosts and off one host below; NO_LIVE_FIRST, NO_REORDER, UNFUSED, PASS_STATS,
+    REFERENCE_TAIL and DEST_PARTITION keep it off at 2^20; LIVE_FIRST turns it on below."""
+    below, at = _ring_with_dead(1), _ring_with_dead(2)
+    assert len(below[0]) - 1 == THRESHOLD - 1 and len(at[0]) - 1 == THRESHOLD
+    assert _lib.host_plan_live(*below) == (False, THRESHOLD - 2, THRESHOLD)       # off: n_live_pad = n_pad
+    assert _lib.host_plan_live(*at) == (True, THRESHOLD - 2, THRESHOLD)           # on: n_live rounded up to a tile (here n_pad as well)
+    assert _lib.host_plan_live(*below, ON) == (True, THRESHOLD - 2, THRESHOLD)
+    for name in ("NO_LIVE_FIRST", "NO_REORDER", "UNFUSED", "PASS_STATS", "REFERENCE_TAIL", "DEST_PARTITION"):
+        flag = getattr(_lib, "HB_FLAG_" + name)
+        assert _lib.host_plan_live(*at, flag)[0] is False, name
+        assert _lib.host_plan_live(*at, flag | ON)[0] is False, name
+    # the order itself at that size: the two dead hosts lie behind every ring host
+    order = _lib.host_plan(*at)["order"]
+    assert sorted(order[-2:].tolist()) == [THRESHOLD - 2, THRESHOLD - 1]
+
+
 def test_graphs_without_dead_or_without_live_hosts():
     ring = np.arange(100, dtype=np.uint32)
     rp = np.arange(101, dtype=np.uint64)

@@ -23,17 +23,25 @@ from tests import test_similarity as tsim
 pytestmark = pytest.mark.gpu
 
 GRAPHS = {"A": dict(n=300, m=2400, seed=7), "B": dict(n=70, m=300, seed=3)}
+FRINGE = {"A_fringe": 70, "B_fringe": 9}  # the same two with so many hosts without an in-link behind them, two links each into the graph
+
+
+@functools.lru_cache(maxsize=None)
+def _tuples(name):
+    base = GRAPHS[name[0]]
+    fringe = [(1001 + d, 1 + (7 * d + k) % base["n"]) for d in range(FRINGE.get(name, 0)) for k in (0, 31)]
+    return graphs.lcg_graph(**base) + fringe
 
 
 @functools.lru_cache(maxsize=None)
 def _edges(name):
-    return EdgeListGraph.from_tuples(graphs.lcg_graph(**GRAPHS[name])).host_edges()
+    return EdgeListGraph.from_tuples(_tuples(name)).host_edges()
 
 
 @functools.lru_cache(maxsize=None)
 def _oracle(name):
     """(ids, row_ptr, src) of the reduced graph and the oracle's HyperBall run on it: (passes, values, kept)"""
-    ids, row_ptr, src = graphs.dense_from_tuples(graphs.lcg_graph(**GRAPHS[name]))
+    ids, row_ptr, src = graphs.dense_from_tuples(_tuples(name))
     o = hbo.Dense(np.ascontiguousarray(ids["lo"]), row_ptr, src)
     T = o.run()
     vals, keep, _ = o.finish()
@@ -86,25 +94,31 @@ def _refused(fn):
     assert e.value.code == _lib.HB_ERR_INVALID
 
 
-@pytest.mark.parametrize("variant", ["default", "no_sparse"])
+@pytest.mark.parametrize("variant", ["default", "no_sparse", "live_first"])
 def test_reload_after_all_five_operators(gpu_ctx_factory, variant):
     # no_sparse: hb_distances owns its transpose, the sampled operator takes the dense / bitmap modes
-    flags = _lib.HB_FLAG_ALL_RELS | (_lib.HB_FLAG_NO_SPARSE if variant == "no_sparse" else 0)
+    # live_first: the live-first device order forced on, both graphs with hosts without an in-link behind them: n_live
+    # and n_live_pad of A (300 and 320 of 370 rows) are too large for B (69 and 128 of 79 rows)
+    flags = _lib.HB_FLAG_ALL_RELS | {"no_sparse": _lib.HB_FLAG_NO_SPARSE, "live_first": _lib.HB_FLAG_LIVE_FIRST}.get(variant, 0)
+    A, B = ("A_fringe", "B_fringe") if variant == "live_first" else ("A", "B")
+    live = {A: (True, 300, 320), B: (True, 69, 128)} if variant == "live_first" else None  # (one host of lcg70 has no in-link by itself)
     with gpu_ctx_factory(flags=flags) as ctx:
-        ctx.load_edges(_edges("A"))
-        _check_operators(ctx, "A")
+        ctx.load_edges(_edges(A))
+        assert live is None and not ctx.plan_live()[0] or ctx.plan_live() == live[A]
+        _check_operators(ctx, A)
         cand_a = td._ints(ctx.sample_sources(5, 10))
 
-        ctx.load_edges(_edges("B"))
+        ctx.load_edges(_edges(B))
+        assert live is None and not ctx.plan_live()[0] or ctx.plan_live() == live[B]
         # nothing of A answers for B: no distances, no histogram, no betweenness, no scores, and the sampler draws from B's candidates
         _refused(ctx.distance_count)
         _refused(ctx.sample_histogram)
         _refused(ctx.betweenness_count)
         _refused(ctx.similarity_all)
-        (ids, row_ptr, src), _ = _oracle("B")
+        (ids, row_ptr, src), _ = _oracle(B)
         cand_b = td._ints(ctx.sample_sources(5, 10))
         assert cand_b == td._ints(ids[ref.sample_sids(len(ids), row_ptr, src, 5, 10)]) and cand_b != cand_a
-        _check_operators(ctx, "B")
+        _check_operators(ctx, B)
 
-        ctx.load_edges(_edges("A"))  # (the allocator hands back memory B and the first A used)
-        _check_run(ctx, "A")
+        ctx.load_edges(_edges(A))  # (the allocator hands back memory B and the first A used)
+        _check_run(ctx, A)

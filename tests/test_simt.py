@@ -24,10 +24,20 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIMT = os.path.join(ROOT, "tests", "simt")
 LIB = os.path.join(SIMT, "_build", "libhyperball_simt.so")
 
-# a slice of tests/test_gpu.py sized for the CPU suite (~1 minute); HB_SIMT_FULL=1: everything the interpreter can run (~3 min)
-QUICK = ("test_per_pass_state_matches_oracle or test_gpu_ingest_equals_host_ingest or test_device_plan_equals_host_plan or "
+# a slice of tests/test_gpu.py sized for the CPU suite (~2 minutes); HB_SIMT_FULL=1: everything the interpreter can run (~5 min)
+# The per-pass variants under the plain order all run; under the live-first order (ids "<variant>-order_live") those of LIVE_QUICK:
+# every pass mode, the chunk trees, the banded and sliced layouts, the lean pass 0, the staged results, the long tail and its kernel,
+# and the variants that must ignore the flag.  The rest of that half runs with HB_SIMT_FULL=1.
+LIVE_QUICK = ("default or chunk4_multilevel or sparse_always_multilevel or frontier_always_multilevel or frontier_always_chunk128 or "
+              "no_reorder_unroll4 or unfused or pass_stats or staged_results_every_pass or staged_results_sweep_tiny_list or "
+              "banded_chunks or xcd_slices_small_bands or few_blocks or sweep_general_seed_path or tail_kernel_after_any_pass")
+PER_PASS = "(test_per_pass_state_matches_oracle and (not order_live or %s))" % LIVE_QUICK
+QUICK = (PER_PASS + " or test_gpu_ingest_equals_host_ingest or test_device_plan_equals_host_plan or test_record_stream_whose_dead_hosts_occur_only_as_from or "
          "test_logical_ranks_on_one_device or test_rccl_call_path_single_rank or test_first_occurrence_flag_wins or "
          "test_empty_and_singleton_graphs or test_streamed_ingest_chunks_refusal_and_spill or test_ampc_counter_table_upsert_semantics")
+# under a shuffled order: the plain half, and of the live half a chunk tree in each pass mode and the long tail
+PER_PASS_SHUFFLED = ("(test_per_pass_state_matches_oracle and (not order_live or chunk4_multilevel or sparse_always_multilevel or "
+                     "frontier_always_multilevel or long_tail_default))")
 FULL = "not test_c2 and not test_caching_allocator_under_memory_pressure"
 
 
@@ -69,7 +79,7 @@ def test_reload_after_all_three_operators_under_the_interpreter(simt_lib):
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_reload.py"), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider"],
                        capture_output=True, text=True, env=_child_env(simt_lib), cwd=ROOT, timeout=1700)
     tail = "\n".join((r.stdout + r.stderr).splitlines()[-40:])
-    assert r.returncode == 0 and "2 passed" in tail and "failed" not in tail, tail
+    assert r.returncode == 0 and "3 passed" in tail and "failed" not in tail, tail
 
 
 def test_no_dependence_on_workgroup_or_lane_order(simt_lib):
@@ -78,10 +88,11 @@ def test_no_dependence_on_workgroup_or_lane_order(simt_lib):
     every launch and of the runnable lanes for every turn ("reverse": descending).  Results that depended on an order - one
     workgroup consuming what another has not produced yet, a lane reading LDS before its neighbour wrote it - would differ from the
     oracle here.  All per-pass variants under a shuffled order (the whole interpretable suite was run under reverse, shuffle:1 and
-    shuffle:2 in round 4: 69 passed each)."""
+    shuffle:2 in round 4: 69 passed each).  HB_SIMT_FULL=1: both halves of the variant matrix, the live-first one whole."""
     env = dict(_child_env(simt_lib), HB_SIMT_ORDER="shuffle:7", HB_SIMT_THREADS="3")  # ... and three host threads share the workgroups: they overlap in time
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu.py"), "-m", "gpu", "-q", "-x", "-k",
-                        "test_per_pass_state_matches_oracle or test_sweep_seeds_with_very_long_reader_lists or test_gpu_ingest_equals_host_ingest",
+                        ("test_per_pass_state_matches_oracle" if os.environ.get("HB_SIMT_FULL") == "1" else PER_PASS_SHUFFLED) +
+                        " or test_sweep_seeds_with_very_long_reader_lists or test_gpu_ingest_equals_host_ingest",
                         "-p", "no:cacheprovider"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=1700)
     tail = "\n".join((r.stdout + r.stderr).splitlines()[-40:])
     assert r.returncode == 0 and " passed" in tail and "failed" not in tail, tail

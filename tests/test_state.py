@@ -25,7 +25,11 @@ from tests import test_similarity as tsim
 
 pytestmark = pytest.mark.gpu
 
-TUPLES = {"lcg70": lambda: graphs.lcg_graph(n=70, m=300, seed=3), "fixture": lambda: list(graphs.FIXTURE)}
+# lcg70_fringe_live: lcg70 and nine hosts without an in-link that link into it, on a context with the live-first device order forced on
+# (DESIGN.md section 32): the borrowed rows of the dead hosts lie behind the last row the passes visit from pass 1 on
+TUPLES = {"lcg70": lambda: graphs.lcg_graph(n=70, m=300, seed=3), "fixture": lambda: list(graphs.FIXTURE),
+          "lcg70_fringe_live": lambda: graphs.lcg_graph(n=70, m=300, seed=3) + [(101 + d, 1 + (7 * d + k) % 70) for d in range(9) for k in (0, 31)]}
+FLAGS = {"lcg70_fringe_live": _lib.HB_FLAG_LIVE_FIRST}
 NAMES = tuple(TUPLES)
 CALLS = ("run", "sampled", "distances", "betweenness", "similarity")
 BORROWERS = ("sampled", "betweenness", "similarity")  # they write the shared rows; hb_distances works in buffers of its own
@@ -49,8 +53,10 @@ class Case:
         self.vals, self.keep, _ = o.finish()
 
     def load(self, factory):
-        ctx = factory(flags=_lib.HB_FLAG_ALL_RELS)
+        ctx = factory(flags=_lib.HB_FLAG_ALL_RELS | FLAGS.get(self.name, 0))
         ctx.load_edges(self.edges)
+        live_first, n_live, _ = ctx.plan_live()
+        assert live_first == (self.name in FLAGS) and (not live_first or 0 < n_live <= len(self.ids) - 9)
         return ctx
 
     def call(self, ctx, which):

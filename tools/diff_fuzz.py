@@ -13,8 +13,13 @@ The operator modes (distances ... sampled; `operators` alternates over all nine)
 CPU restatement of its operator, on contexts of that module's layout recipe: chunk 4 / 8 / 16 / 64, tune[3..5] (band width, minimum
 sources before a band cut, largest row that is not split) and two of NO_REORDER / NO_XCD_MAP / HOST_PLAN / NO_SPARSE.
 
+--order decides the device order of the passes, records and operator contexts: plain draws nothing and replays the
+cases this tool drew before it knew the option; live puts HB_FLAG_LIVE_FIRST on every context - the order every graph of 2^20 hosts and
+more is planned in; mixed (the default) draws one of nothing / HB_FLAG_LIVE_FIRST / HB_FLAG_NO_LIVE_FIRST per case.  Under live and mixed
+the graphs also include `dead_fringe`, and every loaded context's plan_live() is held against the host planner's on the same graph and flags.
+
 usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|operators|distances|betweenness|similarity|nearest_seed|score_hosts|backlinks|forwardlinks|similar_hosts|sampled]
-                          [--ids plain|extreme|mixed] [--seconds S] [--seed N] [--max-nodes N]"""
+                          [--ids plain|extreme|mixed] [--order plain|live|mixed] [--seconds S] [--seed N] [--max-nodes N]"""
 import argparse
 import json
 import os
@@ -34,11 +39,37 @@ from tests import operator_cases as oc  # noqa: E402
 FLAG_POOL = ["NO_REORDER", "NO_XCD_MAP", "UNFUSED", "NO_SPARSE", "NO_FRONTIER", "PASS_STATS", "HOST_PLAN", "NO_INIT_PASS"]
 
 
-def big_graph(rng, max_nodes):
+ORDER_FLAGS = {"": 0, "LIVE_FIRST": _lib.HB_FLAG_LIVE_FIRST, "NO_LIVE_FIRST": _lib.HB_FLAG_NO_LIVE_FIRST}
+
+
+def draw_order(rng, order, what):
+    """The device order of one case, a flag for its context: nothing under `plain` (and nothing is drawn), HB_FLAG_LIVE_FIRST under `live`,
+    one of the three under `mixed`.  Called behind a case's other draws; recorded in `what` where the option is in use."""
+    if order == "plain":
+        return 0
+    name = "LIVE_FIRST" if order == "live" else ("", "LIVE_FIRST", "NO_LIVE_FIRST")[int(rng.integers(0, 3))]
+    what["order"] = name
+    return ORDER_FLAGS[name]
+
+
+def check_plan_live(ctx, flags, chunk, tune, what):
+    """the loaded context's (live-first in use, n_live, n_live_pad) is the host planner's for the same graph, flags and knobs - also
+    where the context must ignore the flag (NO_REORDER, UNFUSED, PASS_STATS)"""
+    _, row_ptr, src = ctx.graph()
+    got, want = ctx.plan_live(), _lib.host_plan_live(row_ptr, src, flags, chunk, tune)
+    assert got == want, ("plan_live: context %s, host planner %s" % (got, want), what)
+    return got
+
+
+def big_graph(rng, max_nodes, order="plain"):
     """Shapes the test-suite generator does not reach: hubs above 4096 in-edges (three-level chunk trees at small chunks), many
-    isolated / source-only nodes, a heavy-tailed in-degree, long chains hanging off a dense core."""
+    isolated / source-only nodes, a heavy-tailed in-degree, long chains hanging off a dense core; where the device order is an option, a
+    quarter of the draws is a `dead_fringe` instead (graphs.dead_fringe_graph: n_live = 64 k - 1, 64 k, 64 k + 1 for k = 1 .. 8, n_dead of
+    1, 63, 64, 65, 200 - the launches that end at n_live_pad and the dead rows' words behind it)."""
     n = int(rng.integers(2, max_nodes))
     kind = ("heavy_tail", "mega_hub", "core_and_chains")[int(rng.integers(0, 3))]
+    if order != "plain" and rng.integers(0, 4) == 0:
+        return graphs.dead_fringe_graph(rng)
     e = set()
     if kind == "heavy_tail":
         m = int(rng.integers(n, 8 * n))
@@ -88,11 +119,11 @@ def relabel_extreme(rng, edges):
     return sorted((new.get(a, a), new.get(b, b)) for a, b in edges)
 
 
-def one_case(rng, max_nodes, case, extreme=False):
+def one_case(rng, max_nodes, case, extreme=False, order="plain"):
     if rng.random() < 0.5:
         kind, edges = graphs.random_graph(rng)
     else:
-        kind, edges = big_graph(rng, max_nodes)
+        kind, edges = big_graph(rng, max_nodes, order)
     if not edges:
         return None
     if extreme:
@@ -108,9 +139,11 @@ def one_case(rng, max_nodes, case, extreme=False):
     for nm in names:
         flags |= getattr(_lib, "HB_FLAG_" + nm)
     what = dict(case=case, kind=kind, n=int(len(ids)), m=int(len(src)), chunk=chunk, tune=tune, flags=names, extreme_ids=extreme)
+    flags |= draw_order(rng, order, what)
     o = hbo.Dense(ids["lo"].copy(), row_ptr, src)
     with _lib.Context(flags=flags, chunk=chunk, tune=tune) as ctx:
         ctx.load_dense(ids, row_ptr, src)
+        check_plan_live(ctx, flags, chunk, tune, what)
         ctx.begin()
         assert np.array_equal(ctx.registers(), o.registers()), ("initial registers", what)
         has, t = True, 0
@@ -123,7 +156,12 @@ def one_case(rng, max_nodes, case, extreme=False):
             os_, oe = o.kahan()
             assert np.array_equal(s.view(np.uint64), os_.view(np.uint64)) and np.array_equal(e.view(np.uint64), oe.view(np.uint64)), ("Kahan words after pass %d" % t, what)
             assert np.array_equal(ctx.sizes(), o.sizes()), ("sizes after pass %d" % t, what)
-            assert ctx.pass_stats()[t]["changed"] == ost["changed"], ("changed count of pass %d" % t, what)
+            ps = ctx.pass_stats()[t]
+            assert ps["changed"] == ost["changed"], ("changed count of pass %d" % t, what)
+            # A_t where the suite compares it (tests/test_gpu.py): counted edge by edge in a bitmap pass under PASS_STATS, the out-degree
+            # sum of the hosts that changed in pass t - 1 otherwise - a dead row wrongly left "changed" shows here first
+            if not flags & _lib.HB_FLAG_PASS_STATS or ps["mode"] == 1:
+                assert ps["active_edges"] == ost["active_edges"], ("active edges of pass %d" % t, what)
             t += 1
         ctx.finish()
         vals, keep, k = o.finish()
@@ -137,7 +175,7 @@ SKIPPED_BITS = [8, 10, 11, 13, 14, 15, 16, 17, 18, 19, 21, 22]  # HB_SKIPPED_REL
 HARMLESS_BITS = [0, 1, 2, 3, 4, 5, 6, 7, 9, 12, 20]
 
 
-def records_case(rng, max_nodes, case, extreme=False):
+def records_case(rng, max_nodes, case, extreme=False, order="plain"):
     """The record boundary: a random stream of SmallEdge records - 128-bit ids (equal low halves, different high halves among them),
     duplicates of a pair with other flags before and after it, skipped and harmless rel flags, self links - handed over in random
     batches (hb_append_edges ... hb_finalize, the device ingest: hash table of provisional ids, one stable sort) or at once, with and
@@ -180,7 +218,20 @@ def records_case(rng, max_nodes, case, extreme=False):
     tune_ctx = (0, int(rng.choice([0, 0, _lib.HB_X_SNAPSHOT_EVERY_PASS, _lib.HB_X_NO_TAIL_PIPELINE, _lib.HB_X_SNAPSHOT_EVERY_PASS | _lib.HB_X_SHORT_FINAL_LIST | _lib.HB_X_ONE_SNAPSHOT, _lib.HB_X_SNAPSHOT_EVERY_PASS | _lib.HB_X_NO_TAIL_PIPELINE])) | int(rng.choice([0, 0, _lib.HB_X_TAIL_KERNEL, _lib.HB_X_TAIL_KERNEL_ANY])), int(rng.choice([0, 0, 101])), 0, 0, 0,
                 int(rng.choice([0, 0, 1])))
     what["tune"] = tune_ctx
-    with _lib.Context(flags=flags_ctx, chunk=int(rng.choice([8, 64])), tune=tune_ctx) as ctx:
+    chunk_ctx = int(rng.choice([8, 64]))
+    flags_ctx |= draw_order(rng, order, what)
+    lonely = np.zeros(0, dtype=_lib.U128)
+    if order != "plain" and how == 2:
+        # hosts the node list names and no record mentions: neither an in- nor an out-link.  The faithful oracle, which takes its hosts
+        # from the records, is told of them by records under a skipped flag; the context is not handed those
+        lonely = np.zeros(int(rng.integers(2, 6)), dtype=_lib.U128)
+        lonely["lo"], lonely["hi"] = np.arange(len(lonely), dtype=np.uint64) + np.uint64(1), np.uint64(1 << 63) + np.uint64(7)
+        told = np.zeros(len(lonely), dtype=_lib.EDGE)
+        told["from"], told["to"], told["rel_flags"] = lonely, np.roll(lonely, 1), np.uint64(1) << np.uint64(SKIPPED_BITS[0])
+        fids, fvals, fst = hbo.faithful_run(np.concatenate([e, told]))
+        fst = dict(fst, m_unique=fst["m_unique"] - len(lonely))  # (the pairs of those records)
+        what["lonely_hosts"] = int(len(lonely))
+    with _lib.Context(flags=flags_ctx, chunk=chunk_ctx, tune=tune_ctx) as ctx:
         if how == 0:
             cuts = np.sort(rng.integers(0, len(e) + 1, int(rng.integers(0, 6))))
             for part in np.split(e, cuts):
@@ -189,8 +240,10 @@ def records_case(rng, max_nodes, case, extreme=False):
         elif how == 1:
             ctx.load_edges(e)
         else:
-            nodes = np.unique(np.concatenate([e["from"], e["to"]]))
+            nodes = np.unique(np.concatenate([e["from"], e["to"], lonely]))
             ctx.load_edges(e, nodes)
+        if order != "plain":
+            check_plan_live(ctx, flags_ctx, chunk_ctx, tune_ctx, what)
         st = ctx.run()
         ids, vals = ctx.results()
     assert (st["n"], st["m_unique"], st["m_eff"], st["passes"]) == (fst["n"], fst["m_unique"], fst["m_eff"], fst["passes"]), ("counts", what, st, fst)
@@ -294,7 +347,7 @@ def ranks_case(rng, max_nodes, case, extreme=False):
 OPERATOR_MODES = ["distances", "betweenness", "similarity", "nearest_seed", "score_hosts", "backlinks", "forwardlinks", "similar_hosts", "sampled"]
 
 
-def operator_case(rng, case, name):
+def operator_case(rng, case, name, order="plain"):
     """One context of the layout recipe of tests/operator_cases.py - a graph of graphs.random_graph with self links, chunk 4 / 8 / 16 /
     64, the planner's cut and split knobs tune[3..5], two layout flags - and on it the body of operator `name`, the one the suite runs
     (tests/test_layouts.py), against the CPU restatement of that operator.  The hubs of the plan's chunk trees and sources inside them
@@ -302,9 +355,12 @@ def operator_case(rng, case, name):
     kind, tuples = oc.draw_graph(rng)
     chunk, tune, flags = oc.draw_layout(rng)
     what = dict(case=case, kind=name + ":" + kind, chunk=chunk, tune=tune, flags=flags)
+    flags |= draw_order(rng, order, what)
     with oc.load(_lib.Context, tuples, chunk, tune, flags) as ctx:
         graph = ctx.graph()
-        picks = oc.picks_of(oc.layout_conditions(ctx.plan(), graph[1], chunk))
+        live = check_plan_live(ctx, flags, chunk, tune, what) if order != "plain" else (False, 0, 0)
+        # (on a live-first plan a live and a dead member of a hub's chunk are among the picks: a dead host is queried, walked from and scored)
+        picks = oc.picks_of(oc.layout_conditions(ctx.plan(), graph[1], chunk, live[1] if live[0] else None))
         passes = oc.BODIES[name](ctx, graph, rng, what, picks)
     what.update(n=int(len(graph[0])), m=int(len(graph[2])), passes=int(passes))
     return what
@@ -314,6 +370,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "operators"] + OPERATOR_MODES, default="passes")
     ap.add_argument("--ids", choices=["plain", "extreme", "mixed"], default="plain")
+    ap.add_argument("--order", choices=["plain", "live", "mixed"], default="mixed")
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-nodes", type=int, default=6000)
@@ -326,17 +383,17 @@ def main():
         extreme = a.ids == "extreme" or (a.ids == "mixed" and case % 2 == 1)
         try:
             if a.mode in OPERATOR_MODES:
-                w = operator_case(rng, case, a.mode)
+                w = operator_case(rng, case, a.mode, a.order)
             elif a.mode == "operators":
-                w = operator_case(rng, case, OPERATOR_MODES[case % len(OPERATOR_MODES)])
+                w = operator_case(rng, case, OPERATOR_MODES[case % len(OPERATOR_MODES)], a.order)
             elif a.mode == "ranks" or (a.mode == "mixed" and case % 6 == 4):
                 w = ranks_case(rng, a.max_nodes, case, extreme)
             elif a.mode == "tail" or (a.mode == "mixed" and case % 6 == 5):
                 w = tail_case(rng, case)
             elif a.mode == "records" or (a.mode == "mixed" and case % 3 == 2):
-                w = records_case(rng, a.max_nodes, case, extreme)
+                w = records_case(rng, a.max_nodes, case, extreme, a.order)
             else:
-                w = one_case(rng, a.max_nodes, case, extreme)
+                w = one_case(rng, a.max_nodes, case, extreme, a.order)
         except AssertionError as e:
             print(json.dumps({"failed": str(e.args[0] if e.args else e), "seed": a.seed, "cases_before": done}))
             sys.exit(1)
@@ -345,7 +402,7 @@ def main():
             done += 1
             edges += w["m"]
             passes += w["passes"]
-    print(json.dumps({"library": _lib.LIB_PATH, "mode": a.mode, "ids": a.ids, "seed": a.seed, "seconds": round(time.time() - t0, 1), "cases": done, "edges": edges, "passes_compared": passes, "failed": None}))
+    print(json.dumps({"library": _lib.LIB_PATH, "mode": a.mode, "ids": a.ids, "order": a.order, "seed": a.seed, "seconds": round(time.time() - t0, 1), "cases": done, "edges": edges, "passes_compared": passes, "failed": None}))
 
 
 if __name__ == "__main__":
