@@ -11,6 +11,7 @@ import pytest
 
 from stract_amd import _lib, ampc
 from tests import ampc_approx_ref as aref
+from tests.ampc_slots import slot_hash
 from tests.test_ampc_edges import distance_table
 from tests.test_ampc_round import graph_of, interpreted, two_workers
 from tests.test_ampc_values import assert_table, canon, dev_values, harmonic_graphs, key_int, u128
@@ -136,15 +137,6 @@ def test_fold_grows_the_value_table():
     with kahan_table(m_cent) as d_cent, kahan_table(m_cent) as d_comp:
         assert fold_checked(dist, d_cent, m_cent, d_comp, ids, 0.5) == (35, 25)
         assert len(d_cent) == 1025
-
-
-def slot_hash(key):
-    """slot_hash() of stract_amd/csrc/hb_table.hip.h restated: the home slot of a key is slot_hash(key) & (slots - 1)"""
-    x = (key & M64) ^ (((key >> 64) * 0x9E3779B97F4A7C15) & M64)
-    for _ in range(2):
-        x ^= x >> 32
-        x = (x * 0xD6E8FEB86659FD93) & M64
-    return x ^ (x >> 32)
 
 
 def test_fold_and_export_reach_the_first_and_the_last_slot():

@@ -18,7 +18,11 @@ cases this tool drew before it knew the option; live puts HB_FLAG_LIVE_FIRST on 
 more is planned in; mixed (the default) draws one of nothing / HB_FLAG_LIVE_FIRST / HB_FLAG_NO_LIVE_FIRST per case.  Under live and mixed
 the graphs also include `dead_fringe`, and every loaded context's plan_live() is held against the host planner's on the same graph and flags.
 
-usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|operators|distances|betweenness|similarity|nearest_seed|score_hosts|backlinks|forwardlinks|similar_hosts|sampled]
+--mode ampc drives the AMPC shard (stract_amd/ampc.py) instead of a context: every case is one sequence of tests/ampc_model.py - 60 to 240
+interleaved calls on tables, graphs and filters that stay alive, each answer against the model, the whole content of every table and
+filter after every eighth call.  A failure prints the case's seed, the operation index and the operations so far.
+
+usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|operators|ampc|distances|betweenness|similarity|nearest_seed|score_hosts|backlinks|forwardlinks|similar_hosts|sampled]
                           [--ids plain|extreme|mixed] [--order plain|live|mixed] [--seconds S] [--seed N] [--max-nodes N]"""
 import argparse
 import json
@@ -366,15 +370,46 @@ def operator_case(rng, case, name, order="plain"):
     return what
 
 
+def ampc_case(rng, case):
+    """one sequence of tests/ampc_model.py under a drawn seed and length, every call on the library and on the model"""
+    from tests import ampc_model
+    seed, n_ops = int(rng.integers(1, 1 << 31)), int(rng.integers(60, 241))
+    handles, log = ampc_model.Handles(), []
+    try:
+        world = ampc_model.run(seed, handles, n_ops, log)
+    finally:
+        handles.close()
+    return dict(case=case, kind="ampc", sequence_seed=seed, operations=n_ops, m=int(world.counts["largest_table"]), passes=len(log))
+
+
+def ampc_main(a):
+    """--mode ampc: `passes_compared` counts the operations compared, `edges` adds up the largest table of every case"""
+    from stract_amd import ampc
+    from tests import ampc_model
+    assert ampc.wave_group_length() == ampc_model.WAVE_GROUP
+    rng = np.random.default_rng(a.seed)
+    t0, done, keys, ops = time.time(), 0, 0, 0
+    while time.time() - t0 < a.seconds:
+        try:
+            w = ampc_case(rng, done)
+        except AssertionError as e:
+            print(json.dumps({"failed": str(e.args[0] if e.args else e), "seed": a.seed, "cases_before": done}))
+            sys.exit(1)
+        done, keys, ops = done + 1, keys + w["m"], ops + w["passes"]
+    print(json.dumps({"library": _lib.LIB_PATH, "mode": a.mode, "seed": a.seed, "seconds": round(time.time() - t0, 1), "cases": done, "largest_tables": keys, "operations_compared": ops, "failed": None}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "operators"] + OPERATOR_MODES, default="passes")
+    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "operators", "ampc"] + OPERATOR_MODES, default="passes")
     ap.add_argument("--ids", choices=["plain", "extreme", "mixed"], default="plain")
     ap.add_argument("--order", choices=["plain", "live", "mixed"], default="mixed")
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-nodes", type=int, default=6000)
     a = ap.parse_args()
+    if a.mode == "ampc":
+        return ampc_main(a)
     rng = np.random.default_rng(a.seed)
     t0 = time.time()
     done, edges, passes = 0, 0, 0
