@@ -224,6 +224,32 @@ def _key_list(ints, key):
     return [(v, int(k)) for v, k in zip(ints, key.tolist()) if k != U64_MAX]
 
 
+def draw_entries(rng, ints, k):
+    """k liked or disliked hosts of hb_inbound_similarity: random nodes; where there is room, an id that is no node and a duplicate"""
+    n = len(ints)
+    e = [ints[int(x)] for x in rng.integers(0, n, k)]
+    if k > 2:
+        e[int(rng.integers(0, k))] = UNKNOWN + int(rng.integers(0, 3))  # no node of the graph
+        e[int(rng.integers(0, k))] = e[0]  # a duplicate
+    return e
+
+
+def draw_shared_pool(rng, ints, picks):
+    """what the requests of one hb_score_hosts call share: twelve random nodes, two ids that are no node, the picks"""
+    return [ints[int(x)] for x in rng.integers(0, len(ints), 12)] + [UNKNOWN + 1, UNKNOWN + 2] + [ints[s] for s in picks]
+
+
+def draw_from_pool(rng, ints, pool, k):
+    """k hosts of a request: every third from the shared pool, the others any node"""
+    return [pool[int(rng.integers(0, len(pool)))] if rng.integers(0, 3) == 0 else ints[int(rng.integers(0, len(ints)))] for _ in range(k)]
+
+
+def draw_liked(rng, ints, count, picks):
+    """the liked hosts of hb_similar_hosts: `count` random nodes, the picks, an id that is no node and a duplicate"""
+    liked = [ints[int(x)] for x in rng.integers(0, len(ints), count)] + [ints[s] for s in picks]
+    return liked + [UNKNOWN + 3, liked[0]]
+
+
 # ---- the bodies -----------------------------------------------------------------------------------------------------------------------
 def distances_case(ctx, graph, rng, what, picks=Picks(), tally=None):
     """hb_distances: random source set x direction x max_dist x forced step, against the host restatement"""
@@ -293,15 +319,8 @@ def similarity_case(ctx, graph, rng, what, picks=Picks(), tally=None):
     ints = _ints(graph)
     n, passes = len(ints), 0
 
-    def draw(k):
-        e = [ints[int(x)] for x in rng.integers(0, n, k)]
-        if k > 2:
-            e[int(rng.integers(0, k))] = UNKNOWN + int(rng.integers(0, 3))  # no node of the graph
-            e[int(rng.integers(0, k))] = e[0]  # a duplicate
-        return e
-
     for r in range(3):
-        liked, disliked = draw(int(rng.integers(0, 40))), draw(int(rng.integers(0, 20)))
+        liked, disliked = draw_entries(rng, ints, int(rng.integers(0, 40))), draw_entries(rng, ints, int(rng.integers(0, 20)))
         if r < 2:  # the picks once under the whole in-lists and once under a cut
             liked += [ints[s] for s in picks.hubs]
             disliked += [ints[s] for s in picks.members[:2]]
@@ -349,10 +368,10 @@ def score_hosts_case(ctx, graph, rng, what, picks=Picks(), tally=None):
     from tests import score_hosts_ref as ref
     ints = _ints(graph)
     n, passes = len(ints), 0
-    pool = [ints[int(x)] for x in rng.integers(0, n, 12)] + [UNKNOWN + 1, UNKNOWN + 2] + [ints[s] for s in picks.all()]  # what the requests share
+    pool = draw_shared_pool(rng, ints, picks.all())
 
     def draw(k):
-        return [pool[int(rng.integers(0, len(pool)))] if rng.integers(0, 3) == 0 else ints[int(rng.integers(0, n))] for _ in range(k)]
+        return draw_from_pool(rng, ints, pool, k)
 
     for r in range(2):
         limit = int(rng.choice(LIMITS))
@@ -480,8 +499,7 @@ def similar_hosts_case(ctx, graph, rng, what, picks=Picks(), tally=None):
     for r in range(3):
         key = _few_keys(rng, n)
         keys = _key_list(ints, key) if r else []
-        liked = [ints[int(x)] for x in rng.integers(0, n, int(rng.integers(1, 9)))] + [ints[s] for s in (picks.hubs if r < 2 else picks.members[:3])]
-        liked += [UNKNOWN + 3, liked[0]]
+        liked = draw_liked(rng, ints, int(rng.integers(1, 9)), picks.hubs if r < 2 else picks.members[:3])
         k = int(rng.choice(LIMITS))
         if tally is not None:
             tally.count("similar_hosts", what["kind"])

@@ -22,7 +22,12 @@ the graphs also include `dead_fringe`, and every loaded context's plan_live() is
 interleaved calls on tables, graphs and filters that stay alive, each answer against the model, the whole content of every table and
 filter after every eighth call.  A failure prints the case's seed, the operation index and the operations so far.
 
-usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|operators|ampc|distances|betweenness|similarity|nearest_seed|score_hosts|backlinks|forwardlinks|similar_hosts|sampled]
+--mode context drives ONE context through interleaved calls of every call family (tests/context_model.py): every case
+draws a sequence seed, a context (nothing / NO_SPARSE / LIVE_FIRST, chunk 0 / 4 / 8 / 16 / 64) and a length of 40 to 160 operations - hb_run,
+hb_begin .. hb_finish, the ten operators with changing arguments, loads of other graphs, hb_release_cached_memory, refusals -, each answer
+as the operator's suite compares it, every reader of every operator after every sixth call.  A failure prints as in --mode ampc.
+
+usage: tools/diff_fuzz.py [--mode passes|records|tail|ranks|mixed|operators|ampc|context|distances|betweenness|similarity|nearest_seed|score_hosts|backlinks|forwardlinks|similar_hosts|sampled]
                           [--ids plain|extreme|mixed] [--order plain|live|mixed] [--seconds S] [--seed N] [--max-nodes N]"""
 import argparse
 import json
@@ -399,9 +404,33 @@ def ampc_main(a):
     print(json.dumps({"library": _lib.LIB_PATH, "mode": a.mode, "seed": a.seed, "seconds": round(time.time() - t0, 1), "cases": done, "largest_tables": keys, "operations_compared": ops, "failed": None}))
 
 
+def context_case(rng, case):
+    """one sequence of tests/context_model.py under a drawn seed, context and length, every call on the library and on the model"""
+    from tests import context_model
+    seed, n_ops = int(rng.integers(1, 1 << 31)), int(rng.integers(40, 161))
+    variant = ("drawn", [(), ("NO_SPARSE",), ("LIVE_FIRST",)][int(rng.integers(0, 3))], int(rng.choice((0,) + oc.CHUNKS)))
+    log = []
+    world = context_model.run(seed, _lib.Context, n_ops, log, variant)
+    return dict(case=case, kind="context", sequence_seed=seed, flags=list(variant[1]), chunk=variant[2], operations=n_ops, m=int(world.counts["loads"]), passes=len(log))
+
+
+def context_main(a):
+    """--mode context: `passes_compared` counts the operations compared, `edges` the graphs loaded"""
+    rng = np.random.default_rng(a.seed)
+    t0, done, loads, ops = time.time(), 0, 0, 0
+    while time.time() - t0 < a.seconds:
+        try:
+            w = context_case(rng, done)
+        except AssertionError as e:
+            print(json.dumps({"failed": str(e.args[0] if e.args else e), "seed": a.seed, "cases_before": done}))
+            sys.exit(1)
+        done, loads, ops = done + 1, loads + w["m"], ops + w["passes"]
+    print(json.dumps({"library": _lib.LIB_PATH, "mode": a.mode, "seed": a.seed, "seconds": round(time.time() - t0, 1), "cases": done, "graphs_loaded": loads, "operations_compared": ops, "failed": None}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "operators", "ampc"] + OPERATOR_MODES, default="passes")
+    ap.add_argument("--mode", choices=["passes", "records", "tail", "ranks", "mixed", "operators", "ampc", "context"] + OPERATOR_MODES, default="passes")
     ap.add_argument("--ids", choices=["plain", "extreme", "mixed"], default="plain")
     ap.add_argument("--order", choices=["plain", "live", "mixed"], default="mixed")
     ap.add_argument("--seconds", type=float, default=60.0)
@@ -410,6 +439,8 @@ def main():
     a = ap.parse_args()
     if a.mode == "ampc":
         return ampc_main(a)
+    if a.mode == "context":
+        return context_main(a)
     rng = np.random.default_rng(a.seed)
     t0 = time.time()
     done, edges, passes = 0, 0, 0
