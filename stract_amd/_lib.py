@@ -88,7 +88,14 @@ class HbOptions(ctypes.Structure):
     ]
 
 
-class HbStats(ctypes.Structure):
+class _Stats(ctypes.Structure):
+    """a stats struct whose dict form is its plain fields"""
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class HbStats(_Stats):
     _fields_ = [
         ("n", ctypes.c_uint64),
         ("m_input", ctypes.c_uint64),
@@ -120,9 +127,6 @@ class HbStats(ctypes.Structure):
         ("pipelined_passes", ctypes.c_uint64),
         ("tail_kernel_passes", ctypes.c_uint64),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class HbPassStats(ctypes.Structure):
@@ -368,16 +372,13 @@ class HbSimilarOptions(ctypes.Structure):
     ]
 
 
-class HbSimilarStats(ctypes.Structure):
+class HbSimilarStats(_Stats):
     _fields_ = [
         ("struct_size", ctypes.c_uint32),
         ("apply", ctypes.c_uint32),
     ] + [(k, ctypes.c_uint64) for k in ("liked_distinct", "unknown", "nb", "forward_entries", "distinct_targets", "count_bound", "taken", "candidates",
                                         "pairs_gated", "pairs_intersected", "written", "device_bytes")] + [
         (k, ctypes.c_double) for k in ("ms_total", "ms_in", "ms_forward", "ms_count", "ms_bitvec", "ms_score", "ms_gpu_lists", "ms_gpu_score")]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 HB_SCORE_SMALL_PIECES = 0x100
@@ -430,7 +431,7 @@ class HbLinksKeyOptions(ctypes.Structure):
     ]
 
 
-class HbLinksKeyStats(ctypes.Structure):
+class HbLinksKeyStats(_Stats):
     _fields_ = [
         ("struct_size", ctypes.c_uint32),
         ("reserved", ctypes.c_uint32),
@@ -440,9 +441,6 @@ class HbLinksKeyStats(ctypes.Structure):
         ("ms_total", ctypes.c_double),
         ("ms_order", ctypes.c_double),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class HbLinksOptions(ctypes.Structure):
@@ -456,7 +454,7 @@ class HbLinksOptions(ctypes.Structure):
     ]
 
 
-class HbLinksStats(ctypes.Structure):
+class HbLinksStats(_Stats):
     _fields_ = [
         ("struct_size", ctypes.c_uint32),
         ("reserved", ctypes.c_uint32),
@@ -474,9 +472,6 @@ class HbLinksStats(ctypes.Structure):
         ("ms_select", ctypes.c_double),
         ("ms_emit", ctypes.c_double),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 # every symbol include/hyperball.h declares: (name, restype, argtypes)
@@ -806,6 +801,47 @@ class Context:
         if rc != HB_OK:
             raise HyperballError(rc, (self.lib.hb_last_error(self.h) or b"").decode())
 
+    def _call(self, fn, opt, stats_cls):
+        """an operator: both struct_size fields, the call, the check; the stats as a dict"""
+        opt.struct_size = ctypes.sizeof(opt)
+        st = stats_cls()
+        st.struct_size = ctypes.sizeof(st)
+        self._check(fn(self.h, ctypes.byref(opt), ctypes.byref(st)))
+        return st.as_dict()
+
+    @staticmethod
+    def _u128_arg(a, empty_len):
+        """a list of node ids as a contiguous U128 array; an empty (or absent) one as `empty_len` zeroed entries to point at"""
+        return np.ascontiguousarray(a, dtype=U128) if a is not None and len(a) else np.zeros(empty_len, dtype=U128)
+
+    def _count(self, fn):
+        k = ctypes.c_uint64(0)
+        self._check(fn(self.h, ctypes.byref(k)))
+        return k.value
+
+    def _pairs(self, count_fn, copy_fn, dtype):
+        """a compacted result: (ids U128, values `dtype`), as many as count_fn says"""
+        k = self._count(count_fn)
+        ids = np.zeros(k, dtype=U128)
+        vals = np.zeros(k, dtype=dtype)
+        self._check(copy_fn(self.h, _ptr(ids), _ptr(vals), k))
+        return ids, vals
+
+    def _per_node(self, fn, dtype, fill):
+        """one value per node, ascending NodeID; `fill` = what a node without a value keeps"""
+        out = np.full(self.n(), fill, dtype=dtype)
+        self._check(fn(self.h, _ptr(out), len(out)))
+        return out
+
+    def _top(self, fn, k, *extra):
+        """the first k entries of a ranking: (ids, float64 values), as many as the library wrote"""
+        k = int(k)
+        ids = np.zeros(k, dtype=U128)
+        vals = np.zeros(k, dtype=np.float64)
+        w = ctypes.c_uint64(0)
+        self._check(fn(self.h, k, *extra, _ptr(ids), _ptr(vals), ctypes.byref(w)))
+        return ids[:w.value], vals[:w.value]
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.hb_destroy(self.h)
@@ -933,20 +969,17 @@ class Context:
         """hb_sampled_harmonic: the results (results / ranks / top / store_harmonic) become the sampled values; returns hb_sample_stats.
         sources: U128 array of node ids (None = the seeded sampler)."""
         o = HbSampleOptions()
-        o.struct_size = ctypes.sizeof(HbSampleOptions)
         o.max_dist, o.seed, o.samples, o.num_nodes, o.epsilon = int(max_dist), int(seed), int(samples), int(num_nodes), float(epsilon)
         if sources is not None:
             # (an empty list stays a list: the library refuses sources with source_count == 0 instead of sampling)
             count = len(sources)
-            sources = np.ascontiguousarray(sources, dtype=U128) if count else np.zeros(1, dtype=U128)
+            sources = self._u128_arg(sources, 1)
             o.sources = sources.ctypes.data
             o.source_count = count
-        st = HbSampleStats()
-        st.struct_size = ctypes.sizeof(HbSampleStats)
         self._sample_levels = 0
-        self._check(self.lib.hb_sampled_harmonic(self.h, ctypes.byref(o), ctypes.byref(st)))
-        self._sample_levels = st.levels
-        return st.as_dict()
+        st = self._call(self.lib.hb_sampled_harmonic, o, HbSampleStats)
+        self._sample_levels = st["levels"]
+        return st
 
     def sample_sources(self, seed, k):
         """hb_sample_sources: the sorted node ids the seeded sampler picks for (seed, k)."""
@@ -970,38 +1003,26 @@ class Context:
 
     def _distances(self, sources, reversed, max_dist, mode, flags):
         o = HbDistanceOptions()
-        o.struct_size = ctypes.sizeof(HbDistanceOptions)
         o.flags = int(flags) | (HB_DIST_REVERSED if reversed else 0) | self._DIST_MODES[mode]
         if max_dist is not None:
             o.flags |= HB_DIST_WITH_MAX
             o.max_dist = int(max_dist)
         count = len(sources)
-        sources = np.ascontiguousarray(sources, dtype=U128) if count else np.zeros(1, dtype=U128)
+        sources = self._u128_arg(sources, 1)
         o.sources = sources.ctypes.data
         o.source_count = count
-        st = HbDistanceStats()
-        st.struct_size = ctypes.sizeof(HbDistanceStats)
-        self._check(self.lib.hb_distances(self.h, ctypes.byref(o), ctypes.byref(st)))
-        return st.as_dict()
+        return self._call(self.lib.hb_distances, o, HbDistanceStats)
 
     def distance_count(self):
-        k = ctypes.c_uint64(0)
-        self._check(self.lib.hb_distance_count(self.h, ctypes.byref(k)))
-        return k.value
+        return self._count(self.lib.hb_distance_count)
 
     def distance_copy(self):
         """The reached nodes of the last distances() call: (ids ascending, dist uint8)."""
-        k = self.distance_count()
-        ids = np.zeros(k, dtype=U128)
-        dist = np.zeros(k, dtype=np.uint8)
-        self._check(self.lib.hb_distance_copy(self.h, _ptr(ids), _ptr(dist), k))
-        return ids, dist
+        return self._pairs(self.lib.hb_distance_count, self.lib.hb_distance_copy, np.uint8)
 
     def distance_all(self):
         """One byte per node of the last distances() call, ascending NodeID; HB_DIST_UNREACHED = no distance."""
-        out = np.full(self.n(), HB_DIST_UNREACHED, dtype=np.uint8)
-        self._check(self.lib.hb_distance_all(self.h, _ptr(out), len(out)))
-        return out
+        return self._per_node(self.lib.hb_distance_all, np.uint8, HB_DIST_UNREACHED)
 
     def distances(self, sources, reversed=False, max_dist=None, mode=None, flags=0):
         """hb_distances from `sources` (U128 array of node ids): (ids, dist, stats) - the reached nodes in ascending NodeID order with
@@ -1021,36 +1042,24 @@ class Context:
 
     def _betweenness(self, sources, raw, mode, flags=0):
         o = HbBetweennessOptions()
-        o.struct_size = ctypes.sizeof(HbBetweennessOptions)
         o.flags = int(flags) | (HB_BC_RAW if raw else 0) | self._BC_MODES[mode]
         if sources is not None:
             count = len(sources)
-            sources = np.ascontiguousarray(sources, dtype=U128) if count else np.zeros(1, dtype=U128)
+            sources = self._u128_arg(sources, 1)
             o.sources = sources.ctypes.data
             o.source_count = count
-        st = HbBetweennessStats()
-        st.struct_size = ctypes.sizeof(HbBetweennessStats)
-        self._check(self.lib.hb_betweenness(self.h, ctypes.byref(o), ctypes.byref(st)))
-        return st.as_dict()
+        return self._call(self.lib.hb_betweenness, o, HbBetweennessStats)
 
     def betweenness_count(self):
-        k = ctypes.c_uint64(0)
-        self._check(self.lib.hb_betweenness_count(self.h, ctypes.byref(k)))
-        return k.value
+        return self._count(self.lib.hb_betweenness_count)
 
     def betweenness_copy(self):
         """The results of the last betweenness() call: (ids ascending, values float64)."""
-        k = self.betweenness_count()
-        ids = np.zeros(k, dtype=U128)
-        vals = np.zeros(k, dtype=np.float64)
-        self._check(self.lib.hb_betweenness_copy(self.h, _ptr(ids), _ptr(vals), k))
-        return ids, vals
+        return self._pairs(self.lib.hb_betweenness_count, self.lib.hb_betweenness_copy, np.float64)
 
     def betweenness_all(self):
         """One float64 per node of the last betweenness() call, ascending NodeID; -1.0 = no result."""
-        out = np.full(self.n(), -1.0, dtype=np.float64)
-        self._check(self.lib.hb_betweenness_all(self.h, _ptr(out), len(out)))
-        return out
+        return self._per_node(self.lib.hb_betweenness_all, np.float64, -1.0)
 
     def betweenness(self, sources=None, raw=False, mode=None, flags=0):
         """hb_betweenness from `sources` (U128 array of node ids; None = every node of a graph of at most 100 000): (ids, vals, stats) -
@@ -1078,30 +1087,23 @@ class Context:
         allowed); returns the stats.  mode: None / "dense" / "sparse" (forced kind of count level).  limit: 0 = whole in-lists,
         1 .. 1024 = every BitVec from the `limit` best backlinks under the current key set (links_set_keys); the reference uses 512."""
         o = HbSimilarityOptions()
-        o.struct_size = ctypes.sizeof(HbSimilarityOptions)
         o.limit = int(limit)
         o.flags = int(flags) | (HB_SIM_NORMALIZED if normalized else 0) | self._SIM_MODES[mode]
         if self_score is not None:
             o.flags |= HB_SIM_SELF_SCORE
             o.self_score = float(self_score)
-        liked = np.ascontiguousarray(liked, dtype=U128) if len(liked) else np.zeros(0, dtype=U128)
-        disliked = np.ascontiguousarray(disliked, dtype=U128) if len(disliked) else np.zeros(0, dtype=U128)
+        liked, disliked = self._u128_arg(liked, 0), self._u128_arg(disliked, 0)
         if len(liked):
             o.liked = liked.ctypes.data
             o.liked_count = len(liked)
         if len(disliked):
             o.disliked = disliked.ctypes.data
             o.disliked_count = len(disliked)
-        st = HbSimilarityStats()
-        st.struct_size = ctypes.sizeof(HbSimilarityStats)
-        self._check(self.lib.hb_inbound_similarity(self.h, ctypes.byref(o), ctypes.byref(st)))
-        return st.as_dict()
+        return self._call(self.lib.hb_inbound_similarity, o, HbSimilarityStats)
 
     def similarity_all(self):
         """One float64 per node of the last inbound_similarity() call, ascending NodeID."""
-        out = np.zeros(self.n(), dtype=np.float64)
-        self._check(self.lib.hb_similarity_all(self.h, _ptr(out), len(out)))
-        return out
+        return self._per_node(self.lib.hb_similarity_all, np.float64, 0)
 
     def similarity_lookup(self, ids):
         """Scorer::score of the given hosts (U128 array); an id that is no node gets the score of an empty BitVec."""
@@ -1112,12 +1114,7 @@ class Context:
 
     def similarity_top(self, k, skip_anchors=False):
         """The k best nodes of the last inbound_similarity() call: (ids, scores), score descending, ties by NodeID descending."""
-        k = int(k)
-        ids = np.zeros(k, dtype=U128)
-        vals = np.zeros(k, dtype=np.float64)
-        w = ctypes.c_uint64(0)
-        self._check(self.lib.hb_similarity_top(self.h, k, HB_SIM_TOP_SKIP_ANCHORS if skip_anchors else 0, _ptr(ids), _ptr(vals), ctypes.byref(w)))
-        return ids[:w.value], vals[:w.value]
+        return self._top(self.lib.hb_similarity_top, k, HB_SIM_TOP_SKIP_ANCHORS if skip_anchors else 0)
 
     def debug_similarity_batch(self):
         """counts (n, 16) uint32 of the LAST batch of the last inbound_similarity() call, and the per-graph bloom masks (n) uint64 and
@@ -1135,7 +1132,6 @@ class Context:
         the smallest (key, NodeID)); returns the stats.  orig_ids / orig_vals: the original centralities (U128 / float64 arrays), or
         from_image=True for the context's live result; key_ids / keys: the order keys (U128 / uint64), unlisted nodes have 2^64 - 1."""
         o = HbNearestSeedOptions()
-        o.struct_size = ctypes.sizeof(HbNearestSeedOptions)
         o.flags = int(flags) | (HB_SEED_FROM_IMAGE if from_image else 0)
         o.discount_factor = float(discount_factor)
         o.rounds = int(rounds)
@@ -1151,38 +1147,22 @@ class Context:
             if len(key_ids) != len(keys):
                 raise ValueError("key_ids and keys differ in length")
             o.key_ids, o.keys, o.key_count = key_ids.ctypes.data, keys.ctypes.data, len(key_ids)
-        st = HbNearestSeedStats()
-        st.struct_size = ctypes.sizeof(HbNearestSeedStats)
-        self._check(self.lib.hb_nearest_seed(self.h, ctypes.byref(o), ctypes.byref(st)))
-        return st.as_dict()
+        return self._call(self.lib.hb_nearest_seed, o, HbNearestSeedStats)
 
     def nearest_seed_count(self):
-        k = ctypes.c_uint64(0)
-        self._check(self.lib.hb_nearest_seed_count(self.h, ctypes.byref(k)))
-        return k.value
+        return self._count(self.lib.hb_nearest_seed_count)
 
     def nearest_seed_copy(self):
         """The results of the last nearest_seed() call: (ids ascending, values float64)."""
-        k = self.nearest_seed_count()
-        ids = np.zeros(k, dtype=U128)
-        vals = np.zeros(k, dtype=np.float64)
-        self._check(self.lib.hb_nearest_seed_copy(self.h, _ptr(ids), _ptr(vals), k))
-        return ids, vals
+        return self._pairs(self.lib.hb_nearest_seed_count, self.lib.hb_nearest_seed_copy, np.float64)
 
     def nearest_seed_all(self):
         """One float64 per node of the last nearest_seed() call, ascending NodeID; -1.0 = no result."""
-        out = np.full(self.n(), -1.0, dtype=np.float64)
-        self._check(self.lib.hb_nearest_seed_all(self.h, _ptr(out), len(out)))
-        return out
+        return self._per_node(self.lib.hb_nearest_seed_all, np.float64, -1.0)
 
     def nearest_seed_top(self, k):
         """The k best results of the last nearest_seed() call: (ids, values), value descending, ties by NodeID ASCENDING."""
-        k = int(k)
-        ids = np.zeros(k, dtype=U128)
-        vals = np.zeros(k, dtype=np.float64)
-        w = ctypes.c_uint64(0)
-        self._check(self.lib.hb_nearest_seed_top(self.h, k, _ptr(ids), _ptr(vals), ctypes.byref(w)))
-        return ids[:w.value], vals[:w.value]
+        return self._top(self.lib.hb_nearest_seed_top, k)
 
     def nearest_seed_seeds(self):
         """seed(v) of every node of the last nearest_seed() call, ascending NodeID: (ids U128, has_seed bool)."""
@@ -1197,7 +1177,6 @@ class Context:
         """hb_links_set_keys: the order keys of the backlink lists (U128 / uint64 arrays; unlisted nodes have 2^64 - 1), or
         from_ranks=True for the harmonic ranks of the context's live result; builds the dense order on the device.  Returns the stats."""
         o = HbLinksKeyOptions()
-        o.struct_size = ctypes.sizeof(HbLinksKeyOptions)
         o.flags = int(flags) | (HB_LINKS_KEYS_FROM_RANKS if from_ranks else 0)
         if key_ids is not None and len(key_ids):
             key_ids = np.ascontiguousarray(key_ids, dtype=U128)
@@ -1205,10 +1184,7 @@ class Context:
             if len(key_ids) != len(keys):
                 raise ValueError("key_ids and keys differ in length")
             o.key_ids, o.keys, o.key_count = key_ids.ctypes.data, keys.ctypes.data, len(key_ids)
-        st = HbLinksKeyStats()
-        st.struct_size = ctypes.sizeof(HbLinksKeyStats)
-        self._check(self.lib.hb_links_set_keys(self.h, ctypes.byref(o), ctypes.byref(st)))
-        return st.as_dict()
+        return self._call(self.lib.hb_links_set_keys, o, HbLinksKeyStats)
 
     def backlinks(self, nodes, limit, flags=0, slots_per_batch=0):
         """hb_backlinks: the first `limit` in-neighbours of every node of `nodes` (U128 array) in the order (key, NodeID); returns the
@@ -1222,17 +1198,13 @@ class Context:
 
     def _links_query(self, call, nodes, limit, flags, slots_per_batch):
         o = HbLinksOptions()
-        o.struct_size = ctypes.sizeof(HbLinksOptions)
         o.flags = int(flags)
         nodes = np.ascontiguousarray(nodes, dtype=U128)
         if len(nodes):
             o.nodes, o.node_count = nodes.ctypes.data, len(nodes)
         o.limit = int(limit)
         o.slots_per_batch = int(slots_per_batch)
-        st = HbLinksStats()
-        st.struct_size = ctypes.sizeof(HbLinksStats)
-        self._check(call(self.h, ctypes.byref(o), ctypes.byref(st)))
-        return st.as_dict()
+        return self._call(call, o, HbLinksStats)
 
     def links_count(self):
         """(queries, entries) of the last backlinks() / forwardlinks() call"""
@@ -1256,25 +1228,16 @@ class Context:
         """hb_similar_hosts: the `limit` hosts most similar to the liked hosts `nodes` (U128 array, caller order; duplicates and unknown
         ids count); returns the stats, similar_copy() the list, similar_candidates() the co-citation pre-selection."""
         o = HbSimilarOptions()
-        o.struct_size = ctypes.sizeof(HbSimilarOptions)
         o.flags = int(flags)
         nodes = np.ascontiguousarray(nodes, dtype=U128)
         if len(nodes):
             o.nodes, o.node_count = nodes.ctypes.data, len(nodes)
         o.limit = int(limit)
-        st = HbSimilarStats()
-        st.struct_size = ctypes.sizeof(HbSimilarStats)
-        self._check(self.lib.hb_similar_hosts(self.h, ctypes.byref(o), ctypes.byref(st)))
-        return st.as_dict()
+        return self._call(self.lib.hb_similar_hosts, o, HbSimilarStats)
 
     def similar_copy(self):
         """(ids U128, scores float64) of the last similar_hosts() call, best first"""
-        k = ctypes.c_uint64(0)
-        self._check(self.lib.hb_similar_count(self.h, ctypes.byref(k)))
-        ids = np.zeros(k.value, dtype=U128)
-        scores = np.zeros(k.value, dtype=np.float64)
-        self._check(self.lib.hb_similar_copy(self.h, _ptr(ids), _ptr(scores), k.value))
-        return ids, scores
+        return self._pairs(self.lib.hb_similar_count, self.lib.hb_similar_copy, np.float64)
 
     def similar_candidates(self):
         """(ids U128, counts uint64): the pre-selection of the last similar_hosts() call after the liked hosts were dropped, in its order"""
@@ -1293,7 +1256,7 @@ class Context:
         keep = []  # (the arrays the request structs point into)
 
         def arr(a):
-            a = np.ascontiguousarray(a, dtype=U128) if a is not None and len(a) else np.zeros(0, dtype=U128)
+            a = self._u128_arg(a, 0)
             keep.append(a)
             return (a.ctypes.data if len(a) else None), len(a)
 
@@ -1307,16 +1270,12 @@ class Context:
                 q.flags |= HB_SIM_SELF_SCORE
                 q.self_score = float(r["self_score"])
         o = HbScoreOptions()
-        o.struct_size = ctypes.sizeof(HbScoreOptions)
         o.flags = int(flags) | (HB_SCORE_SMALL_PIECES if small_pieces else 0)
         if len(requests):
             o.requests, o.request_count = reqs, len(requests)
         o.limit = int(limit)
         o.slots_per_batch = int(slots_per_batch)
-        st = HbScoreStats()
-        st.struct_size = ctypes.sizeof(HbScoreStats)
-        self._check(self.lib.hb_score_hosts(self.h, ctypes.byref(o), ctypes.byref(st)))
-        return st.as_dict()
+        return self._call(self.lib.hb_score_hosts, o, HbScoreStats)
 
     def score_copy(self):
         """The scores of the last score_hosts() call: one float64 array per request, in request order, one value per node entry"""
@@ -1329,19 +1288,12 @@ class Context:
 
     # -- results
     def results(self):
-        k = ctypes.c_uint64(0)
-        self._check(self.lib.hb_result_count(self.h, ctypes.byref(k)))
-        ids = np.zeros(k.value, dtype=U128)
-        vals = np.zeros(k.value, dtype=np.float64)
-        self._check(self.lib.hb_result_copy(self.h, _ptr(ids), _ptr(vals), k.value))
-        return ids, vals
+        return self._pairs(self.lib.hb_result_count, self.lib.hb_result_copy, np.float64)
 
     def ranks(self):
         """harmonic_rank of every result (store_harmonic order), aligned with results()."""
-        k = ctypes.c_uint64(0)
-        self._check(self.lib.hb_result_count(self.h, ctypes.byref(k)))
-        out = np.zeros(k.value, dtype=np.uint64)
-        self._check(self.lib.hb_result_ranks(self.h, _ptr(out), k.value))
+        out = np.zeros(self._count(self.lib.hb_result_count), dtype=np.uint64)
+        self._check(self.lib.hb_result_ranks(self.h, _ptr(out), len(out)))
         return out
 
     def store_harmonic(self, output):
@@ -1353,14 +1305,7 @@ class Context:
 
     def top(self, k):
         """top_nodes(TopNodes::Top(k)) (centrality/mod.rs:33-52): (ids, vals), largest centrality first."""
-        cnt = ctypes.c_uint64(0)
-        self._check(self.lib.hb_result_count(self.h, ctypes.byref(cnt)))
-        k = min(int(k), cnt.value)
-        ids = np.zeros(k, dtype=U128)
-        vals = np.zeros(k, dtype=np.float64)
-        w = ctypes.c_uint64(0)
-        self._check(self.lib.hb_result_top(self.h, k, _ptr(ids), _ptr(vals), ctypes.byref(w)))
-        return ids[:w.value], vals[:w.value]
+        return self._top(self.lib.hb_result_top, min(int(k), self._count(self.lib.hb_result_count)))
 
     # -- debug exports
     def n(self):

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "hb_owned.h" // (after hb_pool.h: DevPtr frees through the allocator this file sees)
@@ -66,6 +67,29 @@ struct OwnedCsr {
     }
 };
 } // namespace
+
+// The tail end of a node-valued operator (hb_distances, hb_betweenness, hb_nearest_seed): one value per node in sid order, and the
+// compacted list of the sids that have one, which is all that hb_*_copy downloads.  Allocated, compacted and read by node_result_*
+// (hb_api_walk.inc).  T = uint8_t (distances): the values ARE the select's flag bytes and its byte output ARE the selected values, so
+// d_flag_sid / d_sel_val alias d_val_sid / d_sel_flag - no second value buffer, no gather
+template <class T>
+struct NodeResult {
+    static constexpr bool kBytes = std::is_same<T, uint8_t>::value;
+    bool valid = false;            // the buffers hold the result of a finished call (an empty graph: no buffers, count == 0)
+    bool compacted = false;        // d_sel_* and d_val_sid describe that result (distances: made by the first reader that needs them)
+    T *d_val_sid = nullptr;        // n: value per sid
+    uint8_t *d_flag_sid = nullptr; // n: 255 = no value (the select's input)
+    uint32_t *d_sel_sid = nullptr; // n: the sids that have a value, ascending
+    uint8_t *d_sel_flag = nullptr; // n: the select's byte output
+    T *d_sel_val = nullptr;        // n: their values
+    uint64_t *d_sel_cnt = nullptr; // the select's count word
+    uint64_t count = 0;            // entries of the compacted list
+    void reset() // a new call begins: nothing to read until it has finished
+    {
+        valid = compacted = false;
+        count = 0;
+    }
+};
 
 // ---- graph lifetime ---------------------------------------------------------------------------------------------------------------
 // What describes the loaded graph on the device: written by plan_and_upload (and, on first use after a load, by the operators), gone
@@ -166,8 +190,6 @@ struct GraphDeviceState {
     // hb_distances (hb_api_distance.inc): the BFS state and the last result, dev_alloc'ed at the first call after a load
     struct DistanceState {
         bool ready = false;     // the buffers below exist
-        bool valid = false;     // they hold the result of a finished hb_distances
-        bool extracted = false; // d_by_sid / d_sel_* describe that result
         uint8_t *d_dist = nullptr;                                       // n_pad: distance per device row, 255 = unreached
         uint32_t *d_vis = nullptr, *d_front = nullptr, *d_next = nullptr; // one bit per row (hb_bfs.hip.h)
         uint32_t *d_heavy = nullptr;
@@ -176,17 +198,12 @@ struct GraphDeviceState {
         unsigned long long *d_cnt = nullptr; // 256 levels x 4 counters
         uint32_t *d_indeg = nullptr;         // rows_total: node sources under every row (reversed switch rule), built at the first reversed call
         bool indeg_valid = false;
-        uint8_t *d_by_sid = nullptr;         // n: distance per sid
-        uint32_t *d_sel_sid = nullptr;       // n: the reached sids, ascending
-        uint8_t *d_sel_dist = nullptr;       // n: their distances
-        uint64_t *d_sel_cnt = nullptr;
         uint64_t words_total = 0;            // words of d_vis / d_next
-        uint64_t reached = 0;
+        NodeResult<uint8_t> res;             // distance per sid and the reached sids; count = reached, known before the lazy compaction
     } dst;
     // hb_betweenness (hb_api_betweenness.inc): the per-batch state, the sums and the last result, dev_alloc'ed at the first call after a load
     struct BetweennessState {
         bool ready = false; // the buffers below exist
-        bool valid = false; // they hold the result of a finished hb_betweenness
         uint8_t *d_dist = nullptr;             // n_pad x 8: distance per device row and lane of the current batch, 255 = unreached
         unsigned long long *d_sigma = nullptr; // n_pad x 8: shortest-path counts
         double *d_delta = nullptr;             // n_pad x 8: dependencies
@@ -198,13 +215,7 @@ struct GraphDeviceState {
         unsigned int *d_heavy_cnt = nullptr;
         uint32_t heavy_cap = 0;                // such rows in the loaded graph (0 = none: no list, no launches)
         hbk::bc_d2 *d_seg = nullptr;           // ... their per-segment partial sums
-        double *d_val_sid = nullptr;           // n: value per sid, -1.0 = no result
-        uint8_t *d_flag_sid = nullptr;         // n: 0 = result, 255 = none (the select's input)
-        uint32_t *d_sel_sid = nullptr;         // n: the results' sids, ascending
-        uint8_t *d_sel_flag = nullptr;
-        double *d_sel_val = nullptr;           // n: their values
-        uint64_t *d_sel_cnt = nullptr;
-        uint64_t results = 0;
+        NodeResult<double> res;                // value per sid, -1.0 = no result; flag 0 = result
         uint64_t bytes = 0;                    // device bytes of the above
         uint32_t last_lanes = 0;               // sources of the last batch run (0 = none)
     } btw;
@@ -236,7 +247,6 @@ struct GraphDeviceState {
     // the first call after a load.  The operator borrows nothing of the HyperBall state
     struct NearestSeedState {
         bool ready = false; // the buffers below exist
-        bool valid = false; // they hold the result of a finished hb_nearest_seed
         uint4 *d_cand = nullptr;                 // n_pad: {key, sid} of the row's node, {~0, kNone} for padding rows
         uint4 *d_part = nullptr;                 // nv x 2: the two best distinct candidates under a chunk row
         uint32_t *d_seed_row = nullptr;          // n_pad: device row of the seed, kNone = none
@@ -246,16 +256,10 @@ struct GraphDeviceState {
         double *d_up_val = nullptr;              // n: the caller's original values by sid
         uint8_t *d_up_has = nullptr;             // n: ... and which sids have one
         unsigned long long *d_cnt = nullptr;     // kCounterWords striped words of a round + 4 plain counters
-        double *d_val_sid = nullptr;             // n: value per sid, -1.0 = no result
-        uint8_t *d_flag_sid = nullptr;           // n: 0 = result, 255 = none (the select's input)
+        NodeResult<double> res;                  // value per sid, -1.0 = no result; flag 0 = result
         uint32_t *d_seed_sid = nullptr;          // n: the seed of every sid as a sid, kNone = none
-        uint32_t *d_sel_sid = nullptr;           // n: the results' sids, ascending
-        uint8_t *d_sel_flag = nullptr;
-        double *d_sel_val = nullptr;             // n: their values
-        uint64_t *d_sel_cnt = nullptr;
         uint64_t *d_top_key = nullptr;           // n: hb_nearest_seed_top's sort keys, reversed sid order
         uint8_t *d_top_keep = nullptr;           // n: ... and which entries are results
-        uint64_t results = 0;
         uint64_t bytes = 0;                      // device bytes of the above
     } nst;
     // hb_links_set_keys / hb_backlinks / hb_forwardlinks (hb_api_links.inc): the key set and its dense order, the buffers of a batch and the last result.

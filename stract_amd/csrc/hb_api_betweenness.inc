@@ -21,12 +21,7 @@ int betweenness_alloc(hb_ctx *c)
     if ((rc = dev_alloc(c, &b.d_sum, p.n_pad))) return rc;
     if ((rc = dev_alloc(c, &b.d_cnt, 257 * 4))) return rc;
     if ((rc = dev_alloc(c, &b.d_srcs, hbk::kBcLanes))) return rc;
-    if ((rc = dev_alloc(c, &b.d_val_sid, p.n))) return rc;
-    if ((rc = dev_alloc(c, &b.d_flag_sid, p.n))) return rc;
-    if ((rc = dev_alloc(c, &b.d_sel_sid, p.n))) return rc;
-    if ((rc = dev_alloc(c, &b.d_sel_flag, p.n))) return rc;
-    if ((rc = dev_alloc(c, &b.d_sel_val, p.n))) return rc;
-    if ((rc = dev_alloc(c, &b.d_sel_cnt, 8))) return rc;
+    if ((rc = node_result_alloc(c, b.res))) return rc;
     if ((rc = ensure_transpose(c, "hb_betweenness"))) return rc;
     // node rows whose reader list the grid sums: their number is the capacity of the heavy list (0 = those kernels are never launched)
     HB_HIP(hipMemsetAsync(b.d_cnt, 0, 4 * sizeof(unsigned long long), c->stream));
@@ -54,21 +49,9 @@ int betweenness_extract(hb_ctx *c, uint64_t S, bool raw)
     const double s = (double)S;
     const double norm = s * (s - 1.0); // betweenness.rs:128-129
     hipLaunchKernelGGL(hbk::bc_result_kernel, dim3(grid_blocks(c, (p.n + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const double *)b.d_sum,
-                       (const uint8_t *)b.d_reached, (const uint32_t *)c->d_dev_of, p.n, p.n_pad, raw ? 1 : 0, norm, b.d_val_sid, b.d_flag_sid);
+                       (const uint8_t *)b.d_reached, (const uint32_t *)c->d_dev_of, p.n, p.n_pad, raw ? 1 : 0, norm, b.res.d_val_sid, b.res.d_flag_sid);
     HB_HIP(hipGetLastError());
-    const std::string e = gpu_select_reached((void *)c->stream, b.d_flag_sid, p.n, b.d_sel_sid, b.d_sel_flag, b.d_sel_cnt);
-    if (!e.empty()) return fail(c, HB_ERR_HIP, "hb_betweenness: " + e);
-    uint64_t got = 0;
-    HB_HIP(hipMemcpyAsync(&got, b.d_sel_cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HB_HIP(hipStreamSynchronize(c->stream));
-    if (got) {
-        hipLaunchKernelGGL(hbk::bc_gather_kernel, dim3(grid_blocks(c, (got + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const double *)b.d_val_sid,
-                           (const uint32_t *)b.d_sel_sid, got, b.d_sel_val);
-        HB_HIP(hipGetLastError());
-        HB_HIP(hipStreamSynchronize(c->stream));
-    }
-    b.results = got;
-    return HB_OK;
+    return node_result_compact(c, b.res, "hb_betweenness"); // (no counter of the operator's own: the select says how many results there are)
 }
 
 int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_stats *st_out)
@@ -83,8 +66,7 @@ int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_
     if (!o.sources && p.n > 100000)
         return fail(c, HB_ERR_INVALID, "hb_betweenness: sources == NULL means every node, which the reference limits to 100000 (betweenness.rs:34); name the sources");
     auto &b = c->btw;
-    b.valid = false;
-    b.results = 0;
+    b.res.reset();
     b.last_lanes = 0;
     hb_betweenness_stats st{};
     // the sources as distinct ascending sids
@@ -104,7 +86,7 @@ int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_
         return HB_OK;
     };
     if (p.n == 0) { // an empty graph: an empty result
-        b.valid = true;
+        b.res.valid = true;
         return finish();
     }
     if ((rc = betweenness_alloc(c))) return rc;
@@ -228,12 +210,14 @@ int betweenness(hb_ctx *c, const hb_betweenness_options *opt_in, hb_betweenness_
         st.ms_backward += ms;
     }
     if ((rc = betweenness_extract(c, S, (o.flags & HB_BC_RAW) != 0))) return rc;
-    st.results = b.results;
-    b.valid = true;
+    st.results = b.res.count;
+    b.res.valid = true;
     return finish();
 }
 
 const char *const kNoBetweenness = "no betweenness result (call hb_betweenness)";
+
+NodeResult<double> *betweenness_result(hb_ctx *c) { return c ? &c->btw.res : nullptr; }
 
 } // namespace
 
@@ -244,47 +228,21 @@ int hb_betweenness(hb_ctx *c, const hb_betweenness_options *opt, hb_betweenness_
     return operator_entry(c, "hb_betweenness", [&]() { return betweenness(c, opt, stats); });
 }
 
-int hb_betweenness_count(hb_ctx *c, uint64_t *count)
-{
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        return result_count(c, c->btw.valid, "hb_betweenness_count", kNoBetweenness, count, c->btw.results);
-    });
-}
+int hb_betweenness_count(hb_ctx *c, uint64_t *count) { return node_result_count(c, betweenness_result(c), "hb_betweenness_count", kNoBetweenness, count); }
 
 int hb_betweenness_copy(hb_ctx *c, hb_u128 *ids, double *vals, uint64_t cap)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        int rc = result_ready(c, c->btw.valid, "hb_betweenness_copy", kNoBetweenness);
-        if (rc) return rc;
-        auto &b = c->btw;
-        const uint64_t k = std::min<uint64_t>(cap, b.results);
-        if (!k || (!ids && !vals)) return HB_OK;
-        // only the results come down: k sids and k values
-        if (ids && (rc = copy_selected_ids(c, b.d_sel_sid, k, ids))) return rc;
-        if (vals) {
-            HB_HIP(hipMemcpyAsync(vals, b.d_sel_val, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            HB_HIP(hipStreamSynchronize(c->stream));
-        }
-        return HB_OK;
-    });
+    return node_result_copy(c, betweenness_result(c), "hb_betweenness_copy", kNoBetweenness, ids, vals, cap);
 }
 
 int hb_betweenness_all(hb_ctx *c, double *vals, uint64_t cap)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        return result_all<double>(c, c->btw.valid, "hb_betweenness_all", "vals", kNoBetweenness, vals, cap, c->btw.d_val_sid);
-    });
+    return node_result_all(c, betweenness_result(c), "hb_betweenness_all", "vals", kNoBetweenness, vals, cap);
 }
 
 int hb_debug_copy_betweenness_batch(hb_ctx *c, uint8_t *dist, uint64_t *sigma, double *delta)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        int rc = result_ready(c, c->btw.valid, "hb_debug_copy_betweenness_batch", kNoBetweenness);
-        if (rc) return rc;
+    return reader_entry(c, c && c->btw.res.valid, "hb_debug_copy_betweenness_batch", kNoBetweenness, [&]() -> int {
         const Plan &p = c->plan;
         auto &b = c->btw;
         if (!p.n) return HB_OK;

@@ -36,10 +36,7 @@ int distance_alloc(hb_ctx *c)
     if ((rc = dev_alloc(c, &d.d_heavy, d.heavy_cap))) return rc;
     if ((rc = dev_alloc(c, &d.d_heavy_cnt, 64))) return rc;
     if ((rc = dev_alloc(c, &d.d_cnt, 256 * 4))) return rc;
-    if ((rc = dev_alloc(c, &d.d_by_sid, p.n))) return rc;
-    if ((rc = dev_alloc(c, &d.d_sel_sid, p.n))) return rc;
-    if ((rc = dev_alloc(c, &d.d_sel_dist, p.n))) return rc;
-    if ((rc = dev_alloc(c, &d.d_sel_cnt, 8))) return rc;
+    if ((rc = node_result_alloc(c, d.res))) return rc;
     if ((rc = ensure_transpose(c, "hb_distances"))) return rc;
     HB_HIP(hipMemsetAsync(d.d_next, 0, d.words_total * sizeof(uint32_t), c->stream)); // all-zero between levels from here on
     HB_HIP(hipMemsetAsync(d.d_heavy_cnt, 0, 64 * sizeof(unsigned int), c->stream));
@@ -81,8 +78,7 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
     if ((o.flags & HB_DIST_WITH_MAX) && o.max_dist > 255) return fail(c, HB_ERR_INVALID, "hb_distances: max_dist > 255 (the reference's is a u8)");
     const Plan &p = c->plan;
     auto &d = c->dst;
-    d.valid = d.extracted = false;
-    d.reached = 0;
+    d.res.reset();
     hb_distance_stats st{};
     auto finish = [&]() {
         st.ms_total = now_ms() - t0;
@@ -92,7 +88,7 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
     std::vector<uint32_t> sids;
     resolve_sources(c, o.sources, o.source_count, &sids, &st.unknown_sources);
     if (p.n == 0) { // an empty graph: every source is unknown
-        d.valid = true;
+        d.res.valid = true;
         return finish();
     }
     if ((rc = distance_alloc(c))) return rc;
@@ -203,32 +199,24 @@ int distances(hb_ctx *c, const hb_distance_options *opt_in, hb_distance_stats *s
     float ms = 0.f;
     HB_HIP(hipEventElapsedTime(&ms, c->ev[kEvStart], c->ev[kEvEnd]));
     st.ms_levels = ms;
-    d.reached = st.reached;
-    d.valid = true;
+    d.res.count = st.reached; // (the compaction, made by the first reader, checks its own count against this one)
+    d.res.valid = true;
     return finish();
 }
 
-// the result in sid order and its compacted form, on the device (once per result)
-int distance_extract(hb_ctx *c)
+// the result in sid order and its compacted form, on the device: once per result, made by the first reader that copies something
+int distance_compact(hb_ctx *c)
 {
     auto &d = c->dst;
-    if (d.extracted) return HB_OK;
+    if (d.res.compacted) return HB_OK;
     const Plan &p = c->plan;
-    if (p.n && d.ready) {
-        const unsigned blocks = grid_blocks(c, (p.n + 255) / 256, 8, 1);
-        hipLaunchKernelGGL(hbk::bfs_by_sid_kernel, dim3(blocks), dim3(256), 0, c->stream, (const uint8_t *)d.d_dist, (const uint32_t *)c->d_dev_of, p.n, p.n_pad,
-                           d.d_by_sid);
-        HB_HIP(hipGetLastError());
-        const std::string e = gpu_select_reached((void *)c->stream, d.d_by_sid, p.n, d.d_sel_sid, d.d_sel_dist, d.d_sel_cnt);
-        if (!e.empty()) return fail(c, HB_ERR_HIP, "hb_distance_copy: " + e);
-        uint64_t got = 0;
-        HB_HIP(hipMemcpyAsync(&got, d.d_sel_cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        HB_HIP(hipStreamSynchronize(c->stream));
-        if (got != d.reached) return fail(c, HB_ERR_INVALID, "hb_distance_copy: the compacted list and the level counters disagree");
-    }
-    d.extracted = true;
-    return HB_OK;
+    hipLaunchKernelGGL(hbk::bfs_by_sid_kernel, dim3(grid_blocks(c, (p.n + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const uint8_t *)d.d_dist, (const uint32_t *)c->d_dev_of,
+                       p.n, p.n_pad, d.res.d_val_sid);
+    HB_HIP(hipGetLastError());
+    return node_result_compact(c, d.res, "hb_distance_copy", &d.res.count, "level counters"); // (count = what the levels reached)
 }
+
+NodeResult<uint8_t> *distance_result(hb_ctx *c) { return c ? &c->dst.res : nullptr; }
 
 const char *const kNoDistances = "no distances (call hb_distances)";
 
@@ -241,40 +229,16 @@ int hb_distances(hb_ctx *c, const hb_distance_options *opt, hb_distance_stats *s
     return operator_entry(c, "hb_distances", [&]() { return distances(c, opt, stats); });
 }
 
-int hb_distance_count(hb_ctx *c, uint64_t *count)
-{
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        return result_count(c, c->dst.valid, "hb_distance_count", kNoDistances, count, c->dst.reached);
-    });
-}
+int hb_distance_count(hb_ctx *c, uint64_t *count) { return node_result_count(c, distance_result(c), "hb_distance_count", kNoDistances, count); }
 
 int hb_distance_copy(hb_ctx *c, hb_u128 *ids, uint8_t *dist, uint64_t cap)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        int rc = result_ready(c, c->dst.valid, "hb_distance_copy", kNoDistances);
-        if (rc) return rc;
-        auto &d = c->dst;
-        const uint64_t k = std::min<uint64_t>(cap, d.reached);
-        if (!k || (!ids && !dist)) return HB_OK;
-        if ((rc = distance_extract(c))) return rc;
-        // only the reached nodes come down: k sids (and k bytes)
-        if (ids && (rc = copy_selected_ids(c, d.d_sel_sid, k, ids))) return rc;
-        if (dist) {
-            HB_HIP(hipMemcpyAsync(dist, d.d_sel_dist, k, hipMemcpyDeviceToHost, c->stream));
-            HB_HIP(hipStreamSynchronize(c->stream));
-        }
-        return HB_OK;
-    });
+    return node_result_copy(c, distance_result(c), "hb_distance_copy", kNoDistances, ids, dist, cap, distance_compact);
 }
 
 int hb_distance_all(hb_ctx *c, uint8_t *dist, uint64_t cap)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        return result_all<uint8_t>(c, c->dst.valid, "hb_distance_all", "dist", kNoDistances, dist, cap, c->dst.d_by_sid, distance_extract);
-    });
+    return node_result_all(c, distance_result(c), "hb_distance_all", "dist", kNoDistances, dist, cap, distance_compact);
 }
 
 } // extern "C"

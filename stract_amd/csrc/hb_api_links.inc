@@ -428,10 +428,7 @@ int hb_forwardlinks(hb_ctx *c, const hb_links_options *opt, hb_links_stats *stat
 
 int hb_links_count(hb_ctx *c, uint64_t *queries, uint64_t *entries)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        const int rc = result_ready(c, c->lnk.valid, "hb_links_count", kNoBacklinks);
-        if (rc) return rc;
+    return reader_entry(c, c && c->lnk.valid, "hb_links_count", kNoBacklinks, [&]() -> int {
         if (queries) *queries = c->lnk.query_slot.size();
         if (entries) *entries = c->lnk.entries;
         return HB_OK;
@@ -440,10 +437,7 @@ int hb_links_count(hb_ctx *c, uint64_t *queries, uint64_t *entries)
 
 int hb_links_copy(hb_ctx *c, uint64_t *offsets, uint64_t *degrees, hb_u128 *ids, uint64_t *keys, uint64_t cap)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        int rc = result_ready(c, c->lnk.valid, "hb_links_copy", kNoBacklinks);
-        if (rc) return rc;
+    return reader_entry(c, c && c->lnk.valid, "hb_links_copy", kNoBacklinks, [&]() -> int {
         auto &s = c->lnk;
         const uint64_t q = s.query_slot.size(), limit = s.limit, U = s.degree.size();
         if ((ids || keys) && cap < s.entries) return fail(c, HB_ERR_INVALID, "hb_links_copy: cap < the entries of hb_links_count");

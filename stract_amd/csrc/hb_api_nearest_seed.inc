@@ -24,13 +24,8 @@ int nearest_seed_alloc(hb_ctx *c)
     if ((rc = dev_alloc(c, &s.d_up_val, p.n))) return rc;
     if ((rc = dev_alloc(c, &s.d_up_has, p.n))) return rc;
     if ((rc = dev_alloc(c, &s.d_cnt, hbk::kCounterWords + 8))) return rc;
-    if ((rc = dev_alloc(c, &s.d_val_sid, p.n))) return rc;
-    if ((rc = dev_alloc(c, &s.d_flag_sid, p.n))) return rc;
     if ((rc = dev_alloc(c, &s.d_seed_sid, p.n))) return rc;
-    if ((rc = dev_alloc(c, &s.d_sel_sid, p.n))) return rc;
-    if ((rc = dev_alloc(c, &s.d_sel_flag, p.n))) return rc;
-    if ((rc = dev_alloc(c, &s.d_sel_val, p.n))) return rc;
-    if ((rc = dev_alloc(c, &s.d_sel_cnt, 8))) return rc;
+    if ((rc = node_result_alloc(c, s.res))) return rc;
     if ((rc = dev_alloc(c, &s.d_top_key, p.n))) return rc;
     if ((rc = dev_alloc(c, &s.d_top_keep, p.n))) return rc;
     s.bytes = c->stats.device_bytes - before;
@@ -93,10 +88,9 @@ int nearest_seed(hb_ctx *c, const hb_nearest_seed_options *opt_in, hb_nearest_se
             up_has[sids[i]] = 1;
         }
     }
-    s.valid = false;
-    s.results = 0;
+    s.res.reset();
     if (n == 0) { // an empty graph: an empty result
-        s.valid = true;
+        s.res.valid = true;
         return finish();
     }
     if ((rc = nearest_seed_alloc(c))) return rc;
@@ -160,31 +154,21 @@ int nearest_seed(hb_ctx *c, const hb_nearest_seed_options *opt_in, hb_nearest_se
     HB_HIP(hipMemsetAsync(cnt4, 0, 4 * sizeof(unsigned long long), c->stream));
     if ((rc = lap_start(c))) return rc;
     hipLaunchKernelGGL(hbk::ns_by_sid_kernel, dim3(sid_blocks), dim3(256), 0, c->stream, (const double *)s.d_val[cur], (const uint8_t *)s.d_has[cur],
-                       (const uint32_t *)s.d_seed_row, (const uint32_t *)c->d_dev_of, (const uint32_t *)c->d_sid_of, n, n_pad, s.d_val_sid, s.d_flag_sid, s.d_seed_sid, cnt4);
+                       (const uint32_t *)s.d_seed_row, (const uint32_t *)c->d_dev_of, (const uint32_t *)c->d_sid_of, n, n_pad, s.res.d_val_sid, s.res.d_flag_sid, s.d_seed_sid, cnt4);
     HB_HIP(hipGetLastError());
     HB_HIP(hipMemcpyAsync(h, cnt4, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     if ((rc = lap(c, &st.ms_fill))) return rc;
     st.results = h[0];
     st.no_seed = h[1];
     st.seed_without_value = h[2];
-    const std::string e = gpu_select_reached((void *)c->stream, s.d_flag_sid, n, s.d_sel_sid, s.d_sel_flag, s.d_sel_cnt);
-    if (!e.empty()) return fail(c, HB_ERR_HIP, "hb_nearest_seed: " + e);
-    uint64_t got = 0;
-    HB_HIP(hipMemcpyAsync(&got, s.d_sel_cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HB_HIP(hipStreamSynchronize(c->stream));
-    if (got != st.results) return fail(c, HB_ERR_INVALID, "hb_nearest_seed: the compacted list and the counters disagree");
-    if (got) {
-        hipLaunchKernelGGL(hbk::bc_gather_kernel, dim3(grid_blocks(c, (got + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const double *)s.d_val_sid,
-                           (const uint32_t *)s.d_sel_sid, got, s.d_sel_val);
-        HB_HIP(hipGetLastError());
-        HB_HIP(hipStreamSynchronize(c->stream));
-    }
-    s.results = got;
-    s.valid = true;
+    if ((rc = node_result_compact(c, s.res, "hb_nearest_seed", &st.results))) return rc;
+    s.res.valid = true;
     return finish();
 }
 
 const char *const kNoNearestSeed = "no nearest-seed result (call hb_nearest_seed)";
+
+NodeResult<double> *nearest_seed_result(hb_ctx *c) { return c ? &c->nst.res : nullptr; }
 
 } // namespace
 
@@ -195,75 +179,36 @@ int hb_nearest_seed(hb_ctx *c, const hb_nearest_seed_options *opt, hb_nearest_se
     return operator_entry(c, "hb_nearest_seed", [&]() { return nearest_seed(c, opt, stats); });
 }
 
-int hb_nearest_seed_count(hb_ctx *c, uint64_t *count)
-{
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        return result_count(c, c->nst.valid, "hb_nearest_seed_count", kNoNearestSeed, count, c->nst.results);
-    });
-}
+int hb_nearest_seed_count(hb_ctx *c, uint64_t *count) { return node_result_count(c, nearest_seed_result(c), "hb_nearest_seed_count", kNoNearestSeed, count); }
 
 int hb_nearest_seed_copy(hb_ctx *c, hb_u128 *ids, double *vals, uint64_t cap)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        int rc = result_ready(c, c->nst.valid, "hb_nearest_seed_copy", kNoNearestSeed);
-        if (rc) return rc;
-        auto &s = c->nst;
-        const uint64_t k = std::min<uint64_t>(cap, s.results);
-        if (!k || (!ids && !vals)) return HB_OK;
-        // only the results come down: k sids and k values
-        if (ids && (rc = copy_selected_ids(c, s.d_sel_sid, k, ids))) return rc;
-        if (vals) {
-            HB_HIP(hipMemcpyAsync(vals, s.d_sel_val, k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            HB_HIP(hipStreamSynchronize(c->stream));
-        }
-        return HB_OK;
-    });
+    return node_result_copy(c, nearest_seed_result(c), "hb_nearest_seed_copy", kNoNearestSeed, ids, vals, cap);
 }
 
 int hb_nearest_seed_all(hb_ctx *c, double *vals, uint64_t cap)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        return result_all<double>(c, c->nst.valid, "hb_nearest_seed_all", "vals", kNoNearestSeed, vals, cap, c->nst.d_val_sid);
-    });
+    return node_result_all(c, nearest_seed_result(c), "hb_nearest_seed_all", "vals", kNoNearestSeed, vals, cap);
 }
 
 int hb_nearest_seed_top(hb_ctx *c, uint64_t k, hb_u128 *ids, double *vals, uint64_t *written)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        if (written) *written = 0;
-        int rc = result_ready(c, c->nst.valid, "hb_nearest_seed_top", kNoNearestSeed);
-        if (rc) return rc;
+    return reader_entry(c, c && c->nst.res.valid, "hb_nearest_seed_top", kNoNearestSeed, [&]() -> int {
         const uint64_t n = c->plan.n;
         auto &s = c->nst;
-        const uint64_t top = std::min<uint64_t>(k, s.results);
+        const uint64_t top = std::min<uint64_t>(k, s.res.count);
         if (!top) return HB_OK;
-        hipLaunchKernelGGL(hbk::ns_top_keys_kernel, dim3(grid_blocks(c, (n + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const double *)s.d_val_sid,
-                           (const uint8_t *)s.d_flag_sid, n, s.d_top_key, s.d_top_keep);
+        hipLaunchKernelGGL(hbk::ns_top_keys_kernel, dim3(grid_blocks(c, (n + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const double *)s.res.d_val_sid,
+                           (const uint8_t *)s.res.d_flag_sid, n, s.d_top_key, s.d_top_keep);
         HB_HIP(hipGetLastError());
-        std::vector<uint32_t> at(top);
-        std::vector<uint64_t> key(top);
-        uint64_t got = 0;
-        const std::string e = gpu_similarity_top((void *)c->stream, s.d_top_key, s.d_top_keep, n, top, at.data(), key.data(), &got);
-        if (!e.empty()) return fail(c, e.find("out of memory") != std::string::npos ? HB_ERR_NOMEM : HB_ERR_HIP, "hb_nearest_seed_top: " + e);
-        for (uint64_t i = 0; i < got; i++) {
-            if (ids) ids[i] = c->g.ids[n - 1 - at[i]]; // (entry i of the keys is sid n - 1 - i: ns_top_keys_kernel)
-            if (vals) std::memcpy(&vals[i], &key[i], sizeof(double));
-        }
-        if (written) *written = got;
-        return HB_OK;
-    });
+        // (entry i of the keys is sid n - 1 - i: ns_top_keys_kernel)
+        return result_top(c, "hb_nearest_seed_top", s.d_top_key, s.d_top_keep, n, top, [n](uint32_t at) { return n - 1 - at; }, ids, vals, written);
+    }, written);
 }
 
 int hb_nearest_seed_seeds(hb_ctx *c, hb_u128 *seed, uint8_t *has_seed, uint64_t cap)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        int rc = result_ready(c, c->nst.valid, "hb_nearest_seed_seeds", kNoNearestSeed);
-        if (rc) return rc;
+    return reader_entry(c, c && c->nst.res.valid, "hb_nearest_seed_seeds", kNoNearestSeed, [&]() -> int {
         const uint64_t n = c->plan.n;
         if (cap < n) return fail(c, HB_ERR_INVALID, "hb_nearest_seed_seeds: cap < n");
         if (!n || (!seed && !has_seed)) return HB_OK;

@@ -263,10 +263,7 @@ int hb_score_hosts(hb_ctx *c, const hb_score_options *opt, hb_score_stats *stats
 
 int hb_score_count(hb_ctx *c, uint64_t *requests, uint64_t *scores)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        const int rc = result_ready(c, c->sco.valid, "hb_score_count", kNoScores);
-        if (rc) return rc;
+    return reader_entry(c, c && c->sco.valid, "hb_score_count", kNoScores, [&]() -> int {
         if (requests) *requests = c->sco.offsets.size() - 1;
         if (scores) *scores = c->sco.scores.size();
         return HB_OK;
@@ -275,10 +272,7 @@ int hb_score_count(hb_ctx *c, uint64_t *requests, uint64_t *scores)
 
 int hb_score_copy(hb_ctx *c, uint64_t *offsets, double *scores, uint64_t cap)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        const int rc = result_ready(c, c->sco.valid, "hb_score_copy", kNoScores);
-        if (rc) return rc;
+    return reader_entry(c, c && c->sco.valid, "hb_score_copy", kNoScores, [&]() -> int {
         const auto &s = c->sco;
         if (scores && cap < s.scores.size()) return fail(c, HB_ERR_INVALID, "hb_score_copy: cap < the scores of hb_score_count");
         if (offsets) std::copy(s.offsets.begin(), s.offsets.end(), offsets);

@@ -205,10 +205,7 @@ int hb_similar_count(hb_ctx *c, uint64_t *count)
 
 int hb_similar_copy(hb_ctx *c, hb_u128 *ids, double *scores, uint64_t cap)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        const int rc = result_ready(c, c->shs.valid, "hb_similar_copy", kNoSimilarHosts);
-        if (rc) return rc;
+    return reader_entry(c, c && c->shs.valid, "hb_similar_copy", kNoSimilarHosts, [&]() -> int {
         const auto &s = c->shs;
         if (cap < s.top_sid.size()) return fail(c, HB_ERR_INVALID, "hb_similar_copy: cap < the entries of hb_similar_count");
         for (size_t i = 0; i < s.top_sid.size(); i++) {
@@ -222,10 +219,7 @@ int hb_similar_copy(hb_ctx *c, hb_u128 *ids, double *scores, uint64_t cap)
 
 int hb_similar_candidates(hb_ctx *c, hb_u128 *ids, uint64_t *counts, uint64_t cap, uint64_t *written)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        const int rc = result_ready(c, c->shs.valid, "hb_similar_candidates", kNoSimilarHosts);
-        if (rc) return rc;
+    return reader_entry(c, c && c->shs.valid, "hb_similar_candidates", kNoSimilarHosts, [&]() -> int {
         const auto &s = c->shs;
         if (written) *written = s.cand_sid.size();
         if ((ids || counts) && cap < s.cand_sid.size()) return fail(c, HB_ERR_INVALID, "hb_similar_candidates: cap < the candidates");

@@ -367,11 +367,7 @@ int hb_similarity_lookup(hb_ctx *c, const hb_u128 *ids, uint64_t count, double *
 
 int hb_similarity_top(hb_ctx *c, uint64_t k, uint32_t flags, hb_u128 *ids, double *vals, uint64_t *written)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        if (written) *written = 0;
-        int rc = result_ready(c, c->sim.valid, "hb_similarity_top", kNoSimilarity);
-        if (rc) return rc;
+    return reader_entry(c, c && c->sim.valid, "hb_similarity_top", kNoSimilarity, [&]() -> int {
         const uint64_t n = c->plan.n;
         auto &s = c->sim;
         const uint64_t top = std::min<uint64_t>(k, n);
@@ -379,26 +375,13 @@ int hb_similarity_top(hb_ctx *c, uint64_t k, uint32_t flags, hb_u128 *ids, doubl
         hipLaunchKernelGGL(hbk::sim_top_keys_kernel, dim3(grid_blocks(c, (n + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const double *)s.d_score,
                            (const uint8_t *)s.d_anchor, (flags & HB_SIM_TOP_SKIP_ANCHORS) ? 1 : 0, n, s.d_key, s.d_keep);
         HB_HIP(hipGetLastError());
-        std::vector<uint32_t> sid(top);
-        std::vector<uint64_t> key(top);
-        uint64_t got = 0;
-        const std::string e = gpu_similarity_top((void *)c->stream, s.d_key, s.d_keep, n, top, sid.data(), key.data(), &got);
-        if (!e.empty()) return fail(c, e.find("out of memory") != std::string::npos ? HB_ERR_NOMEM : HB_ERR_HIP, "hb_similarity_top: " + e);
-        for (uint64_t i = 0; i < got; i++) {
-            if (ids) ids[i] = c->g.ids[sid[i]];
-            if (vals) std::memcpy(&vals[i], &key[i], sizeof(double));
-        }
-        if (written) *written = got;
-        return HB_OK;
-    });
+        return result_top(c, "hb_similarity_top", s.d_key, s.d_keep, n, top, [](uint32_t at) { return at; }, ids, vals, written);
+    }, written);
 }
 
 int hb_debug_copy_similarity_batch(hb_ctx *c, uint32_t *counts, uint64_t *bloom, uint32_t *len)
 {
-    return guarded(c, [&]() -> int {
-        if (!c) return HB_ERR_INVALID;
-        int rc = result_ready(c, c->sim.valid, "hb_debug_copy_similarity_batch", kNoSimilarity);
-        if (rc) return rc;
+    return reader_entry(c, c && c->sim.valid, "hb_debug_copy_similarity_batch", kNoSimilarity, [&]() -> int {
         const Plan &p = c->plan;
         auto &s = c->sim;
         if (!p.n) return HB_OK;

@@ -1,7 +1,9 @@
 // hb_api_walk.inc - part of the hb_api.hip translation unit (included before the operator files; uses its hb_ctx and helpers).
-// What hb_sampled_harmonic, hb_distances, hb_betweenness and hb_inbound_similarity share on the host: who holds the shared rows and the
-// result image, their entry and its refusals, the virtual levels in order, the sources as sids, the row -> readers transpose, the download
-// of a result - and, for the operators that walk 64-byte rows (device side: hb_walk.hip.h), the launcher and one forward level.
+// What the operators share on the host: who holds the shared rows and the result image, their entry and its refusals, the virtual levels
+// in order, the sources as sids, the row -> readers transpose; the entry of a reader, the result record of the node-valued operators
+// (NodeResult: d_val_sid / d_flag_sid, the compacted d_sel_sid / d_sel_val, count, valid, compacted) with its allocation, compaction and
+// three readers, the shared _top reader - and, for the operators that walk 64-byte rows (device side: hb_walk.hip.h), the launcher and
+// one forward level.
 
 namespace {
 
@@ -96,11 +98,26 @@ int ensure_transpose(hb_ctx *c, const char *who)
     return HB_OK;
 }
 
+// ---- results and their readers --------------------------------------------------------------------------------------------------------
 // a result is there to be read: `missing` = what to say when it is not
 int result_ready(hb_ctx *c, bool valid, const char *who, const char *missing)
 {
     if (!c->loaded || !valid) return fail(c, HB_ERR_INVALID, std::string(who) + ": " + missing);
     return set_device(c);
+}
+
+// The entry of a reader or a debug export of an operator's result: the context, `zeroed` (an output that is 0 whatever happens: the
+// _top readers' *written), that the result is there - callers write `valid` as `c && c->x.valid` -, then the body.  A reader that tests
+// an argument BEFORE the result (result_count, result_all, hb_similarity_lookup) keeps its own order and does not come through here
+template <class BODY>
+int reader_entry(hb_ctx *c, bool valid, const char *who, const char *missing, BODY body, uint64_t *zeroed = nullptr)
+{
+    return guarded(c, [&]() -> int {
+        if (!c) return HB_ERR_INVALID;
+        if (zeroed) *zeroed = 0;
+        const int rc = result_ready(c, valid, who, missing);
+        return rc ? rc : body();
+    });
 }
 
 // hb_*_count: the number of entries of a compacted result
@@ -112,9 +129,9 @@ int result_count(hb_ctx *c, bool valid, const char *who, const char *missing, ui
     return rc;
 }
 
-// hb_*_all: one value per node in sid order, from d_by_sid (`prepare`, if given, fills it first); `arg` = the caller's name of `out`
+// hb_*_all: one value per node in sid order, from d_val_sid (`prepare`, if given, fills it first); `arg` = the caller's name of `out`
 template <class T>
-int result_all(hb_ctx *c, bool valid, const char *who, const char *arg, const char *missing, T *out, uint64_t cap, const T *d_by_sid, int (*prepare)(hb_ctx *) = nullptr)
+int result_all(hb_ctx *c, bool valid, const char *who, const char *arg, const char *missing, T *out, uint64_t cap, const T *d_val_sid, int (*prepare)(hb_ctx *) = nullptr)
 {
     if (!out) return fail(c, HB_ERR_INVALID, std::string(who) + ": " + arg + " == NULL");
     int rc = result_ready(c, valid, who, missing);
@@ -123,7 +140,7 @@ int result_all(hb_ctx *c, bool valid, const char *who, const char *arg, const ch
     if (cap < n) return fail(c, HB_ERR_INVALID, std::string(who) + ": cap < n");
     if (!n) return HB_OK;
     if (prepare && (rc = prepare(c))) return rc;
-    HB_HIP(hipMemcpyAsync(out, d_by_sid, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    HB_HIP(hipMemcpyAsync(out, d_val_sid, n * sizeof(T), hipMemcpyDeviceToHost, c->stream));
     HB_HIP(hipStreamSynchronize(c->stream));
     return HB_OK;
 }
@@ -135,6 +152,105 @@ int copy_selected_ids(hb_ctx *c, const uint32_t *d_sel_sid, uint64_t k, hb_u128 
     HB_HIP(hipMemcpyAsync(sid.data(), d_sel_sid, k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HB_HIP(hipStreamSynchronize(c->stream));
     for (uint64_t i = 0; i < k; i++) ids[i] = c->g.ids[sid[i]];
+    return HB_OK;
+}
+
+// ---- the node-valued operators' result (NodeResult, hb_api.hip): hb_distances, hb_betweenness, hb_nearest_seed --------------------------
+// its buffers, once per loaded graph, on the context's `allocs` list (the caller's `bytes` count and hb_stats.device_bytes see them)
+template <class T>
+int node_result_alloc(hb_ctx *c, NodeResult<T> &r)
+{
+    const uint64_t n = c->plan.n;
+    int rc;
+    constexpr bool own = !NodeResult<T>::kBytes; // flags and selected values have buffers of their own
+    if ((rc = dev_alloc(c, &r.d_val_sid, n))) return rc;
+    if constexpr (own) rc = dev_alloc(c, &r.d_flag_sid, n);
+    else r.d_flag_sid = r.d_val_sid;
+    if (rc || (rc = dev_alloc(c, &r.d_sel_sid, n)) || (rc = dev_alloc(c, &r.d_sel_flag, n))) return rc;
+    if constexpr (own) rc = dev_alloc(c, &r.d_sel_val, n);
+    else r.d_sel_val = r.d_sel_flag;
+    return rc ? rc : dev_alloc(c, &r.d_sel_cnt, 8);
+}
+
+// The compacted form of d_val_sid / d_flag_sid: the select, its count read back, the check against the operator's own count (`expect`;
+// `counters` = what the refusal calls its source), the gather of the selected values, and the stream drained.  Sets count and compacted
+template <class T>
+int node_result_compact(hb_ctx *c, NodeResult<T> &r, const char *who, const uint64_t *expect = nullptr, const char *counters = "counters")
+{
+    const std::string e = gpu_select_reached((void *)c->stream, r.d_flag_sid, c->plan.n, r.d_sel_sid, r.d_sel_flag, r.d_sel_cnt);
+    if (!e.empty()) return fail(c, HB_ERR_HIP, std::string(who) + ": " + e);
+    uint64_t got = 0;
+    HB_HIP(hipMemcpyAsync(&got, r.d_sel_cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HB_HIP(hipStreamSynchronize(c->stream));
+    if (expect && got != *expect) return fail(c, HB_ERR_INVALID, std::string(who) + ": the compacted list and the " + counters + " disagree");
+    if constexpr (!NodeResult<T>::kBytes) {
+        if (got) {
+            hipLaunchKernelGGL(hbk::gather_selected_kernel, dim3(grid_blocks(c, (got + 255) / 256, 8, 1)), dim3(256), 0, c->stream, (const T *)r.d_val_sid,
+                               (const uint32_t *)r.d_sel_sid, got, r.d_sel_val);
+            HB_HIP(hipGetLastError());
+            HB_HIP(hipStreamSynchronize(c->stream));
+        }
+    }
+    r.count = got;
+    r.compacted = true;
+    return HB_OK;
+}
+
+// hb_*_count / _copy / _all of such a result.  `r` = the record of a non-NULL context (callers: c ? &c->x.res : nullptr); `compact`, if
+// given, makes d_val_sid and the compacted list when the first reader needs them (the distances) - after every refusal and only when
+// something is to be copied
+template <class T>
+int node_result_count(hb_ctx *c, const NodeResult<T> *r, const char *who, const char *missing, uint64_t *count)
+{
+    return guarded(c, [&]() -> int {
+        if (!c) return HB_ERR_INVALID;
+        return result_count(c, r->valid, who, missing, count, r->count);
+    });
+}
+
+template <class T>
+int node_result_copy(hb_ctx *c, const NodeResult<T> *r, const char *who, const char *missing, hb_u128 *ids, T *vals, uint64_t cap, int (*compact)(hb_ctx *) = nullptr)
+{
+    return reader_entry(c, r && r->valid, who, missing, [&]() -> int {
+        const uint64_t k = std::min<uint64_t>(cap, r->count);
+        if (!k || (!ids && !vals)) return HB_OK;
+        int rc;
+        if (compact && (rc = compact(c))) return rc;
+        // only the entries come down: k sids and k values
+        if (ids && (rc = copy_selected_ids(c, r->d_sel_sid, k, ids))) return rc;
+        if (vals) {
+            HB_HIP(hipMemcpyAsync(vals, r->d_sel_val, k * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+            HB_HIP(hipStreamSynchronize(c->stream));
+        }
+        return HB_OK;
+    });
+}
+
+template <class T>
+int node_result_all(hb_ctx *c, const NodeResult<T> *r, const char *who, const char *arg, const char *missing, T *out, uint64_t cap, int (*compact)(hb_ctx *) = nullptr)
+{
+    return guarded(c, [&]() -> int {
+        if (!c) return HB_ERR_INVALID;
+        return result_all<T>(c, r->valid, who, arg, missing, out, cap, r->d_val_sid, compact);
+    });
+}
+
+// What hb_nearest_seed_top and hb_similarity_top do once their keys kernel has run: the first `top` entries of d_key (over the entries
+// whose d_keep byte is set) in the order key descending, ties by entry descending; an entry is sid_of_entry(at), its value the key's bits
+template <class SID>
+int result_top(hb_ctx *c, const char *who, const uint64_t *d_key, const uint8_t *d_keep, uint64_t n, uint64_t top, SID sid_of_entry, hb_u128 *ids, double *vals,
+               uint64_t *written)
+{
+    std::vector<uint32_t> at(top);
+    std::vector<uint64_t> key(top);
+    uint64_t got = 0;
+    const std::string e = gpu_similarity_top((void *)c->stream, d_key, d_keep, n, top, at.data(), key.data(), &got);
+    if (!e.empty()) return fail(c, e.find("out of memory") != std::string::npos ? HB_ERR_NOMEM : HB_ERR_HIP, std::string(who) + ": " + e);
+    for (uint64_t i = 0; i < got; i++) {
+        if (ids) ids[i] = c->g.ids[sid_of_entry(at[i])];
+        if (vals) std::memcpy(&vals[i], &key[i], sizeof(double));
+    }
+    if (written) *written = got;
     return HB_OK;
 }
 

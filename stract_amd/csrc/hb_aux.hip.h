@@ -493,4 +493,11 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const uint4 *regs, con
     out[t] = regs[(uint64_t)dev_of[sid] * 4 + (t & 3)];
 }
 
+// the values of the selected sids of a node-valued result (node_result_compact, hb_api_walk.inc): out[i] = val[sel_sid[i]]
+__global__ __launch_bounds__(256) void gather_selected_kernel(const double *val, const uint32_t *sel_sid, uint64_t count, double *out)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) out[i] = val[sel_sid[i]];
+}
+
 } // namespace hbk

@@ -407,10 +407,4 @@ __global__ __launch_bounds__(256) void bc_result_kernel(const double *sum, const
     (void)n_pad;
 }
 
-__global__ __launch_bounds__(256) void bc_gather_kernel(const double *val, const uint32_t *sel_sid, uint64_t count, double *out)
-{
-    const uint64_t stride = (uint64_t)gridDim.x * 256;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) out[i] = val[sel_sid[i]];
-}
-
 } // namespace hbk

@@ -268,8 +268,9 @@ struct DevicePlan {
 std::string device_offsets(void *stream, uint32_t *d_counts, uint64_t count, uint64_t *d_offsets, uint64_t expect);
 // d_offsets[0 .. count]: exclusive prefix sums of d_counts (count + 1 outputs)
 std::string device_prefix(void *stream, const uint32_t *d_counts, uint64_t count, uint64_t *d_offsets);
-// the reached nodes of a distance run (hb_api_distance.inc): (sid, distance) of every sid with d_by_sid[sid] != 255, ascending sid
-std::string gpu_select_reached(void *stream, const uint8_t *d_by_sid, uint64_t n, uint32_t *d_sids, uint8_t *d_dist, uint64_t *d_count);
+// the compaction of a node-valued result (node_result_compact, hb_api_walk.inc): (sid, flag byte) of every sid with d_flag_sid[sid] != 255,
+// ascending sid, and their number
+std::string gpu_select_reached(void *stream, const uint8_t *d_flag_sid, uint64_t n, uint32_t *d_sel_sid, uint8_t *d_sel_flag, uint64_t *d_sel_cnt);
 // hb_similarity_top (hb_api_similarity.inc): the first `top` (sid, key) pairs in the order key descending, ties sid descending, over
 // the sids whose d_keep byte is non-zero; h_sid / h_key hold `top` entries, *written = how many were filled
 std::string gpu_similarity_top(void *stream, const uint64_t *d_key, const uint8_t *d_keep, uint64_t n, uint64_t top, uint32_t *h_sid, uint64_t *h_key,

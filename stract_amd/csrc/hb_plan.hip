@@ -581,26 +581,26 @@ std::string device_prefix(void *stream_v, const uint32_t *d_counts, uint64_t cou
     return "";
 }
 
-// hb_distance_copy: the reached nodes of a distance run in ascending sid order.  d_by_sid = one distance byte per sid (255 = unreached);
-// d_sids / d_dist (n entries each) receive the compacted (sid, distance) pairs, *d_count their number.  Two order-preserving selects
-// over the same flags.
-std::string gpu_select_reached(void *stream_v, const uint8_t *d_by_sid, uint64_t n, uint32_t *d_sids, uint8_t *d_dist, uint64_t *d_count)
+// The sids of a node-valued result that have a value, in ascending sid order.  d_flag_sid = one flag byte per sid (255 = none; for the
+// distances the byte is the distance); d_sel_sid / d_sel_flag (n entries each) receive the compacted (sid, byte) pairs, *d_sel_cnt their
+// number.  Two order-preserving selects over the same flags.
+std::string gpu_select_reached(void *stream_v, const uint8_t *d_flag_sid, uint64_t n, uint32_t *d_sel_sid, uint8_t *d_sel_flag, uint64_t *d_sel_cnt)
 {
     hipStream_t stream = (hipStream_t)stream_v;
     if (!n) {
-        PL_HIP(hipMemsetAsync(d_count, 0, sizeof(uint64_t), stream));
+        PL_HIP(hipMemsetAsync(d_sel_cnt, 0, sizeof(uint64_t), stream));
         return "";
     }
     auto iota = rocprim::make_counting_iterator<uint32_t>(0);
-    auto flags = rocprim::make_transform_iterator(d_by_sid, DistReached());
+    auto flags = rocprim::make_transform_iterator(d_flag_sid, DistReached());
     size_t b0 = 0, b1 = 0;
     void *tmp = nullptr;
-    PL_HIP(rocprim::select(nullptr, b0, iota, flags, d_sids, d_count, (size_t)n, stream));
-    PL_HIP(rocprim::select(nullptr, b1, d_by_sid, flags, d_dist, d_count, (size_t)n, stream));
+    PL_HIP(rocprim::select(nullptr, b0, iota, flags, d_sel_sid, d_sel_cnt, (size_t)n, stream));
+    PL_HIP(rocprim::select(nullptr, b1, d_flag_sid, flags, d_sel_flag, d_sel_cnt, (size_t)n, stream));
     size_t bytes = std::max<size_t>(std::max(b0, b1), 256);
     PL_HIP(hipMalloc(&tmp, bytes));
-    hipError_t e = rocprim::select(tmp, bytes, iota, flags, d_sids, d_count, (size_t)n, stream);
-    if (e == hipSuccess) e = rocprim::select(tmp, bytes, d_by_sid, flags, d_dist, d_count, (size_t)n, stream);
+    hipError_t e = rocprim::select(tmp, bytes, iota, flags, d_sel_sid, d_sel_cnt, (size_t)n, stream);
+    if (e == hipSuccess) e = rocprim::select(tmp, bytes, d_flag_sid, flags, d_sel_flag, d_sel_cnt, (size_t)n, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     (void)hipFree(tmp);
     if (e != hipSuccess) return std::string("gpu_select_reached: ") + hipGetErrorString(e);
