@@ -114,6 +114,13 @@ typedef struct hb_edge {
                                           other context ignores both flags and plans as before.  Default: on when n >= 2^20.  This flag
                                           forces it on for smaller graphs, HB_FLAG_NO_LIVE_FIRST off for larger ones (tests, A/B runs)  */
 #define HB_FLAG_NO_LIVE_FIRST 0x20000u /* never use the live-first order (wins over HB_FLAG_LIVE_FIRST)                               */
+#define HB_FLAG_NO_SATURATION 0x40000u /* dense passes gather for every row.  Default (off): a node row whose counter is, register by
+                                          register, at least U - the maximum over the initial counters of the hosts with an out-link -
+                                          can never change again; from then on the dense passes t >= 1 neither gather for it nor compute
+                                          the hub chunks below it.  Same results and per-pass statistics (`touched`
+                                          of a bitmap pass may differ on split rows, as between two layouts).  Used where the argument
+                                          holds for the whole graph: one rank, no communicator, no destination partition, fused passes,
+                                          no HB_FLAG_PASS_STATS - every other context runs as with this flag (tests, A/B runs)        */
 #define HB_FLAG_RCCL_SELF     0x80u /* world_size == 1 but still create a 1-rank communicator and run
                                        the collectives (exercises the RCCL call path on one GPU)   */
 
@@ -924,6 +931,11 @@ int hb_debug_copy_plan(hb_ctx *ctx, uint64_t sizes[4], uint32_t *order, uint64_t
  * >= 1 in-edge (device rows [0, n_live) when the order is in use), n_live_pad = the end of the node-row launches of passes t >= 1
  * (n_live rounded up to 64 with the order, n_pad without)}. */
 int hb_debug_plan_live(hb_ctx *ctx, uint64_t live[3]);
+/* The saturated rows of the run in progress (HB_FLAG_NO_SATURATION): info = {1 if the context skips saturated rows else 0, n, nv};
+ * u[64] = U, the register-wise maximum of the initial counters of the hosts with an out-link; node_bits[n] = 1 where the host's row
+ * (input order, like hb_debug_copy_registers) is marked saturated; virt_bits[nv] = the same for the hub-chunk rows in the order of
+ * hb_debug_copy_plan.  Pointers may be NULL; a context that does not skip reports info[0] = 0 and writes nothing else. */
+int hb_debug_saturation(hb_ctx *ctx, uint64_t info[3], uint8_t *u, uint8_t *node_bits, uint8_t *virt_bits);
 /* Emulates the collective of one pass between `count` logical ranks that live on ONE device
  * (contexts created with HB_FLAG_NO_RCCL; RCCL refuses two ranks on one device).
  *   phase 0, between hb_step_local and hb_step_finish of every context:

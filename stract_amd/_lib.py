@@ -46,6 +46,7 @@ HB_FLAG_NO_INIT_PASS = 0x4000
 HB_FLAG_ALL_RELS = 0x8000
 HB_FLAG_LIVE_FIRST = 0x10000
 HB_FLAG_NO_LIVE_FIRST = 0x20000
+HB_FLAG_NO_SATURATION = 0x40000
 HB_SAMPLE_MAX_LEVELS = 16
 
 # switches of the experiments build in hb_options.tune[1] (stract_amd/csrc/hb_experiments.h describes each)
@@ -527,6 +528,7 @@ _SIGNATURES = [
     ("hb_host_plan", ctypes.c_int, [_U64, _P, _P, ctypes.c_uint32, ctypes.c_uint32, _P, _P, _P, _P, _P, _P]),
     ("hb_host_plan_live", ctypes.c_int, [_U64, _P, _P, ctypes.c_uint32, ctypes.c_uint32, _P, _P]),
     ("hb_debug_plan_live", ctypes.c_int, [_P, _P]),
+    ("hb_debug_saturation", ctypes.c_int, [_P, _P, _P, _P, _P]),
 ]
 # include/hb_webgraph.h
 _SIGNATURES += [
@@ -1357,6 +1359,19 @@ class Context:
         out = np.zeros(3, dtype=np.uint64)
         self._check(self.lib.hb_debug_plan_live(self.h, _ptr(out)))
         return bool(out[0]), int(out[1]), int(out[2])
+
+    def saturation(self):
+        """(skipping in use, U[64], node bits[n] in input order, hub-chunk bits[nv] in plan order) of the run in progress
+        (hb_debug_saturation); (False, None, None, None) for a context that does not skip saturated rows."""
+        info = np.zeros(3, dtype=np.uint64)
+        self._check(self.lib.hb_debug_saturation(self.h, _ptr(info), None, None, None))
+        if not info[0]:
+            return False, None, None, None
+        u = np.zeros(64, dtype=np.uint8)
+        node = np.zeros(int(info[1]), dtype=np.uint8)
+        virt = np.zeros(int(info[2]), dtype=np.uint8)
+        self._check(self.lib.hb_debug_saturation(self.h, _ptr(info), _ptr(u), _ptr(node), _ptr(virt)))
+        return True, u, node.astype(bool), virt.astype(bool)
 
     def graph(self):
         st = self.stats()

@@ -102,6 +102,8 @@ struct GraphDeviceState {
     bool level0_all_real = false;    // no row of the first hub-chunk level reads virtual rows (checked at load): pass 0 may run init_level1_kernel there
     uint32_t *d_virt_rows = nullptr; // one bit per work row: its sources are virtual rows (pass 0, PassParams::virt_rows)
     uint16_t *d_self_jp = nullptr; // per node row: its OWN initial register in the same format (the lean pass 0 reads it instead of the counters)
+    uint32_t *d_sat = nullptr;     // saturated rows (PassParams::sat): one bit per work row, cleared by hb_begin.  NULL: the context is outside the gate
+    uint32_t *d_sat_u = nullptr;   // U of the saturation bound, one word per register (sat_bound_kernel at load)
     uint4 *d_regs[2] = {nullptr, nullptr};
     uint4 *d_part = nullptr;
     uint32_t *d_bits[2] = {nullptr, nullptr};
@@ -618,6 +620,12 @@ bool live_first_by_flags(uint32_t flags, uint64_t n)
 {
     if (flags & (HB_FLAG_NO_REORDER | HB_FLAG_PASS_STATS | HB_FLAG_UNFUSED | HB_FLAG_REFERENCE_TAIL | HB_FLAG_NO_LIVE_FIRST)) return false;
     return n >= (1u << 20) || (flags & HB_FLAG_LIVE_FIRST);
+}
+// saturated rows, the part of the gate the option flags decide: fused passes that do not count their gathers.
+// On by default; a context adds what it alone knows (plan_and_upload: one rank, no communicator, no destination partition)
+bool saturation_by_flags(uint32_t flags)
+{
+    return !(flags & (HB_FLAG_PASS_STATS | HB_FLAG_UNFUSED | HB_FLAG_REFERENCE_TAIL | HB_FLAG_NO_SATURATION));
 }
 
 bool multi_rank(const hb_ctx *c) { return c->opt.world_size > 1; }
@@ -1319,6 +1327,7 @@ int hb_begin(hb_ctx *c)
         // reading it (hb_kernels.hip.h)
         HB_HIP(hipMemsetAsync(c->d_bits[0], 0, c->bits_words * 4, c->stream));
         HB_HIP(hipMemsetAsync(c->d_bits[1], 0, c->bits_words * 4, c->stream));
+        if (c->d_sat) HB_HIP(hipMemsetAsync(c->d_sat, 0, c->bits_words * 4, c->stream)); // nothing is saturated yet: pass 0 gathers and overwrites every partial
         HB_HIP(hipMemsetAsync(c->d_counters, 0, ((size_t)c->max_passes + 1) * hbk::kCounterWords * sizeof(unsigned long long), c->stream));
         if (c->d_sparse_counts) HB_HIP(hipMemsetAsync(c->d_sparse_counts, 0, 64 * sizeof(unsigned int), c->stream));
         if (c->ksum_len > p.n_pad) // slice padding beyond the rows init_kernel writes (all-reduce mode)

@@ -22,6 +22,37 @@ int hb_debug_copy_registers(hb_ctx *c, uint8_t *out)
     });
 }
 
+// the saturated rows of the run in progress (DESIGN.md section 38): U, and the bitmap unpacked to one byte per node (input order) /
+// per hub chunk (plan order)
+int hb_debug_saturation(hb_ctx *c, uint64_t info[3], uint8_t *u, uint8_t *node_bits, uint8_t *virt_bits)
+{
+    return guarded(c, [&]() -> int {
+        if (!c || !info) return HB_ERR_INVALID;
+        if (!c->loaded) return fail(c, HB_ERR_INVALID, "hb_debug_saturation: no graph loaded");
+        int rc = set_device(c);
+        if (rc) return rc;
+        const Plan &p = c->plan;
+        info[0] = (c->d_sat != nullptr && !unfused(c) && !linked(c)) ? 1 : 0;
+        info[1] = p.n;
+        info[2] = p.nv;
+        if (!info[0]) return HB_OK;
+        if ((rc = need_host_dev_of(c))) return rc;
+        uint32_t hu[64];
+        std::vector<uint32_t> words(c->bits_words);
+        HB_HIP(hipMemcpyAsync(hu, c->d_sat_u, sizeof(hu), hipMemcpyDeviceToHost, c->stream));
+        HB_HIP(hipMemcpyAsync(words.data(), c->d_sat, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HB_HIP(hipStreamSynchronize(c->stream));
+        auto bit = [&](uint64_t row) { return (uint8_t)((words[row >> 5] >> (row & 31u)) & 1u); };
+        if (u)
+            for (int k = 0; k < 64; k++) u[k] = (uint8_t)hu[k];
+        if (node_bits)
+            for (uint64_t s = 0; s < p.n; s++) node_bits[s] = bit(p.dev_of[s]);
+        if (virt_bits)
+            for (uint64_t v = 0; v < p.nv; v++) virt_bits[v] = bit(p.n_pad + v);
+        return HB_OK;
+    });
+}
+
 int hb_debug_copy_kahan(hb_ctx *c, double *sum, double *err)
 {
     return guarded(c, [&]() -> int {

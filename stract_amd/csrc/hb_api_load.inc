@@ -360,6 +360,17 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
         HB_HIP(hipStreamSynchronize(c->stream));
     }
     lap("id_low");
+    if (p.n_pad && saturation_by_flags(c->opt.flags) && !multi_rank(c) && !linked(c) && !dest_mode(c)) {
+        // saturated rows (DESIGN.md section 38): U depends on the graph alone, the bitmap is hb_begin's to clear
+        if ((rc = dev_alloc(c, &c->d_sat_u, 64))) return rc;
+        if ((rc = dev_alloc(c, &c->d_sat, c->bits_words))) return rc;
+        HB_HIP(hipMemsetAsync(c->d_sat_u, 0, 64 * sizeof(uint32_t), c->stream));
+        HB_HIP(hipMemsetAsync(c->d_sat, 0, c->bits_words * sizeof(uint32_t), c->stream));
+        hipLaunchKernelGGL(hbk::sat_bound_kernel, dim3(grid_blocks(c, (p.n_pad + 255) / 256, 8)), dim3(256), 0, c->stream, (const uint64_t *)c->d_idlow,
+                           (const uint32_t *)c->d_sid_of, (const uint32_t *)c->d_outdeg, p.n_pad, c->d_sat_u);
+        HB_HIP(hipGetLastError());
+        lap("saturation bound");
+    }
     if (src_len && !(c->opt.flags & HB_FLAG_NO_INIT_PASS)) {
         if ((rc = dev_alloc(c, &c->d_src_jp, src_len + 4))) return rc;
         const unsigned blocks = grid_blocks(c, (src_len + 255) / 256, 16);

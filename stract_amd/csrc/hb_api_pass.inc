@@ -134,6 +134,10 @@ int ensure_initial_state(hb_ctx *c)
 // counter in both buffers, its (0, 0) / lc[63] Kahan and size words in place and its changed / Kahan-dirty bits at zero.
 bool skips_dead_rows(const hb_ctx *c) { return c->plan.live_first && c->t >= 1 && !unfused(c) && !linked(c); } // (a plan is only laid out so for such a context)
 
+// saturated rows (DESIGN.md section 38): the dense passes t >= 1 of a context inside the gate neither gather for a row whose bit is set
+// nor compute the hub chunks below it.  Pass 0 gathers everything and overwrites every partial (hb_begin relies on that).
+bool skips_saturated_rows(const hb_ctx *c) { return c->d_sat != nullptr && c->t >= 1 && !unfused(c) && !linked(c); } // (d_sat exists only inside the gate)
+
 hbk::PassParams make_params(hb_ctx *c)
 {
     const Plan &p = c->plan;
@@ -171,6 +175,8 @@ hbk::PassParams make_params(hb_ctx *c)
     pp.virt_rows = c->d_virt_rows;
     pp.xflags = xbit(c, HB_X_PROBE_NO_SIZE) ? 1u : 0u;
     pp.live_limit = skips_dead_rows(c) ? (uint32_t)p.n_live : hbk::kNone;
+    pp.sat = skips_saturated_rows(c) ? c->d_sat : nullptr; // (only the dense kernels read it)
+    pp.sat_u = c->d_sat_u;
     return pp;
 }
 
@@ -653,6 +659,16 @@ int level_pass(hb_ctx *c, hbk::PassParams pp, hipEvent_t *E, bool frontier, bool
             // so that no later bitmap or sweep pass finds a dead row "changed" (n_live_pad is a multiple of 64: whole words)
             HB_HIP(hipMemsetAsync(c->d_bits[c->cur] + p.n_live_pad / 32, 0, (p.n_pad - p.n_live_pad) / 32 * sizeof(uint32_t), c->stream));
         }
+        if (!frontier && pp.sat) {
+            // the node rows have marked the top chunks of every hub row that is saturated now: hand the bit down the trees, top level
+            // first, so that the next dense pass skips all of them (a first level known to read node rows only has nothing below it)
+            for (size_t l = p.level_begin.empty() ? 0 : p.level_begin.size() - 1; l-- > 0;) {
+                const uint64_t lo = p.level_begin[l], hi = p.level_begin[l + 1];
+                if (hi > lo && !(l == 0 && c->level0_all_real))
+                    hipLaunchKernelGGL(hbk::sat_down_kernel, dim3(grid_blocks(c, (hi - lo + 63) / 64, 8)), dim3(256), 0, c->stream, (const uint64_t *)c->d_row_ptr,
+                                       (const uint32_t *)c->d_src, lo, hi, p.n_pad, c->d_sat);
+            }
+        }
     }
     HB_HIP(hipEventRecord(E[kEvMerge], c->stream));
     return HB_OK;
@@ -1090,6 +1106,7 @@ int warm_kernels(hb_ctx *c)
     warm(bitmap_kernel(false, false, false, compact));
     warm(bitmap_kernel(true, fused, false, compact));
     if (!fused) warm(hbk::epilogue_kernel);
+    if (c->d_sat) hipLaunchKernelGGL(hbk::sat_down_kernel, one, blk, 0, s, (const uint64_t *)c->d_row_ptr, (const uint32_t *)c->d_src, 0ull, 0ull, 0ull, c->d_sat);
     if (c->sparse_ok) {
         const hbk::SweepParams sp = make_sweep_params(c, pp, 0, nullptr); // (the counters: zeroed here, and again by every hb_begin)
         HB_HIP(hipMemsetAsync(c->d_sparse_counts, 0, 64 * sizeof(unsigned int), s));

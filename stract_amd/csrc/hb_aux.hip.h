@@ -41,6 +41,40 @@ __global__ __launch_bounds__(256) void validate_plan_kernel(const uint64_t *row_
     if (b3) atomicAdd(&bad[3], (unsigned long long)b3);
 }
 
+// ---- saturated rows (PassParams::sat) ----------------------------------------------------------------
+// U at load: per register the largest value an initial counter of a node WITH an out-link holds (only such a node is ever anybody's
+// source).  u[64] is zeroed by the caller; per-block maxima in LDS, then at most 64 atomic maxima per block.  Padding rows hold no id.
+__global__ __launch_bounds__(256) void sat_bound_kernel(const uint64_t *id_low, const uint32_t *sid_of, const uint32_t *outdeg, uint64_t n_pad, uint32_t *u)
+{
+    __shared__ uint32_t s_u[64];
+    if (threadIdx.x < 64) s_u[threadIdx.x] = 0;
+    __syncthreads();
+    for (uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x; r < n_pad; r += (uint64_t)gridDim.x * 256) {
+        if (sid_of[r] == kNone || outdeg[r] == 0) continue;
+        const uint32_t jp = initial_register_jp(id_low[r]);
+        atomicMax(&s_u[jp & 63u], jp >> 8);
+    }
+    __syncthreads();
+    if (threadIdx.x < 64 && s_u[threadIdx.x]) atomicMax(&u[threadIdx.x], s_u[threadIdx.x]);
+}
+// The bit of a saturated hub row's chunks goes down its tree: one launch per hub-chunk level, top level first, behind the node rows of
+// a dense pass.  A chunk of [lo, hi) whose bit is set and whose sources are chunks themselves sets theirs (a quad per row).
+__global__ __launch_bounds__(256) void sat_down_kernel(const uint64_t *row_ptr, const uint32_t *src, uint64_t lo, uint64_t hi, uint64_t n_pad, uint32_t *sat)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const uint64_t nq = (uint64_t)gridDim.x * 64;
+    const int q = threadIdx.x & 3;
+    for (uint64_t row = lo + (t >> 2); row < hi; row += nq) {
+        if (!((sat[row >> 5] >> (row & 31u)) & 1u)) continue;
+        const uint64_t b = row_ptr[row], e = row_ptr[row + 1];
+        if (b >= e || src[b] < n_pad) continue;
+        for (uint64_t k = b + q; k < e; k += 4) {
+            const uint32_t v = src[k];
+            atomicOr(&sat[v >> 5], 1u << (v & 31u));
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void hll_size_kernel(const uint4 *regs, uint64_t count, uint64_t *out,
                                                        const double *raw, const double *bias, const uint8_t *lc)
 {

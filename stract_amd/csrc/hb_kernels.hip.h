@@ -119,6 +119,13 @@ struct PassParams {
                               // still the initial one, and pass 0 has merged that into every reader
     const uint16_t *self_jp;  // per device row: register index | value << 8 of the node's OWN initial counter (0 = padding row), written at
                               // load time with the same arithmetic as src_jp (lean pass 0)
+    // saturated rows, dense passes t >= 1 of a context inside the gate; NULL = gather every row.  sat_u = U, the
+    // register-wise maximum of the initial counters of the nodes with an out-link (one u32 per register, written at load): no source
+    // ever holds more, so a row whose counter is >= U in every register cannot change any more.  sat = one bit per WORK row: a node row
+    // with that property, or a hub chunk below one.  A set bit's row gathers nothing (a chunk writes no partial); the node-row launch
+    // tests every row it visits and sets the bits, and a hub row that has just become saturated sets those of its virtual sources
+    uint32_t *sat;
+    const uint32_t *sat_u;
 };
 
 // (initial_register_jp / counter_quarter_of_jp - the entry format of src_jp / self_jp - live in hb_regs.hip.h: the AMPC shard's edge step
@@ -155,6 +162,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
             s_bias[i] = p.bias[i];
         }
         if (threadIdx.x < 65) s_lc[threadIdx.x] = p.lc[threadIdx.x];
+        __syncthreads();
+    }
+    // saturated rows (PassParams::sat): U lies in LDS, as the four quarters a quad compares its counter with
+    __shared__ uint4 s_satu[4];
+    const bool sat_on = !INIT && p.sat != nullptr; // kernel-uniform
+    if (!INIT && REAL && sat_on) {
+        if (threadIdx.x < 64) ((uint8_t *)s_satu)[threadIdx.x] = (uint8_t)p.sat_u[threadIdx.x];
         __syncthreads();
     }
     const int lane = threadIdx.x & 63;
@@ -228,6 +242,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
     uint64_t nbeg = 0, nend = 0;
     uint32_t nod = 0;
     uint32_t nvirt = 0; // (INIT) the row's sources are virtual rows (PassParams::virt_rows)
+    uint32_t nsat = 0;  // the row's bit of PassParams::sat
     uint4 nself = make_uint4(0, 0, 0, 0);
     const bool by_bitmap = INIT && p.virt_rows != nullptr;             // kernel-uniform
     const bool lean = INIT && REAL && FUSED && p.rd_init != nullptr; // kernel-uniform (PassParams::rd_init)
@@ -243,6 +258,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
             if (REAL && FUSED) nod = p.outdeg[r0];
             if (kDenseReal) nself = own_counter(r0);
             if (INIT && by_bitmap) nvirt = (p.virt_rows[r0 >> 5] >> (r0 & 31u)) & 1u;
+            if (!INIT && sat_on) nsat = (p.sat[r0 >> 5] >> (r0 & 31u)) & 1u;
         }
     }
     for (uint64_t tile = tile0; tile < ntiles; tile += tstride) {
@@ -252,12 +268,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
         const uint64_t beg = nbeg, end = nend;
         const uint32_t od = nod; // out-degree of the row's node, used in the epilogue
         const uint32_t virt = nvirt;
+        const bool satb = !INIT && nsat != 0; // saturated: no gather, and nothing below can change the row
         uint4 selfv = nself;
         {   // requests for the next tile of this workgroup
             const uint64_t nrow = row + (tstride << 6);
             nbeg = nend = 0;
             nod = 0;
             nvirt = 0;
+            nsat = 0;
             nself = make_uint4(0, 0, 0, 0);
             if (tile + tstride < ntiles && nrow < row_hi) {
                 nbeg = p.row_ptr[nrow];
@@ -265,6 +283,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
                 if (REAL && FUSED) nod = p.outdeg[nrow];
                 if (kDenseReal) nself = own_counter(nrow);
                 if (INIT && by_bitmap) nvirt = (p.virt_rows[nrow >> 5] >> (nrow & 31u)) & 1u;
+                if (!INIT && sat_on) nsat = (p.sat[nrow >> 5] >> (nrow & 31u)) & 1u;
             }
         }
         // dense fused node rows: 4 of 5 rows change, so the estimator/Kahan words are requested now, unconditionally
@@ -299,7 +318,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
         // dominates the stored partial (counters only grow), so the partial is overwritten without being read, and no
         // changed bit is kept (nobody tests it in a dense pass).
         if (kDenseReal && valid) acc_merge(acc, selfv);
-        if (beg < end) {
+        bool virt_src = false; // (node rows) a hub row: its sources are virtual rows
+        if (beg < end && !satb) {
             // all sources of one row are of one kind: real nodes (read rd) or virtual rows (read part)
             uint32_t first;
             bool real_src;
@@ -311,6 +331,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
                 first = p.src[beg];
                 real_src = first < p.n_pad;
             }
+            virt_src = !real_src;
             const uint4 *base = real_src ? p.rd : (const uint4 *)(p.part - p.n_pad * 4);
             // a slot is gathered iff its id is below `limit`: kNone (out-of-row slots) never is, and with the live-first order neither is a
             // dead real source (PassParams::live_limit).  The lists ascend, so a row whose first source is dead has only dead ones: no gather
@@ -396,9 +417,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
         const bool kd = (kd16 >> g) & 1u;
         const bool need = valid;
         const uint4 accv = acc_value(acc);
-        const bool lane_diff = need && (!REAL || u4_ne(accv, selfv));
+        const bool lane_diff = need && !satb && (!REAL || u4_ne(accv, selfv)); // (a saturated chunk gathered nothing: its partial stays)
         const uint64_t bal = __ballot(lane_diff);
         const bool changed = ((bal >> qshift) & 0xFull) != 0;
+        if (!INIT && REAL && sat_on) {
+            // every visited row: counter >= U in all 64 registers?  Bit 4 g of sb = all four quarters of row g say so
+            uint64_t sb = __ballot(need && counter_ge(accv, s_satu[q]));
+            sb &= sb >> 1;
+            sb &= sb >> 2;
+            sb &= 0x1111111111111111ull;
+            if (((sb >> qshift) & 1ull) && !satb && virt_src) { // a hub row, saturated from now on: so are the chunks it reads
+                for (uint64_t e = beg + (uint64_t)q; e < end; e += 4) {
+                    const uint32_t v = p.src[e];
+                    HB_DBG_ASSERT(v >= p.n_pad && v < p.rows_total);
+                    atomicOr(&p.sat[v >> 5], 1u << (v & 31u));
+                }
+            }
+            if (lane == 0 && row16 < row_hi) ((uint16_t *)p.sat)[row16 >> 4] = (uint16_t)pack16(sb);
+        }
         if (REAL) {
             // lazy double buffer: wr[row] already holds the right value unless the row changed in this or in the previous pass
             // [r5: used by the fused dense pass too - a fifth of the hosts of an R-MAT graph have no in-link at all and never

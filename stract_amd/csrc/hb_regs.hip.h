@@ -69,6 +69,18 @@ __device__ __forceinline__ bool u4_ne(const uint4 &a, const uint4 &b)
 {
     return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) != 0;
 }
+// a >= b in each of the 16 registers: the byte-wise maximum of the two (even and odd bytes as 16-bit lanes, as in acc_merge) is a
+__device__ __forceinline__ bool counter_ge(const uint4 &a, const uint4 &b)
+{
+    const uint32_t x[4] = {a.x, a.y, a.z, a.w}, y[4] = {b.x, b.y, b.z, b.w};
+    uint32_t diff = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const uint32_t xe = x[k] & 0x00FF00FFu, xo = (x[k] >> 8) & 0x00FF00FFu;
+        diff |= (pkmax(xe, y[k] & 0x00FF00FFu) ^ xe) | (pkmax(xo, (y[k] >> 8) & 0x00FF00FFu) ^ xo);
+    }
+    return diff == 0;
+}
 
 // the one register HyperLogLog::default(); add_u128(id) sets (hyperloglog.rs:4385-4400 with FastHasher :4311-4313; only the low 64 bits of
 // the id are hashed), as index | value << 8 - the entry format of src_jp / self_jp

@@ -16,7 +16,8 @@ sources before a band cut, largest row that is not split) and two of NO_REORDER 
 --order decides the device order of the passes, records and operator contexts: plain draws nothing and replays the
 cases this tool drew before it knew the option; live puts HB_FLAG_LIVE_FIRST on every context - the order every graph of 2^20 hosts and
 more is planned in; mixed (the default) draws one of nothing / HB_FLAG_LIVE_FIRST / HB_FLAG_NO_LIVE_FIRST per case.  Under live and mixed
-the graphs also include `dead_fringe`, and every loaded context's plan_live() is held against the host planner's on the same graph and flags.
+the graphs also include `dead_fringe`, and every loaded context's plan_live() is held against the host planner's on the same graph and flags;
+one case in three of them also runs with HB_FLAG_NO_SATURATION (the dense passes gather for saturated rows as well).
 
 --mode ampc drives the AMPC shard (stract_amd/ampc.py) instead of a context: every case is one sequence of tests/ampc_model.py - 60 to 240
 interleaved calls on tables, graphs and filters that stay alive, each answer against the model, the whole content of every table and
@@ -58,7 +59,9 @@ def draw_order(rng, order, what):
         return 0
     name = "LIVE_FIRST" if order == "live" else ("", "LIVE_FIRST", "NO_LIVE_FIRST")[int(rng.integers(0, 3))]
     what["order"] = name
-    return ORDER_FLAGS[name]
+    # ... and, with it, whether the dense passes skip saturated rows (the default) or gather for every row
+    what["saturation"] = bool(rng.integers(0, 3))
+    return ORDER_FLAGS[name] | (0 if what["saturation"] else _lib.HB_FLAG_NO_SATURATION)
 
 
 def check_plan_live(ctx, flags, chunk, tune, what):
