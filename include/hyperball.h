@@ -121,6 +121,14 @@ typedef struct hb_edge {
                                           of a bitmap pass may differ on split rows, as between two layouts).  Used where the argument
                                           holds for the whole graph: one rank, no communicator, no destination partition, fused passes,
                                           no HB_FLAG_PASS_STATS - every other context runs as with this flag (tests, A/B runs)        */
+#define HB_FLAG_NO_EARLY_EXIT  0x80000u /* a dense pass gathers every source of every row it gathers for.  Default (off), in the contexts
+                                          that skip saturated rows: once the rows saturated so far in the run hold at least 1/64 of the
+                                          edges as sources, the dense passes leave a row's (or hub chunk's) gather loop after the round in
+                                          which its accumulator has reached U - no later source can raise it.  Same
+                                          results and statistics.  HB_FLAG_NO_SATURATION implies this flag (tests, A/B runs)             */
+#define HB_FLAG_FORCE_EARLY_EXIT 0x100000u /* those dense passes test for the early exit from pass 1 on, whatever is saturated (tests: small
+                                          graphs reach the code in passes where nothing is saturated yet).  Same results; loses to
+                                          HB_FLAG_NO_EARLY_EXIT and HB_FLAG_NO_SATURATION                                                  */
 #define HB_FLAG_RCCL_SELF     0x80u /* world_size == 1 but still create a 1-rank communicator and run
                                        the collectives (exercises the RCCL call path on one GPU)   */
 
@@ -931,11 +939,13 @@ int hb_debug_copy_plan(hb_ctx *ctx, uint64_t sizes[4], uint32_t *order, uint64_t
  * >= 1 in-edge (device rows [0, n_live) when the order is in use), n_live_pad = the end of the node-row launches of passes t >= 1
  * (n_live rounded up to 64 with the order, n_pad without)}. */
 int hb_debug_plan_live(hb_ctx *ctx, uint64_t live[3]);
-/* The saturated rows of the run in progress (HB_FLAG_NO_SATURATION): info = {1 if the context skips saturated rows else 0, n, nv};
+/* The saturated rows of the run in progress (HB_FLAG_NO_SATURATION): info = {1 if the context skips saturated rows else 0, n, nv,
+ * the work rows (node rows and hub chunks) of the last dense pass that left their gather loop early, 1 if that pass ran the early-exit
+ * instances else 0 (HB_FLAG_NO_EARLY_EXIT; a pass that did not counts nothing)};
  * u[64] = U, the register-wise maximum of the initial counters of the hosts with an out-link; node_bits[n] = 1 where the host's row
  * (input order, like hb_debug_copy_registers) is marked saturated; virt_bits[nv] = the same for the hub-chunk rows in the order of
  * hb_debug_copy_plan.  Pointers may be NULL; a context that does not skip reports info[0] = 0 and writes nothing else. */
-int hb_debug_saturation(hb_ctx *ctx, uint64_t info[3], uint8_t *u, uint8_t *node_bits, uint8_t *virt_bits);
+int hb_debug_saturation(hb_ctx *ctx, uint64_t info[5], uint8_t *u, uint8_t *node_bits, uint8_t *virt_bits);
 /* Emulates the collective of one pass between `count` logical ranks that live on ONE device
  * (contexts created with HB_FLAG_NO_RCCL; RCCL refuses two ranks on one device).
  *   phase 0, between hb_step_local and hb_step_finish of every context:

@@ -47,6 +47,8 @@ HB_FLAG_ALL_RELS = 0x8000
 HB_FLAG_LIVE_FIRST = 0x10000
 HB_FLAG_NO_LIVE_FIRST = 0x20000
 HB_FLAG_NO_SATURATION = 0x40000
+HB_FLAG_NO_EARLY_EXIT = 0x80000      # dense passes gather every source of a row (A/B and test switch of DESIGN.md section 39)
+HB_FLAG_FORCE_EARLY_EXIT = 0x100000  # ... test for the early exit from pass 1 on, whatever is saturated (tests)
 HB_SAMPLE_MAX_LEVELS = 16
 
 # switches of the experiments build in hb_options.tune[1] (stract_amd/csrc/hb_experiments.h describes each)
@@ -1363,7 +1365,7 @@ class Context:
     def saturation(self):
         """(skipping in use, U[64], node bits[n] in input order, hub-chunk bits[nv] in plan order) of the run in progress
         (hb_debug_saturation); (False, None, None, None) for a context that does not skip saturated rows."""
-        info = np.zeros(3, dtype=np.uint64)
+        info = np.zeros(5, dtype=np.uint64)
         self._check(self.lib.hb_debug_saturation(self.h, _ptr(info), None, None, None))
         if not info[0]:
             return False, None, None, None
@@ -1372,6 +1374,13 @@ class Context:
         virt = np.zeros(int(info[2]), dtype=np.uint8)
         self._check(self.lib.hb_debug_saturation(self.h, _ptr(info), _ptr(u), _ptr(node), _ptr(virt)))
         return True, u, node.astype(bool), virt.astype(bool)
+
+    def early_exit(self):
+        """(the last dense pass ran the early-exit instances, work rows of that pass that left their gather loop early)
+        (hb_debug_saturation)"""
+        info = np.zeros(5, dtype=np.uint64)
+        self._check(self.lib.hb_debug_saturation(self.h, _ptr(info), None, None, None))
+        return bool(info[4]), int(info[3])
 
     def graph(self):
         st = self.stats()

@@ -104,6 +104,12 @@ struct GraphDeviceState {
     uint16_t *d_self_jp = nullptr; // per node row: its OWN initial register in the same format (the lean pass 0 reads it instead of the counters)
     uint32_t *d_sat = nullptr;     // saturated rows (PassParams::sat): one bit per work row, cleared by hb_begin.  NULL: the context is outside the gate
     uint32_t *d_sat_u = nullptr;   // U of the saturation bound, one word per register (sat_bound_kernel at load)
+    // early exit: the dense passes of this run that follow enough saturation leave a row's gather loop once its
+    // accumulator has reached U (the EARLY instances of pass_kernel)
+    unsigned long long *d_early = nullptr; // kStripes words: rows of the last EARLY pass that left their loop early (allocated with d_sat)
+    uint64_t sat_out_sum = 0;      // out-degree sum of the rows saturated so far in this run (word 1 of the dense passes' counters)
+    bool early_now = false;        // the dense pass being launched runs the EARLY instances
+    bool last_dense_early = false; // ... and so did the last dense pass that was launched (hb_debug_saturation)
     uint4 *d_regs[2] = {nullptr, nullptr};
     uint4 *d_part = nullptr;
     uint32_t *d_bits[2] = {nullptr, nullptr};
@@ -1335,6 +1341,8 @@ int hb_begin(hb_ctx *c)
         c->cur = 0;
         c->t = 0;
         c->lean_init = false;
+        c->sat_out_sum = 0;
+        c->early_now = c->last_dense_early = false;
         if (p.n_pad) {
             if (lean_pass0(c)) {
                 // [r6] pass 0 produces the initial state itself (hb_kernels.hip.h PassParams::rd_init): hb_begin writes two bitmaps instead of

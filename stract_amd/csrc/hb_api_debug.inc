@@ -23,8 +23,9 @@ int hb_debug_copy_registers(hb_ctx *c, uint8_t *out)
 }
 
 // the saturated rows of the run in progress (DESIGN.md section 38): U, and the bitmap unpacked to one byte per node (input order) /
-// per hub chunk (plan order)
-int hb_debug_saturation(hb_ctx *c, uint64_t info[3], uint8_t *u, uint8_t *node_bits, uint8_t *virt_bits)
+// per hub chunk (plan order); of the last dense pass: the work rows that left their gather loop early, and whether it ran the EARLY
+// instances at all (DESIGN.md section 39)
+int hb_debug_saturation(hb_ctx *c, uint64_t info[5], uint8_t *u, uint8_t *node_bits, uint8_t *virt_bits)
 {
     return guarded(c, [&]() -> int {
         if (!c || !info) return HB_ERR_INVALID;
@@ -35,7 +36,15 @@ int hb_debug_saturation(hb_ctx *c, uint64_t info[3], uint8_t *u, uint8_t *node_b
         info[0] = (c->d_sat != nullptr && !unfused(c) && !linked(c)) ? 1 : 0;
         info[1] = p.n;
         info[2] = p.nv;
+        info[3] = info[4] = 0;
         if (!info[0]) return HB_OK;
+        if (c->last_dense_early) {
+            unsigned long long he[hbk::kStripes];
+            HB_HIP(hipMemcpyAsync(he, c->d_early, sizeof(he), hipMemcpyDeviceToHost, c->stream));
+            HB_HIP(hipStreamSynchronize(c->stream));
+            for (int s = 0; s < hbk::kStripes; s++) info[3] += he[s];
+            info[4] = 1;
+        }
         if ((rc = need_host_dev_of(c))) return rc;
         uint32_t hu[64];
         std::vector<uint32_t> words(c->bits_words);

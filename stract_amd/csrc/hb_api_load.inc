@@ -364,6 +364,8 @@ int plan_and_upload(hb_ctx *c, OwnedCsr in, uint64_t m_eff)
         // saturated rows (DESIGN.md section 38): U depends on the graph alone, the bitmap is hb_begin's to clear
         if ((rc = dev_alloc(c, &c->d_sat_u, 64))) return rc;
         if ((rc = dev_alloc(c, &c->d_sat, c->bits_words))) return rc;
+        if ((rc = dev_alloc(c, &c->d_early, hbk::kStripes))) return rc; // (DESIGN.md section 39; cleared before every EARLY pass)
+        HB_HIP(hipMemsetAsync(c->d_early, 0, hbk::kStripes * sizeof(unsigned long long), c->stream));
         HB_HIP(hipMemsetAsync(c->d_sat_u, 0, 64 * sizeof(uint32_t), c->stream));
         HB_HIP(hipMemsetAsync(c->d_sat, 0, c->bits_words * sizeof(uint32_t), c->stream));
         hipLaunchKernelGGL(hbk::sat_bound_kernel, dim3(grid_blocks(c, (p.n_pad + 255) / 256, 8)), dim3(256), 0, c->stream, (const uint64_t *)c->d_idlow,

@@ -7,19 +7,24 @@
 using PassKernel = void (*)(const hbk::PassParams);
 using SweepKernel = void (*)(const hbk::SweepParams);
 
-template <bool REAL, bool FUSED, bool STATS, bool INIT, bool EPI4>
+template <bool REAL, bool FUSED, bool STATS, bool INIT, bool EPI4, bool EARLY = false>
 PassKernel dense_by_unroll(int unroll)
 {
     if constexpr (!INIT) { // (the INIT form exists for 2 and 4 only)
-        if (unroll == 1) return hbk::pass_kernel<REAL, FUSED, STATS, 1, INIT, EPI4>;
+        if (unroll == 1) return hbk::pass_kernel<REAL, FUSED, STATS, 1, INIT, EPI4, EARLY>;
     }
-    if (unroll == 2) return hbk::pass_kernel<REAL, FUSED, STATS, 2, INIT, EPI4>;
-    return hbk::pass_kernel<REAL, FUSED, STATS, 4, INIT, EPI4>;
+    if (unroll == 2) return hbk::pass_kernel<REAL, FUSED, STATS, 2, INIT, EPI4, EARLY>;
+    return hbk::pass_kernel<REAL, FUSED, STATS, 4, INIT, EPI4, EARLY>;
 }
 template <bool REAL, bool FUSED>
-PassKernel dense_kernel_of(bool stats, int unroll, bool init, bool epi4)
+PassKernel dense_kernel_of(bool stats, int unroll, bool init, bool epi4, bool early)
 {
     if (stats) return dense_by_unroll<REAL, FUSED, true, false, false>(unroll); // (a counting pass has neither the INIT nor the EPI4 form)
+    if constexpr (REAL == FUSED) {
+        // EARLY: a row leaves its gather loop once its accumulator is >= U (the fused node rows and the hub chunks of a context that
+        // skips saturated rows; never pass 0)
+        if (early && !init) return epi4 ? dense_by_unroll<REAL, FUSED, false, false, REAL, true>(unroll) : dense_by_unroll<REAL, FUSED, false, false, false, true>(unroll);
+    }
     if constexpr (REAL && FUSED) {
         // EPI4: the once-per-row estimator / Kahan epilogue (default for the fused node rows)
         if (epi4) return init ? dense_by_unroll<true, true, false, true, true>(unroll) : dense_by_unroll<true, true, false, false, true>(unroll);
@@ -27,13 +32,13 @@ PassKernel dense_kernel_of(bool stats, int unroll, bool init, bool epi4)
     return init ? dense_by_unroll<REAL, FUSED, false, true, false>(unroll) : dense_by_unroll<REAL, FUSED, false, false, false>(unroll);
 }
 // dense pass.  real: node rows (else hub chunks, which are never fused); init: pass 0, the sources' initial registers stream in with
-// the edge list (hb_kernels.hip.h)
-PassKernel dense_kernel(bool real, bool fused, bool stats, int unroll, bool init, bool epi4)
+// the edge list (hb_kernels.hip.h); early: the EARLY instances (launch_pass asks for them under early_exit_rule)
+PassKernel dense_kernel(bool real, bool fused, bool stats, int unroll, bool init, bool epi4, bool early)
 {
     init = init && unroll != 1;
-    if (real && fused) return dense_kernel_of<true, true>(stats, unroll, init, epi4);
-    if (real) return dense_kernel_of<true, false>(stats, unroll, init, false);
-    return dense_kernel_of<false, false>(stats, unroll, init, false);
+    if (real && fused) return dense_kernel_of<true, true>(stats, unroll, init, epi4, early);
+    if (real) return dense_kernel_of<true, false>(stats, unroll, init, false, false);
+    return dense_kernel_of<false, false>(stats, unroll, init, false, early);
 }
 
 template <bool REAL, bool FUSED>
@@ -97,7 +102,7 @@ void launch_pass(hb_ctx *c, const hbk::PassParams &pp, bool real, bool frontier,
         blocks = grid_blocks(c, ntiles, bpc);
         if (pp.xcd_map) blocks = std::max((blocks + 7) / 8 * 8, 8u); // 8 queues, equal shares of the grid
         kernel = frontier ? bitmap_kernel(real, fused, stats, !xbit(c, HB_X_BITMAP_SLOTWISE))
-                          : dense_kernel(real, fused, stats, pass_unroll(c, real), init, !xbit(c, HB_X_TILE_EPILOGUE));
+                          : dense_kernel(real, fused, stats, pass_unroll(c, real), init, !xbit(c, HB_X_TILE_EPILOGUE), c->early_now && pp.sat != nullptr);
     }
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, c->stream, pp);
 }
@@ -138,6 +143,17 @@ bool skips_dead_rows(const hb_ctx *c) { return c->plan.live_first && c->t >= 1 &
 // nor compute the hub chunks below it.  Pass 0 gathers everything and overwrites every partial (hb_begin relies on that).
 bool skips_saturated_rows(const hb_ctx *c) { return c->d_sat != nullptr && c->t >= 1 && !unfused(c) && !linked(c); } // (d_sat exists only inside the gate)
 
+// early exit (DESIGN.md section 39): the dense passes t >= 1 of a context that skips saturated rows run the EARLY instances - a row
+// leaves its gather loop once its accumulator is >= U - when enough sources are saturated for rows to reach U before their lists end:
+// the rows saturated so far hold at least 1/64 of the edges as sources (sat_out_sum, booked by step_finish).  Before that the per-round
+// test only costs; a graph on which nothing saturates never launches one.  HB_FLAG_FORCE_EARLY_EXIT: from pass 1 on, whatever the sum
+// says (tests); HB_FLAG_NO_EARLY_EXIT: never (A/B runs, tests).  Every choice gives the same bits.
+bool early_exit_rule(const hb_ctx *c)
+{
+    if (!skips_saturated_rows(c) || (c->opt.flags & HB_FLAG_NO_EARLY_EXIT)) return false;
+    return (c->opt.flags & HB_FLAG_FORCE_EARLY_EXIT) || (c->sat_out_sum && c->sat_out_sum * 64 >= c->m_global);
+}
+
 hbk::PassParams make_params(hb_ctx *c)
 {
     const Plan &p = c->plan;
@@ -177,6 +193,7 @@ hbk::PassParams make_params(hb_ctx *c)
     pp.live_limit = skips_dead_rows(c) ? (uint32_t)p.n_live : hbk::kNone;
     pp.sat = skips_saturated_rows(c) ? c->d_sat : nullptr; // (only the dense kernels read it)
     pp.sat_u = c->d_sat_u;
+    pp.early_cnt = c->d_early;
     return pp;
 }
 
@@ -601,6 +618,9 @@ int sweep_pass(hb_ctx *c, const hbk::PassParams &pp, hipEvent_t *E)
 int level_pass(hb_ctx *c, hbk::PassParams pp, hipEvent_t *E, bool frontier, bool fused, bool lean)
 {
     const Plan &p = c->plan;
+    c->early_now = !frontier && pp.sat && early_exit_rule(c);
+    if (!frontier) c->last_dense_early = c->early_now;
+    if (c->early_now) HB_HIP(hipMemsetAsync(c->d_early, 0, hbk::kStripes * sizeof(unsigned long long), c->stream));
     for (size_t l = 0; l + 1 < p.level_begin.size(); l++) {
         pp.row_lo = p.level_begin[l];
         pp.row_hi = p.level_begin[l + 1];
@@ -876,6 +896,7 @@ int step_finish(hb_ctx *c, int *has_changes)
         HB_HIP(hipStreamSynchronize(c->stream));
     }
     sum_stripes(c->h_counters, c->h_counters);
+    if (c->cur_mode == kModeDense && skips_saturated_rows(c)) c->sat_out_sum += c->h_counters[1]; // (the rows this pass found saturated: early_exit_rule)
     hb_pass_stats ps{};
     ps.active_edges = (c->opt.flags & HB_FLAG_PASS_STATS) ? c->h_counters[1] : c->last_active; // A_t
     ps.mode = c->cur_mode;
@@ -1096,12 +1117,16 @@ int warm_kernels(hb_ctx *c)
     const bool fused = !unfused(c), epi4 = !xbit(c, HB_X_TILE_EPILOGUE), compact = !xbit(c, HB_X_BITMAP_SLOTWISE);
     const int hub_unroll = pass_unroll(c, false), node_unroll = pass_unroll(c, true);
     auto warm = [&](PassKernel k) { hipLaunchKernelGGL(k, one, blk, 0, s, pp); };
-    warm(dense_kernel(false, false, false, hub_unroll, false, false));
-    warm(dense_kernel(true, fused, false, node_unroll, false, epi4));
+    warm(dense_kernel(false, false, false, hub_unroll, false, false, false));
+    warm(dense_kernel(true, fused, false, node_unroll, false, epi4, false));
+    if (c->d_sat && fused && !(c->opt.flags & HB_FLAG_NO_EARLY_EXIT)) { // the EARLY instances of a context that may leave rows early
+        warm(dense_kernel(false, false, false, hub_unroll, false, false, true));
+        warm(dense_kernel(true, true, false, node_unroll, false, epi4, true));
+    }
     if (fused && pass0_streams_initial_registers(c)) { // pass 0 as the INIT launch
-        warm(dense_kernel(false, false, false, hub_unroll, true, false));
+        warm(dense_kernel(false, false, false, hub_unroll, true, false, false));
         warm(hbk::init_level1_kernel);
-        warm(dense_kernel(true, true, false, node_unroll, true, epi4));
+        warm(dense_kernel(true, true, false, node_unroll, true, epi4, false));
     }
     warm(bitmap_kernel(false, false, false, compact));
     warm(bitmap_kernel(true, fused, false, compact));

@@ -126,6 +126,9 @@ struct PassParams {
     // tests every row it visits and sets the bits, and a hub row that has just become saturated sets those of its virtual sources
     uint32_t *sat;
     const uint32_t *sat_u;
+    // early exit, the EARLY instances only: kStripes words, a wave adds the number of its work rows that left their
+    // gather loop with rounds still to go (debug read-out; the host clears it before such a pass)
+    unsigned long long *early_cnt;
 };
 
 // (initial_register_jp / counter_quarter_of_jp - the entry format of src_jp / self_jp - live in hb_regs.hip.h: the AMPC shard's edge step
@@ -150,7 +153,11 @@ namespace hbk {
 // EPI4      dense fused node rows only: the estimator's f64 half and the Kahan update are deferred until four tiles
 //           (64 rows) are merged and then run ONCE PER ROW, lane (g, q) taking row g of the q-th pending tile, instead
 //           of four times redundantly per quad; same arithmetic per row, same bits.
-template <bool REAL, bool FUSED, bool STATS, int UNROLL, bool INIT = false, bool EPI4 = false>
+// EARLY     dense passes t >= 1 with PassParams::sat set, never with INIT or STATS: after every gather round the accumulator is tested
+//           against U; once it is >= U in all 64 registers no remaining source can change it (every source is <= U) and the row leaves
+//           its loop.  The lists ascend in device order - descending out-degree -, so what is skipped is the cold end.  The epilogue
+//           is the same: a chunk that left early stores the true maximum (exactly U) as its partial.
+template <bool REAL, bool FUSED, bool STATS, int UNROLL, bool INIT = false, bool EPI4 = false, bool EARLY = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UNROLL >= 4) ? 3 : 4))) void pass_kernel(const PassParams p)
 {
     __shared__ double s_raw[FUSED ? kTableLen : 1];
@@ -167,7 +174,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
     // saturated rows (PassParams::sat): U lies in LDS, as the four quarters a quad compares its counter with
     __shared__ uint4 s_satu[4];
     const bool sat_on = !INIT && p.sat != nullptr; // kernel-uniform
-    if (!INIT && REAL && sat_on) {
+    if (!INIT && (REAL || EARLY) && sat_on) {
         if (threadIdx.x < 64) ((uint8_t *)s_satu)[threadIdx.x] = (uint8_t)p.sat_u[threadIdx.x];
         __syncthreads();
     }
@@ -186,6 +193,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
     }
     const uint64_t ntiles = (row_hi - row_lo + 63) >> 6;
     unsigned long long cnt_changed = 0, cnt_active = 0, cnt_rows = 0, cnt_out = 0;
+    unsigned long long cnt_sat = 0; // node rows, sat_on: out-degree sum of the rows whose saturation bit goes from 0 to 1 in this pass
+    uint32_t cnt_early = 0;         // (EARLY) rows of this lane's quads that left their loop with rounds to go, counted by lane q = 0
 
     // Software pipeline over the tiles of this workgroup: the row pointers / out-degree / own counter of the
     // NEXT tile are requested before the gathers of the current one, and the Kahan/size words of the current
@@ -388,6 +397,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
                         for (int j = 0; j < 4; j++) acc_merge(acc, r[u][j]);
                     }
                 }
+                if (EARLY && sat_on) {
+                    // after the round's merges: >= U in all four quarters of the row (the quad's own four bits: the loop is divergent
+                    // between quads) - nothing that is still to come can raise a register
+                    const uint64_t eb = __ballot(acc_ge(acc, s_satu[q]));
+                    if (((eb >> qshift) & 0xFull) == 0xFull) {
+                        cnt_early += (q == 0 && e + 4 * UNROLL < end);
+                        break;
+                    }
+                }
             }
         }
         if (INIT) {
@@ -434,6 +452,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
                 }
             }
             if (lane == 0 && row16 < row_hi) ((uint16_t *)p.sat)[row16 >> 4] = (uint16_t)pack16(sb);
+            if (((sb >> qshift) & 1ull) && !satb && q == 0) cnt_sat += od; // saturated sources from the next pass on (the host's EARLY rule)
         }
         if (REAL) {
             // lazy double buffer: wr[row] already holds the right value unless the row changed in this or in the previous pass
@@ -501,10 +520,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((REAL && UN
         for (int off = 32; off > 0; off >>= 1) {
             cnt_out += __shfl_down(cnt_out, off);
             if (STATS) cnt_active += __shfl_down(cnt_active, off);
+            if (!STATS && !INIT && REAL) cnt_sat += __shfl_down(cnt_sat, off);
         }
-        // cnt_changed is identical in all lanes of the wave (derived from a ballot)
-        const unsigned long long v[4] = {cnt_changed, cnt_active, cnt_rows, cnt_out};
-        block_add_counters(p.counters, v, (REAL ? 0x9u : 0u) | (STATS ? 0x2u : 0u));
+        // cnt_changed is identical in all lanes of the wave (derived from a ballot); word 1 of a pass that does not count active edges
+        // (no saturation bitmap exists in a counting context): the out-degree sum of the newly saturated rows
+        const unsigned long long v[4] = {cnt_changed, STATS ? cnt_active : cnt_sat, cnt_rows, cnt_out};
+        block_add_counters(p.counters, v, (REAL ? 0x9u : 0u) | ((STATS || (!INIT && REAL)) ? 0x2u : 0u));
+    }
+    if (EARLY) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) cnt_early += __shfl_down(cnt_early, off);
+        if (lane == 0 && cnt_early) atomicAdd(&p.early_cnt[blockIdx.x & (kStripes - 1)], (unsigned long long)cnt_early);
     }
 }
 

@@ -82,6 +82,17 @@ __device__ __forceinline__ bool counter_ge(const uint4 &a, const uint4 &b)
     return diff == 0;
 }
 
+// the accumulator >= b in each of the 16 registers, without acc_value(): the even bytes are clean 16-bit lanes; an odd byte is the high
+// byte of its lane of o[], which is >= the lane of b with the low byte cleared exactly when its high byte is >= b's
+__device__ __forceinline__ bool acc_ge(const Acc &a, const uint4 &b)
+{
+    const uint32_t y[4] = {b.x, b.y, b.z, b.w};
+    uint32_t diff = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) diff |= (pkmax(a.e[k], y[k] & 0x00FF00FFu) ^ a.e[k]) | (pkmax(a.o[k], y[k] & 0xFF00FF00u) ^ a.o[k]);
+    return diff == 0;
+}
+
 // the one register HyperLogLog::default(); add_u128(id) sets (hyperloglog.rs:4385-4400 with FastHasher :4311-4313; only the low 64 bits of
 // the id are hashed), as index | value << 8 - the entry format of src_jp / self_jp
 __device__ __forceinline__ uint16_t initial_register_jp(uint64_t id_low)

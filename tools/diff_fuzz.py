@@ -17,7 +17,9 @@ sources before a band cut, largest row that is not split) and two of NO_REORDER 
 cases this tool drew before it knew the option; live puts HB_FLAG_LIVE_FIRST on every context - the order every graph of 2^20 hosts and
 more is planned in; mixed (the default) draws one of nothing / HB_FLAG_LIVE_FIRST / HB_FLAG_NO_LIVE_FIRST per case.  Under live and mixed
 the graphs also include `dead_fringe`, and every loaded context's plan_live() is held against the host planner's on the same graph and flags;
-one case in three of them also runs with HB_FLAG_NO_SATURATION (the dense passes gather for saturated rows as well).
+one case in three of them also runs with HB_FLAG_NO_SATURATION (the dense passes gather for saturated rows as well),
+and every case draws one of nothing / HB_FLAG_FORCE_EARLY_EXIT / HB_FLAG_NO_EARLY_EXIT (a dense row leaves its gather
+loop once its accumulator has reached U - under the default rule, from pass 1 on, never).
 
 --mode ampc drives the AMPC shard (stract_amd/ampc.py) instead of a context: every case is one sequence of tests/ampc_model.py - 60 to 240
 interleaved calls on tables, graphs and filters that stay alive, each answer against the model, the whole content of every table and
@@ -61,7 +63,11 @@ def draw_order(rng, order, what):
     what["order"] = name
     # ... and, with it, whether the dense passes skip saturated rows (the default) or gather for every row
     what["saturation"] = bool(rng.integers(0, 3))
-    return ORDER_FLAGS[name] | (0 if what["saturation"] else _lib.HB_FLAG_NO_SATURATION)
+    # ... and whether a dense row may leave its gather loop once it has reached U: under the rule of the sum of
+    # saturated out-degrees, from pass 1 on, or never
+    what["early_exit"] = ("rule", "forced", "off")[int(rng.integers(0, 3))]
+    early = {"rule": 0, "forced": _lib.HB_FLAG_FORCE_EARLY_EXIT, "off": _lib.HB_FLAG_NO_EARLY_EXIT}[what["early_exit"]]
+    return ORDER_FLAGS[name] | (0 if what["saturation"] else _lib.HB_FLAG_NO_SATURATION) | early
 
 
 def check_plan_live(ctx, flags, chunk, tune, what):
