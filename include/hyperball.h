@@ -129,6 +129,17 @@ typedef struct hb_edge {
 #define HB_FLAG_FORCE_EARLY_EXIT 0x100000u /* those dense passes test for the early exit from pass 1 on, whatever is saturated (tests: small
                                           graphs reach the code in passes where nothing is saturated yet).  Same results; loses to
                                           HB_FLAG_NO_EARLY_EXIT and HB_FLAG_NO_SATURATION                                                  */
+#define HB_FLAG_PACKED_WIRE   0x200000u /* every exchange that moves WHOLE counters moves them as 48-byte packed rows: a plain
+                                          little-endian bit stream of 64 six-bit codes, code = r for r <= 58 and 63 for r == 65 (a
+                                          register of this library is 0, 1..58 or 65, so the packing is exact).  The destination
+                                          partition's all-gather ships S x 48 bytes per rank; the edge partition's all-reduce(max) - plain
+                                          and HB_FLAG_CHANGED_ONLY - becomes: pack, all-to-all of the ranks' slices, maximum of the
+                                          received pieces, all-gather of the packed slices, unpack (0.75 x the bytes, same results; the
+                                          per-range pipeline of the plain form is off).  The destination partition's changed-only
+                                          exchange is packed already and does not change.  A context without a communicator and without
+                                          caller collectives (one rank, no HB_FLAG_RCCL_SELF) ignores the flag.  Not with
+                                          HB_FLAG_REFERENCE_TAIL.  With hb_set_collectives on the edge partition: hb_set_all_to_all too
+                                           */
 #define HB_FLAG_RCCL_SELF     0x80u /* world_size == 1 but still create a 1-rank communicator and run
                                        the collectives (exercises the RCCL call path on one GPU)   */
 
@@ -891,6 +902,12 @@ typedef struct hb_collectives {
     int (*broadcast)(void *user, void *buf, uint64_t bytes, int root, void *stream);
 } hb_collectives;
 int hb_set_collectives(hb_ctx *ctx, const hb_collectives *ops);
+/* The one collective hb_collectives lacks, for HB_FLAG_PACKED_WIRE on the edge partition: piece k of `send`
+ * (world x bytes_per_rank bytes) goes to rank k, piece k of `recv` comes from rank k; send != recv.  `user` is the pointer of
+ * hb_set_collectives; device pointers and `stream` as for the other three.  Set after hb_set_collectives (which also clears it) and
+ * before the graph is loaded; NULL removes it.  hb_begin refuses (HB_ERR_INVALID) on an edge-partitioned context that has
+ * HB_FLAG_PACKED_WIRE and caller collectives but not this one.  A context with a communicator does the exchange itself. */
+int hb_set_all_to_all(hb_ctx *ctx, int (*all_to_all)(void *user, const void *send, void *recv, uint64_t bytes_per_rank, void *stream));
 /* helper for host-staged implementations of the above: copy on `stream`, then synchronise it (to_device: host -> device) */
 int hb_debug_staged_copy(void *dst, const void *src, uint64_t bytes, int to_device, void *stream);
 
@@ -952,8 +969,15 @@ int hb_debug_saturation(hb_ctx *ctx, uint64_t info[5], uint8_t *u, uint8_t *node
  *     edge partition:        all-reduce(max) of the pending counters
  *     destination partition: all-gather of the owned counter / changed-bit slices, sum of the
  *                            changed counts (ctxs[i] must be rank i)
+ *     HB_FLAG_PACKED_WIRE contexts: the packed forms of these, device copies in place of the collectives
  *   phase 1, before hb_finish: all-gather of the Kahan-sum slices. */
 int hb_debug_exchange(hb_ctx **ctxs, int count, int phase);
+/* The three kernels of HB_FLAG_PACKED_WIRE on arbitrary rows (unit-test and measurement door): rows = pieces x count x 64 host bytes
+ * (piece k = rows [k count, (k + 1) count)) are uploaded, packed to 48-byte rows, the register-wise maximum over the pieces is taken
+ * in packed form and unpacked.  packed_max = count x 48 bytes, rows_out = count x 64 bytes (either may be NULL); ms = the GPU time
+ * of the pack of all pieces, of the maximum and of the unpack, by events on the context's stream.  rows == NULL: every piece is the
+ * context's own resident counters (count <= the padded row count of the loaded graph, after hb_begin), nothing is uploaded. */
+int hb_debug_wire6(hb_ctx *ctx, const uint8_t *rows, uint64_t count, uint32_t pieces, uint8_t *packed_max, uint8_t *rows_out, float ms[3]);
 /* Two halves of hb_step: local pull into the pending counters; [collective, or hb_debug_exchange];
  * then (edge partition / HB_FLAG_UNFUSED) estimator/Kahan/changed detection, bookkeeping. */
 int hb_step_local(hb_ctx *ctx);

@@ -49,6 +49,7 @@ HB_FLAG_NO_LIVE_FIRST = 0x20000
 HB_FLAG_NO_SATURATION = 0x40000
 HB_FLAG_NO_EARLY_EXIT = 0x80000      # dense passes gather every source of a row (A/B and test switch of DESIGN.md section 39)
 HB_FLAG_FORCE_EARLY_EXIT = 0x100000  # ... test for the early exit from pass 1 on, whatever is saturated (tests)
+HB_FLAG_PACKED_WIRE = 0x200000      # whole counters travel as 48-byte rows, 6 bits per register
 HB_SAMPLE_MAX_LEVELS = 16
 
 # switches of the experiments build in hb_options.tune[1] (stract_amd/csrc/hb_experiments.h describes each)
@@ -75,6 +76,10 @@ HB_X_SIM_SMALL_PIECES = 0x20000000
 U128 = np.dtype([("lo", "<u8"), ("hi", "<u8")])
 EDGE = np.dtype([("from", U128), ("to", U128), ("rel_flags", "<u8")])
 assert U128.itemsize == 16 and EDGE.itemsize == 40
+
+
+# int all_to_all(void *user, const void *send, void *recv, uint64_t bytes_per_rank, void *stream) - hb_set_all_to_all
+ALL_TO_ALL_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p)
 
 
 class HbOptions(ctypes.Structure):
@@ -495,6 +500,7 @@ _SIGNATURES = [
     ("hb_tail_segment_end", ctypes.c_int, [_P]),
     ("hb_debug_set_ingest_limits", ctypes.c_int, [_P, _U64, _U64, _U64]),
     ("hb_set_collectives", ctypes.c_int, [_P, _P]),
+    ("hb_set_all_to_all", ctypes.c_int, [_P, _P]),
     ("hb_debug_staged_copy", ctypes.c_int, [_P, _P, _U64, ctypes.c_int, _P]),
     ("hb_pinned_alloc", ctypes.c_int, [_U64, ctypes.POINTER(ctypes.c_void_p)]),
     ("hb_pinned_free", None, [ctypes.c_void_p]),
@@ -523,6 +529,7 @@ _SIGNATURES = [
     ("hb_debug_copy_graph", ctypes.c_int, [_P, _P, _P, _P]),
     ("hb_debug_copy_plan", ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     ("hb_debug_exchange", ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
+    ("hb_debug_wire6", ctypes.c_int, [_P, _P, _U64, ctypes.c_uint32, _P, _P, _P]),
     ("hb_step_local", ctypes.c_int, [_P]),
     ("hb_step_finish", ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int)]),
     ("hb_host_ingest", ctypes.c_int, [_P, _U64, _P, _U64, ctypes.POINTER(_U64), ctypes.POINTER(_U64),
@@ -940,6 +947,27 @@ class Context:
         """Emulated collective between logical ranks on one device (hb_debug_exchange)."""
         arr = (ctypes.c_void_p * len(ctxs))(*[c.h for c in ctxs])
         ctxs[0]._check(ctxs[0].lib.hb_debug_exchange(arr, len(ctxs), phase))
+
+    def set_all_to_all(self, callback):
+        """hb_set_all_to_all: `callback` is a ctypes function pointer (ALL_TO_ALL_FN) the caller keeps alive, or None."""
+        self._check(self.lib.hb_set_all_to_all(self.h, ctypes.cast(callback, ctypes.c_void_p) if callback is not None else None))
+
+    def wire6(self, rows=None, pieces=1, count=None):
+        """hb_debug_wire6: the three kernels of HB_FLAG_PACKED_WIRE on `rows` (pieces x count x 64 uint8, or pieces * count rows of 64):
+        pack, register-wise maximum over the pieces in packed form, unpack.  Returns (packed_max count x 48, rows_out count x 64,
+        (ms_pack, ms_max, ms_unpack)).  rows=None: every piece is the context's resident counters (`count` rows of them, after
+        begin()); nothing is uploaded or downloaded and both arrays are None."""
+        ms = (ctypes.c_float * 3)()
+        if rows is None:
+            self._check(self.lib.hb_debug_wire6(self.h, None, int(count), int(pieces), None, None, ms))
+            return None, None, tuple(ms)
+        rows = np.ascontiguousarray(rows, dtype=np.uint8).reshape(-1, 64)
+        assert len(rows) % pieces == 0
+        count = len(rows) // pieces
+        packed = np.zeros((count, 48), dtype=np.uint8)
+        out = np.zeros((count, 64), dtype=np.uint8)
+        self._check(self.lib.hb_debug_wire6(self.h, _ptr(rows), count, int(pieces), _ptr(packed), _ptr(out), ms))
+        return packed, out, tuple(ms)
 
     def finish(self):
         self._check(self.lib.hb_finish(self.h))

@@ -140,6 +140,9 @@ struct GraphDeviceState {
     uint32_t *d_lbits = nullptr, *d_lbits_all = nullptr, *d_ubits = nullptr;
     bool ubits_valid = false; // d_ubits holds this pass' union (set by the exchange, consumed by the epilogue)
     unsigned long long *d_rank_cnt = nullptr; // world words: every rank's changed rows of this pass (summed over the ranks)
+    // HB_FLAG_PACKED_WIRE: 48-byte rows, world x slice_rows of them each - [0] the packed rows / gathered slices, [1] the pieces an
+    // all-to-all delivered (edge partition only); allocated by the first pass that exchanges (ensure_wire6_buffers)
+    uint32_t *d_w6[2] = {nullptr, nullptr};
     // the far tail as one workgroup (hb_tail.hip.h): work lists, their counts / status words, and whether the lists describe the
     // bitmaps as they are now (any pass run by other kernels invalidates them: the next entry collects them again)
     uint32_t *d_tl_changed[2] = {nullptr, nullptr}, *d_tl_vchanged[2] = {nullptr, nullptr}, *d_tl_dirty[2] = {nullptr, nullptr};
@@ -383,6 +386,7 @@ struct hb_ctx : GraphDeviceState {
     hipStream_t stream = nullptr;
     ncclComm_t comm = nullptr;
     hb_collectives coll{}; // hb_set_collectives: the per-pass exchanges go through these instead of RCCL (HB_FLAG_NO_RCCL contexts)
+    int (*coll_a2a)(void *user, const void *send, void *recv, uint64_t bytes_per_rank, void *stream) = nullptr; // hb_set_all_to_all
     std::string err;
     std::string arch;
     uint64_t lim_records = 0, lim_bytes = 0, lim_chunk = 0; // hb_debug_set_ingest_limits (0 = no limit / default)
@@ -684,6 +688,33 @@ int coll_broadcast(hb_ctx *c, void *buf, uint64_t count, ncclDataType_t dt, int 
         return fail(c, HB_ERR_RCCL, "the caller's broadcast (hb_set_collectives) failed");
     return HB_OK;
 }
+// piece k of send (world x bytes_per_rank) to rank k, piece k of recv from rank k; send != recv (HB_FLAG_PACKED_WIRE, edge partition)
+int coll_all_to_all(hb_ctx *c, const void *send, void *recv, uint64_t bytes_per_rank, hipStream_t s)
+{
+    if (c->comm) {
+        const int world = std::max(c->opt.world_size, 1);
+        if (world == 1) { // (HB_FLAG_RCCL_SELF: the one piece is this rank's own)
+            if (bytes_per_rank) HB_HIP(hipMemcpyAsync(recv, send, bytes_per_rank, hipMemcpyDeviceToDevice, s));
+            return HB_OK;
+        }
+#ifdef NCCL_VERSION_CODE
+        // NEVER RUN: two ranks of a communicator need two GPUs, and no test of this repository has had them.  The grouped
+        // point-to-point form is RCCL's documented all-to-all (one send and one receive per peer inside one group).
+        HB_NCCL(ncclGroupStart());
+        for (int k = 0; k < world; k++) {
+            HB_NCCL(ncclSend((const uint8_t *)send + (uint64_t)k * bytes_per_rank, bytes_per_rank, ncclUint8, k, c->comm, s));
+            HB_NCCL(ncclRecv((uint8_t *)recv + (uint64_t)k * bytes_per_rank, bytes_per_rank, ncclUint8, k, c->comm, s));
+        }
+        HB_NCCL(ncclGroupEnd());
+        return HB_OK;
+#else
+        return fail(c, HB_ERR_RCCL, "all-to-all between the ranks of a communicator: this build's RCCL header has no ncclSend / ncclRecv");
+#endif
+    }
+    if (!c->coll_a2a) return fail(c, HB_ERR_INVALID, "HB_FLAG_PACKED_WIRE on the edge partition needs hb_set_all_to_all beside hb_set_collectives");
+    if (c->coll_a2a(c->coll.user, send, recv, bytes_per_rank, (void *)s)) return fail(c, HB_ERR_RCCL, "the caller's all_to_all (hb_set_all_to_all) failed");
+    return HB_OK;
+}
 int coll_group_start(hb_ctx *c)
 {
     if (c->comm) HB_NCCL(ncclGroupStart());
@@ -707,6 +738,8 @@ bool ref_tail(const hb_ctx *c) { return (c->opt.flags & HB_FLAG_REFERENCE_TAIL) 
 // rel-flag bits that drop a record at ingest: SKIPPED_REL (harmonic.rs:131), none with HB_FLAG_ALL_RELS (ForwardlinksQuery has no
 // rel filter, query/forwardlink.rs:44-53: the page graph of approx_harmonic.rs follows every edge)
 uint64_t skip_mask(const hb_ctx *c) { return (c->opt.flags & HB_FLAG_ALL_RELS) ? 0ull : HB_SKIPPED_REL_MASK; }
+// HB_FLAG_PACKED_WIRE: whole counters travel as 48-byte rows; a context that exchanges nothing ignores the flag
+bool packed_wire(const hb_ctx *c) { return (c->opt.flags & HB_FLAG_PACKED_WIRE) && (multi_rank(c) || linked(c)); }
 bool unfused(const hb_ctx *c)
 {
     return edge_partitioned(c) || (linked(c) && !dest_mode(c)) || (c->opt.flags & HB_FLAG_UNFUSED) || ref_tail(c);
@@ -875,6 +908,12 @@ int hb_create(const hb_options *opt, hb_ctx **out)
 #endif
         if ((o.flags & HB_FLAG_REFERENCE_TAIL) && (o.world_size > 1 || (o.flags & (HB_FLAG_RCCL_SELF | HB_FLAG_DEST_PARTITION))))
             return fail(c, HB_ERR_INVALID, "HB_FLAG_REFERENCE_TAIL is a single-rank mode (no partition / RCCL flags)");
+        if ((o.flags & HB_FLAG_PACKED_WIRE) && (o.flags & HB_FLAG_REFERENCE_TAIL))
+            return fail(c, HB_ERR_INVALID, "HB_FLAG_PACKED_WIRE and HB_FLAG_REFERENCE_TAIL exclude each other (the tail mode is a single-rank mode: it has no wire)");
+#ifdef HB_EXPERIMENTS
+        if ((o.flags & HB_FLAG_PACKED_WIRE) && (HB_XBITS(o.tune[1]) & HB_X_WIRE_64B))
+            return fail(c, HB_ERR_INVALID, "HB_FLAG_PACKED_WIRE and HB_X_WIRE_64B exclude each other (48-byte rows everywhere against 64-byte rows in the changed-only exchange)");
+#endif
         if ((o.flags & HB_FLAG_ALL_RELS) && (o.flags & HB_FLAG_REFERENCE_TAIL))
             return fail(c, HB_ERR_INVALID, "HB_FLAG_ALL_RELS and HB_FLAG_REFERENCE_TAIL exclude each other (the tail mode replays the rel filter)");
         hb_ctx *ctx = new (std::nothrow) hb_ctx();
@@ -1147,6 +1186,7 @@ int hb_set_collectives(hb_ctx *c, const hb_collectives *ops)
         if (!c) return HB_ERR_INVALID;
         if (c->comm) return fail(c, HB_ERR_INVALID, "hb_set_collectives: the context already has an RCCL communicator (create it with HB_FLAG_NO_RCCL)");
         if (c->loaded) return fail(c, HB_ERR_INVALID, "hb_set_collectives: set the collectives before the graph is loaded");
+        c->coll_a2a = nullptr; // (hb_set_all_to_all comes after this call)
         if (!ops) {
             c->coll = hb_collectives{};
             return HB_OK;
@@ -1162,6 +1202,18 @@ int hb_set_collectives(hb_ctx *c, const hb_collectives *ops)
             }
         }
         c->coll = *ops;
+        return HB_OK;
+    });
+}
+
+int hb_set_all_to_all(hb_ctx *c, int (*all_to_all)(void *user, const void *send, void *recv, uint64_t bytes_per_rank, void *stream))
+{
+    return guarded(c, [&]() -> int {
+        if (!c) return HB_ERR_INVALID;
+        if (c->comm) return fail(c, HB_ERR_INVALID, "hb_set_all_to_all: the context has an RCCL communicator and exchanges by itself (create it with HB_FLAG_NO_RCCL)");
+        if (c->loaded) return fail(c, HB_ERR_INVALID, "hb_set_all_to_all: set it before the graph is loaded");
+        if (all_to_all && !c->coll.all_reduce) return fail(c, HB_ERR_INVALID, "hb_set_all_to_all: call hb_set_collectives first (its `user` pointer is passed on)");
+        c->coll_a2a = all_to_all;
         return HB_OK;
     });
 }
@@ -1325,6 +1377,9 @@ int hb_begin(hb_ctx *c)
         const Plan &p = c->plan;
         if (p.n_pad * 4 >= 0xFFFFFFFFull) return fail(c, HB_ERR_LIMIT, "more than 2^30 nodes: init_kernel is one quad per node in one dispatch");
         if ((rc = refuse_stale_error(c, "hb_begin"))) return rc;
+        if (packed_wire(c) && edge_partitioned(c) && c->coll.all_reduce && !c->coll_a2a)
+            return fail(c, HB_ERR_INVALID, "hb_begin: HB_FLAG_PACKED_WIRE on the edge partition with caller collectives needs hb_set_all_to_all (the packed "
+                                           "all-reduce is an all-to-all of slices, a local maximum and an all-gather)");
         // the rows are nobody's until the initial state is complete (an error return below leaves them so)
         c->rows = RowsOf::Nobody;
         c->run_open = false;

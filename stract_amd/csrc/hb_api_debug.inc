@@ -136,6 +136,59 @@ int hb_debug_hll_size(hb_ctx *c, const uint8_t *regs, uint64_t count, uint64_t *
     });
 }
 
+// pack -> maximum over the pieces -> unpack on arbitrary rows, each launch timed (the unit-test and measurement door of the
+// HB_FLAG_PACKED_WIRE kernels); rows == NULL: every piece is the resident counters of the run in progress
+int hb_debug_wire6(hb_ctx *c, const uint8_t *rows, uint64_t count, uint32_t pieces, uint8_t *packed_max, uint8_t *rows_out, float ms[3])
+{
+    return guarded(c, [&]() -> int {
+        if (!c || !pieces) return HB_ERR_INVALID;
+        if (count >= (1ull << 40) / pieces) return fail(c, HB_ERR_LIMIT, "hb_debug_wire6: too many rows");
+        int rc = set_device(c);
+        if (rc) return rc;
+        if (ms) ms[0] = ms[1] = ms[2] = 0.f;
+        if (!count) return HB_OK;
+        const uint4 *src = nullptr;
+        DevPtr<uint4> d_rows, d_out;
+        DevPtr<uint32_t> d_packed, d_max;
+        if (rows) {
+            HB_HIP_AS("", d_rows.alloc((uint64_t)pieces * count * 4));
+            HB_HIP_AS("", hipMemcpyAsync(d_rows.get(), rows, (uint64_t)pieces * count * 64, hipMemcpyHostToDevice, c->stream));
+            src = d_rows.get();
+        } else {
+            if (c->rows != RowsOf::HyperBall) return fail(c, HB_ERR_INVALID, "hb_debug_wire6 without rows: call hb_begin first");
+            if (count > c->plan.n_pad) return fail(c, HB_ERR_INVALID, "hb_debug_wire6 without rows: count exceeds the padded row count");
+            if ((rc = ensure_initial_state(c))) return rc;
+            src = c->d_regs[c->cur];
+        }
+        HB_HIP_AS("", d_packed.alloc((uint64_t)pieces * count * 12));
+        HB_HIP_AS("", d_max.alloc(count * 12));
+        HB_HIP_AS("", d_out.alloc(count * 4));
+        hipEvent_t *E = c->ev; // (no pass is in flight inside a debug call: kEvStart .. kEvMerge mark the four instants)
+        HB_HIP(hipEventRecord(E[kEvStart], c->stream));
+        if (rows) {
+            hipLaunchKernelGGL(hbk::pack6_rows_kernel, dim3(wire6_blocks(c, (uint64_t)pieces * count)), dim3(256), 0, c->stream, src, (uint64_t)pieces * count, (uint64_t)pieces * count, d_packed.get());
+        } else {
+            for (uint32_t k = 0; k < pieces; k++)
+                hipLaunchKernelGGL(hbk::pack6_rows_kernel, dim3(wire6_blocks(c, count)), dim3(256), 0, c->stream, src, count, count, d_packed.get() + (uint64_t)k * count * 12);
+        }
+        HB_HIP(hipEventRecord(E[kEvLevel1], c->stream));
+        hipLaunchKernelGGL(hbk::max6_pieces_kernel, dim3(wire6_blocks(c, count)), dim3(256), 0, c->stream, (const uint32_t *)d_packed.get(), count * 12, pieces, count, d_max.get());
+        HB_HIP(hipEventRecord(E[kEvLevels], c->stream));
+        hipLaunchKernelGGL(hbk::unpack6_rows_kernel, dim3(wire6_blocks(c, count)), dim3(256), 0, c->stream, (const uint32_t *)d_max.get(), count, d_out.get());
+        HB_HIP(hipEventRecord(E[kEvMerge], c->stream));
+        HB_HIP(hipGetLastError());
+        if (packed_max) HB_HIP_AS("", hipMemcpyAsync(packed_max, d_max.get(), count * 48, hipMemcpyDeviceToHost, c->stream));
+        if (rows_out) HB_HIP_AS("", hipMemcpyAsync(rows_out, d_out.get(), count * 64, hipMemcpyDeviceToHost, c->stream));
+        HB_HIP_AS("", hipStreamSynchronize(c->stream));
+        if (ms) {
+            HB_HIP(hipEventElapsedTime(&ms[0], E[kEvStart], E[kEvLevel1]));
+            HB_HIP(hipEventElapsedTime(&ms[1], E[kEvLevel1], E[kEvLevels]));
+            HB_HIP(hipEventElapsedTime(&ms[2], E[kEvLevels], E[kEvMerge]));
+        }
+        return HB_OK;
+    });
+}
+
 int hb_debug_state_hash(hb_ctx *c, uint64_t out[2])
 {
     return guarded(c, [&]() -> int {
@@ -340,6 +393,38 @@ int hb_debug_exchange(hb_ctx **ctxs, int count, int phase)
             HB_HIP(hipStreamSynchronize(c->stream));
             return HB_OK;
         }
+        const bool wire6 = packed_wire(c); // HB_FLAG_PACKED_WIRE: the packed forms, the same kernels and steps as the pass driver's
+        for (int i = 0; i < count; i++)
+            if (packed_wire(ctxs[i]) != wire6 || (wire6 && ctxs[i]->opt.world_size != count))
+                return fail(c, HB_ERR_INVALID, "HB_FLAG_PACKED_WIRE: every context needs the flag, and ctxs must be all `count` ranks of the world");
+        // packed_all_reduce_max between logical ranks: rows_of(ctx) = its R rows; device copies in place of the all-to-all and the all-gather
+        auto packed_all_reduce = [&](auto rows_of, uint64_t R, uint64_t S) -> int {
+            for (int i = 0; i < count; i++) {
+                const int rc2 = wire6_pack_all(ctxs[i], rows_of(ctxs[i]), R, S, ctxs[i]->stream);
+                if (rc2) return rc2;
+                HB_HIP(hipStreamSynchronize(ctxs[i]->stream));
+            }
+            for (int i = 0; i < count && S; i++)
+                for (int j = 0; j < count; j++)
+                    HB_HIP(hipMemcpyAsync(ctxs[i]->d_w6[1] + (uint64_t)j * S * 12, ctxs[j]->d_w6[0] + (uint64_t)i * S * 12, S * 48, hipMemcpyDeviceToDevice, c->stream));
+            HB_HIP(hipStreamSynchronize(c->stream));
+            for (int i = 0; i < count; i++) {
+                const int rc2 = wire6_reduce_slice(ctxs[i], S, (uint64_t)i, ctxs[i]->stream);
+                if (rc2) return rc2;
+                HB_HIP(hipStreamSynchronize(ctxs[i]->stream));
+            }
+            for (int i = 0; i < count && S; i++)
+                for (int j = 0; j < count; j++)
+                    if (i != j)
+                        HB_HIP(hipMemcpyAsync(ctxs[i]->d_w6[0] + (uint64_t)j * S * 12, ctxs[j]->d_w6[0] + (uint64_t)j * S * 12, S * 48, hipMemcpyDeviceToDevice, c->stream));
+            HB_HIP(hipStreamSynchronize(c->stream));
+            for (int i = 0; i < count; i++) {
+                const int rc2 = wire6_unpack_all(ctxs[i], rows_of(ctxs[i]), R, ctxs[i]->stream);
+                if (rc2) return rc2;
+                HB_HIP(hipStreamSynchronize(ctxs[i]->stream));
+            }
+            return HB_OK;
+        };
         if (!dest_mode(c) && edge_changed_only(c)) {
             // the changed-only all-reduce between logical ranks: union of the locally-changed bitmaps, every context packs
             // its rows of the union, the packed buffers are max-folded (the all-reduce), every context unpacks
@@ -359,18 +444,27 @@ int hb_debug_exchange(hb_ctx **ctxs, int count, int phase)
                 HB_HIP(hipStreamSynchronize(ctxs[i]->stream));
             }
             const uint64_t count4 = c->co_rows * 4;
-            for (int i = 1; i < count && count4; i++) {
+            if (wire6 && count4) {
+                const int rc2 = packed_all_reduce([](hb_ctx *x) { return x->d_pack; }, c->co_rows, wire6_co_slice(c));
+                if (rc2) return rc2;
+            }
+            for (int i = 1; i < count && count4 && !wire6; i++) {
                 hipLaunchKernelGGL(hbk::merge_max_kernel, dim3(2048), dim3(256), 0, c->stream, c->d_pack, (const uint4 *)ctxs[i]->d_pack, count4);
                 HB_HIP(hipGetLastError());
             }
-            for (int i = 1; i < count && count4; i++) HB_HIP(hipMemcpyAsync(ctxs[i]->d_pack, c->d_pack, count4 * 16, hipMemcpyDeviceToDevice, c->stream));
+            for (int i = 1; i < count && count4 && !wire6; i++) HB_HIP(hipMemcpyAsync(ctxs[i]->d_pack, c->d_pack, count4 * 16, hipMemcpyDeviceToDevice, c->stream));
             HB_HIP(hipStreamSynchronize(c->stream));
             for (int i = 0; i < count; i++) {
                 int rc2 = edge_co_unpack(ctxs[i]);
                 if (rc2) return rc2;
-                ctxs[i]->wire_bytes += (uint64_t)(count - 1) * words * 4 + 2 * (uint64_t)(count - 1) * ctxs[i]->co_rows * 64 / (uint64_t)count;
+                ctxs[i]->wire_bytes += (uint64_t)(count - 1) * words * 4 + (wire6 ? wire6_co_bytes(ctxs[i]) : 2 * (uint64_t)(count - 1) * ctxs[i]->co_rows * 64 / (uint64_t)count);
                 HB_HIP(hipStreamSynchronize(ctxs[i]->stream));
             }
+        } else if (!dest_mode(c) && wire6) {
+            // the packed all-reduce(max) of the pending counters
+            const int rc2 = packed_all_reduce([](hb_ctx *x) { return x->d_regs[x->cur ^ 1]; }, p.n_pad, wire6_slice(c));
+            if (rc2) return rc2;
+            for (int i = 0; i < count; i++) ctxs[i]->wire_bytes += wire6_all_reduce_bytes(ctxs[i], wire6_slice(c));
         } else if (!dest_mode(c)) {
             // all-reduce(max) of the pending counters: fold everything into ctxs[0], then copy out
             const uint64_t count4 = p.n_pad * 4;
@@ -392,18 +486,34 @@ int hb_debug_exchange(hb_ctx **ctxs, int count, int phase)
             for (int i = 0; i < count; i++)
                 for (size_t k = 0; k < W; k++) total[k] += cnt[(size_t)i * W + k];
             const bool packed = changed_only(c);
+            const bool whole6 = wire6 && !packed; // whole slices as 48-byte rows: pack, move S x 48 bytes, unpack the foreign slices
+            for (int i = 0; i < count && whole6; i++) {
+                const int rc2 = wire6_pack_own_slice(ctxs[i]);
+                if (rc2) return rc2;
+                HB_HIP(hipStreamSynchronize(ctxs[i]->stream));
+            }
             for (int i = 0; i < count; i++) {
                 hb_ctx *d = ctxs[i];
                 for (int j = 0; j < count; j++) {
                     if (i == j || !S) continue;
                     hb_ctx *o = ctxs[j];
-                    if (!packed)
+                    if (whole6)
+                        HB_HIP(hipMemcpyAsync(d->d_w6[0] + (uint64_t)j * S * 12, o->d_w6[0] + (uint64_t)j * S * 12, S * 48, hipMemcpyDeviceToDevice, c->stream));
+                    else if (!packed)
                         HB_HIP(hipMemcpyAsync(d->d_regs[d->cur ^ 1] + (uint64_t)j * S * 4, o->d_regs[o->cur ^ 1] + (uint64_t)j * S * 4, S * 64,
                                               hipMemcpyDeviceToDevice, c->stream));
                     HB_HIP(hipMemcpyAsync(d->d_bits[d->cur ^ 1] + (uint64_t)j * (S / 32), o->d_bits[o->cur ^ 1] + (uint64_t)j * (S / 32), S / 8,
                                           hipMemcpyDeviceToDevice, c->stream));
                 }
                 HB_HIP(hipMemcpyAsync(d->d_counters + W * d->t, total.data(), W * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+            }
+            if (whole6) {
+                HB_HIP(hipStreamSynchronize(c->stream));
+                for (int i = 0; i < count; i++) {
+                    const int rc2 = wire6_unpack_foreign_slices(ctxs[i]);
+                    if (rc2) return rc2;
+                    HB_HIP(hipStreamSynchronize(ctxs[i]->stream));
+                }
             }
             if (packed) {
                 // the changed-only protocol with copies in place of the broadcasts: pack everywhere, move the runs, unpack

@@ -248,7 +248,8 @@ int resolve_pass_times(hb_ctx *c)
 // plain edge partition on a communicator: pipeline merge / all-reduce / epilogue over row ranges
 bool edge_overlap(const hb_ctx *c)
 {
-    return linked(c) && !dest_mode(c) && !ref_tail(c) && !(c->opt.flags & HB_FLAG_CHANGED_ONLY) && !xbit(c, HB_X_NO_EDGE_OVERLAP) && c->comm_stream;
+    // (HB_FLAG_PACKED_WIRE: one packed all-reduce over all rows; a packed form of the pipelined ranges waits for a wire to measure it on)
+    return linked(c) && !dest_mode(c) && !ref_tail(c) && !(c->opt.flags & HB_FLAG_CHANGED_ONLY) && !xbit(c, HB_X_NO_EDGE_OVERLAP) && c->comm_stream && !packed_wire(c);
 }
 // edge partition (all-reduce) with HB_FLAG_CHANGED_ONLY: only the rows some rank's local merge changed are exchanged
 bool edge_changed_only(const hb_ctx *c)
@@ -391,6 +392,111 @@ int exchange_unpack(hb_ctx *c)
         HB_HIP(hipGetLastError());
     }
     return HB_OK;
+}
+
+// ---- whole counters as 48-byte rows (HB_FLAG_PACKED_WIRE, DESIGN.md section 40) ------------------------------------------------
+// d_w6[0..nbuf): world x wire6_slice packed rows each.  The slice is >= ceil(n_pad / world) in both decompositions, so the buffers hold
+// the pieces of every exchange below: the destination partition's slices, the edge partition's (plain: one slice per piece;
+// changed-only: ceil(co_rows / world) rows, never more than a slice).  Allocated by the first pass that exchanges, like ensure_pack_buffers.
+// rows per rank's slice: the destination partition's owner slice; on the edge partition the Kahan slice of a linked context
+// (slice_rows) - which logical ranks without collectives (hb_debug_exchange) do not have, so it is restated here
+uint64_t wire6_slice(const hb_ctx *c)
+{
+    const uint64_t world = (uint64_t)std::max(c->opt.world_size, 1);
+    return dest_mode(c) ? c->slice_rows : ((c->plan.n_pad + world - 1) / world + 63) / 64 * 64;
+}
+int ensure_wire6_buffers(hb_ctx *c, int nbuf)
+{
+    const uint64_t world = (uint64_t)std::max(c->opt.world_size, 1);
+    for (int k = 0; k < nbuf; k++) {
+        if (c->d_w6[k]) continue;
+        const int rc = dev_alloc(c, &c->d_w6[k], world * wire6_slice(c) * 12 + 4);
+        if (rc) return rc;
+    }
+    return HB_OK;
+}
+unsigned wire6_blocks(const hb_ctx *c, uint64_t rows) { return grid_blocks(c, (rows * 4 + 255) / 256, 16, 1); }
+// "R rows of 64 bytes, present on every rank, to be max-reduced everywhere" in its five steps; S = rows per slice (world x S >= R).
+// hb_debug_exchange runs the same three launches with device copies between them.
+// step 1: all R rows packed into d_w6[0], the tail of the last pieces padded with zero codes
+int wire6_pack_all(hb_ctx *c, const uint4 *rows, uint64_t R, uint64_t S, hipStream_t stream)
+{
+    const uint64_t world = (uint64_t)std::max(c->opt.world_size, 1);
+    if (world * S < R || S > wire6_slice(c)) return fail(c, HB_ERR_INVALID, "packed all-reduce: the slices do not cover the rows");
+    const int rc = ensure_wire6_buffers(c, 2);
+    if (rc) return rc;
+    if (!S) return HB_OK;
+    hipLaunchKernelGGL(hbk::pack6_rows_kernel, dim3(wire6_blocks(c, world * S)), dim3(256), 0, stream, rows, R, world * S, c->d_w6[0]);
+    HB_HIP(hipGetLastError());
+    return HB_OK;
+}
+// step 3: the maximum over the `world` pieces of rank `rank`'s slice that the all-to-all left in d_w6[1], packed, at its place in d_w6[0]
+int wire6_reduce_slice(hb_ctx *c, uint64_t S, uint64_t rank, hipStream_t stream)
+{
+    if (!S) return HB_OK;
+    hipLaunchKernelGGL(hbk::max6_pieces_kernel, dim3(wire6_blocks(c, S)), dim3(256), 0, stream, (const uint32_t *)c->d_w6[1], S * 12, (uint32_t)std::max(c->opt.world_size, 1), S,
+                       c->d_w6[0] + rank * S * 12);
+    HB_HIP(hipGetLastError());
+    return HB_OK;
+}
+// step 5: d_w6[0] holds every rank's reduced slice: back to 64-byte rows
+int wire6_unpack_all(hb_ctx *c, uint4 *rows, uint64_t R, hipStream_t stream)
+{
+    if (!R) return HB_OK;
+    hipLaunchKernelGGL(hbk::unpack6_rows_kernel, dim3(wire6_blocks(c, R)), dim3(256), 0, stream, (const uint32_t *)c->d_w6[0], R, rows);
+    HB_HIP(hipGetLastError());
+    return HB_OK;
+}
+int packed_all_reduce_max(hb_ctx *c, uint4 *rows, uint64_t R, uint64_t S, hipStream_t stream)
+{
+    const uint64_t r = (uint64_t)c->opt.rank;
+    int rc;
+    if ((rc = wire6_pack_all(c, rows, R, S, stream))) return rc;
+    HB_COLL(coll_all_to_all(c, c->d_w6[0], c->d_w6[1], S * 48, stream));                            // step 2
+    if ((rc = wire6_reduce_slice(c, S, r, stream))) return rc;
+    HB_COLL(coll_all_gather(c, c->d_w6[0] + r * S * 12, c->d_w6[0], S * 48, ncclUint8, stream));   // step 4 (in place)
+    return wire6_unpack_all(c, rows, R, stream);
+}
+// destination partition, full form: this rank's slice of the pending counters packed at its place in d_w6[0] ...
+int wire6_pack_own_slice(hb_ctx *c)
+{
+    const Plan &p = c->plan;
+    const uint64_t S = c->slice_rows, r = (uint64_t)c->opt.rank;
+    const int rc = ensure_wire6_buffers(c, 1);
+    if (rc) return rc;
+    const uint64_t lo = std::min<uint64_t>(r * S, p.n_pad), hi = std::min<uint64_t>(lo + S, p.n_pad);
+    if (!S) return HB_OK;
+    hbk::PassParams pp = make_params(c);
+    hipLaunchKernelGGL(hbk::pack6_rows_kernel, dim3(wire6_blocks(c, S)), dim3(256), 0, c->stream, (const uint4 *)(pp.wr + lo * 4), hi - lo, S, c->d_w6[0] + r * S * 12);
+    HB_HIP(hipGetLastError());
+    return HB_OK;
+}
+// ... and, once the slices of all ranks are there, the foreign ones unpacked into the pending counters (the own slice is not rewritten)
+int wire6_unpack_foreign_slices(hb_ctx *c)
+{
+    const Plan &p = c->plan;
+    const uint64_t S = c->slice_rows, r = (uint64_t)c->opt.rank;
+    hbk::PassParams pp = make_params(c);
+    const uint64_t lo = std::min<uint64_t>(r * S, p.n_pad), hi = std::min<uint64_t>(lo + S, p.n_pad);
+    const uint64_t ranges[2][2] = {{0, lo}, {hi, p.n_pad}};
+    for (auto &rg : ranges) {
+        if (rg[1] <= rg[0]) continue;
+        hipLaunchKernelGGL(hbk::unpack6_rows_kernel, dim3(wire6_blocks(c, rg[1] - rg[0])), dim3(256), 0, c->stream, (const uint32_t *)(c->d_w6[0] + rg[0] * 12), rg[1] - rg[0],
+                           pp.wr + rg[0] * 4);
+        HB_HIP(hipGetLastError());
+    }
+    c->wire_bytes += (p.n_pad - std::min<uint64_t>(S, p.n_pad)) * 48 + (p.n_pad - std::min<uint64_t>(S, p.n_pad)) / 8;
+    return HB_OK;
+}
+// what a rank receives in one packed all-reduce: world - 1 pieces in the all-to-all, world - 1 slices in the all-gather
+uint64_t wire6_all_reduce_bytes(const hb_ctx *c, uint64_t S) { return 2 * (uint64_t)(std::max(c->opt.world_size, 1) - 1) * S * 48; }
+// edge partition + changed-only: the union's co_rows rows in slices of ceil(co_rows / world); booked without the padding of the last
+// piece, 3/4 of what the 64-byte all-reduce books
+uint64_t wire6_co_slice(const hb_ctx *c) { return (c->co_rows + (uint64_t)std::max(c->opt.world_size, 1) - 1) / (uint64_t)std::max(c->opt.world_size, 1); }
+uint64_t wire6_co_bytes(const hb_ctx *c)
+{
+    const uint64_t world = (uint64_t)std::max(c->opt.world_size, 1);
+    return world > 1 ? 2 * (world - 1) * c->co_rows * 48 / world : 0;
 }
 
 // ---- reference-tail mode ---------------------------------------------------------------------------------
@@ -801,9 +907,14 @@ int step_finish(hb_ctx *c, int *has_changes)
             HB_HIP(hipGetLastError());
             int rc = edge_co_pack(c);
             if (rc) return rc;
-            if (c->co_rows) HB_COLL(coll_all_reduce(c, c->d_pack, c->co_rows * 64, ncclUint8, ncclMax, c->stream));
+            if (c->co_rows && packed_wire(c)) {
+                if ((rc = packed_all_reduce_max(c, c->d_pack, c->co_rows, wire6_co_slice(c), c->stream))) return rc;
+            } else if (c->co_rows) {
+                HB_COLL(coll_all_reduce(c, c->d_pack, c->co_rows * 64, ncclUint8, ncclMax, c->stream));
+            }
             if ((rc = edge_co_unpack(c))) return rc;
-            c->wire_bytes += (uint64_t)(world - 1) * words * 4 + (world > 1 ? 2 * (uint64_t)(world - 1) * c->co_rows * 64 / (uint64_t)world : 0);
+            c->wire_bytes += (uint64_t)(world - 1) * words * 4 +
+                             (packed_wire(c) ? wire6_co_bytes(c) : (world > 1 ? 2 * (uint64_t)(world - 1) * c->co_rows * 64 / (uint64_t)world : 0));
         } else if (linked(c) && c->ov_ranges) {
             // pipelined: all-reduce of range k on comm_stream as soon as it is merged; its epilogue on the main stream as
             // soon as it is reduced (the epilogue launches below wait for ov_reduced[k])
@@ -814,6 +925,10 @@ int step_finish(hb_ctx *c, int *has_changes)
                 HB_HIP(hipEventRecord(c->ov_reduced[k], c->comm_stream));
             }
             c->wire_bytes += c->opt.world_size > 1 ? 2 * (uint64_t)(c->opt.world_size - 1) * p.n_pad * 64 / (uint64_t)c->opt.world_size : 0;
+        } else if (linked(c) && packed_wire(c)) {
+            const int rc = packed_all_reduce_max(c, pp.wr, p.n_pad, wire6_slice(c), c->stream);
+            if (rc) return rc;
+            c->wire_bytes += wire6_all_reduce_bytes(c, wire6_slice(c));
         } else if (linked(c)) {
             HB_COLL(coll_all_reduce(c, pp.wr, p.n_pad * 64, ncclUint8, ncclMax, c->stream));
             c->wire_bytes += c->opt.world_size > 1 ? 2 * (uint64_t)(c->opt.world_size - 1) * p.n_pad * 64 / (uint64_t)c->opt.world_size : 0;
@@ -875,6 +990,15 @@ int step_finish(hb_ctx *c, int *has_changes)
             }
             HB_COLL(coll_group_end(c));
             if ((rc = exchange_unpack(c))) return rc;
+        } else if (packed_wire(c)) {
+            int rc = wire6_pack_own_slice(c);
+            if (rc) return rc;
+            HB_COLL(coll_group_start(c));
+            HB_COLL(coll_all_gather(c, c->d_w6[0] + r * S * 12, c->d_w6[0], S * 48, ncclUint8, c->stream));
+            HB_COLL(coll_all_gather(c, pp.bits_wr + r * (S / 32), pp.bits_wr, S / 32, ncclUint32, c->stream));
+            HB_COLL(coll_all_reduce(c, pp.counters, hbk::kCounterWords, ncclUint64, ncclSum, c->stream));
+            HB_COLL(coll_group_end(c));
+            if ((rc = wire6_unpack_foreign_slices(c))) return rc;
         } else {
             HB_COLL(coll_group_start(c));
             HB_COLL(coll_all_gather(c, pp.wr + r * S * 4, pp.wr, S * 64, ncclUint8, c->stream));

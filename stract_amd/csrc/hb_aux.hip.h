@@ -223,6 +223,80 @@ __global__ __launch_bounds__(256) void unpack6_changed_kernel(uint4 *wr, const u
     }
 }
 
+// ---- whole counters at 6 bits per register (HB_FLAG_PACKED_WIRE) ---------------------------------------
+// The exchanges that move WHOLE counters - the destination partition's full all-gather, the edge partition's all-reduce(max) and
+// its changed-only form - ship 48-byte rows as well: a contiguous run of 64-byte rows <-> the same run packed.  A quad per row
+// as above; lane t of the grid owns bytes 12 t .. 12 t + 11 of the packed run, so a wave's 16 rows are 768 contiguous bytes on
+// the packed side and 1024 on the other.  Streaming kernels: 28 bytes moved per lane against ~100 integer operations.
+// pack: rows [0, count) from `rows`; rows [count, total) - the padding that gives every rank's piece the same size - as zero codes
+__global__ __launch_bounds__(256) void pack6_rows_kernel(const uint4 *rows, uint64_t count, uint64_t total, uint32_t *pack6)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < total * 4; t += stride) {
+        Packed12 p = {{0u, 0u, 0u}};
+        if (t < count * 4) p = pack6_quarter(rows[t]);
+        uint32_t *dst = pack6 + t * 3;
+        dst[0] = p.w[0];
+        dst[1] = p.w[1];
+        dst[2] = p.w[2];
+    }
+}
+__global__ __launch_bounds__(256) void unpack6_rows_kernel(const uint32_t *pack6, uint64_t count, uint4 *rows)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < count * 4; t += stride) {
+        const uint32_t *src = pack6 + t * 3;
+        Packed12 p;
+        p.w[0] = src[0];
+        p.w[1] = src[1];
+        p.w[2] = src[2];
+        rows[t] = unpack6_quarter(p);
+    }
+}
+// out = the register-wise maximum over `world` packed pieces of `count` rows each, piece k at pieces + k * piece_words, packed again.
+// The code is monotone in the register (0..58 as themselves, 63 for 65), so the maximum is taken on the codes: no piece is ever
+// unpacked to bytes, and the sixteen codes of a quarter are put together once, after the last piece.
+__global__ __launch_bounds__(256) void max6_pieces_kernel(const uint32_t *pieces, uint64_t piece_words, uint32_t world, uint64_t count, uint32_t *out)
+{
+    const uint64_t stride = (uint64_t)gridDim.x * 256;
+    for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < count * 4; t += stride) {
+        uint32_t m[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++) m[i] = 0;
+        const uint32_t *src = pieces + t * 3;
+#pragma unroll 2
+        for (uint32_t k = 0; k < world; k++, src += piece_words) {
+            const uint32_t w0 = src[0], w1 = src[1], w2 = src[2];
+            const uint64_t lo = ((uint64_t)w1 << 32) | w0;
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                uint32_t code;
+                if (i < 5) code = (w0 >> (6 * i)) & 63u;
+                else if (i == 5) code = (uint32_t)(lo >> 30) & 63u;
+                else if (i < 10) code = (w1 >> (6 * i - 32)) & 63u;
+                else if (i == 10) code = (w1 >> 28) | ((w2 & 3u) << 4);
+                else code = (w2 >> (2 + 6 * (i - 11))) & 63u;
+                m[i] = code > m[i] ? code : m[i];
+            }
+        }
+        uint64_t lo = 0;
+        uint32_t hi = 0;
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const uint64_t code = m[i];
+            if (i < 10) lo |= code << (6 * i);
+            else if (i == 10) {
+                lo |= (code & 15u) << 60;
+                hi |= (uint32_t)(code >> 4);
+            } else hi |= (uint32_t)code << (2 + 6 * (i - 11));
+        }
+        uint32_t *dst = out + t * 3;
+        dst[0] = (uint32_t)lo;
+        dst[1] = (uint32_t)(lo >> 32);
+        dst[2] = hi;
+    }
+}
+
 // quad per row of [row_lo, row_hi)
 __global__ __launch_bounds__(256) void pack_changed_kernel(const uint4 *wr, const uint32_t *bits, const uint64_t *prefix, uint64_t row_lo,
                                                            uint64_t row_hi, uint4 *pack)

@@ -100,7 +100,7 @@ class HostStagedCollectives:
     """hb_set_collectives over torch.distributed tensors in HOST memory (any backend that moves CPU tensors: gloo): every
     exchange of the pass driver - all-reduce(max, u8) of the counters, the pipelined per-range form, the changed-only packing
     with its all-gather of bitmaps and per-rank broadcasts, the destination partition's all-gathers, the all-gather of the
-    Kahan slices - runs as the LIBRARY's code, with N processes that may all sit on one device (RCCL refuses that).  Slow by
+    Kahan slices, the all-to-all of HB_FLAG_PACKED_WIRE's packed all-reduce (hb_set_all_to_all) - runs as the LIBRARY's code, with N processes that may all sit on one device (RCCL refuses that).  Slow by
     construction (device -> host -> wire -> host -> device, blocking); its purpose is correctness of the multi-process
     protocol where only one GPU exists (tests/test_gpu.py), and as a template for integrators with their own fabric.
 
@@ -123,7 +123,7 @@ class HostStagedCollectives:
         self.world = td.get_world_size(group)
         self.rank = td.get_rank(group)
         self.lib = ctx.lib  # (the build that owns the context: product, or the experiments build when the context asked for one of its switches)
-        self.calls = {"all_reduce": 0, "all_gather": 0, "broadcast": 0, "bytes": 0}
+        self.calls = {"all_reduce": 0, "all_gather": 0, "broadcast": 0, "all_to_all": 0, "bytes": 0}
         self.error = None
         np_of = {_lib.HB_COLL_U8: np.uint8, _lib.HB_COLL_U32: np.uint32, _lib.HB_COLL_U64: np.uint64, _lib.HB_COLL_F64: np.float64}
 
@@ -184,7 +184,28 @@ class HostStagedCollectives:
             self.calls["broadcast"] += 1
             self.calls["bytes"] += int(nbytes)
 
+        @guard
+        def all_to_all(user, send, recv, nbytes, stream):
+            # piece k of `send` to rank k, piece k of `recv` from rank k (HB_FLAG_PACKED_WIRE on the edge partition).  gloo's
+            # all_to_all_single where this torch has it for CPU tensors; otherwise every rank gathers all send buffers and keeps its column
+            mine = torch.from_numpy(to_host(send, nbytes * self.world, stream))
+            got = torch.empty(nbytes * self.world, dtype=torch.uint8)
+            if self._a2a_single:
+                try:
+                    td.all_to_all_single(got, mine, group=self.group)
+                except (RuntimeError, NotImplementedError):
+                    self._a2a_single = False
+            if not self._a2a_single:
+                parts = [torch.empty(nbytes * self.world, dtype=torch.uint8) for _ in range(self.world)]
+                td.all_gather(parts, mine, group=self.group)
+                got = torch.cat([q[self.rank * nbytes:(self.rank + 1) * nbytes] for q in parts])
+            to_device(recv, got.numpy(), stream)
+            self.calls["all_to_all"] += 1
+            self.calls["bytes"] += int(nbytes * self.world)
+
+        self._a2a_single = hasattr(td, "all_to_all_single")
         self._cb = (self._ALL_REDUCE(all_reduce), self._ALL_GATHER(all_gather), self._BROADCAST(broadcast))
+        self._a2a_cb = _lib.ALL_TO_ALL_FN(all_to_all)
 
         class Ops(ctypes.Structure):
             _fields_ = [("user", ctypes.c_void_p), ("all_reduce", self._ALL_REDUCE), ("all_gather", self._ALL_GATHER), ("broadcast", self._BROADCAST)]
@@ -193,3 +214,4 @@ class HostStagedCollectives:
         rc = self.lib.hb_set_collectives(ctx.h, ctypes.byref(self._ops))
         if rc != _lib.HB_OK:
             raise _lib.HyperballError(rc, (self.lib.hb_last_error(ctx.h) or b"").decode())
+        ctx.set_all_to_all(self._a2a_cb)
